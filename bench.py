@@ -221,6 +221,22 @@ def pmc_mfma(workload: str, nd: int, kernel_avg_s: float):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """Writes each device array as out_dir/<name>.npy in float64.  Above DUMP_LIMIT_BYTES in all, every array is cut to the same
+    fixed, seeded sample of flat positions (sorted), so that two builds of the project write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 8
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float64, copy=False)
+        if total > DUMP_LIMIT_BYTES:
+            keep = min(a.size, DUMP_LIMIT_BYTES // 8 // len(arrays))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,7 +248,12 @@ def main():
     ap.add_argument("--n-dens", type=int, choices=[1, 2, 4, 8, 16], default=1,
                     help="densities per step (2 = a UHF build: alpha and beta in one pass; 4, 8, 16 = a finite-field batch: pairs of densities per pass)")
     ap.add_argument("--layout", choices=["packed", "rows", "tiles"], default="packed", help="ERI storage layout (tunafock.h: tf_set_eri_layout)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the J and K of the last one as DIR/J.npy and DIR/K.npy (float64, [n_dens, N, N]; "
+                         "a fixed seeded sample of the elements when both exceed 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -352,6 +373,8 @@ def main():
     # sanity of the timed result: J symmetric, tr-type identity <P|J> > 0
     Jh = dJK[0, 0].cpu().numpy()
     ok = bool(np.isfinite(Jh).all() and np.abs(Jh - Jh.T).max() < 1e-8 * max(1.0, np.abs(Jh).max()))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"J": dJK[0], "K": dJK[1]})
 
     if rank == 0:
         layout = st["layout"]

@@ -6,8 +6,8 @@ tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this 
 product package (tuna_amd/) never does.
 
 Parity status: PINNED against the reference engine and its golden vectors (tests/test_oracle.py:
-test_oracle_matches_compiled_reference_on_random_basis runs the compiled engine of oracle/_ref beside the
-restatement where /root/reference exists; the other tests replay tests/golden/, which that engine produced).
+test_oracle_matches_compiled_reference_on_random_basis replays the full output of the compiled engine of
+oracle/_ref on a random s..g basis; the other tests replay tests/golden/, which that engine produced too).
 """
 from __future__ import annotations
 

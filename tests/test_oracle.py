@@ -141,10 +141,11 @@ def test_golden_anchor_energies(golden):
     assert abs(float(z["h2_sto3g__scf_energy"]) - (-1.1167593075)) < 5e-10
 
 
-def test_oracle_matches_compiled_reference_on_random_basis():
-    """Direct check against the compiled, unmodified reference engine (oracle/_ref) when it is present."""
-    if orc.ref_engine() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+def test_oracle_matches_compiled_reference_on_random_basis(golden):
+    """Direct check against what the compiled, unmodified reference engine returns for a random s..g basis
+    (tools/make_golden.py --random-basis-only -> tests/golden/random_basis.npz: the one-electron matrices in full,
+    the ERI tensor as the 8-fold unique values the reference's loop writes to all eight images)."""
+    g = golden("random_basis")
     rng = np.random.default_rng(7)
     from tuna_amd import molecule as mol
     basis = {6: [("S", [(float(rng.uniform(0.3, 8)), 0.4), (float(rng.uniform(0.1, 0.3)), 0.7)]),
@@ -153,10 +154,17 @@ def test_oracle_matches_compiled_reference_on_random_basis():
                  ("G", [(0.9, 1.0)])]}
     atoms = mol.make_atoms(["C", "F"], 2.3)
     aos = mol.expand_cartesian_aos(mol.build_shells(atoms, basis))
-    assert np.abs(orc.eri(aos) - orc.ref_eri(aos)).max() < 1e-14
+    for name in ("exps", "coefs", "lmn", "origin", "prim_off"):       # the stored run is of this very basis
+        np.testing.assert_array_equal(getattr(aos, name), g[name])
+    n = aos.n
+    i, j, k, l = np.indices((n,) * 4)
+    ij = np.maximum(i, j) * (np.maximum(i, j) + 1) // 2 + np.minimum(i, j)
+    kl = np.maximum(k, l) * (np.maximum(k, l) + 1) // 2 + np.minimum(k, l)
+    ref_eri = g["eri_unique"][np.maximum(ij, kl) * (np.maximum(ij, kl) + 1) // 2 + np.minimum(ij, kl)]
+    assert np.abs(orc.eri(aos) - ref_eri).max() < 1e-14
     xyz, chg = [a.origin for a in atoms], [float(a.charge) for a in atoms]
-    for a, b in zip(orc.one_electron(aos, xyz, chg, [0, 0, 1.0]), orc.ref_one_electron(aos, xyz, chg, [0, 0, 1.0])):
-        assert np.abs(a - b).max() < 1e-13
+    for a, name in zip(orc.one_electron(aos, xyz, chg, [0, 0, 1.0]), ("S", "T", "V", "D", "Q")):
+        assert np.abs(a - g[name]).max() < 1e-13
 
 
 @pytest.mark.parametrize("tag", ["o2_triplet_sto3g", "o2_triplet_ccpvdz", "no_doublet_631g", "oh_doublet_ccpvdz", "li_doublet_631g"])

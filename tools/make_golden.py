@@ -747,6 +747,41 @@ def make_keyword_golden(scf, blocks, ortho):
     json.dump(out, open(os.path.join(GOLD, "keyword_runs.json"), "w"), indent=0)
 
 
+def random_basis_system():
+    """The C-F pair with random exponents (s, p, d, f and g shells) of tests/test_oracle.py's direct check."""
+    rng = np.random.default_rng(7)
+    basis = {6: [("S", [(float(rng.uniform(0.3, 8)), 0.4), (float(rng.uniform(0.1, 0.3)), 0.7)]),
+                 ("P", [(float(rng.uniform(0.2, 3)), 1.0)]), ("F", [(float(rng.uniform(0.3, 2)), 1.0)])],
+             9: [("S", [(float(rng.uniform(0.3, 5)), 1.0)]), ("D", [(float(rng.uniform(0.2, 2)), 0.5), (0.31, 0.6)]),
+                 ("G", [(0.9, 1.0)])]}
+    return system(["C", "F"], 2.3, basis)
+
+
+def unique_eri_index(n):
+    """Flat position of every (i, j, k, l) among the 8-fold unique values: pair (ij) = i(i+1)/2 + j for i >= j, quartet
+    (ij)((ij)+1)/2 + (kl) for (ij) >= (kl) -- the order of the reference's own loop (pyx:1300-1338), which writes each
+    value it computes to all eight images, so these values determine its tensor exactly."""
+    i, j, k, l = np.indices((n,) * 4)
+    ij = np.maximum(i, j) * (np.maximum(i, j) + 1) // 2 + np.minimum(i, j)
+    kl = np.maximum(k, l) * (np.maximum(k, l) + 1) // 2 + np.minimum(k, l)
+    return np.maximum(ij, kl) * (np.maximum(ij, kl) + 1) // 2 + np.minimum(ij, kl)
+
+
+def make_random_basis_golden():
+    """The compiled reference engine on random_basis_system(): one-electron matrices in full, the ERI tensor as its 8-fold unique
+    values (unique_eri_index).  Data only."""
+    atoms, shells, aos = random_basis_system()
+    xyz, chg = [a.origin for a in atoms], [float(a.charge) for a in atoms]
+    S, T, V, D, Q = orc.ref_one_electron(aos, xyz, chg, [0, 0, 1.0])
+    E = orc.ref_eri(aos)
+    npair = aos.n * (aos.n + 1) // 2
+    eri_unique = np.zeros(npair * (npair + 1) // 2)
+    eri_unique[unique_eri_index(aos.n).ravel()] = E.ravel()
+    np.savez_compressed(os.path.join(GOLD, "random_basis.npz"), S=S, T=T, V=V, D=D, Q=Q, eri_unique=eri_unique,
+                        exps=aos.exps, coefs=aos.coefs, lmn=aos.lmn, origin=aos.origin, prim_off=aos.prim_off)
+    print("random_basis", aos.n, len(eri_unique))
+
+
 def run_reference_scf(scf, ortho, atoms, shells, S, T, V, ERI, n_occ, conv="extreme", damping=True, F_fld=None):
     """Core-Hamiltonian guess (tuna_guess.py calculate_core_guess: diagonalise H_core, fill n_occ) + reference loop."""
     X, smallest, S_inv = ortho(S, None, True)
@@ -781,6 +816,9 @@ def run_reference_scf(scf, ortho, atoms, shells, S, T, V, ERI, n_occ, conv="extr
 def main():
     os.makedirs(GOLD, exist_ok=True)
     assert orc.ref_engine() is not None, "run oracle/build_ref.sh first"
+    if "--random-basis-only" in sys.argv:
+        make_random_basis_golden()
+        return
     scf = load_reference_scf()
     blocks, ortho = load_reference_kernel_bits()
     if "--uhf-only" in sys.argv:
@@ -917,6 +955,7 @@ def main():
     make_mp2_golden(scf, blocks, ortho)
     make_sad_golden(scf, blocks, ortho)
     make_dft_golden(scf, blocks, ortho)
+    make_random_basis_golden()
 
 
 if __name__ == "__main__":
