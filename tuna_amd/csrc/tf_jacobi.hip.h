@@ -7,6 +7,8 @@
 // Output convention (same as tfscf::eigh): eigenvalues ascending in vals; W row k = eigenvector k.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
 
 namespace tfjac {
 
@@ -64,7 +66,30 @@ __global__ __launch_bounds__(TFJ_THREADS) void jacobi_eigh_kernel(int n, double 
         sV[i * ldv + j] = warm ? V0[e] : ((i == j) ? 1.0 : 0.0);
     }
     const int m = n + (n & 1), half = m / 2;
+    const int lane = tid & 63, wv = tid >> 6;
     int sweeps = 0;
+    // the stopping test squares elements: outside 2^-100 <= max|a| <= 2^100 bring the matrix there by a power of two (exact; as LAPACK's
+    // dsyev does), else its sums overflow or underflow near 1e+-154 and the sweeps stop before the first rotation.  Inside, nothing changes.
+    // (tfscf::eigh scales the same way before any solver when it checks the solve at once; this covers the solves inside a cycle.)
+    {
+        double am = 0.0;
+        for (int e = tid; e < n * n; e += TFJ_THREADS) am = fmax(am, fabs(W[e]));
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) am = fmax(am, __shfl_xor(am, d, 64));
+        if (lane == 0) sRed[wv] = am;
+        __syncthreads();
+        if (tid == 0) {
+            double a2 = 0.0;
+            for (int u = 0; u < TFJ_THREADS / 64; ++u) a2 = fmax(a2, sRed[u]);
+            int ex = 0;
+            if (a2 > 0.0 && (a2 < 0x1p-100 || a2 > 0x1p100) && isfinite(a2)) { (void)frexp(a2, &ex); }
+            sDone = ex;                                     // (sDone doubles as the broadcast slot: the sweeps overwrite it)
+        }
+        __syncthreads();
+    }
+    const int scale_ex = sDone;
+    if (scale_ex != 0)
+        for (int e = tid; e < n * n; e += TFJ_THREADS) { const int i = e / n, j = e - i * n; sA[i * lda + j] = ldexp(sA[i * lda + j], -scale_ex); }
     __syncthreads();
     if (warm) {
         // third LDS matrix (after the int scratch): T = A V^T, then A0 = V T, upper triangle mirrored
@@ -86,7 +111,6 @@ __global__ __launch_bounds__(TFJ_THREADS) void jacobi_eigh_kernel(int n, double 
         }
         __syncthreads();
     }
-    const int lane = tid & 63, wv = tid >> 6;
     for (; sweeps < max_sweeps; ++sweeps) {
         // convergence: off-diagonal weight relative to the whole matrix (wave shuffles, then the 16 wave sums: two barriers)
         double off = 0.0, tot = 0.0;
@@ -167,7 +191,7 @@ __global__ __launch_bounds__(TFJ_THREADS) void jacobi_eigh_kernel(int n, double 
             rank += (dj < di || (dj == di && j < i)) ? 1 : 0;
         }
         sPQ[i] = rank;                       // safe: the pair codes are no longer needed
-        vals[rank] = di;
+        vals[rank] = scale_ex ? ldexp(di, scale_ex) : di;
     }
     __syncthreads();
     for (int e = tid; e < n * n; e += TFJ_THREADS) {
@@ -188,6 +212,16 @@ inline size_t lds_bytes(int n, bool v_in_lds, bool warm = false)
     return b;
 }
 
+// sweep cap of every launch: 100.  A cold solve converges in ~8 sweeps, but some Fock matrices with exactly degenerate pi pairs converge
+// only linearly (HeH+/cc-pVTZ, n = 28: the off-diagonal weight falls by 4x per sweep from the third sweep on and needs ~45 sweeps; the old
+// cap of 40 returned such solves unconverged, with nobody reading `info`).  TF_JACOBI_SWEEPS overrides -- a test knob: a low cap makes
+// ordinary input fail to converge, which the callers must detect through `info` and route to another solver.
+inline int max_sweeps()
+{
+    static const int cap = getenv("TF_JACOBI_SWEEPS") ? std::max(0, atoi(getenv("TF_JACOBI_SWEEPS"))) : 100;
+    return cap;
+}
+
 // returns false if n is outside the kernel's range (caller falls back to rocSOLVER)
 inline bool launch(int n, double *W, double *vals, double *Vscratch, int *info, hipStream_t st, hipError_t *err,
                    const double *V0 = nullptr, double *Vkeep = nullptr)
@@ -205,10 +239,10 @@ inline bool launch(int n, double *W, double *vals, double *Vscratch, int *info, 
     if (v_in) {
         const bool warm = V0 != nullptr && lds_bytes(n, true, true) <= cap;
         hipLaunchKernelGGL(jacobi_eigh_kernel<true>, dim3(1), dim3(TFJ_THREADS), lds_bytes(n, true, warm), st, n, W, vals, Vscratch,
-                           warm ? V0 : nullptr, Vkeep, 40, info);
+                           warm ? V0 : nullptr, Vkeep, max_sweeps(), info);
     } else
         hipLaunchKernelGGL(jacobi_eigh_kernel<false>, dim3(1), dim3(TFJ_THREADS), lds_bytes(n, false), st, n, W, vals, Vscratch,
-                           (const double *)nullptr, Vkeep, 40, info);
+                           (const double *)nullptr, Vkeep, max_sweeps(), info);
     *err = hipGetLastError();
     return *err == hipSuccess;
 }
@@ -224,7 +258,7 @@ inline bool launch_batch(int nb, int mmax, const int *d_sizes, double *W, long l
         attr_set = true;
     }
     hipLaunchKernelGGL(jacobi_eigh_kernel<true>, dim3(nb), dim3(TFJ_THREADS), lds_bytes(mmax, true, V0 != nullptr), st, mmax, W, vals,
-                       (double *)nullptr, V0, Vkeep, 40, info, d_sizes, stride, vstride);
+                       (double *)nullptr, V0, Vkeep, max_sweeps(), info, d_sizes, stride, vstride);
     *err = hipGetLastError();
     return *err == hipSuccess;
 }

@@ -89,6 +89,13 @@ struct Workspace {
     double *sym_prev = nullptr;      // device [nb][mmax][mmax]: block eigenvectors of the previous solve (warm start of the batched Jacobi)
     int sym_prev_n = 0;              // 0 = none
     long long sym_solves = 0, sym_declined = 0;
+    // solver status words (`info` of the Jacobi kernels and of rocSOLVER): checked at once (one read-back per solve), or -- inside the
+    // iterations of a native cycle, which must not wait on the device per solve -- counted on the device into *eig_fail, which the cycle
+    // reads back with the density changes of the iteration
+    double *eig_fail = nullptr;
+    double *jac_in = nullptr;        // device [n][n]: the matrix handed to the full-matrix Jacobi kernel (to solve it again with dsyevd)
+    size_t jac_in_cap = 0;
+    long long jac_fallbacks = 0;     // full-matrix Jacobi solves that did not converge and went to dsyevd
 };
 
 inline void release(Workspace &w)
@@ -102,6 +109,7 @@ inline void release(Workspace &w)
     if (w.ev1) (void)hipEventDestroy(w.ev1);
     if (w.jac_scratch) (void)hipFree(w.jac_scratch);
     if (w.jac_prev) (void)hipFree(w.jac_prev);
+    if (w.jac_in) (void)hipFree(w.jac_in);
     if (w.ref_buf) (void)hipFree(w.ref_buf);
     if (w.ref_alt_buf) (void)hipFree(w.ref_alt_buf);
     if (w.h_pin) (void)hipHostFree(w.h_pin);
@@ -451,7 +459,38 @@ __global__ void k_blk_labels(const int *__restrict__ src, int mmax, int n, int *
     if (r < n) out[r] = src[r] / mmax;
 }
 
-// TF_OK: solved (W rows = eigenvectors, vals ascending).  TF_EINVAL with an empty msg: declined, the caller solves the full matrix.
+// acc[0] += 1 if any of the cnt status words is non-zero (a solver that did not converge); single thread
+__global__ void k_info_fold(const int *__restrict__ info, int cnt, double *__restrict__ acc)
+{
+    int bad = 0;
+    for (int i = 0; i < cnt; ++i) bad |= info[i] != 0;
+    if (bad) acc[0] += 1.0;
+}
+
+// out = max |a| as the bits of a non-negative double (a NaN or an infinity compares above every finite value)
+__global__ void k_amax_bits(const double *__restrict__ A, long long nn, unsigned long long *__restrict__ out)
+{
+    unsigned long long m = 0;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nn; e += (long long)gridDim.x * blockDim.x)
+        m = max(m, (unsigned long long)__double_as_longlong(fabs(A[e])));
+    for (int d = 32; d > 0; d >>= 1) m = max(m, (unsigned long long)__shfl_xor((long long)m, d, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, m);
+}
+
+// status words of the solve just queued: *bad = some solver did not converge.  Inside a cycle (w.eig_fail set) nothing is read here:
+// the words are counted on the device and *bad stays false.
+inline int solver_failed(Workspace &w, const rocblas_int *d_info, int cnt, bool *bad, std::string &msg)
+{
+    *bad = false;
+    if (w.eig_fail) { hipLaunchKernelGGL(k_info_fold, dim3(1), dim3(1), 0, TFS_ST, (const int *)d_info, cnt, w.eig_fail); return TF_OK; }
+    rocblas_int h[4] = {0, 0, 0, 0};
+    TFS_HIP(tfs_memcpy(h, d_info, cnt * sizeof(rocblas_int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < cnt; ++i) *bad = *bad || h[i] != 0;
+    return TF_OK;
+}
+
+// TF_OK: solved (W rows = eigenvectors, vals ascending).  TF_EINVAL with an empty msg: declined, the caller solves the full matrix
+// (also when a block solve did not converge: W and vals are untouched until every block is known to be solved).
 inline int eigh_blocked(Workspace &w, int n, double *W, double *vals, std::string &msg)
 {
     static const bool off = getenv("TF_EIGH_BLOCKS") && getenv("TF_EIGH_BLOCKS")[0] == '0';
@@ -512,6 +551,13 @@ inline int eigh_blocked(Workspace &w, int n, double *W, double *vals, std::strin
         TFS_BLAS(rocsolver_dsyevd_strided_batched(w.blas, rocblas_evect_original, rocblas_fill_upper, mmax, B, mmax, (rocblas_stride)mmax * mmax,
                                                   D, mmax, E, mmax, w.sym_info, nb));
     }
+    bool bad = false;
+    if (int rc = solver_failed(w, w.sym_info, nb, &bad, msg)) return rc;
+    if (bad) {                                                     // a block did not converge: forget its vectors, solve the full matrix
+        w.sym_prev_n = 0; w.blk_ref_n = 0;
+        ++w.sym_declined;
+        return TF_EINVAL;
+    }
     hipLaunchKernelGGL(k_blk_rank, dim3(1), dim3(1024), 0, TFS_ST, D, w.sym_idx, nb, mmax, vals, w.sym_src);
     hipLaunchKernelGGL(k_blk_scatter, dim3(n), dim3(128), 0, TFS_ST, B, w.sym_idx, w.sym_src, n, mmax, W, sizes);
     ++w.sym_solves;
@@ -522,7 +568,7 @@ inline int eigh_blocked(Workspace &w, int n, double *W, double *vals, std::strin
 // Symmetric eigenproblem: W (in: symmetric matrix, out: row k = eigenvector k in row-major terms), vals ascending.
 // n <= 64: single-launch in-LDS Jacobi (tf_jacobi.hip.h; measured 0.06/0.23/0.96 ms at n = 10/28/60 against 0.24/0.67/1.22 ms
 // for dsyevd); larger: rocsolver_dsyevd (faster from n ~ 70 on).  TF_EIGH=rocsolver|jacobi overrides.
-inline int eigh(Workspace &w, int n, double *W, double *vals, double *work_e, std::string &msg)
+inline int eigh_route(Workspace &w, int n, double *W, double *vals, double *work_e, std::string &msg)
 {
     static const bool force_rocsolver = getenv("TF_EIGH") && std::string(getenv("TF_EIGH")) == "rocsolver";
     static const bool force_jacobi = getenv("TF_EIGH") && std::string(getenv("TF_EIGH")) == "jacobi";
@@ -549,15 +595,62 @@ inline int eigh(Workspace &w, int n, double *W, double *vals, double *work_e, st
         }
         static const bool no_warm = getenv("TF_EIGH_COLD") != nullptr;
         const double *V0 = (w.warm_ok && !no_warm && w.jac_prev_n == n) ? w.jac_prev : nullptr;
+        if (!w.eig_fail) {                                         // checked at once: keep the matrix for dsyevd should the sweeps not converge
+            if (w.jac_in_cap < (size_t)n * n) {
+                if (w.jac_in) (void)hipFree(w.jac_in);
+                w.jac_in = nullptr; w.jac_in_cap = 0;
+                TFS_HIP(hipMalloc((void **)&w.jac_in, (size_t)n * n * sizeof(double)));
+                w.jac_in_cap = (size_t)n * n;
+            }
+            TFS_HIP(hipMemcpyAsync(w.jac_in, W, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
+        }
         hipError_t e = hipSuccess;
         if (tfjac::launch(n, W, vals, w.jac_scratch, (int *)w.d_info, TFS_ST, &e, V0, w.warm_ok ? w.jac_prev : nullptr)) {
-            if (w.warm_ok) w.jac_prev_n = n;
-            return TF_OK;
-        }
-        if (e != hipSuccess) { msg = std::string("Jacobi eigensolver launch failed: ") + hipGetErrorString(e); return TF_ENODEVICE; }
+            bool bad = false;
+            if (int rc = solver_failed(w, w.d_info, 1, &bad, msg)) return rc;
+            if (!bad) {
+                if (w.warm_ok) w.jac_prev_n = n;
+                return TF_OK;
+            }
+            ++w.jac_fallbacks;
+            w.jac_prev_n = 0;
+            TFS_HIP(hipMemcpyAsync(W, w.jac_in, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
+        } else if (e != hipSuccess) { msg = std::string("Jacobi eigensolver launch failed: ") + hipGetErrorString(e); return TF_ENODEVICE; }
     }
     TFS_BLAS(rocsolver_dsyevd(w.blas, rocblas_evect_original, rocblas_fill_upper, n, W, n, vals, work_e, w.d_info));
+    bool bad = false;
+    if (int rc = solver_failed(w, w.d_info, 1, &bad, msg)) return rc;
+    if (bad) { msg = "Eigenvalues did not converge (rocsolver_dsyevd)"; return TF_ELINALG; }
     return TF_OK;
+}
+
+// x <- x 2^e (exact)
+__global__ void k_ldexp(double *__restrict__ x, long long m, int e)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (long long)gridDim.x * blockDim.x) x[i] = ldexp(x[i], e);
+}
+
+// eigh_route, and where the solve is checked at once (outside the iterations of a native cycle): a matrix with a NaN or an infinity is an
+// error (np.linalg.eigh raises LinAlgError, scf:244), and one whose largest element lies outside [2^-100, 2^100] is solved at a power-of-two
+// scale (exact; LAPACK's dsyev scales too, rocSOLVER's dsyevd does not: it returns wrong eigenvalues at 1e-100 and fails at 1e200).
+inline int eigh(Workspace &w, int n, double *W, double *vals, double *work_e, std::string &msg)
+{
+    if (w.eig_fail) return eigh_route(w, n, W, vals, work_e, msg);
+    unsigned long long *am = (unsigned long long *)(w.d_scal + 48);
+    TFS_HIP(hipMemsetAsync(am, 0, sizeof(*am), TFS_ST));
+    const int g = std::min(256, (n * n + 255) / 256);
+    hipLaunchKernelGGL(k_amax_bits, dim3(g), dim3(256), 0, TFS_ST, W, (long long)n * n, am);
+    unsigned long long hb = 0;
+    TFS_HIP(tfs_memcpy(&hb, am, sizeof(hb), hipMemcpyDeviceToHost));
+    if (hb >= 0x7ff0000000000000ULL) { w.sym_last_blocked = false; msg = "eigensolver: the matrix has non-finite elements"; return TF_ELINALG; }
+    double amax;
+    std::memcpy(&amax, &hb, sizeof(amax));
+    int ex = 0;
+    if (amax > 0.0 && (amax < 0x1p-100 || amax > 0x1p100)) (void)std::frexp(amax, &ex);
+    if (ex) hipLaunchKernelGGL(k_ldexp, dim3(g), dim3(256), 0, TFS_ST, W, (long long)n * n, -ex);
+    const int rc = eigh_route(w, n, W, vals, work_e, msg);
+    if (rc == TF_OK && ex) hipLaunchKernelGGL(k_ldexp, dim3(1), dim3(256), 0, TFS_ST, vals, (long long)n, ex);
+    return rc;
 }
 
 // dense solve A x = b for the (m <= 9) DIIS system; false if A is exactly singular (np.linalg.solve -> LinAlgError)
@@ -1190,7 +1283,9 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     int n_hist = 0;
     w.warm_ok = true;                 // successive Fock matrices are close: warm-start the Jacobi solver from the last eigenvectors
     w.jac_prev_n = 0; w.sym_prev_n = 0;   // (no warm start across cycles: a cycle's result must not depend on what the context solved before)
-    struct WarmGuard { Workspace &w; ~WarmGuard() { w.warm_ok = false; w.jac_prev_n = 0; w.sym_prev_n = 0; } } warm_guard{w};
+    struct WarmGuard { Workspace &w; ~WarmGuard() { w.warm_ok = false; w.jac_prev_n = 0; w.sym_prev_n = 0; w.eig_fail = nullptr; } } warm_guard{w};
+    w.eig_fail = w.d_scal + 23;           // solver status of the iteration, read back with its density changes
+    TFS_HIP(hipMemsetAsync(w.eig_fail, 0, sizeof(double), TFS_ST));
     double E = E0, E_old = E0, commutator = 1.0;
     double comps[7] = {0, 0, 0, 0, 0, 0, 0};
     out.fock_seconds = 0; out.eig_seconds = 0; out.n_iter = 0; out.converged = 0;
@@ -1323,8 +1418,9 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, damp, dPold, 1.0 - damp, dPbd, dP, (int)nn);
         // changes and convergence (scf:261-333)
         launch_delta_norms(w, dP, dPold, (int)nn, w.d_scal + 16);
-        double res[7];
-        TFS_HIP(tfs_memcpy(res, w.d_scal + 16, 7 * sizeof(double), hipMemcpyDeviceToHost));
+        double res[8];
+        TFS_HIP(tfs_memcpy(res, w.d_scal + 16, 8 * sizeof(double), hipMemcpyDeviceToHost));
+        if (res[7] != 0.0) { msg = "Eigenvalues did not converge (SCF iteration " + std::to_string(step) + ")"; return TF_ELINALG; }
         {
             const double eT = res[2], eV = res[3], eF = res[4], eJ = res[5], eK = res[6];
             comps[0] = eT; comps[1] = eV; comps[2] = (1.0 / 2.0) * eJ; comps[3] = -(1.0 / 4.0) * eK * o.hfx + xc3[1]; comps[4] = xc3[2];   // scf:380-394
@@ -1353,6 +1449,7 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         if (out.eps) TFS_HIP(tfs_memcpy(out.eps, vals_save, n * sizeof(double), hipMemcpyDeviceToHost));
         if (out.C) TFS_HIP(tfs_memcpy(out.C, dCsave, nn * sizeof(double), hipMemcpyDeviceToHost));
     }
+    w.eig_fail = nullptr;
     if (!orbitals_final && (out.eps || out.C) && out.n_iter > 0) {
         // orbitals and orbital energies of the last Fock matrix (what the reference's last diagonalisation leaves, scf:1133)
         TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, dF, 0.0, t1));
@@ -1466,6 +1563,9 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     };
     w.ref_n = 0; w.ref_alt_n = 0; w.ref_vcls_n = 0; w.ref_alt_vcls_n = 0; w.blk_ref_n = 0; w.blk_alt_ref_n = 0;
     w.warm_ok = false; w.jac_prev_n = 0; w.sym_prev_n = 0;          // two alternating spins: no warm start for the (rare) Jacobi solves
+    struct FailGuard { Workspace &w; ~FailGuard() { w.eig_fail = nullptr; } } fail_guard{w};
+    w.eig_fail = w.d_scal + 30;           // solver status of the iteration, read back with its density changes
+    TFS_HIP(hipMemsetAsync(w.eig_fail, 0, sizeof(double), TFS_ST));
     bool orbitals_current[2] = {false, false}, orbitals_final[2] = {false, false};
     // diagonalise F_s (AO) -> P_s = C_occ C_occ^T symmetrised (one electron per orbital, scf:1227-1228)
     auto diag_density = [&](int sp, const double *Fao, double *Pout) -> int {
@@ -1636,8 +1736,9 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, damp[sp], dPold[sp], 1.0 - damp[sp], dPn[sp], dP[sp], (int)nn);
         hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dP[0], 1.0, dP[1], dPt, (int)nn);
         launch_delta_norms(w, dPt, dPtold, (int)nn, w.d_scal + 16);
-        double res[14];
-        TFS_HIP(tfs_memcpy(res, w.d_scal + 16, 14 * sizeof(double), hipMemcpyDeviceToHost));
+        double res[15];
+        TFS_HIP(tfs_memcpy(res, w.d_scal + 16, 15 * sizeof(double), hipMemcpyDeviceToHost));
+        if (res[14] != 0.0) { msg = "Eigenvalues did not converge (SCF iteration " + std::to_string(step) + ")"; return TF_ELINALG; }
         {
             const double *hd = res + 2;
             comps[0] = hd[0] + hd[6]; comps[1] = hd[1] + hd[7]; comps[5] = hd[2] + hd[8];
@@ -1664,6 +1765,7 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             break;
         }
     }
+    w.eig_fail = nullptr;
     // orbitals and orbital energies of the last Fock matrices (what the reference's last diagonalisations leave, scf:1224-1225)
     for (int sp = 0; sp < 2 && out.n_iter > 0; ++sp) {
         if (!uo.eps[sp] && !uo.C[sp]) continue;

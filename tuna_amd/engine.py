@@ -236,9 +236,10 @@ class Engine:
     def eigh_stats(self):
         """Counters of the eigensolver paths of this engine's workspace (tunafock.h: tf_eigh_stats)."""
         import ctypes as C
-        out = (C.c_int64 * 5)()
+        out = (C.c_int64 * 6)()
         self._check(self._L.tf_eigh_stats(self._ctx, out))
-        return dict(zip(("refined_solves", "refinement_steps", "refinement_fallbacks", "blocked_solves", "blocked_declined"), (int(v) for v in out)))
+        return dict(zip(("refined_solves", "refinement_steps", "refinement_fallbacks", "blocked_solves", "blocked_declined", "jacobi_fallbacks"),
+                        (int(v) for v in out)))
 
     def jk_path_stats(self):
         """Fock builds of the native cycles over the class-diagonal task list / over the full list (tunafock.h: tf_jk_path_stats)."""
