@@ -127,3 +127,79 @@ def test_mp2_input_line(engine, mp2_golden):
     assert abs(out.energy - (float(g["E_SCF"]) + e_corr)) < 1e-8
     text = "\n".join(lines)
     assert "MP2 correlation energy:" in text and "Final single point energy:" in text
+
+
+def _mp2_numpy(E, C, eps, n_occ, n_frozen=0):
+    """(E_OS, E_SS) from the dense spherical tensor E (tuna_ci.py:204-255 restricted to (ia|jb), tuna_mp.py:882-890)"""
+    Co, Cv = C[:, n_frozen:n_occ], C[:, n_occ:]
+    g = np.einsum("mnls,mi,na,lj,sb->iajb", E, Co, Cv, Co, Cv, optimize=True)
+    eo, ev = eps[n_frozen:n_occ], eps[n_occ:]
+    D = eo[:, None, None, None] - ev[None, :, None, None] + eo[None, None, :, None] - ev[None, None, None, :]
+    return float(np.sum(g * g / D)), float(np.sum(g * (g - g.transpose(0, 3, 2, 1)) / D))
+
+
+@pytest.fixture(scope="module")
+def n2_tz_oracle(engine):
+    atoms, shells, aos, nocc = make_system("c2_n2_ccpvtz")
+    engine.set_basis(aos)
+    return aos, so.eri_to_spherical(engine.sph_matrix(), orc.eri(aos))
+
+
+@pytest.mark.parametrize("n_occ", [1, 16, 17, 20, 21, 32, 33, 40])
+def test_rmp2_occupied_widths_against_the_oracle_tensor(engine, n2_tz_oracle, n_occ):
+    """tf_mp2_rhf with 1 - 40 occupied orbitals on N2/cc-pVTZ (N = 60): one and two MFMA column tiles of the first quarter, the vector-ALU
+    columns (17, 20), the edge 32 | 33 where the energy moves to the expanded-block path, against NumPy on the oracle tensor; random
+    orthonormal orbitals, occupied and virtual energies separated by a gap."""
+    aos, E = n2_tz_oracle
+    engine.set_basis(aos).build_eri(True)
+    N = engine.N
+    rng = np.random.default_rng(60 + n_occ)
+    C = np.linalg.qr(rng.standard_normal((N, N)))[0]
+    eps = np.concatenate([np.sort(rng.uniform(-4.0, -0.6, n_occ)), np.sort(rng.uniform(0.3, 8.0, N - n_occ))])
+    r = engine.mp2_rhf(C, eps, n_occ)
+    e_os, e_ss = _mp2_numpy(E, C, eps, n_occ)
+    assert abs(r["E_OS"] - e_os) <= 1e-10 and abs(r["E_SS"] - e_ss) <= 1e-10, (r, e_os, e_ss)
+
+
+def test_rmp2_frozen_core_and_bad_arguments(engine, mp2_golden, n2_tz_oracle):
+    """Frozen core (n_frozen 1, 2, 6 of the 7 occupied orbitals of N2/cc-pVTZ, reference orbitals) against NumPy on the oracle tensor; the
+    arguments tf_mp2_rhf refuses (n_frozen < 0, n_frozen = n_occ, n_occ >= N) raise TF_EINVAL and leave the context usable."""
+    from tuna_amd._lib import TunaError
+    g = mp2_golden["c5_n2_ccpvtz"]
+    aos, E = n2_tz_oracle
+    engine.set_basis(aos).build_eri(True)
+    N = engine.N
+    C, eps = g["C"], g["eps"]
+    r0 = engine.mp2_rhf(C, eps, 7)
+    assert abs(r0["E_OS"] - float(g["E_OS"])) < 1e-10 and abs(r0["E_SS"] - float(g["E_SS"])) < 1e-10
+    for nf in (1, 2, 6):
+        r = engine.mp2_rhf(C, eps, 7, nf)
+        e_os, e_ss = _mp2_numpy(E, C, eps, 7, nf)
+        assert abs(r["E_OS"] - e_os) <= 1e-10 and abs(r["E_SS"] - e_ss) <= 1e-10, (nf, r, e_os, e_ss)
+        assert r["E_MP2"] > r0["E_MP2"]                                        # (freezing removes negative pair energies)
+    for n_occ, nf in ((7, -1), (7, 7), (8, 9), (N, 0), (N + 3, 1)):
+        with pytest.raises(TunaError) as ei:
+            engine.mp2_rhf(C, eps, n_occ, nf)
+        assert ei.value.code == -1, (n_occ, nf, ei.value.code)                # TF_EINVAL
+    r1 = engine.mp2_rhf(C, eps, 7)
+    assert r1["E_OS"] == r0["E_OS"] and r1["E_SS"] == r0["E_SS"]
+
+
+@pytest.mark.parametrize("layout", ["tiles", "rows"])
+def test_rmp2_energy_and_mo_integrals_on_other_layouts(engine, mp2_golden, layout):
+    """As test_rmp2_energy_and_mo_integrals (N2/cc-pVTZ against the reference goldens), on the tiles layout and on the rows layout of one
+    rank; the shared context gets the default layout back."""
+    g = mp2_golden["c5_n2_ccpvtz"]
+    atoms, shells, aos, nocc = _system("c5_n2_ccpvtz")
+    try:
+        engine.set_basis(aos).build_eri(True, layout=layout)
+        assert engine.eri_storage()["layout"] == layout
+        r = engine.mp2_rhf(g["C"], g["eps"], nocc)
+        MO = engine.ao_to_mo(g["C"])
+    finally:
+        engine._check(engine._L.tf_set_eri_layout(engine._ctx, -1))
+    assert abs(r["E_OS"] - float(g["E_OS"])) < 1e-10 and abs(r["E_SS"] - float(g["E_SS"])) < 1e-10
+    idx = g["mo_idx"]
+    assert np.abs(MO[idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]] - g["mo_val"]).max() < 1e-11
+    for perm in [(1, 0, 2, 3), (2, 3, 0, 1)]:
+        assert np.abs(MO - MO.transpose(perm)).max() < 1e-11

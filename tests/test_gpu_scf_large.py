@@ -13,6 +13,10 @@ pytestmark = pytest.mark.gpu
 
 # converged RHF energy of the synth-400 bench workload (core guess, TIGHT, dynamic damping) from the LAPACK loop
 E_SYNTH400 = -1053.630104643514
+# RMP2 correlation energy of the same workload (bench.py: scf_on_workload -> mp2_leg, "E_MP2_Eh") on the LAPACK-loop orbitals; the
+# tolerance is ten times the spread measured between the LAPACK-loop and the native orbitals (test_synth400_rhf_against_the_lapack_loop)
+E_MP2_SYNTH400 = -1.2716640569772766
+E_MP2_SYNTH400_TOL = 3e-10
 
 
 def _setup(eng, name):
@@ -103,6 +107,12 @@ def test_synth400_rhf_against_the_lapack_loop():
         assert dev["dE"] <= 5e-9 and dev["deps"] <= 1e-8 and dev["dP"] <= 1e-8, dev
         assert abs(r["n_iter"] - o["n_iter"]) <= 6, dev
         assert abs(o["energy"] - E_SYNTH400) <= 1e-9 and abs(r["energy"] - E_SYNTH400) <= 5e-9, (o["energy"], r["energy"])
+        # RMP2 on both orbital sets (tf_mp2_rhf: the bench's MP2 leg) against the pin; measured on MI355X: -1.2716640569773 (LAPACK loop),
+        # -1.2716640569466 (native), spread 3.1e-11; the bench line printed -1.271664056949
+        m_o, m_r = eng.mp2_rhf(o["C"], o["epsilons"], nocc)["E_MP2"], eng.mp2_rhf(r["C"], r["epsilons"], nocc)["E_MP2"]
+        print(f"\n[synth-400 RMP2] LAPACK-loop orbitals {m_o:.12f}, native {m_r:.12f}, spread {abs(m_o - m_r):.2e}, "
+              f"pin {E_MP2_SYNTH400:.12f}")
+        assert abs(m_o - E_MP2_SYNTH400) <= E_MP2_SYNTH400_TOL and abs(m_r - E_MP2_SYNTH400) <= E_MP2_SYNTH400_TOL, (m_o, m_r)
         Xl, sml, Sil = eng.orthogonaliser(S)
         _, _, Sio = so.orthogonaliser(S)
         kappa = 1.0 / smin * np.abs(np.linalg.eigvalsh(S)).max()
