@@ -138,21 +138,36 @@ def _rank_scf(rank, world, port, kind, tag, ret):
         from tuna_amd import distributed as tdist, molecule as mol
         from tuna_amd.engine import Engine, SCF_CONVERGENCE
         with Engine(0, rank, world) as eng:
-            if kind == "rhf":
-                atoms, shells, aos, nocc = make_system(tag)
+            if kind in ("rhf", "rks"):
+                if kind == "rks":                                    # Kohn-Sham: every rank evaluates the whole V_XC on the whole grid
+                    from conftest import DFT_SYSTEMS
+                    from tuna_amd import dft
+                    sym, R, basis, nocc, method, grid = DFT_SYSTEMS[tag]
+                    atoms = mol.make_atoms(sym, R)
+                    shells = mol.build_shells(atoms, basis)
+                    aos = mol.expand_cartesian_aos(shells)
+                else:
+                    atoms, shells, aos, nocc = make_system(tag)
                 eng.set_basis(aos).build_eri(True)
-                xyz, chg, org = atom_arrays(atoms)
+                hfx = 1.0
+                if kind == "rks":
+                    pts, wts, _ = dft.integration_grid(atoms, grid)
+                    hfx = eng.dft_setup(pts, wts, method)["hfx"]
+                xyz, chg = [a.origin for a in atoms], [float(a.charge) for a in atoms]
+                org = atom_arrays(atoms)[2] if kind == "rhf" else [0, 0, 0.0]
                 S, T, V, _, _ = eng.one_electron(xyz, chg, org, spherical=True)
                 X, _, _ = eng.orthogonaliser(S)
                 P0, E0 = so.core_guess(T, V, X, nocc)
                 ranges = [sum(s.n_sph for s in shells if s.atom == a) for a in range(len(atoms))]
                 try:
-                    eng.scf_rhf(S, T, V, P0, E0, nocc, mol.nuclear_repulsion(atoms), X=X, conv="extreme", damping="dynamic", n_atom_ao=ranges)
+                    eng.scf_rhf(S, T, V, P0, E0, nocc, mol.nuclear_repulsion(atoms), X=X, conv="extreme", damping="dynamic", n_atom_ao=ranges,
+                                hfx=hfx)
                     refused = False
                 except Exception as e:                               # no all-reduce registered yet: partial sums must not be used
                     refused = "tf_set_allreduce" in str(e)
                 tdist.attach_allreduce(eng)
-                r = eng.scf_rhf(S, T, V, P0, E0, nocc, mol.nuclear_repulsion(atoms), X=X, conv="extreme", damping="dynamic", n_atom_ao=ranges)
+                r = eng.scf_rhf(S, T, V, P0, E0, nocc, mol.nuclear_repulsion(atoms), X=X, conv="extreme", damping="dynamic", n_atom_ao=ranges,
+                                hfx=hfx)
                 ret[rank] = (refused, r["energy"], r["n_iter"], r["table"], r["epsilons"])
             else:
                 from tuna_amd import scf
@@ -167,8 +182,8 @@ def _rank_scf(rank, world, port, kind, tag, ret):
 
 
 @pytest.mark.parametrize("kind,tag,plan", [("rhf", "n2_ccpvdz", ""), ("rhf", "c4_co_def2tzvp", ""), ("uhf", "oh_doublet_ccpvdz", ""),
-                                           ("rhf", "c4_co_def2tzvp", "shells")])
-def test_native_scf_cycle_on_a_sharded_tensor(kind, tag, plan, golden, uhf_golden, monkeypatch):
+                                           ("rhf", "c4_co_def2tzvp", "shells"), ("rks", "c4_co_b3lyp_def2tzvp", "")])
+def test_native_scf_cycle_on_a_sharded_tensor(kind, tag, plan, golden, uhf_golden, dft_golden, monkeypatch):
     """The native cycles with the tensor split over two ranks: per iteration ONE all-reduce of the stacked [J;K], everything else on
     the device of each rank -- same trajectory as the reference run (golden) on every rank."""
     import torch.multiprocessing as mp
@@ -183,6 +198,9 @@ def test_native_scf_cycle_on_a_sharded_tensor(kind, tag, plan, golden, uhf_golde
     if kind == "rhf":
         g = golden(tag)
         ref_E, ref_table = float(g["scf_energy"]), g["scf_table"]
+    elif kind == "rks":
+        g = dft_golden[tag]
+        ref_E, ref_table = float(g["energy"]), g["table"]
     else:
         g = uhf_golden[tag]
         ref_E, ref_table = float(g["scf_energy_nodamp"]) - float(g["V_NN"]), g["scf_table_nodamp"]
@@ -193,7 +211,7 @@ def test_native_scf_cycle_on_a_sharded_tensor(kind, tag, plan, golden, uhf_golde
     assert abs(res[0][1] - res[1][1]) < 1e-10 and res[0][2] == res[1][2]
     np.testing.assert_allclose(res[0][3][:, 1], res[1][3][:, 1], atol=1e-9)          # both ranks walk the same trajectory
     n = min(res[0][2], len(ref_table))
-    if kind == "rhf":
+    if kind in ("rhf", "rks"):
         np.testing.assert_allclose(res[0][3][:n, 1], ref_table[:n, 1], atol=1e-8)
         np.testing.assert_allclose(res[0][3][:n, 6], ref_table[:n, 6], atol=1e-6)    # damping factors
 
