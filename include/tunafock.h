@@ -215,6 +215,13 @@ typedef struct {
 int tf_scf_uhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V,
                const double *Fext, const double *X, const double *P0_alpha, const double *P0_beta, double E0,
                int n_alpha, int n_beta, double V_NN, tf_scf_uhf_result *out);
+/* Unrestricted Kohn-Sham: the same cycle with V_XC^alpha, V_XC^beta of the iteration's input densities added to the Fock matrices
+ * (tuna_scf.py:1237-1260) and the grid's exchange / correlation energies in components[3] / [4].  Arguments as tf_scf_uhf.  Needs a
+ * grid set by tf_dft_setup (TF_EINVAL without one) and an unsharded tensor: world > 1 returns TF_EINVAL (no sharded test exists for
+ * this path yet).  tf_scf_uhf with a grid set keeps refusing. */
+int tf_scf_uks(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V,
+               const double *Fext, const double *X, const double *P0_alpha, const double *P0_beta, double E0,
+               int n_alpha, int n_beta, double V_NN, tf_scf_uhf_result *out);
 
 /* Several restricted cycles on the SAME tensor advanced in lockstep: what the reference's finite-field drivers run one after the other
  * (tuna_energy.py:315-540: 2, 8 or 12 energy evaluations that differ only in the field term F_fld, kernel:660-677).  Arguments as
@@ -243,6 +250,11 @@ int tf_dft_setup(tf_ctx *ctx, int64_t n_points, const double *xyz, const double 
 /* V_XC [N,N] = V_X*DFX + V_C*DFC for the closed-shell density P [N,N] (calculate_restricted_exchange_correlation_matrix,
  * tuna_scf.py:600-654), the grid integral of the density and the scaled exchange / correlation energies. */
 int tf_dft_vxc(tf_ctx *ctx, const double *P, double *Vxc, double *n_elec, double *e_x, double *e_c);
+/* Spin-resolved V_XC^alpha, V_XC^beta [N,N] for the densities P_alpha, P_beta [N,N] (calculate_unrestricted_exchange_correlation_matrix,
+ * tuna_scf.py:665-750), the grid integrals n_elec = {n_alpha, n_beta}, e_x = {E_X,alpha * DFX, E_X,beta * DFX} and e_c = E_C * DFC.
+ * Its buffers are allocated on the first call and released with the grid.  Output pointers n_elec, e_x, e_c may be NULL. */
+int tf_dft_vxc_unrestricted(tf_ctx *ctx, const double *P_alpha, const double *P_beta, double *Vxc_alpha, double *Vxc_beta,
+                            double n_elec[2], double e_x[2], double *e_c);
 /* Back to Hartree-Fock. */
 int tf_dft_clear(tf_ctx *ctx);
 

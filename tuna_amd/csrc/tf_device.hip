@@ -3445,6 +3445,33 @@ int tf_dft_vxc(tf_ctx *ctx, const double *P, double *Vxc, double *n_elec, double
     return TF_OK;
 }
 
+int tf_dft_vxc_unrestricted(tf_ctx *ctx, const double *P_alpha, const double *P_beta, double *Vxc_alpha, double *Vxc_beta, double n_elec[2],
+                            double e_x[2], double *e_c)
+{
+    if (!ctx) return TF_EINVAL;
+    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: call tf_dft_setup first");
+    if (!ctx->have_eri || ctx->grid.N != ctx->N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: the grid was set up for a different tensor (call tf_build_eri, then tf_dft_setup again)");
+    if (!P_alpha || !P_beta || !Vxc_alpha || !Vxc_beta) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    int rc = tfdft::ensure_spin(ctx->grid, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const size_t nn = (size_t)ctx->N * ctx->N;
+    double *io = ctx->grid.sio;                                  // P_alpha, P_beta, V_alpha, V_beta
+    HIPCHK(ctx, hipMemcpy(io, P_alpha, nn * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(io + nn, P_beta, nn * sizeof(double), hipMemcpyHostToDevice));
+    double o5[5];
+    rc = tfdft::vxc_unrestricted(ctx->scf.blas, ctx->grid, io, io + nn, io + 2 * nn, io + 3 * nn, o5, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    HIPCHK(ctx, hipMemcpy(Vxc_alpha, io + 2 * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(Vxc_beta, io + 3 * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_elec) { n_elec[0] = o5[0]; n_elec[1] = o5[1]; }
+    if (e_x) { e_x[0] = o5[2]; e_x[1] = o5[3]; }
+    if (e_c) *e_c = o5[4];
+    return TF_OK;
+}
+
 // ---- AO->MO transformation and RMP2 (next row of the hot path: consumers of the resident tensor) ----------------------
 
 static int mo_transform_device(tf_ctx *ctx, const double *C1, int n1, const double *C2, int n2, const double *C3, int n3, const double *C4,
@@ -3792,7 +3819,8 @@ int tf_scf_uhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uhf: call tf_build_eri first");
     if (!opts || !S || !T || !V || !P0_alpha || !P0_beta || !out || n_alpha < 1 || n_alpha > ctx->N || n_beta < 0 || n_beta > n_alpha)
         TF_FAIL(ctx, TF_EINVAL, "tf_scf_uhf: bad arguments");
-    if (ctx->grid.G > 0) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uhf: unrestricted Kohn-Sham is not implemented (call tf_dft_clear)");
+    if (ctx->grid.G > 0)
+        TF_FAIL(ctx, TF_EINVAL, "tf_scf_uhf: unrestricted Kohn-Sham is not implemented by the Hartree-Fock entry point (call tf_scf_uks, or tf_dft_clear)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string msg;
     auto jk2 = [&](const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st) {
@@ -3809,6 +3837,41 @@ int tf_scf_uhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     offer_symmetry(ctx, ctx->scf, ctx->N);
     int rc = tfscf::run_uhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, jk2, ctx->world,
                             out->common, uo, msg);
+    if (rc && !msg.empty()) ctx->err = msg;
+    return rc;
+}
+
+
+int tf_scf_uks(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V, const double *Fext,
+               const double *X, const double *P0_alpha, const double *P0_beta, double E0, int n_alpha, int n_beta, double V_NN,
+               tf_scf_uhf_result *out)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: call tf_build_eri first");
+    if (!opts || !S || !T || !V || !P0_alpha || !P0_beta || !out || n_alpha < 1 || n_alpha > ctx->N || n_beta < 0 || n_beta > n_alpha)
+        TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: bad arguments");
+    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: call tf_dft_setup first (unrestricted Hartree-Fock is tf_scf_uhf)");
+    if (ctx->grid.N != ctx->N) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: the DFT grid was set up for a different AO dimension");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: unrestricted Kohn-Sham runs on an unsharded tensor (world = 1) in this build");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    auto jk2 = [&](const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st) {
+        const double *p[2] = {dPa, dPb};
+        double *j[2] = {dJa, dJb}, *k[2] = {dKa, dKb};
+        ctx->jk_try_class_diagonal = true;
+        int rcj = launch_jk(ctx, 2, p, j, k, st);
+        ctx->jk_try_class_diagonal = false;
+        return rcj ? rcj : allreduce_jk(ctx, 2, j, k, st);
+    };
+    tfscf::XC2Fn xc = [&](const double *dPa, const double *dPb, double *dVa, double *dVb, double *o5) {
+        return tfdft::vxc_unrestricted(ctx->scf.blas, ctx->grid, dPa, dPb, dVa, dVb, o5, msg);
+    };
+    tfscf::UhfOut uo;
+    for (int sp = 0; sp < 2; ++sp) { uo.P[sp] = out->P_spin[sp]; uo.C[sp] = out->C_spin[sp]; uo.eps[sp] = out->eps_spin[sp]; uo.F[sp] = out->F_spin[sp]; }
+    ShardedCycleGuard guard(ctx);
+    offer_symmetry(ctx, ctx->scf, ctx->N);
+    int rc = tfscf::run_uhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, jk2, ctx->world,
+                            out->common, uo, msg, xc);
     if (rc && !msg.empty()) ctx->err = msg;
     return rc;
 }

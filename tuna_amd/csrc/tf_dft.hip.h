@@ -31,11 +31,16 @@ struct Grid {
     double *B = nullptr, *D = nullptr;                           // [G][N]
     double *rho = nullptr, *grad = nullptr, *vrho = nullptr, *vsig = nullptr, *ex = nullptr, *ec = nullptr;   // [G], [3][G], ...
     double *V = nullptr, *part = nullptr;                        // [VSPLIT + 1][N][N] split-K partials of V, reduction partials
+    // unrestricted path (vxc_unrestricted), allocated on its first use: both spins side by side in every row
+    double *sP = nullptr, *sB = nullptr, *sD = nullptr;          // [N][2N] packed P_alpha|P_beta rows, [G][2N], [G][2N]
+    double *spt = nullptr, *sV = nullptr, *spart = nullptr;      // [SPT][G] per-point data, [VSPLIT + 2][N][2N], [5][NPART]
+    double *sio = nullptr;                                       // [4][N][N] host <-> device staging of tf_dft_vxc_unrestricted
 };
 
 inline void release(Grid &g)
 {
-    for (double *p : {g.w, g.phi, g.dphi, g.B, g.D, g.rho, g.grad, g.vrho, g.vsig, g.ex, g.ec, g.V, g.part})
+    for (double *p : {g.w, g.phi, g.dphi, g.B, g.D, g.rho, g.grad, g.vrho, g.vsig, g.ex, g.ec, g.V, g.part, g.sP, g.sB, g.sD, g.spt, g.sV,
+                      g.spart, g.sio})
         if (p) (void)hipFree(p);
     g = Grid();
 }
@@ -324,5 +329,352 @@ inline int vxc(rocblas_handle blas, Grid &g, const double *dP, double *dVxc, dou
     out3[1] *= g.dfx; out3[2] *= g.dfc;
     return TF_OK;
 }
+
+// ---- unrestricted (spin-polarised) path: calculate_unrestricted_exchange_correlation_matrix, tuna_scf.py:665-750 --------------------
+// Exchange of spin s is the closed-shell functional at (2 rho_s, 4 sigma_ss), integrated against rho_s (tuna_scf.py:467-468, :719-741);
+// correlation is the spin-polarised functional of (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb).  Per point and spin the D row is
+//     D_s = w (v_rho_s Phi + c_s . grad Phi),   c_s = 4 (2 DFX dfds_X,s + DFC v_sigma_ss) grad rho_s + 2 DFC v_sigma_ab grad rho_s'
+// (calculate_V_X / calculate_V_C, tuna_dft.py:788-888).  Both spins share every pass over Phi and grad Phi: the density kernel reads
+// them once for both B rows, the D kernel reads them once and writes both D rows; the two GEMMs run on 2N-wide operands.
+// Floors as the reference: rho_s >= 1e-23 each, sigma_ss >= 1e-46, sigma_ab not floored, zeta clipped to [-1, 1] (tuna_dft.py:677-744,
+// tuna_xc.py:31-125).
+
+struct XcSpin { double va, vb, vaa, vbb, vab, e; };            // df/drho_a, df/drho_b, df/dsigma_aa, _bb, _ab; energy per particle
+
+__device__ inline void vwn_pot(double n, double x_0, double b, double c, double A, double &e, double &dedr)   // tuna_xc.py:1802-1860
+{
+    const double Q = sqrt(4.0 * c - b * b);
+    const double X_0 = x_0 * x_0 + b * x_0 + c;
+    const double c_1 = -b * x_0 / X_0;
+    const double c_2 = 2.0 * b * (c - x_0 * x_0) / (Q * X_0);
+    const double r_s = cbrt(3.0 / (4.0 * 3.141592653589793) * (1.0 / n));
+    const double x = sqrt(r_s);
+    const double xm = x - x_0;
+    const double Xx = r_s + b * x + c;
+    const double combo = (2.0 / x + 2.0 * c_1 / xm - (2.0 * x + b) * (1.0 + c_1) / Xx - (1.0 / 2.0) * c_2 * Q / Xx);
+    e = A * (log(r_s / Xx) + c_1 * log(xm * xm / Xx) + c_2 * atan(Q / (2.0 * x + b)));
+    dedr = (A / 2.0) * combo / x;
+}
+
+__device__ inline double spin_f(double z)                       // tuna_xc.py:126-178
+{
+    const double p = cbrt(1.0 + z), m = cbrt(1.0 - z), t = cbrt(2.0);
+    return (p * p * p * p + m * m * m * m - 2.0) / (t * t * t * t - 2.0);
+}
+__device__ inline double spin_fp(double z)
+{
+    const double t = cbrt(2.0);
+    return (cbrt(1.0 + z) - cbrt(1.0 - z)) / (t * t * t * t - 2.0) * 4.0 / 3.0;
+}
+
+__device__ inline XcSpin vwn3_spin(double na, double nb, double n)                 // tuna_xc.py:1542-1600
+{
+    double e0, d0, e1, d1;
+    vwn_pot(n, -0.409286, 13.0720, 42.7198, 0.0310907, e0, d0);
+    vwn_pot(n, -0.743294, 20.1231, 101.578, 0.01554535, e1, d1);
+    const double z = fmin(fmax((na - nb) / (na + nb), -1.0), 1.0);
+    const double f = spin_f(z), fp = spin_fp(z);
+    const double r_s = cbrt(3.0 / (4.0 * 3.141592653589793) * (1.0 / n));
+    XcSpin o{0, 0, 0, 0, 0, 0};
+    o.e = e0 + (e1 - e0) * f;
+    const double dedr = d0 + (d1 - d0) * f, dedz = (e1 - e0) * fp;
+    o.va = o.e - r_s / 3.0 * dedr - (z - 1.0) * dedz;
+    o.vb = o.e - r_s / 3.0 * dedr - (z + 1.0) * dedz;
+    return o;
+}
+
+__device__ inline XcSpin vwn5_spin(double na, double nb, double n)                 // tuna_xc.py:1631-1669, :1870-1935
+{
+    double e0, d0, e1, d1, ma, dma;
+    vwn_pot(n, -0.10498, 3.72744, 12.9352, 0.0310907, e0, d0);
+    vwn_pot(n, -0.32500, 7.06042, 18.0578, 0.01554535, e1, d1);
+    vwn_pot(n, -0.0047584, 1.13107, 13.0045, 1.0 / (6.0 * 3.141592653589793 * 3.141592653589793), ma, dma);
+    const double alpha = -ma, dalpha_dr = -dma;
+    const double z = fmin(fmax((na - nb) / (na + nb), -1.0), 1.0);
+    const double z4 = z * z * z * z;
+    const double f = spin_f(z), fp = spin_fp(z);
+    const double t = cbrt(2.0), fpp0 = 8.0 / (9.0 * (t * t * t * t - 2.0));
+    XcSpin o{0, 0, 0, 0, 0, 0};
+    o.e = e0 + alpha * f / fpp0 * (1.0 - z4) + (e1 - e0) * f * z4;
+    const double r_s = cbrt(3.0 / (4.0 * 3.141592653589793) * (1.0 / n));
+    const double dedr = d0 * (1.0 - f * z4) + d1 * f * z4 + dalpha_dr * f * (1.0 - z4) / fpp0;
+    const double dedz = 4.0 * z * z * z * f * (e1 - e0 - alpha / fpp0) + fp * (z4 * (e1 - e0) + (1.0 - z4) * alpha / fpp0);
+    o.va = o.e - r_s / 3.0 * dedr - (z - 1.0) * dedz;
+    o.vb = o.e - r_s / 3.0 * dedr - (z + 1.0) * dedz;
+    return o;
+}
+
+__device__ inline XcSpin lyp_spin(double na, double nb, double n, double saa, double sbb, double sab)   // tuna_xc.py:2271-2370
+{
+    const double a = 0.04918, b = 0.132, c = 0.2533, d = 0.349;
+    const double PI = 3.141592653589793;
+    const double ca = cbrt(na), cb = cbrt(nb);
+    const double inv_n = 1.0 / n;
+    const double cn = cbrt(n), icn = 1.0 / cn;
+    const double X = 1.0 + d * icn;
+    const double t = cbrt(2.0), k = cbrt(3.0 * PI * PI);
+    const double t2 = t * t, t4 = t2 * t2, t8 = t4 * t4;
+    const double C = t8 * t2 * t * 3.0 / 10.0 * (k * k);
+    const double prod = na * nb;
+    const double ca2 = ca * ca, ca4 = ca2 * ca2, ca8 = ca4 * ca4, cb2 = cb * cb, cb4 = cb2 * cb2, cb8 = cb4 * cb4;
+    const double psum = ca8 + cb8;
+    const double icn2 = icn * icn, icn4 = icn2 * icn2, icn8 = icn4 * icn4;
+    const double w = icn8 * icn2 * icn * exp(-c * icn) / X;
+    const double delta = icn * (c + d / X);
+    const double mabw = -a * b * w;
+    const double w_prime = -(1.0 / 3.0) * icn4 * w * (11.0 * cn - c - d / X);
+    const double delta_prime = (1.0 / 3.0) * (d * d * icn4 * icn / (X * X) - delta * inv_n);
+    const double wpw = -(1.0 / 3.0) * icn4 * (11.0 * cn - c - d / X);
+    XcSpin o;
+    o.vaa = mabw * ((1.0 / 9.0) * prod * (1.0 - 3.0 * delta - (delta - 11.0) * na * inv_n) - nb * nb);
+    o.vbb = mabw * ((1.0 / 9.0) * prod * (1.0 - 3.0 * delta - (delta - 11.0) * nb * inv_n) - na * na);
+    o.vab = mabw * ((1.0 / 9.0) * prod * (47.0 - 7.0 * delta) - (4.0 / 3.0) * n * n);
+    o.e = inv_n * (prod * (C * mabw * psum - 4.0 * a / X * inv_n) + o.vaa * saa + o.vbb * sbb + o.vab * sab);
+    const double d_a_aa = wpw * o.vaa + mabw * ((1.0 / 9.0) * nb * (1.0 - 3.0 * delta - (delta - 11.0) * na * inv_n) -
+                                                (1.0 / 9.0) * prod * (delta_prime * (3.0 + na * inv_n) + (delta - 11.0) * nb * inv_n * inv_n));
+    const double d_b_bb = wpw * o.vbb + mabw * ((1.0 / 9.0) * na * (1.0 - 3.0 * delta - (delta - 11.0) * nb * inv_n) -
+                                                (1.0 / 9.0) * prod * (delta_prime * (3.0 + nb * inv_n) + (delta - 11.0) * na * inv_n * inv_n));
+    const double d_a_ab = wpw * o.vab + mabw * ((1.0 / 9.0) * nb * (47.0 - 7.0 * delta) - (7.0 / 9.0) * prod * delta_prime - (8.0 / 3.0) * n);
+    const double d_b_ab = wpw * o.vab + mabw * ((1.0 / 9.0) * na * (47.0 - 7.0 * delta) - (7.0 / 9.0) * prod * delta_prime - (8.0 / 3.0) * n);
+    const double d_a_bb = wpw * o.vbb + mabw * ((1.0 / 9.0) * nb * (1.0 - 3.0 * delta - (delta - 11.0) * nb * inv_n) -
+                                                (1.0 / 9.0) * prod * ((3.0 + nb * inv_n) * delta_prime - (delta - 11.0) * nb * inv_n * inv_n) - 2.0 * na);
+    const double d_b_aa = wpw * o.vaa + mabw * ((1.0 / 9.0) * na * (1.0 - 3.0 * delta - (delta - 11.0) * na * inv_n) -
+                                                (1.0 / 9.0) * prod * ((3.0 + na * inv_n) * delta_prime - (delta - 11.0) * na * inv_n * inv_n) - 2.0 * nb);
+    o.va = -4.0 * a / X * prod * inv_n * ((1.0 / 3.0) * d * icn4 / X + 1.0 / na - inv_n) -
+           C * a * b * (w_prime * prod * psum + w * nb * (11.0 / 3.0 * ca8 + cb8)) + d_a_aa * saa + d_a_bb * sbb + d_a_ab * sab;
+    o.vb = -4.0 * a / X * prod * inv_n * ((1.0 / 3.0) * d * icn4 / X + 1.0 / nb - inv_n) -
+           C * a * b * (w_prime * prod * psum + w * na * (11.0 / 3.0 * cb8 + ca8)) + d_b_bb * sbb + d_b_aa * saa + d_b_ab * sab;
+    return o;
+}
+
+// per-point rows of Grid::spt ([SPT][G]): 0-1 rho_a, rho_b (raw, then floored); 2-4, 5-7 grad rho_a, grad rho_b; 8-9 v_rho_a, v_rho_b;
+// 10-12, 13-15 c_a, c_b; 16-18 e_X,a rho_a, e_X,b rho_b, e_C rho
+const int SPT = 19;
+
+// rho_s and grad rho_s of both spins from B2 = Phi [P_a | P_b]: sixteen lanes per grid point as xc_density_kernel, every Phi / grad Phi
+// element read once for both spins
+__global__ __launch_bounds__(256) void xc_density2_kernel(long long G, int N, const double *__restrict__ phi, const double *__restrict__ dphi,
+                                                          const double *__restrict__ B2, int gga, double *__restrict__ pt)
+{
+    const int grp = threadIdx.x >> 4, l = threadIdx.x & 15;
+    const long long g = (long long)blockIdx.x * 16 + grp;
+    double na = 0.0, nb = 0.0, ax = 0.0, ay = 0.0, az = 0.0, bx = 0.0, by = 0.0, bz = 0.0;
+    if (g < G) {
+        const double *ba = B2 + g * 2 * N, *bb = ba + N, *f = phi + g * N;
+        if (gga) {
+            const double *fx = dphi + g * N, *fy = dphi + G * N + g * N, *fz = dphi + 2 * G * N + g * N;
+            for (int i = l; i < N; i += 16) {
+                const double p = ba[i], q = bb[i], x = fx[i], y = fy[i], z = fz[i], v = f[i];
+                na += p * v; nb += q * v;
+                ax += p * x; ay += p * y; az += p * z;
+                bx += q * x; by += q * y; bz += q * z;
+            }
+        } else {
+            for (int i = l; i < N; i += 16) { const double v = f[i]; na += ba[i] * v; nb += bb[i] * v; }
+        }
+    }
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) {
+        na += __shfl_xor(na, d, 16); nb += __shfl_xor(nb, d, 16);
+        ax += __shfl_xor(ax, d, 16); ay += __shfl_xor(ay, d, 16); az += __shfl_xor(az, d, 16);
+        bx += __shfl_xor(bx, d, 16); by += __shfl_xor(by, d, 16); bz += __shfl_xor(bz, d, 16);
+    }
+    if (l == 0 && g < G) {
+        pt[g] = na; pt[G + g] = nb;
+        if (gga) {
+            pt[2 * G + g] = 2.0 * ax; pt[3 * G + g] = 2.0 * ay; pt[4 * G + g] = 2.0 * az;
+            pt[5 * G + g] = 2.0 * bx; pt[6 * G + g] = 2.0 * by; pt[7 * G + g] = 2.0 * bz;
+        }
+    }
+}
+
+__device__ inline XcOut exchange_of(int xid, double n, double sigma, double x_alpha)
+{
+    XcOut X{0, 0, 0};
+    if (xid == X_SLATER) X = slater_x(n, x_alpha);
+    else if (xid == X_B88) X = b88_x(n, sigma, x_alpha);
+    else if (xid == X_B3) {                                                 // 0.9 B88 + 0.1 Slater, tuna_xc.py:1462-1494
+        const XcOut s = slater_x(n, x_alpha), bb = b88_x(n, sigma, x_alpha);
+        X.dfdn = 0.9 * bb.dfdn + 0.1 * s.dfdn; X.dfds = 0.9 * bb.dfds; X.e = 0.9 * bb.e + 0.1 * s.e;
+    }
+    return X;
+}
+
+__device__ inline XcSpin correlation_of(int cid, double na, double nb, double n, double saa, double sbb, double sab)
+{
+    XcSpin C{0, 0, 0, 0, 0, 0};
+    if (cid == C_VWN5) C = vwn5_spin(na, nb, n);
+    else if (cid == C_VWN3) C = vwn3_spin(na, nb, n);
+    else if (cid == C_LYP) C = lyp_spin(na, nb, n, saa, sbb, sab);
+    else if (cid == C_3P_VWN5 || cid == C_3P_VWN3) {                        // 0.81 LYP + 0.19 VWN, tuna_xc.py:5893-5950
+        const XcSpin l = (cid == C_3P_VWN5) ? vwn5_spin(na, nb, n) : vwn3_spin(na, nb, n);
+        const XcSpin y = lyp_spin(na, nb, n, saa, sbb, sab);
+        C.va = 0.81 * y.va + 0.19 * l.va; C.vb = 0.81 * y.vb + 0.19 * l.vb;
+        C.vaa = 0.81 * y.vaa; C.vbb = 0.81 * y.vbb; C.vab = 0.81 * y.vab;
+        C.e = 0.81 * y.e + 0.19 * l.e;
+    }
+    return C;
+}
+
+__global__ void xc_point2_kernel(long long G, int gga, int xid, int cid, double dfx, double dfc, double x_alpha, double *__restrict__ pt)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const double na = fmax(pt[g], 1e-23), nb = fmax(pt[G + g], 1e-23);
+    const double n = na + nb;
+    double ga[3] = {0.0, 0.0, 0.0}, gb[3] = {0.0, 0.0, 0.0};
+    if (gga)
+        for (int a = 0; a < 3; ++a) { ga[a] = pt[(2 + a) * G + g]; gb[a] = pt[(5 + a) * G + g]; }
+    const double saa = fmax(ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], 1e-46);
+    const double sbb = fmax(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 1e-46);
+    const double sab = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+    const XcOut Xa = exchange_of(xid, 2.0 * na, 4.0 * saa, x_alpha), Xb = exchange_of(xid, 2.0 * nb, 4.0 * sbb, x_alpha);
+    const XcSpin C = correlation_of(cid, na, nb, n, saa, sbb, sab);
+    pt[g] = na; pt[G + g] = nb;
+    pt[8 * G + g] = dfx * Xa.dfdn + dfc * C.va;
+    pt[9 * G + g] = dfx * Xb.dfdn + dfc * C.vb;
+    if (gga) {
+        const double ka = 4.0 * (dfx * 2.0 * Xa.dfds + dfc * C.vaa), kb = 4.0 * (dfx * 2.0 * Xb.dfds + dfc * C.vbb), kab = 2.0 * dfc * C.vab;
+        for (int a = 0; a < 3; ++a) {
+            pt[(10 + a) * G + g] = ka * ga[a] + kab * gb[a];
+            pt[(13 + a) * G + g] = kb * gb[a] + kab * ga[a];
+        }
+    }
+    pt[16 * G + g] = Xa.e * na;
+    pt[17 * G + g] = Xb.e * nb;
+    pt[18 * G + g] = C.e * n;
+}
+
+// D2[g][s N + i] = w (v_rho_s phi + c_s . grad phi): one element of Phi (and of grad Phi) per thread, both spins written
+__global__ void xc_dmat2_kernel(long long G, int N, const double *__restrict__ w, const double *__restrict__ phi, const double *__restrict__ dphi,
+                                const double *__restrict__ pt, int gga, double *__restrict__ D2)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G * N) return;
+    const long long g = e / N;
+    const long long i = e - g * N;
+    const double f = phi[e];
+    double va = pt[8 * G + g] * f, vb = pt[9 * G + g] * f;
+    if (gga) {
+        const double x = dphi[e], y = dphi[G * N + e], z = dphi[2 * G * N + e];
+        va += pt[10 * G + g] * x + pt[11 * G + g] * y + pt[12 * G + g] * z;
+        vb += pt[13 * G + g] * x + pt[14 * G + g] * y + pt[15 * G + g] * z;
+    }
+    const double wg = w[g];
+    D2[g * 2 * N + i] = wg * va;
+    D2[g * 2 * N + N + i] = wg * vb;
+}
+
+// partial sums of w rho_a, w rho_b, w e_X,a rho_a, w e_X,b rho_b, w e_C rho
+__global__ __launch_bounds__(256) void xc_reduce5_kernel(long long G, const double *__restrict__ w, const double *__restrict__ pt,
+                                                         double *__restrict__ part)
+{
+    __shared__ double sm[5][256];
+    const int rows[5] = {0, 1, 16, 17, 18};
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (long long)gridDim.x * blockDim.x) {
+        const double wg = w[g];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) acc[q] += wg * pt[rows[q] * G + g];
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) sm[q][threadIdx.x] = acc[q];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s)
+            for (int q = 0; q < 5; ++q) sm[q][threadIdx.x] += sm[q][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 5) part[5 * blockIdx.x + threadIdx.x] = sm[threadIdx.x][0];
+}
+
+// P2[k][s N + i] = P_s[k][i]: the two densities as one N x 2N operand
+__global__ void pack2_kernel(const double *__restrict__ Pa, const double *__restrict__ Pb, double *__restrict__ P2, int N)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 2LL * N * N) return;
+    const long long k = e / (2 * N);
+    const long long r = e - k * 2 * N;
+    P2[e] = r < N ? Pa[k * N + r] : Pb[k * N + (r - N)];
+}
+
+// out_s = sym(V_s) from the summed [N][2N] product (row j holds (Phi^T D_s)[:, j] of both spins)
+__global__ void sym2_kernel(const double *__restrict__ tmp, double *__restrict__ Va, double *__restrict__ Vb, int N)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long nn = (long long)N * N;
+    if (e >= 2 * nn) return;
+    const int s = (int)(e / nn);
+    const long long q = e - s * nn;
+    const long long r = q / N, c = q - r * N;
+    (s ? Vb : Va)[q] = (1.0 / 2.0) * (tmp[r * 2 * N + s * N + c] + tmp[c * 2 * N + s * N + r]);
+}
+
+inline int ensure_spin(Grid &g, std::string &msg)
+{
+    if (g.sB) return TF_OK;
+    const size_t G = (size_t)g.G, N = (size_t)g.N, nn = N * N;
+    const size_t sizes[7] = {2 * nn, G * 2 * N, G * 2 * N, (size_t)SPT * G, (size_t)(VSPLIT + 2) * 2 * nn, (size_t)5 * NPART, 4 * nn};
+    double **ptrs[7] = {&g.sP, &g.sB, &g.sD, &g.spt, &g.sV, &g.spart, &g.sio};
+    for (int k = 0; k < 7; ++k) {
+        const hipError_t e = ::hipMalloc((void **)ptrs[k], sizes[k] * sizeof(double));
+        if (e != hipSuccess) {
+            for (int q = 0; q < 7; ++q) if (*ptrs[q]) { (void)hipFree(*ptrs[q]); *ptrs[q] = nullptr; }
+            msg = std::string("unrestricted V_XC buffers: hipMalloc failed: ") + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? TF_ENOMEM : TF_ENODEVICE;
+        }
+    }
+    if (!g.gga) TFD_HIP(hipMemset(g.spt, 0, (size_t)SPT * G * sizeof(double)));   // (LDA: the gradient rows stay zero)
+    return TF_OK;
+}
+
+// V_XC^alpha, V_XC^beta (device, [N][N]) and {n_alpha, n_beta, E_X,alpha*DFX, E_X,beta*DFX, E_C*DFC} for the device densities dPa, dPb
+inline int vxc_unrestricted(rocblas_handle blas, Grid &g, const double *dPa, const double *dPb, double *dVa, double *dVb, double out5[5],
+                            std::string &msg)
+{
+    int rc = ensure_spin(g, msg);
+    if (rc) return rc;
+    const int N = g.N, N2 = 2 * g.N;
+    const long long G = g.G;
+    const size_t nn = (size_t)N * N;
+    const double one = 1.0, zero = 0.0;
+    hipLaunchKernelGGL(pack2_kernel, dim3((unsigned)((2 * nn + 255) / 256)), dim3(256), 0, 0, dPa, dPb, g.sP, N);
+    // B2 (G x 2N, row-major) = Phi (G x N) * [P_a | P_b] (N x 2N)
+    TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none, N2, (rocblas_int)G, N, &one, g.sP, N2, g.phi, N, &zero, g.sB, N2));
+    hipLaunchKernelGGL(xc_density2_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.sB, g.gga ? 1 : 0, g.spt);
+    hipLaunchKernelGGL(xc_point2_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.gga ? 1 : 0, g.xid, g.cid, g.dfx, g.dfc,
+                       g.x_alpha, g.spt);
+    hipLaunchKernelGGL(xc_dmat2_kernel, dim3((unsigned)((G * N + 255) / 256)), dim3(256), 0, 0, G, N, g.w, g.phi, g.dphi, g.spt,
+                       g.gga ? 1 : 0, g.sD);
+    // [N][2N] = (Phi^T D2)^T, split over the grid points as in vxc
+    {
+        const long long Kc = G / VSPLIT, rem = G - Kc * VSPLIT;
+        const size_t n2 = 2 * nn;
+        int nparts = 0;
+        if (Kc > 0) {
+            TFD_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, N2, N, (rocblas_int)Kc, &one, g.sD, N2,
+                                                   (rocblas_stride)(Kc * N2), g.phi, N, (rocblas_stride)(Kc * N), &zero, g.sV, N2, (rocblas_stride)n2,
+                                                   VSPLIT));
+            nparts = VSPLIT;
+        }
+        if (rem > 0) {
+            TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_transpose, N2, N, (rocblas_int)rem, &one, g.sD + Kc * VSPLIT * N2,
+                                   N2, g.phi + Kc * VSPLIT * N, N, &zero, g.sV + (size_t)nparts * n2, N2));
+            ++nparts;
+        }
+        double *tmp = g.sV + (size_t)(VSPLIT + 1) * n2;
+        hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, g.sV, nparts, tmp, (int)n2);
+        hipLaunchKernelGGL(sym2_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, tmp, dVa, dVb, N);
+    }
+    hipLaunchKernelGGL(xc_reduce5_kernel, dim3(NPART), dim3(256), 0, 0, G, g.w, g.spt, g.spart);
+    std::vector<double> h(5 * NPART);
+    TFD_HIP(hipMemcpy(h.data(), g.spart, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int q = 0; q < 5; ++q) out5[q] = 0.0;
+    for (int b = 0; b < NPART; ++b)
+        for (int q = 0; q < 5; ++q) out5[q] += h[5 * b + q];
+    out5[2] *= g.dfx; out5[3] *= g.dfx; out5[4] *= g.dfc;
+    return TF_OK;
+}
+
 
 }  // namespace tfdft

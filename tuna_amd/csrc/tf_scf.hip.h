@@ -1489,15 +1489,18 @@ using JK2Fn = std::function<int(const double *, const double *, double *, double
 struct UhfOut {
     double *P[2], *C[2], *eps[2], *F[2];                        // host buffers, each may be nullptr
 };
+// unrestricted Kohn-Sham hook: V_XC^alpha, V_XC^beta (device [N,N]) and {n_alpha, n_beta, E_X,alpha, E_X,beta, E_C} for the device
+// densities (tfdft::vxc_unrestricted); empty for Hartree-Fock
+using XC2Fn = std::function<int(const double *, const double *, double *, double *, double *)>;
 
 inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, const double *T, const double *V, const double *Fext,
                    const double *X, const double *Pa0, const double *Pb0, double E0, int n_alpha, int n_beta, double V_NN, const JK2Fn &jk2,
-                   int world, tf_scf_result &out, const UhfOut &uo, std::string &msg)
+                   int world, tf_scf_result &out, const UhfOut &uo, std::string &msg, const XC2Fn &xc = XC2Fn())
 {
     (void)world;                                                    // (sharded tensors: see run_rhf)
     if (o.max_diis > TF_MAX_DIIS) { msg = "tf_scf_uhf: at most 64 DIIS matrices are held by the native cycle"; return TF_EINVAL; }
     const int max_diis = std::max(1, (int)o.max_diis);
-    const int n_fixed = 30;
+    const int n_fixed = xc ? 32 : 30;                               // (Kohn-Sham: V_XC^alpha, V_XC^beta in mat(30), mat(31))
     const int n_mats = n_fixed + 4 * max_diis;
     int rc = ensure(w, n, n_mats, msg);
     if (rc) return rc;
@@ -1512,6 +1515,7 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     double *dP[2] = {mat(13), mat(14)}, *dPold[2] = {mat(15), mat(16)}, *dPn[2] = {mat(17), mat(18)}, *dF[2] = {mat(19), mat(20)};
     double *dJ[2] = {mat(21), mat(22)}, *dK[2] = {mat(23), mat(24)}, *dCsave[2] = {mat(25), mat(26)};
     double *dJt = mat(27);                                       // J_alpha + J_beta; mat(28), mat(29): orthogonaliser scratch
+    double *dVxc[2] = {xc ? mat(30) : nullptr, xc ? mat(31) : nullptr};
     double *hist = mat(n_fixed);
     double *vals = base + (size_t)n_mats * nn, *ework = vals + n, *vals_save[2] = {ework + n, ework + 2 * (size_t)n};
     std::vector<int> slot(max_diis);                             // logical history entry -> physical slot (see run_rhf)
@@ -1624,7 +1628,13 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         E_old = E;
         TFS_HIP(hipMemcpyAsync(dPtold, dPt, nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
         for (int sp = 0; sp < 2; ++sp) TFS_HIP(hipMemcpyAsync(dPold[sp], dP[sp], nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
-        // Fock matrices (scf:542-589): F_s = H + J_alpha + J_beta - HFX K_s, symmetrised
+        // Kohn-Sham: exchange-correlation matrices and energies from the iteration's input densities (scf:1237-1240)
+        double xc5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (xc) {
+            rc = xc(dP[0], dP[1], dVxc[0], dVxc[1], xc5);
+            if (rc) { msg = "exchange-correlation evaluation failed"; return rc; }
+        }
+        // Fock matrices (scf:542-589): F_s = H + J_alpha + J_beta - HFX K_s (+ V_XC^s), symmetrised
         const int tf = span_begin(0);
         rc = jk2(dP[0], dP[1], dJ[0], dJ[1], dK[0], dK[1], TFS_ST);
         if (rc) { msg.clear(); return rc; }
@@ -1638,6 +1648,7 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         }
         for (int sp = 0; sp < 2; ++sp) {
             hipLaunchKernelGGL(k_fock, dim3(g), dim3(256), 0, TFS_ST, dH, dJt, dK[sp], 2.0 * o.hfx, t1, (int)nn);   // k_fock: H + J - hfx/2 K
+            if (xc) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, t1, 1.0, dVxc[sp], t1, (int)nn);
             hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, dF[sp], n);
             // e_s = X^T (F_s P_s S - S P_s F_s) X   (scf:906-920)
             TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, dF[sp], dP[sp], 0.0, t1));
@@ -1745,6 +1756,7 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             comps[2] = (1.0 / 2.0) * (hd[3] + hd[9]);                                        // scf:462
             comps[3] = -(1.0 / 2.0) * hd[4] * o.hfx + -(1.0 / 2.0) * hd[10] * o.hfx;         // scf:465-466
             comps[4] = 0.0; comps[6] = 0.0;
+            if (xc) { comps[3] += xc5[2] + xc5[3]; comps[4] = xc5[4]; }                       // scf:467-472
             E = comps[0] + comps[1] + comps[2] + comps[3] + comps[4] + comps[5] + comps[6];
         }
         const double dE = E - E_old, maxDP = res[0], rmsDP = std::sqrt(res[1] / (double)nn);

@@ -4,7 +4,8 @@
     out = run("SPE : N N 1.0977 : HF CC-PVTZ : EXTREME NODAMP")
 
 Input line format `TYPE : A B R : METHOD BASIS : KEYWORDS` (tuna.py:87-99).  Supported here: TYPE = SPE, METHOD = HF
-(restricted) or UHF / any multiplicity via ML (unrestricted), the basis sets shipped in tuna_amd/data, and the SCF keywords of SURVEY.md section 5
+(restricted) or UHF / any multiplicity via ML (unrestricted), a functional of tuna_amd.dft.FUNCTIONALS (restricted Kohn-Sham; unrestricted
+with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tuna_amd/data, and the SCF keywords of SURVEY.md section 5
 (LOOSE/MEDIUM/TIGHT/EXTREME, MAXITER n, DIIS [n]/NODIIS, DAMP x/NODAMP/MAXDAMP x, SLOWCONV/VERYSLOWCONV, HFX x,
 CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
@@ -205,8 +206,6 @@ def build_molecule_and_integrals(symbols, R_bohr, calc: Calculation, engine: Eng
     integrals = Integrals(S, T, V, D, Q, DeviceERI(engine, fock))
     if calc.functional is not None:                         # Kohn-Sham: grid + AOs on the grid (tuna_dft.py:94-208)
         from . import dft as dft_mod
-        if calc.reference == "UHF":
-            raise TunaError("unrestricted Kohn-Sham is not on the GPU path in this build")
         t0 = time.perf_counter()
         pts, wts, ginfo = dft_mod.integration_grid(atoms, calc.grid_conv)
         f = engine.dft_setup(pts, wts, calc.functional, calc.X_alpha)
@@ -259,7 +258,10 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
         timings["Self-consistent field"] = time.perf_counter() - t0
         out.timings.update(timings)
         if not silent:
-            if calc.functional is not None:
+            if calc.functional is not None and calc.reference == "UHF":
+                space = " " * max(0, 8 - len(calc.functional))
+                log(f"\n Unrestricted {calc.functional} energy: {space}    " + f"{out.energy:16.10f}")   # kernel:856-858
+            elif calc.functional is not None:
                 space = " " * max(0, 8 - len(calc.functional))
                 log(f"\n Restricted {calc.functional} energy: {space}      " + f"{out.energy:16.10f}")     # kernel:854
             else:
@@ -311,10 +313,21 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
     if ctype != "SPE":
         raise TunaError(f"Calculation type \"{ctype}\" is not supported.")
     from . import dft as dft_mod
+    # a "U" prefix asks for the unrestricted reference (tuna.py:186-201): UB3LYP is B3LYP on the unrestricted cycle
+    unrestricted_ks = method.startswith("U") and method[1:] in dft_mod.FUNCTIONALS
+    if unrestricted_ks:
+        method = method[1:]
     if method not in ("HF", "RHF", "UHF", "MP2", "RMP2") and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP2" in method else "HF"), basis))
     if method == "UHF":
+        calc.reference = "UHF"
+    if unrestricted_ks:
+        if calc.multiplicity == 1:
+            # the reference rotates the guess orbitals of an unrestricted singlet (tuna_guess.py:165-200, :396-398); without that rotation
+            # the cycle would stay on the restricted solution and report it as unrestricted
+            raise TunaError(f"Unrestricted {method} for a singlet needs the guess-orbital rotation, which this build does not have: "
+                            f"use {method} for the restricted singlet, or ML n >= 2 for an open shell.")
         calc.reference = "UHF"
     if method in dft_mod.FUNCTIONALS:
         calc.functional = method

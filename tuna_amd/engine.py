@@ -202,6 +202,18 @@ class Engine:
         self._check(self._L.tf_dft_vxc(self._ctx, ptr(P), ptr(V), ctypes.byref(n), ctypes.byref(ex), ctypes.byref(ec)))
         return V, n.value, ex.value, ec.value
 
+    def dft_vxc_unrestricted(self, P_alpha, P_beta):
+        """(V_XC^alpha, V_XC^beta, (n_alpha, n_beta), (E_X,alpha * DFX, E_X,beta * DFX), E_C * DFC) for the spin densities
+        (calculate_unrestricted_exchange_correlation_matrix, tuna_scf.py:665-750)."""
+        import ctypes
+        Pa, Pb = f64(P_alpha), f64(P_beta)
+        Va, Vb = np.zeros_like(Pa), np.zeros_like(Pb)
+        n, ex = np.zeros(2), np.zeros(2)
+        ec = ctypes.c_double()
+        self._check(self._L.tf_dft_vxc_unrestricted(self._ctx, ptr(Pa), ptr(Pb), ptr(Va), ptr(Vb), n.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                    ex.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(ec)))
+        return Va, Vb, (float(n[0]), float(n[1])), (float(ex[0]), float(ex[1])), ec.value
+
     def dft_clear(self):
         self._check(self._L.tf_dft_clear(self._ctx))
         self.functional = None
@@ -362,6 +374,29 @@ class Engine:
             r.P_spin[sp], r.C_spin[sp], r.F_spin[sp], r.eps_spin[sp] = (a[sp].ctypes.data for a in (P, Cm, F, eps))
         arrs = [f64(S), f64(T), f64(V), None if Fext is None else f64(Fext), None if X is None else f64(X), f64(P0_alpha), f64(P0_beta)]
         rc = self._L.tf_scf_uhf(self._ctx, C.byref(o), *[ptr(a) for a in arrs], float(E0), int(n_alpha), int(n_beta), float(V_NN), C.byref(r))
+        c = r.common
+        res = {"energy": c.energy, "components": np.array(c.components[:]), "n_iter": c.n_iter, "converged": bool(c.converged),
+               "P": Pt, "P_spin": P, "C_spin": Cm, "F_spin": F, "epsilons_spin": eps, "table": table[:c.n_iter].copy(),
+               "fock_seconds": c.fock_seconds, "eig_seconds": c.eig_seconds, "wall_seconds": c.wall_seconds}
+        if rc != 0:
+            err = TunaError(self._L.tf_last_error(self._ctx).decode(), rc)
+            err.partial = res
+            raise err
+        return res
+
+    def scf_uks(self, S, T, V, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, *, X=None, Fext=None, max_iter=100, **opts):
+        """tf_scf_uks: unrestricted Kohn-Sham with the functional of dft_setup -- the cycle of scf_uhf with V_XC^alpha, V_XC^beta
+        (tuna_scf.py:1237-1260); components[3] holds HF + grid exchange, components[4] the correlation energy."""
+        N = self.N
+        o = self._scf_opts(max_iter=max_iter, **opts)
+        r = ScfUhfResult()
+        Pt, table = np.zeros((N, N)), np.zeros((max_iter, 7))
+        P, Cm, F, eps = np.zeros((2, N, N)), np.zeros((2, N, N)), np.zeros((2, N, N)), np.zeros((2, N))
+        r.common.P, r.common.table = Pt.ctypes.data, table.ctypes.data
+        for sp in range(2):
+            r.P_spin[sp], r.C_spin[sp], r.F_spin[sp], r.eps_spin[sp] = (a[sp].ctypes.data for a in (P, Cm, F, eps))
+        arrs = [f64(S), f64(T), f64(V), None if Fext is None else f64(Fext), None if X is None else f64(X), f64(P0_alpha), f64(P0_beta)]
+        rc = self._L.tf_scf_uks(self._ctx, C.byref(o), *[ptr(a) for a in arrs], float(E0), int(n_alpha), int(n_beta), float(V_NN), C.byref(r))
         c = r.common
         res = {"energy": c.energy, "components": np.array(c.components[:]), "n_iter": c.n_iter, "converged": bool(c.converged),
                "P": Pt, "P_spin": P, "C_spin": Cm, "F_spin": F, "epsilons_spin": eps, "table": table[:c.n_iter].copy(),

@@ -423,9 +423,14 @@ def _cycle_steps(molecule, integrals, V_NN, X, P, E, o, Fext):
 
 def _run_unrestricted(molecule, calculation, integrals, V_NN, X, guess_objects, silent, log) -> Output:
     """run_unrestricted_SCF_cycle (scf:1165-1281) inside the outer loop (scf:1292-1435).  One GPU: the whole cycle in the library
-    (tf_scf_uhf); a sharded tensor (world > 1) or TUNA_AMD_HOST_UHF=1: the host-orchestrated loop below."""
+    (tf_scf_uhf); a sharded tensor (world > 1) or TUNA_AMD_HOST_UHF=1: the host-orchestrated loop below.  With a functional
+    (calculation.DFT_calculation, grid set by Engine.dft_setup) the library's unrestricted Kohn-Sham cycle (tf_scf_uks), one GPU only."""
     import os
     eng = _device(integrals.ERI_AO).engine
+    ks = bool(getattr(calculation, "DFT_calculation", False))
+    if ks and (eng.world > 1 or os.environ.get("TUNA_AMD_HOST_UHF")):
+        raise TunaError("unrestricted Kohn-Sham runs in the native cycle on one GPU only in this build "
+                        "(no sharded tensor, no TUNA_AMD_HOST_UHF)")
     if os.environ.get("TUNA_AMD_HOST_UHF"):
         return _python_level_unrestricted(molecule, calculation, integrals, V_NN, X, guess_objects, silent, log)
     if eng.world > 1 and not getattr(eng, "has_allreduce", False):
@@ -437,8 +442,9 @@ def _run_unrestricted(molecule, calculation, integrals, V_NN, X, guess_objects, 
         log_cycle_header(calculation, o, log)
     Fext = integrals.F + integrals.G
     try:
-        r = eng.scf_uhf(integrals.S, integrals.T, integrals.V_NE, Pa, Pb, E, molecule.n_alpha, molecule.n_beta, V_NN, X=X,
-                        Fext=Fext if np.any(Fext) else None, n_atom_ao=molecule.partition_ranges, **o)
+        cycle = eng.scf_uks if ks else eng.scf_uhf
+        r = cycle(integrals.S, integrals.T, integrals.V_NE, Pa, Pb, E, molecule.n_alpha, molecule.n_beta, V_NN, X=X,
+                  Fext=Fext if np.any(Fext) else None, n_atom_ao=molecule.partition_ranges, **o)
     except TunaError as e:
         if not silent and getattr(e, "partial", None) is not None:
             for row in e.partial["table"]:
