@@ -274,6 +274,18 @@ int tf_ao_to_mo(tf_ctx *ctx, int n1, const double *C1, int n2, const double *C2,
  * E_MP2 = e_os + e_ss.  seconds (may be NULL): wall time of transform + energy.  world > 1: as tf_ao_to_mo (one all-reduce of
  * the (ia|jb) block, then every rank evaluates the same sums). */
 int tf_mp2_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double *e_os, double *e_ss, double *seconds);
+/* Unrestricted MP2 pair energies from canonical UHF orbitals C_alpha, C_beta [N,N] and eps_alpha, eps_beta [N] (tuna_mp.py:987-1117,
+ * energy part), in spatial orbitals with chemists' (ia|jb) and D = e_i + e_j - e_a - e_b; occupied windows [n_frozen_s, n_s),
+ * virtual windows [n_s, N):
+ *   e_pairs[0] = E_aa = 1/2 sum_{ij,ab in alpha} (ia|jb) [(ia|jb) - (ib|ja)] / D,  e_pairs[1] = E_bb likewise for beta,
+ *   e_pairs[2] = E_ab = sum_{i,a alpha; j,b beta} (ia|jb)^2 / D;   E_SS = E_aa + E_bb, E_OS = E_ab.
+ * An empty spin block gives 0 and launches nothing.  TF_EINVAL (the context stays usable) without a tensor, on a NULL pointer, or
+ * unless 0 <= n_frozen_s <= n_s < N.  Packed layout with at most 32 occupied orbitals per spin (and 48 together): one pass of the
+ * first quarter per spin, the stacked bra [C_occ,a | C_occ,b], the L-transforms of the spin blocks completed in the energy kernel;
+ * otherwise the general transformation block by block.  seconds (may be NULL): wall time.  world > 1: as tf_ao_to_mo (the
+ * transformed blocks are summed over the ranks before the energy). */
+int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+               const double *eps_alpha, const double *eps_beta, double e_pairs[3], double *seconds);
 
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */

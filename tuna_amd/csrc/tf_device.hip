@@ -3621,6 +3621,149 @@ int tf_mp2_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
     return TF_OK;
 }
 
+// One UMP2 spin block: sum of tfmp2::ump2_energy_kernel's partials in block order (an empty block is 0 and launches nothing)
+static int ump2_block_energy(tf_ctx *ctx, const double *A, const double *B, int o1, int v1, int o2, int v2, const double *eo1, const double *ev1,
+                             const double *eo2, const double *ev2, int same_spin, double *d_part, double *sum)
+{
+    const int nblk = 1024;
+    *sum = 0.0;
+    if ((long long)o1 * v1 * o2 * v2 == 0) return TF_OK;
+    hipLaunchKernelGGL(tfmp2::ump2_energy_kernel, dim3(nblk), dim3(256), 0, 0, A, B, o1, v1, o2, v2, eo1, ev1, eo2, ev2, same_spin, d_part);
+    std::vector<double> part(nblk);
+    HIPCHK(ctx, hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += part[b];
+    *sum = s;
+    return TF_OK;
+}
+
+int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+               const double *eps_alpha, const double *eps_beta, double e_pairs[3], double *seconds)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!C_alpha || !C_beta || !eps_alpha || !eps_beta || !e_pairs || n_frozen_alpha < 0 || n_frozen_alpha > n_alpha || n_frozen_beta < 0 ||
+        n_frozen_beta > n_beta || n_alpha >= N || n_beta >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf: bad arguments");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int oa = n_alpha - n_frozen_alpha, ob = n_beta - n_frozen_beta, va = N - n_alpha, vb = N - n_beta, n1 = oa + ob;
+    e_pairs[0] = e_pairs[1] = e_pairs[2] = 0.0;
+    if (n1 == 0) {                                           // no correlated electron: every block is empty
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return TF_OK;
+    }
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    if (ctx->world > 1 && !ctx->allreduce && !ctx->comm)
+        TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf on a sharded tensor (world > 1) needs an RCCL communicator (tf_comm_init) or the all-reduce hook (tf_set_allreduce)");
+    // host: occupied / virtual windows of both spins, and the stacked bra [C_occ,a | C_occ,b]
+    std::vector<double> Coa((size_t)N * oa), Cva((size_t)N * va), Cob((size_t)N * ob), Cvb((size_t)N * vb), Cbra((size_t)N * n1);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < oa; ++i) Coa[(size_t)m * oa + i] = Cbra[(size_t)m * n1 + i] = C_alpha[(size_t)m * N + n_frozen_alpha + i];
+        for (int i = 0; i < ob; ++i) Cob[(size_t)m * ob + i] = Cbra[(size_t)m * n1 + oa + i] = C_beta[(size_t)m * N + n_frozen_beta + i];
+        for (int a = 0; a < va; ++a) Cva[(size_t)m * va + a] = C_alpha[(size_t)m * N + n_alpha + a];
+        for (int a = 0; a < vb; ++a) Cvb[(size_t)m * vb + a] = C_beta[(size_t)m * N + n_beta + a];
+    }
+    // device eps: occ a | vir a | occ b | vir b, and the energy partials
+    const int nblk = 1024;
+    double *d_eps = nullptr, *d_part = nullptr, *d_C = nullptr, *d_G = nullptr;
+    auto cleanup = [&]() { for (double *p : {d_eps, d_part, d_C, d_G}) if (p) (void)tf_free(p); };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    if (tf_malloc(&d_eps, (size_t)2 * N * sizeof(double)) != hipSuccess || tf_malloc(&d_part, (size_t)nblk * sizeof(double)) != hipSuccess)
+        return fail(TF_ENOMEM, "tf_mp2_uhf: out of device memory");
+    if (hipMemcpy(d_eps, eps_alpha + n_frozen_alpha, (size_t)(N - n_frozen_alpha) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_eps + N, eps_beta + n_frozen_beta, (size_t)(N - n_frozen_beta) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
+    const double *eoa = d_eps, *eva = d_eps + oa, *eob = d_eps + N, *evb = d_eps + N + ob;
+    double E_ss[2] = {0.0, 0.0}, E_ab = 0.0;
+    // the spin-blocked route: packed layout, first quarter on the segments, every occupied space <= 32 and the stacked bra <= 48
+    const bool packed = ctx->layout >= 1, tiles = ctx->layout == 2;
+    const char *q1env = getenv("TF_MO_Q1");
+    const bool spin_blocked = packed && !tiles && !(q1env && q1env[0] == '0') && oa <= 32 && ob <= 32 && n1 <= 48 &&
+                              tfmp2::bra1_lds(N, n1) <= ((size_t)150 << 10);
+    if (spin_blocked) {
+        // L-transforms G_L(aa|aa) | G_L(bb|aa) | G_L(aa|bb) | G_L(bb|bb) | status word of the hook's exchange
+        const size_t Baa = (size_t)oa * va * oa * va, Bba = (size_t)ob * vb * oa * va, Bab = (size_t)oa * va * ob * vb, Bbb = (size_t)ob * vb * ob * vb;
+        const size_t total = Baa + Bba + Bab + Bbb;
+        if (tf_malloc(&d_G, (total + 1) * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp2_uhf: out of device memory");
+        double *Gaa = d_G, *Gba = Gaa + Baa, *Gab = Gba + Bba, *Gbb = Gab + Bab;
+        double *dCbra = nullptr, *dCoa = nullptr, *dCva = nullptr, *dCob = nullptr, *dCvb = nullptr;
+        const size_t nC = (size_t)N * (2 * n1 + va + vb);
+        bool ok = tf_malloc(&d_C, nC * sizeof(double)) == hipSuccess;
+        if (ok) {
+            dCbra = d_C; dCoa = dCbra + (size_t)N * n1; dCob = dCoa + (size_t)N * oa; dCva = dCob + (size_t)N * ob; dCvb = dCva + (size_t)N * va;
+            const std::vector<double> *hv[5] = {&Cbra, &Coa, &Cob, &Cva, &Cvb};
+            double *dv[5] = {dCbra, dCoa, dCob, dCva, dCvb};
+            for (int k = 0; k < 5 && ok; ++k) ok = hv[k]->empty() || hipMemcpy(dv[k], hv[k]->data(), hv[k]->size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok) msg = "tf_mp2_uhf: copy failed";
+        } else {
+            msg = "tf_mp2_uhf: out of device memory";
+        }
+        // the work space of the short-index-first transformation, kept by the context (grown when this call needs more)
+        const size_t need = tfmp2::ump2_pool_doubles(N, ctx->n_rows, oa, ob, va, vb) * sizeof(double);
+        if (ok && need > ctx->mo_pool_bytes) {
+            if (ctx->mo_pool) { (void)tf_free(ctx->mo_pool); ctx->mo_pool = nullptr; ctx->mo_pool_bytes = 0; }
+            if (tf_malloc(&ctx->mo_pool, need) == hipSuccess) ctx->mo_pool_bytes = need;
+            else { ctx->mo_pool = nullptr; (void)hipGetLastError(); ok = false; msg = "tf_mp2_uhf: out of device memory for the transformation work space"; }
+        }
+        int prc = ok ? TF_OK : TF_ENOMEM;
+        for (int s = 0; s < 2 && prc == TF_OK; ++s) {          // ket spin a: G_L(aa|aa), G_L(bb|aa); ket spin b: G_L(aa|bb), G_L(bb|bb)
+            if ((s ? ob : oa) == 0) continue;
+            prc = tfmp2::ump2_spin_pass(ctx->scf.blas, ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
+                                        dCbra, oa, ob, dCva, va, dCvb, vb, s ? dCob : dCoa, s ? ob : oa, s ? dCvb : dCva, s ? vb : va,
+                                        s ? Gab : Gaa, s ? Gbb : Gba, ctx->mo_pool, msg);
+        }
+        if (ctx->world > 1) {
+            // the L-transforms are linear in the rows a rank owns: sum them before the quadratic energy step.  A rank whose part failed
+            // sends zeros and a non-zero status word, so that every rank stops together.
+            if (hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: the transformation failed on the device");
+            if (prc != TF_OK && hipMemset(d_G, 0, total * sizeof(double)) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: memset failed");
+            const double st = prc != TF_OK ? 1.0 : 0.0;
+            if (hipMemcpy(d_G + total, &st, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
+            if (ctx->comm) {
+                if (comm_allreduce(ctx, d_G, total + 1, nullptr)) return fail(TF_ENODEVICE, ctx->err);
+            } else {
+                const int arc = ctx->allreduce(ctx->allreduce_user, d_G, (long long)(total + 1), nullptr);
+                if (arc) return fail(TF_ENODEVICE, "tf_mp2_uhf: the all-reduce hook failed (code " + std::to_string(arc) + ")");
+            }
+            double status = 0.0;
+            if (hipMemcpy(&status, d_G + total, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
+            if (prc != TF_OK) return fail(prc, msg);
+            if (status != 0.0) return fail(TF_ENODEVICE, "tf_mp2_uhf: the transformation failed on a rank: every rank stops");
+        }
+        if (prc != TF_OK) return fail(prc, msg);
+        if ((rc = ump2_block_energy(ctx, Gaa, Gaa, oa, va, oa, va, eoa, eva, eoa, eva, 1, d_part, &E_ss[0]))) { cleanup(); return rc; }
+        if ((rc = ump2_block_energy(ctx, Gbb, Gbb, ob, vb, ob, vb, eob, evb, eob, evb, 1, d_part, &E_ss[1]))) { cleanup(); return rc; }
+        if ((rc = ump2_block_energy(ctx, Gab, Gba, oa, va, ob, vb, eoa, eva, eob, evb, 0, d_part, &E_ab))) { cleanup(); return rc; }
+    } else {
+        // every other layout, or an occupied space above 32: the general transformation, one complete block (ia|jb) at a time
+        struct Blk { const std::vector<double> *Co1, *Cv1, *Co2, *Cv2; int o1, v1, o2, v2; const double *eo1, *ev1, *eo2, *ev2; int same; double *out; };
+        const Blk blks[3] = {{&Coa, &Cva, &Coa, &Cva, oa, va, oa, va, eoa, eva, eoa, eva, 1, &E_ss[0]},
+                             {&Cob, &Cvb, &Cob, &Cvb, ob, vb, ob, vb, eob, evb, eob, evb, 1, &E_ss[1]},
+                             {&Coa, &Cva, &Cob, &Cvb, oa, va, ob, vb, eoa, eva, eob, evb, 0, &E_ab}};
+        for (const Blk &k : blks) {
+            if ((long long)k.o1 * k.v1 * k.o2 * k.v2 == 0) continue;
+            double *d_g = nullptr;
+            if ((rc = mo_transform_device(ctx, k.Co1->data(), k.o1, k.Cv1->data(), k.v1, k.Co2->data(), k.o2, k.Cv2->data(), k.v2, &d_g, nullptr))) {
+                const std::string m = ctx->err;
+                return fail(rc, m);
+            }
+            rc = ump2_block_energy(ctx, d_g, nullptr, k.o1, k.v1, k.o2, k.v2, k.eo1, k.ev1, k.eo2, k.ev2, k.same, d_part, k.out);
+            (void)tf_free(d_g);
+            if (rc) { cleanup(); return rc; }
+        }
+    }
+    cleanup();
+    e_pairs[0] = 0.5 * E_ss[0];
+    e_pairs[1] = 0.5 * E_ss[1];
+    e_pairs[2] = E_ab;
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return TF_OK;
+}
+
 int tf_eigh_probe(tf_ctx *ctx, int n, int variant, int reps, double *seconds)
 {
     if (!ctx || n < 1 || reps < 1 || !seconds) return TF_EINVAL;

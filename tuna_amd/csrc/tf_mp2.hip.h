@@ -507,8 +507,10 @@ done:
 // every block), C1 (original AO order) and the row numbers of the workgroup's nu in LDS, the next K step's loads in flight.
 // Grid: (ceil(Y / (64 waves)), N); a workgroup works on ONE nu.
 #define TFB1_THREADS 384          // six waves share one staging of C1: two workgroups per CU by LDS = three waves per SIMD (157 VGPRs)
+// MT = 3 (a stacked bra of 33 - 48 orbitals, tf_mp2_uhf): 48 accumulator tiles do not fit the register budget of three waves per SIMD
+// (it spilled to scratch and ran 7x slower); its C1 staging (N x 48 doubles) leaves one workgroup per CU by LDS anyway.
 template <int MT>
-__global__ __launch_bounds__(TFB1_THREADS, 3) void mo_bra1_kernel(const double *__restrict__ R, const double *__restrict__ C1, const int *__restrict__ rowmap,
+__global__ __launch_bounds__(TFB1_THREADS, MT == 3 ? 1 : 3) void mo_bra1_kernel(const double *__restrict__ R, const double *__restrict__ C1, const int *__restrict__ rowmap,
                                                                  BLayout L, int n1, int Y, double *__restrict__ T)
 {
     extern __shared__ double sB1[];
@@ -596,23 +598,13 @@ inline size_t q1_pool_doubles(int N, long long n_rows, int n1, int n2, int n3, i
     return std::max((size_t)std::max<long long>(1, n_rows) * Y, (size_t)n1 * n2 * Y) + (size_t)n1 * N * Y + (size_t)N * NP + (size_t)N * n4 + 64;
 }
 
-inline int transform_q1(rocblas_handle blas, const double *d_eri, const long long *d_rowoff, const int *d_rowsec, const BLayout &BL,
-                        const int2 *d_row_ij, const int *d_rowmap, long long n_rows, int N, const double *dC1, int n1, const double *dC2, int n2,
-                        const double *dC3, int n3, const double *dC4, int n4, double *d_out, double *pool, double *seconds, std::string &msg)
+// First quarter of transform_q1 on the packed segments: R[local row][N internal sigma][n3] = mo_q1_kernel with C3 (padded, internal
+// order) in dC3p.  n3 <= 32.
+inline int launch_q1(const double *d_eri, const long long *d_rowoff, const int *d_rowsec, const BLayout &BL, const int2 *d_row_ij, long long n_rows,
+                     int N, const double *dC3p, int n3, double *dR, std::string &msg)
 {
     int rc = TF_OK;
-    const double one = 1.0, zero = 0.0;
     const int NT = (n3 + 15) / 16, NP = 16 * NT;
-    const size_t X = (size_t)N * N * n3, Y = (size_t)N * n3;
-    const size_t r_doubles = std::max((size_t)std::max<long long>(1, n_rows) * Y, (size_t)n1 * n2 * Y);
-    double *dR = pool, *dT = dR + r_doubles, *dC3p = dT + (size_t)n1 * X, *dC4i = dC3p + (size_t)N * NP, *dT2 = dR;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (X > 0x7fffffffULL || (size_t)n1 * n2 > 0x7fffffffULL) { msg = "AO->MO transformation: dimension overflow"; return TF_EINVAL; }
-    TFM_HIP(hipEventCreate(&e0));
-    TFM_HIP(hipEventCreate(&e1));
-    TFM_HIP(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(permute_rows_padded_kernel, dim3((unsigned)((N * NP + 255) / 256)), dim3(256), 0, 0, dC3, BL.origI, N, n3, NP, dC3p);
-    hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)((N * n4 + 255) / 256)), dim3(256), 0, 0, dC4, BL.origI, N, n4, dC4i);
     if (n_rows > 0) {
         const char *dbg = getenv("TF_Q1_DBG");
         Q1Args Q{d_eri, d_rowoff, d_rowsec, d_row_ij, dC3p, dR, n3, NP, dbg ? atoi(dbg) : 0};
@@ -655,19 +647,56 @@ inline int transform_q1(rocblas_handle blas, const double *d_eri, const long lon
         else hipLaunchKernelGGL((mo_q1_kernel<2, false>), dim3(grid), dim3(TFQ1_THREADS), lds, 0, Q, BL, n3r, rpw, n_rows, nblk);
         TFM_HIP(hipGetLastError());
     }
-    // T[p1][nu][y] = sum_mu C1[mu][p1] R[row(mu, nu)][y]: the hand-written bra kernel follows the row map (n1 <= 32)
+done:
+    return rc;
+}
+
+// LDS of mo_bra1_kernel for n1 orbitals (the caller checks it against 150 KB)
+inline size_t bra1_lds(int N, int n1) { return (size_t)N * ((n1 + 1) & ~1) * sizeof(double) + (size_t)N * sizeof(int); }
+
+// T[p1][nu][y] = sum_mu C1[mu][p1] R[row(mu, nu)][y] for n1 <= 48 orbitals (one, two or three MFMA row tiles)
+inline int launch_bra1(const double *dR, const double *dC1, const int *d_rowmap, const BLayout &BL, int N, int n1, int Y, double *dT, std::string &msg)
+{
+    int rc = TF_OK;
+    const size_t lds1 = bra1_lds(N, n1);
+    if (n1 > 48 || lds1 > ((size_t)150 << 10)) { msg = "AO->MO transformation: the bra kernel holds at most 48 orbitals in 150 KB of LDS"; rc = TF_EINVAL; goto done; }
+    if (lds1 > ((size_t)64 << 10)) {                              // (N > ~450 at 18 orbitals: one workgroup per CU)
+        TFM_HIP(hipFuncSetAttribute((const void *)mo_bra1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+        TFM_HIP(hipFuncSetAttribute((const void *)mo_bra1_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+        TFM_HIP(hipFuncSetAttribute((const void *)mo_bra1_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    }
     {
-        const size_t lds1 = (size_t)N * ((n1 + 1) & ~1) * sizeof(double) + (size_t)N * sizeof(int);
-        if (n1 > 32 || lds1 > ((size_t)150 << 10)) { msg = "AO->MO transformation: the bra kernel holds at most 32 orbitals in 150 KB of LDS"; rc = TF_EINVAL; goto done; }
-        if (lds1 > ((size_t)64 << 10)) {                              // (N > ~450 at 18 orbitals: one workgroup per CU)
-            TFM_HIP(hipFuncSetAttribute((const void *)mo_bra1_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            TFM_HIP(hipFuncSetAttribute((const void *)mo_bra1_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        }
         const dim3 grid1((unsigned)((Y + TFB1_THREADS - 1) / TFB1_THREADS), (unsigned)N);
-        if (n1 <= 16) hipLaunchKernelGGL(mo_bra1_kernel<1>, grid1, dim3(TFB1_THREADS), lds1, 0, dR, dC1, d_rowmap, BL, n1, (int)Y, dT);
-        else hipLaunchKernelGGL(mo_bra1_kernel<2>, grid1, dim3(TFB1_THREADS), lds1, 0, dR, dC1, d_rowmap, BL, n1, (int)Y, dT);
+        if (n1 <= 16) hipLaunchKernelGGL(mo_bra1_kernel<1>, grid1, dim3(TFB1_THREADS), lds1, 0, dR, dC1, d_rowmap, BL, n1, Y, dT);
+        else if (n1 <= 32) hipLaunchKernelGGL(mo_bra1_kernel<2>, grid1, dim3(TFB1_THREADS), lds1, 0, dR, dC1, d_rowmap, BL, n1, Y, dT);
+        else hipLaunchKernelGGL(mo_bra1_kernel<3>, grid1, dim3(TFB1_THREADS), lds1, 0, dR, dC1, d_rowmap, BL, n1, Y, dT);
         TFM_HIP(hipGetLastError());
     }
+done:
+    return rc;
+}
+
+inline int transform_q1(rocblas_handle blas, const double *d_eri, const long long *d_rowoff, const int *d_rowsec, const BLayout &BL,
+                        const int2 *d_row_ij, const int *d_rowmap, long long n_rows, int N, const double *dC1, int n1, const double *dC2, int n2,
+                        const double *dC3, int n3, const double *dC4, int n4, double *d_out, double *pool, double *seconds, std::string &msg)
+{
+    int rc = TF_OK;
+    const double one = 1.0, zero = 0.0;
+    const int NT = (n3 + 15) / 16, NP = 16 * NT;
+    const size_t X = (size_t)N * N * n3, Y = (size_t)N * n3;
+    const size_t r_doubles = std::max((size_t)std::max<long long>(1, n_rows) * Y, (size_t)n1 * n2 * Y);
+    double *dR = pool, *dT = dR + r_doubles, *dC3p = dT + (size_t)n1 * X, *dC4i = dC3p + (size_t)N * NP, *dT2 = dR;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (X > 0x7fffffffULL || (size_t)n1 * n2 > 0x7fffffffULL) { msg = "AO->MO transformation: dimension overflow"; return TF_EINVAL; }
+    TFM_HIP(hipEventCreate(&e0));
+    TFM_HIP(hipEventCreate(&e1));
+    TFM_HIP(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(permute_rows_padded_kernel, dim3((unsigned)((N * NP + 255) / 256)), dim3(256), 0, 0, dC3, BL.origI, N, n3, NP, dC3p);
+    hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)((N * n4 + 255) / 256)), dim3(256), 0, 0, dC4, BL.origI, N, n4, dC4i);
+    if ((rc = launch_q1(d_eri, d_rowoff, d_rowsec, BL, d_row_ij, n_rows, N, dC3p, n3, dR, msg))) goto done;
+    // T[p1][nu][y] = sum_mu C1[mu][p1] R[row(mu, nu)][y]: the hand-written bra kernel follows the row map (n1 <= 32)
+    if (n1 > 32 || bra1_lds(N, n1) > ((size_t)150 << 10)) { msg = "AO->MO transformation: the bra kernel holds at most 32 orbitals in 150 KB of LDS"; rc = TF_EINVAL; goto done; }
+    if ((rc = launch_bra1(dR, dC1, d_rowmap, BL, N, n1, (int)Y, dT, msg))) goto done;
     // T2[p1] (Y x n2) = T[p1] (Y x N) * C2^T (N x n2)
     TFM_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)Y, n2, N, &one, dT, (rocblas_int)Y,
                                            (rocblas_stride)N * Y, dC2, n2, 0, &zero, dT2, (rocblas_int)Y, (rocblas_stride)n2 * Y, n1));
@@ -681,6 +710,96 @@ done:
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     return rc;
+}
+
+// ---- unrestricted MP2 (tuna_mp.py:987-1117, energy part) on the packed layout ----------------------------------------------------
+// One pass per KET spin s: R_s = first quarter with C3 = C_occ,s (the tensor is read once per spin), then the bra kernel with the
+// stacked bra C1 = [C_occ,a | C_occ,b] (up to 48 orbitals, mo_bra1_kernel<3>), then the two rocBLAS quarters split by the spin of the
+// bra rows (C_vir,a for the a rows, C_vir,b for the b rows) and with C_vir,s on the ket.  A pass writes the L-transforms of two
+// blocks, G_L(aa|ss) [oa][va][os][vs] and G_L(bb|ss) [ob][vb][os][vs] (L = the stored part of the tensor, its diagonal halved, as
+// transform() documents); ump2_energy_kernel completes them (g = L + L^T) on the fly.
+inline size_t ump2_pool_doubles(int N, long long n_rows, int oa, int ob, int va, int vb)
+{
+    size_t need = 0;
+    for (int s = 0; s < 2; ++s) {
+        const int os = s ? ob : oa, vs = s ? vb : va;
+        if (os == 0) continue;
+        const size_t Y = (size_t)N * os, NP = (size_t)16 * ((os + 15) / 16);
+        const size_t r = std::max((size_t)std::max<long long>(1, n_rows) * Y, ((size_t)oa * va + (size_t)ob * vb) * Y);
+        need = std::max(need, r + (size_t)(oa + ob) * N * Y + (size_t)N * NP + (size_t)N * vs + 64);
+    }
+    return need;
+}
+
+inline int ump2_spin_pass(rocblas_handle blas, const double *d_eri, const long long *d_rowoff, const int *d_rowsec, const BLayout &BL,
+                          const int2 *d_row_ij, const int *d_rowmap, long long n_rows, int N, const double *dCbra, int oa, int ob,
+                          const double *dCva, int va, const double *dCvb, int vb, const double *dCos, int os, const double *dCvs, int vs,
+                          double *d_out_a, double *d_out_b, double *pool, std::string &msg)
+{
+    int rc = TF_OK;
+    const double one = 1.0, zero = 0.0;
+    const int n1 = oa + ob, NP = 16 * ((os + 15) / 16);
+    const size_t Y = (size_t)N * os;
+    const size_t r_doubles = std::max((size_t)std::max<long long>(1, n_rows) * Y, ((size_t)oa * va + (size_t)ob * vb) * Y);
+    double *dR = pool, *dT = dR + r_doubles, *dC3p = dT + (size_t)n1 * N * Y, *dC4i = dC3p + (size_t)N * NP, *dT2 = dR;
+    if ((size_t)N * Y > 0x7fffffffULL || (size_t)oa * va > 0x7fffffffULL || (size_t)ob * vb > 0x7fffffffULL) { msg = "UMP2: dimension overflow"; return TF_EINVAL; }
+    hipLaunchKernelGGL(permute_rows_padded_kernel, dim3((unsigned)((N * NP + 255) / 256)), dim3(256), 0, 0, dCos, BL.origI, N, os, NP, dC3p);
+    hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)((N * vs + 255) / 256)), dim3(256), 0, 0, dCvs, BL.origI, N, vs, dC4i);
+    if ((rc = launch_q1(d_eri, d_rowoff, d_rowsec, BL, d_row_ij, n_rows, N, dC3p, os, dR, msg))) goto done;
+    if ((rc = launch_bra1(dR, dCbra, d_rowmap, BL, N, n1, (int)Y, dT, msg))) goto done;
+    // T2[p1] (Y x v) = T[p1] (Y x N) * C_vir^T (N x v), the virtuals of the spin of bra row p1; the a rows first, then the b rows
+    if (oa > 0)
+        TFM_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)Y, va, N, &one, dT, (rocblas_int)Y,
+                                               (rocblas_stride)N * Y, dCva, va, 0, &zero, dT2, (rocblas_int)Y, (rocblas_stride)va * Y, oa));
+    if (ob > 0)
+        TFM_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, (rocblas_int)Y, vb, N, &one, dT + (size_t)oa * N * Y,
+                                               (rocblas_int)Y, (rocblas_stride)N * Y, dCvb, vb, 0, &zero, dT2 + (size_t)oa * va * Y, (rocblas_int)Y,
+                                               (rocblas_stride)vb * Y, ob));
+    // out[p1 p2] (vs x os) = C_vir,s (vs x N, internal order) * T2[p1 p2]^T (N x os)
+    if (oa > 0)
+        TFM_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, vs, os, N, &one, dC4i, vs, 0, dT2, os,
+                                               (rocblas_stride)Y, &zero, d_out_a, vs, (rocblas_stride)os * vs, oa * va));
+    if (ob > 0)
+        TFM_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, vs, os, N, &one, dC4i, vs, 0,
+                                               dT2 + (size_t)oa * va * Y, os, (rocblas_stride)Y, &zero, d_out_b, vs, (rocblas_stride)os * vs, ob * vb));
+done:
+    return rc;
+}
+
+// One spin block of the UMP2 energy: g[i a][j b] = A[i a][j b] (+ B[j b][i a] when B is given: A and B are the L-transforms of the two
+// bra/ket orders, B = A for a same-spin block), i < o1, a < v1 of the first spin, j < o2, b < v2 of the second, D = eo1_i + eo2_j -
+// ev1_a - ev2_b.  partial[block] = sum g (g - g[i b][j a]) / D (same_spin: then o1 == o2, v1 == v2) or sum g^2 / D, summed by the
+// caller in block order (fixed grid: bitwise reproducible).
+__global__ void ump2_energy_kernel(const double *__restrict__ A, const double *__restrict__ B, int o1, int v1, int o2, int v2,
+                                   const double *__restrict__ eo1, const double *__restrict__ ev1, const double *__restrict__ eo2,
+                                   const double *__restrict__ ev2, int same_spin, double *__restrict__ partial)
+{
+    __shared__ double s_e[256];
+    const long long n1 = (long long)o1 * v1, n2 = (long long)o2 * v2, total = n1 * n2;
+    double acc = 0.0;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        const long long ia = e / n2, jb = e - ia * n2;
+        const int i = (int)(ia / v1), a = (int)(ia - (long long)i * v1);
+        const int j = (int)(jb / v2), b = (int)(jb - (long long)j * v2);
+        double g = A[e];
+        if (B) g += B[jb * n1 + ia];
+        const double D = eo1[i] + eo2[j] - ev1[a] - ev2[b];
+        if (same_spin) {
+            const long long ib = (long long)i * v1 + b, ja = (long long)j * v1 + a;
+            double gx = A[ib * n2 + ja];
+            if (B) gx += B[ja * n1 + ib];
+            acc += g * (g - gx) / D;
+        } else {
+            acc += g * g / D;
+        }
+    }
+    s_e[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) s_e[threadIdx.x] += s_e[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = s_e[0];
 }
 
 }  // namespace tfmp2

@@ -54,6 +54,9 @@ class Calculation:
     electric_field_gradient: tuple = (0.0, 0.0, 0.0)   # EGX, EGY, EGZ, calc:163-165, 432
     S_eigenvalue_threshold: float = 1e-7               # STHRESH, calc:157
     number_of_threads: int = 4                         # THREADS, calc:153 (host threads of the reference's OpenMP loops: no meaning here)
+    spin_component_scaling: bool = False               # SCS-MP2 / USCS-MP2 (tuna_mp.py:872, :1042)
+    same_spin_scaling: float = 1 / 3                   # SSS, calc:208
+    opposite_spin_scaling: float = 6 / 5               # OSS, calc:209
 
 
 @dataclass
@@ -150,6 +153,10 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.number_of_threads = int(value())           # accepted and ignored: the integrals run on the GPU
         elif p == "STHRESH":
             calc.S_eigenvalue_threshold = float(value())
+        elif p == "SSS":                                     # accepted on plain MP2 as in the reference, where it changes nothing
+            calc.same_spin_scaling = float(value())
+        elif p == "OSS":
+            calc.opposite_spin_scaling = float(value())
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -268,20 +275,36 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                 label = "\n Unrestricted Hartree-Fock energy: " if calc.reference == "UHF" else "\n Restricted Hartree-Fock energy:   "
                 log(label + f"{out.energy:16.10f}")                                      # kernel:846-850
         if calc.method == "MP2":
-            # second-order Moller-Plesset correlation energy on the device-resident tensor (tuna_mp.py:834-906; all-electron,
-            # SURVEY.md section 8d config 5): AO->MO of the (ia|jb) block + the energy sums, tf_mp2_rhf
-            if calc.reference == "UHF":
-                raise TunaError("MP2 is available for a restricted reference only in this build.")
+            # second-order Moller-Plesset correlation energy on the device-resident tensor (all-electron, SURVEY.md section 8d
+            # config 5): restricted, AO->MO of the (ia|jb) block + the energy sums, tf_mp2_rhf (tuna_mp.py:834-906); unrestricted, the
+            # three spin blocks, tf_mp2_uhf (tuna_mp.py:987-1117)
             t0 = time.perf_counter()
-            r = engine.mp2_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0)
+            if calc.reference == "UHF":
+                r = engine.mp2_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta,
+                                   molecule.n_alpha, molecule.n_beta)
+            else:
+                r = engine.mp2_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0)
             out.timings["MP2 energy"] = time.perf_counter() - t0
+            E_SS, E_OS = r["E_SS"], r["E_OS"]
+            if calc.spin_component_scaling:                  # mp:474-503
+                E_SS, E_OS = calc.same_spin_scaling * E_SS, calc.opposite_spin_scaling * E_OS
+                r = dict(r, E_SS=E_SS, E_OS=E_OS, E_MP2=E_SS + E_OS)
+                if not silent:
+                    log(f"  Same-spin scaling: {calc.same_spin_scaling:.3f}")
+                    log(f"  Opposite-spin scaling: {calc.opposite_spin_scaling:.3f}\n")
             out.mp2 = r
             E_SCF = out.energy
             out.correlation_energy_mp2 = r["E_MP2"]
             out.energy = E_SCF + r["E_MP2"]
             if not silent:
-                log(f"\n  Same spin contribution:             {r['E_SS']:13.10f}")       # mp:904-906
-                log(f"  Opposite spin contribution:         {r['E_OS']:13.10f}")
+                if calc.reference == "UHF":
+                    log(f"  Energy from alpha-alpha pairs:      {r['E_aa']:13.10f}")     # mp:1111-1117
+                    log(f"  Energy from beta-beta pairs:        {r['E_bb']:13.10f}")
+                    log(f"  Energy from alpha-beta pairs:       {r['E_ab']:13.10f}")
+                    log(f"\n  Same spin contribution:             {E_SS:13.10f}")
+                else:
+                    log(f"\n  Same spin contribution:             {E_SS:13.10f}")       # mp:904-906
+                log(f"  Opposite spin contribution:         {E_OS:13.10f}")
                 log(f"\n  MP2 correlation energy:             {r['E_MP2']:13.10f}")
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
@@ -317,10 +340,21 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
     unrestricted_ks = method.startswith("U") and method[1:] in dft_mod.FUNCTIONALS
     if unrestricted_ks:
         method = method[1:]
-    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2") and method not in dft_mod.FUNCTIONALS:
+    # UMP2 / USCS-MP2: MP2 on the unrestricted reference, as MP2 with ML n >= 2 is (tuna_mp.py:987-1222)
+    unrestricted_mp2 = method in ("UMP2", "USCS-MP2")
+    if unrestricted_mp2:
+        method = method[1:]
+    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2") and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP2" in method else "HF"), basis))
+    calc.spin_component_scaling = method == "SCS-MP2"
     if method == "UHF":
+        calc.reference = "UHF"
+    if unrestricted_mp2:
+        if calc.multiplicity == 1:
+            # as for the Kohn-Sham singlet below: without the guess-orbital rotation the cycle stays on the restricted solution
+            raise TunaError(f"Unrestricted {method} for a singlet needs the guess-orbital rotation, which this build does not have: "
+                            f"use {method} for the restricted singlet, or ML n >= 2 for an open shell.")
         calc.reference = "UHF"
     if unrestricted_ks:
         if calc.multiplicity == 1:

@@ -237,6 +237,20 @@ class Engine:
                                        ctypes.byref(t)))
         return {"E_MP2": os_.value + ss.value, "E_OS": os_.value, "E_SS": ss.value, "seconds": t.value}
 
+    def mp2_uhf(self, C_alpha, C_beta, eps_alpha, eps_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0) -> dict:
+        """UMP2 pair energies from canonical UHF orbitals (tuna_mp.py:987-1117): {"E_aa", "E_bb", "E_ab", "E_SS", "E_OS", "E_MP2",
+        "seconds"}, E_SS = E_aa + E_bb, E_OS = E_ab."""
+        Ca, Cb, ea, eb = f64(C_alpha), f64(C_beta), f64(eps_alpha), f64(eps_beta)
+        if Ca.shape != (self.N, self.N) or Cb.shape != (self.N, self.N) or ea.shape != (self.N,) or eb.shape != (self.N,):
+            raise TunaError(f"mp2_uhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        import ctypes
+        e = (ctypes.c_double * 3)()
+        t = ctypes.c_double()
+        self._check(self._L.tf_mp2_uhf(self._ctx, int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca), ptr(Cb), ptr(ea),
+                                       ptr(eb), e, ctypes.byref(t)))
+        E_aa, E_bb, E_ab = e[0], e[1], e[2]
+        return {"E_aa": E_aa, "E_bb": E_bb, "E_ab": E_ab, "E_SS": E_aa + E_bb, "E_OS": E_ab, "E_MP2": E_aa + E_bb + E_ab, "seconds": t.value}
+
     def diagonalise(self, F, X):
         """(epsilons, molecular_orbitals) = eigh(sym(X^T F X)), C = X C' on the device (scf:222-250)."""
         F, X = f64(F), f64(X)
