@@ -286,6 +286,16 @@ int tf_mp2_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
  * transformed blocks are summed over the ranks before the energy). */
 int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
                const double *eps_alpha, const double *eps_beta, double e_pairs[3], double *seconds);
+/* Restricted MP3 from canonical RHF orbitals C [N,N] and eps [N] (run_restricted_MP3, tuna_mp.py:1410-1470); occupied window
+ * [n_frozen, n_occ), virtual window [n_occ, N), D = e_i + e_j - e_a - e_b, t_ijab = (ia|jb) / D, t'_ijab = 2 [2 (ia|jb) - (ib|ja)] / D:
+ *   e_mp2 = {E_OS, E_SS}, exactly what tf_mp2_rhf returns for the same orbitals;
+ *   e_mp3 = the unscaled terms of E_MP3 = sum t'_ijab X_ijab: [0] particle-particle ladder 1/2 sum_cd t_ijcd (ac|bd), [1] hole-hole
+ *           ladder 1/2 sum_kl t_klab (ki|lj), [2] ring terms; E_MP3 is their sum.
+ * The ladder never forms (ac|bd): with T_ij = C_v t_ij C_v^T it is 1/2 C_v^T Z_ij C_v, Z_ij = sum (mu lambda|nu sigma) T_ij[lambda][sigma].
+ * Packed layout: Z from one pass of a matrix-core kernel over the stored rows per batch of 64 pairs; rows and tiles layouts: Z from
+ * the general-density exchange build.  seconds (may be NULL): [0] wall time, [1] MO blocks, [2] ladder, [3] the rest.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL pointer, unless 0 <= n_frozen < n_occ < N, or with world > 1. */
+int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double *seconds);
 
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */

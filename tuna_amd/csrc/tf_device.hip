@@ -32,6 +32,7 @@
 #include "tf_oneel.hip.h"
 #include "tf_scf.hip.h"
 #include "tf_mp2.hip.h"
+#include "tf_mp3.hip.h"
 #include "tf_dft.hip.h"
 
 // ---- small-block cache for THIS file's device allocations ------------------------------------------------------------------------
@@ -3761,6 +3762,160 @@ int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_f
     e_pairs[1] = 0.5 * E_ss[1];
     e_pairs[2] = E_ab;
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return TF_OK;
+}
+
+// Restricted MP3 (run_restricted_MP3, tuna_mp.py:1410-1470; tf_mp3.hip.h has the expressions).  Stages: the MO blocks (ia|jb),
+// (ij|ab), (ki|lj) through mo_transform_device; amplitudes and MP2 partials (mp3_amp_kernel); the particle-particle ladder in the AO
+// basis, batches of TFL_W pairs; the hole-hole and ring GEMMs; one energy reduction.
+int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double *seconds)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!C || !eps || !e_mp2 || !e_mp3 || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: bad arguments (needs C, eps, outputs and 0 <= n_frozen < n_occ < N)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: a sharded tensor (world > 1) is not supported");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o, nn = (long long)N * N;
+    if (ov > 0x7fffffffLL || (long long)v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: dimension overflow");
+    const bool packed = ctx->layout == 1;                     // the AO-direct ladder kernel; rows / tiles: the exchange build
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *work = nullptr, *d_eps = nullptr, *d_part = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *batch = nullptr;
+    auto cleanup = [&]() { for (double *p : {g1, g2, g3, work, d_eps, d_part, d_Cv, d_Cvi, batch}) if (p) (void)tf_free(p); };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- MO blocks: (ia|jb) = g1[i][a][j][b], (ab|ij) = g2[a][b][i][j], (ki|lj) = g3[k][i][l][j]
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, &g1, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    {
+        // (ab|ij) = g2[a][b][i][j], in slices of the first virtual index: on the packed and tiles layouts the transformation also forms
+        // the image with (ab) on the ket side, whose work space grows as N^2 v^2 (190 GB at N = 400); a slice of nc virtuals keeps it
+        // near 4 GB
+        if (tf_malloc(&g2, (size_t)v * v * o * o * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory");
+        const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
+        std::vector<double> Cs((size_t)N * nc);
+        for (int a0 = 0; a0 < v; a0 += nc) {
+            const int na = std::min(nc, v - a0);
+            for (int m = 0; m < N; ++m)
+                for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = Cv[(size_t)m * v + a0 + a];
+            double *d_s = nullptr;
+            if ((rc = mo_transform_device(ctx, Cs.data(), na, Cv.data(), v, Co.data(), o, Co.data(), o, &d_s, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+            const hipError_t ce = hipMemcpy(g2 + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
+            (void)tf_free(d_s);
+            if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
+        }
+    }
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Co.data(), o, &g3, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t1 = stamp();
+    // ---- work space: tov | too | tp | tsw | Moo | M1 | M2 | S13 | S2 | Xhh | Y
+    const size_t nwork = (size_t)10 * B2 + (size_t)o4;
+    double *tov, *too, *tp, *tsw, *Moo, *M1, *M2, *S13, *S2, *Xhh, *Y;
+    const int nblk = 1024;
+    if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || tf_malloc(&d_eps, (size_t)N * sizeof(double)) != hipSuccess ||
+        tf_malloc(&d_part, (size_t)3 * nblk * sizeof(double)) != hipSuccess || tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess ||
+        tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess)
+        return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory");
+    tov = work; too = tov + B2; tp = too + B2; tsw = tp + B2; M1 = tsw + B2; M2 = M1 + B2; S13 = M2 + B2; S2 = S13 + B2; Xhh = S2 + B2; Y = Xhh + B2;
+    Moo = Y + B2;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
+    // ---- amplitudes and the MP2 partials
+    hipLaunchKernelGGL(tfmp3::mp3_amp_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, tov, too, tp, tsw, d_part);
+    {
+        std::vector<double> part(2 * nblk);
+        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
+        double os = 0.0, ss = 0.0;
+        for (int b = 0; b < nblk; ++b) { os += part[2 * b]; ss += part[2 * b + 1]; }
+        e_mp2[0] = os; e_mp2[1] = ss;
+    }
+    const auto t2 = stamp();
+    // ---- particle-particle ladder: Y[ij][a][b] = 1/2 C_v^T Z C_v, in batches of TFL_W pairs
+    rocblas_handle blas = ctx->scf.blas;
+    const int W = TFL_W, npair = o * o;
+    const size_t nU = (size_t)W * v * N, nT = (size_t)W * nn;
+    // batch work space: U [W][v][N] (later V [W][N][v]) | T [W][N][N] | Tt [N][N][W] (packed) or J [chunk][N][N] (exchange route) | Zh [W][N][N]
+    const int chunk = ctx->layout == 2 ? 8 : 2;
+    const size_t nbatch = nU + nT + (packed ? nT : (size_t)chunk * nn) + nT;
+    if (tf_malloc(&batch, nbatch * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory for the ladder work space");
+    double *U = batch, *Tm = U + nU, *Tt = Tm + nT, *Jx = Tt, *Zh = Tt + (packed ? nT : (size_t)chunk * nn);
+    const double *Cvl = d_Cv;                                 // C_v in the AO order of T and Z (internal order on the packed layout)
+    if (packed) {
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
+        Cvl = d_Cvi;
+    }
+    int csize[4];
+    for (int q = 0; q < 4; ++q) csize[q] = ctx->hl.csize[q];
+    const int lblk = tfmp3::ladder_blocks(csize);
+#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp3_rhf: rocBLAS failed: " #call); } while (0)
+    for (int p0 = 0; p0 < npair; p0 += W) {
+        const int nb = std::min(W, npair - p0);
+        const double *tb = too + (size_t)p0 * v * v;
+        // U_p = t_p C_v^T (packed: Zh of T_p; exchange route: K of T_p^T, so t_p^T), T_p = C_v U_p
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
+        if (packed) {
+            const long long tot = nn * W;
+            hipLaunchKernelGGL(tfmp3::mp3_pairs_last_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb, Tt);
+            tfmp3::LadderArgs LA{ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, lblk};
+            tfmp3::launch_ladder(LA, ctx->bl, N, 0);
+            if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: ladder kernel launch failed");
+        } else {
+            for (int d = 0; d < nb; d += chunk) {
+                const int nd = std::min(chunk, nb - d);
+                const double *pp[8]; double *jj[8], *kk[8];
+                int nonsym[8];
+                for (int q = 0; q < 8; ++q) {
+                    const int dq = d + std::min(q, nd - 1);
+                    pp[q] = Tm + (size_t)dq * nn; jj[q] = Jx + (size_t)std::min(q, nd - 1) * nn; kk[q] = Zh + (size_t)dq * nn; nonsym[q] = 1;
+                }
+                if ((rc = launch_jk(ctx, nd, pp, jj, kk, 0, nonsym))) { const std::string m = ctx->err; return fail(rc, m); }
+            }
+        }
+        // V_p = Z_p C_v, Y_p = 1/2 C_v^T V_p
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, v, N, 1.0, Zh, N, nn, Cvl, v, 0, 0.0, U, v, (long long)N * v, nb));
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, N, 0.5, Cvl, v, 0, U, v, (long long)N * v, 0.0, Y + (size_t)p0 * v * v, v,
+                                        (long long)v * v, nb));
+    }
+    const auto t3 = stamp();
+    // ---- hole-hole and ring terms
+    {
+        const long long tot = std::max(B2, o4);
+        hipLaunchKernelGGL(tfmp3::mp3_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3, o, v, Moo, M1, M2);
+    }
+    // Xhh[(ij)][(ab)] = 1/2 Moo[(ij)][(kl)] too[(kl)][(ab)]
+    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, o * o, v * v, o * o, 0.5, Moo, o * o, too, v * v, 0.0, Xhh, v * v));
+    // S13 = tov M1 - tsw g1;  S2 = tsw M2   (all [(ov)][(ov)])
+    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, 1.0, tov, (int)ov, M1, (int)ov, 0.0, S13, (int)ov));
+    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, -1.0, tsw, (int)ov, g1, (int)ov, 1.0, S13, (int)ov));
+    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, 1.0, tsw, (int)ov, M2, (int)ov, 0.0, S2, (int)ov));
+#undef MP3_BLAS
+    hipLaunchKernelGGL(tfmp3::mp3_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, Y, packed ? 1 : 0, Xhh, S13, S2, o, v, d_part);
+    {
+        std::vector<double> part(3 * nblk);
+        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: the MP3 kernels failed on the device");
+        double e[3] = {0.0, 0.0, 0.0};
+        for (int b = 0; b < nblk; ++b)
+            for (int q = 0; q < 3; ++q) e[q] += part[3 * b + q];
+        for (int q = 0; q < 3; ++q) e_mp3[q] = e[q];
+    }
+    const auto t4 = stamp();
+    cleanup();
+    if (seconds) {
+        seconds[0] = std::chrono::duration<double>(t4 - t0).count();
+        seconds[1] = std::chrono::duration<double>(t1 - t0).count();
+        seconds[2] = std::chrono::duration<double>(t3 - t2).count();
+        seconds[3] = std::chrono::duration<double>((t2 - t1) + (t4 - t3)).count();
+    }
     return TF_OK;
 }
 

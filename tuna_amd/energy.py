@@ -57,6 +57,8 @@ class Calculation:
     spin_component_scaling: bool = False               # SCS-MP2 / USCS-MP2 (tuna_mp.py:872, :1042)
     same_spin_scaling: float = 1 / 3                   # SSS, calc:208
     opposite_spin_scaling: float = 6 / 5               # OSS, calc:209
+    mp3: bool = False                                  # MP3 / SCS-MP3 after the MP2 step (tuna_mp.py:1814-1828)
+    MP3_scaling: float = 1 / 4                         # MP3S / MP3SCALING / MP3SCAL, calc:183 (applied by SCS-MP3 only)
 
 
 @dataclass
@@ -157,6 +159,8 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.same_spin_scaling = float(value())
         elif p == "OSS":
             calc.opposite_spin_scaling = float(value())
+        elif p in ("MP3S", "MP3SCALING", "MP3SCAL"):
+            calc.MP3_scaling = float(value())
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -282,6 +286,10 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             if calc.reference == "UHF":
                 r = engine.mp2_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta,
                                    molecule.n_alpha, molecule.n_beta)
+            elif calc.mp3:
+                # MP3 / SCS-MP3 (tuna_mp.py:1418-1493): tf_mp3_rhf returns the MP2 components of the same orbitals as well
+                r3 = engine.mp3_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0)
+                r = {k: r3[k] for k in ("E_OS", "E_SS", "E_MP2", "seconds")}
             else:
                 r = engine.mp2_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0)
             out.timings["MP2 energy"] = time.perf_counter() - t0
@@ -306,6 +314,24 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(f"\n  Same spin contribution:             {E_SS:13.10f}")       # mp:904-906
                 log(f"  Opposite spin contribution:         {E_OS:13.10f}")
                 log(f"\n  MP2 correlation energy:             {r['E_MP2']:13.10f}")
+            if calc.mp3:
+                E_MP3 = r3["E_MP3"]
+                if not silent:
+                    log(f"\n  MP3 correlation energy:             {E_MP3:13.10f}")                  # mp:1472
+                if calc.spin_component_scaling:                                                    # mp:1476-1482
+                    E_MP3 *= calc.MP3_scaling
+                    if not silent:
+                        log(f"\n  Scaling for MP3: {calc.MP3_scaling:.3f}\n")
+                        log(f"  Scaled MP3 correlation energy:    {E_MP3:15.10f}")
+                        log(f"  SCS-MP3 correlation energy:       {(E_MP3 + r['E_MP2']):15.10f}")
+                out.mp3 = dict(r3, E_MP3_scaled=E_MP3)
+                out.correlation_energy_mp3 = E_MP3
+                out.energy += E_MP3
+                if not silent:                                                                     # kernel:1223-1239
+                    tag = "SCS-" if calc.spin_component_scaling else ""
+                    log(f"\n Correlation energy from {tag}MP2:  {' ' * (4 - len(tag))}" + f"{r['E_MP2']:16.10f}")
+                    log(f" Correlation energy from {tag}MP3:  {' ' * (4 - len(tag))}" + f"{E_MP3:16.10f}\n")
+                    log(" Total correlation energy:         " + f"{r['E_MP2'] + E_MP3:16.10f}\n")
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
         if calc.dipole or calc.polarisability or calc.hyperpolarisability:
@@ -344,10 +370,18 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
     unrestricted_mp2 = method in ("UMP2", "USCS-MP2")
     if unrestricted_mp2:
         method = method[1:]
-    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2") and method not in dft_mod.FUNCTIONALS:
+    if method in ("UMP3", "USCS-MP3"):
+        raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP3 runs on a closed-shell restricted reference.")
+    mp3 = method in ("MP3", "SCS-MP3")
+    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3") and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
-    calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP2" in method else "HF"), basis))
-    calc.spin_component_scaling = method == "SCS-MP2"
+    calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP" in method else "HF"), basis))
+    calc.spin_component_scaling = method in ("SCS-MP2", "SCS-MP3")      # tuna_mp.py:872: "SCS" in the name scales the MP2 part too
+    calc.mp3 = mp3
+    if mp3 and calc.multiplicity != 1:
+        raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
+    if mp3 and (calc.dipole or calc.polarisability or calc.hyperpolarisability):
+        raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
     if method == "UHF":
         calc.reference = "UHF"
     if unrestricted_mp2:

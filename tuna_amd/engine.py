@@ -251,6 +251,21 @@ class Engine:
         E_aa, E_bb, E_ab = e[0], e[1], e[2]
         return {"E_aa": E_aa, "E_bb": E_bb, "E_ab": E_ab, "E_SS": E_aa + E_bb, "E_OS": E_ab, "E_MP2": E_aa + E_bb + E_ab, "seconds": t.value}
 
+    def mp3_rhf(self, C, eps, n_occ, n_frozen=0) -> dict:
+        """Restricted MP3 from canonical RHF orbitals (tuna_mp.py:1410-1470): {"E_OS", "E_SS", "E_MP2", "E_pp", "E_hh", "E_ring", "E_MP3",
+        "seconds"}; the MP3 terms are unscaled, E_MP3 = E_pp + E_hh + E_ring; seconds = [wall, MO blocks, ladder, rest]."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"mp3_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        import ctypes
+        e2 = (ctypes.c_double * 2)()
+        e3 = (ctypes.c_double * 3)()
+        t = (ctypes.c_double * 4)()
+        self._check(self._L.tf_mp3_rhf(self._ctx, int(n_occ), int(n_frozen), ptr(C), ptr(eps), e2, e3, t))
+        E_OS, E_SS = e2[0], e2[1]
+        return {"E_OS": E_OS, "E_SS": E_SS, "E_MP2": E_OS + E_SS, "E_pp": e3[0], "E_hh": e3[1], "E_ring": e3[2],
+                "E_MP3": e3[0] + e3[1] + e3[2], "seconds": list(t)}
+
     def diagonalise(self, F, X):
         """(epsilons, molecular_orbitals) = eigh(sym(X^T F X)), C = X C' on the device (scf:222-250)."""
         F, X = f64(F), f64(X)
