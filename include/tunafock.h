@@ -296,6 +296,15 @@ int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_f
  * the general-density exchange build.  seconds (may be NULL): [0] wall time, [1] MO blocks, [2] ladder, [3] the rest.
  * TF_EINVAL (the context stays usable) without a tensor, on a NULL pointer, unless 0 <= n_frozen < n_occ < N, or with world > 1. */
 int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double *seconds);
+/* The particle-particle ladder contraction of tf_mp3_rhf on its own (instrumentation, tests): T = n matrices [n][N][N] and
+ * Zh [n][N][N], host buffers in the caller's AO order,
+ *   Zh[p][mu][nu] = sum_{lambda sigma} R_(mu lambda)[nu][sigma] T[p][lambda][sigma],
+ * R_(mu lambda) = the stored part of the tensor row (mu lambda) expanded to a symmetric matrix, the row's own pair halved: the
+ * contraction with the stored triangle, so that Z[T] = Zh[T] + Zh[T^T]^T with Z[T][mu][nu] = sum (mu lambda|nu sigma) T[lambda][sigma].
+ * Runs the batches of 64 matrices through the very routine tf_mp3_rhf calls per batch of pairs; only the permutation between the
+ * caller's and the internal AO order is added.  An output element the kernel does not write comes back as a NaN.
+ * TF_EINVAL (the context stays usable) without a tensor, with n < 1, on a NULL pointer, on the rows and tiles layouts, or with world > 1. */
+int tf_mp3_ladder_probe(tf_ctx *ctx, int n, const double *T, double *Zh);
 
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */

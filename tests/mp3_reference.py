@@ -105,3 +105,54 @@ def mo_ladder(E, C, eps, n_occ, n_frozen=0):
     Co, Cv, eo, ev = _windows(C, eps, n_occ, n_frozen)
     t, _ = amplitudes(mo_tensor(E, Co, Cv, Co, Cv), eo, ev)
     return 0.5 * np.einsum("ijcd,acbd->ijab", t, mo_tensor(E, Cv, Cv, Cv, Cv), optimize=True)
+
+
+def blocks_from_coulomb(J_of, Co, Cv, batch=64):
+    """(oovv[i j a b] = (ij|ab), oooo[k i l j] = (ki|lj)) from Coulomb matrices: with D_ij = (c_i c_j^T + c_j c_i^T) / 2,
+    J(D_ij)[la][si] = (la si|ij), so (ij|ab) = C_v^T J(D_ij) C_v and (ij|kl) = C_o^T J(D_ij) C_o.  J_of maps a batch of symmetric
+    densities [n, N, N] to their Coulomb matrices; one density per pair i <= j."""
+    o, v = Co.shape[1], Cv.shape[1]
+    oovv, oooo = np.empty((o, o, v, v)), np.empty((o, o, o, o))
+    pairs = [(i, j) for i in range(o) for j in range(i + 1)]
+    for s in range(0, len(pairs), batch):
+        chunk = pairs[s:s + batch]
+        D = np.stack([0.5 * (np.outer(Co[:, i], Co[:, j]) + np.outer(Co[:, j], Co[:, i])) for i, j in chunk])
+        J = np.asarray(J_of(D)).reshape(len(chunk), Co.shape[0], Co.shape[0])
+        vv, oo = np.matmul(Cv.T, np.matmul(J, Cv)), np.matmul(Co.T, np.matmul(J, Co))
+        for n, (i, j) in enumerate(chunk):
+            oovv[i, j], oovv[j, i] = vv[n], vv[n]
+            oooo[i, j], oooo[j, i] = oo[n], oo[n]
+    return oovv, oooo
+
+
+def terms_from_blocks(ovov, oovv, oooo, Z_of, Cv, eo, ev, batch=64):
+    """((E_pp, E_hh, E_ring), (S_pp, S_hh, S_ring)): the expressions of restricted_terms from the blocks ovov[i a j b] = (ia|jb),
+    oovv[i j a b] = (ij|ab), oooo[k i l j] = (ki|lj) and a callback Z_of that maps a batch of AO matrices T [n, N, N] to
+    Z[T][mu][nu] = sum (mu la|nu si) T[la][si]; never forms (ac|bd).  S = sum |t'_ijab X_ijab| per term: the yardstick of an error in the
+    term, which cancellation inside the sum cannot shrink.  The hole-hole and ring contractions are explicit reshaped GEMMs (BLAS)."""
+    o, v = len(eo), len(ev)
+    ov = o * v
+    t, tp = amplitudes(ovov, eo, ev)                                # [i j a b]
+    # particle-particle ladder: T_ij = C_v t_ij C_v^T, X_ij = 1/2 C_v^T Z_ij C_v
+    tf = t.reshape(o * o, v, v)
+    X_pp = np.empty((o * o, v, v))
+    for s in range(0, o * o, batch):
+        T = np.matmul(Cv, np.matmul(tf[s:s + batch], Cv.T))
+        Z = np.asarray(Z_of(T)).reshape(T.shape)
+        X_pp[s:s + batch] = 0.5 * np.matmul(Cv.T, np.matmul(Z, Cv))
+    X_pp = X_pp.reshape(o, o, v, v)
+    # hole-hole ladder: X[(ij)][(ab)] = 1/2 sum_(kl) (ki|lj) t[(kl)][(ab)]
+    M = np.ascontiguousarray(oooo.transpose(1, 3, 0, 2)).reshape(o * o, o * o)
+    X_hh = (0.5 * (M @ t.reshape(o * o, v * v))).reshape(o, o, v, v)
+    # ring: with A[(ia)][(kc)] = t_ikac, A'[(ja)][(kc)] = t_kjac, G[(kc)][(jb)] = (kc|jb), H[(kc)][(jb)] = (kj|bc):
+    #   X_ijab = [A (2 G - H)][(ia)][(jb)] - [A' H][(ja)][(ib)] - [A' G][(ia)][(jb)]
+    A = np.ascontiguousarray(t.transpose(0, 2, 1, 3)).reshape(ov, ov)
+    A2 = np.ascontiguousarray(t.transpose(1, 2, 0, 3)).reshape(ov, ov)
+    G = np.ascontiguousarray(ovov).reshape(ov, ov)
+    H = np.ascontiguousarray(oovv.transpose(0, 3, 1, 2)).reshape(ov, ov)
+    R = A @ (2.0 * G - H) - A2 @ G                                  # [(ia)][(jb)]
+    R2 = A2 @ H                                                     # [(ja)][(ib)]
+    X_ring = R.reshape(o, v, o, v).transpose(0, 2, 1, 3) - R2.reshape(o, v, o, v).transpose(2, 0, 1, 3)
+    E = tuple(float(np.sum(tp * X)) for X in (X_pp, X_hh, X_ring))
+    S = tuple(float(np.sum(np.abs(tp * X))) for X in (X_pp, X_hh, X_ring))
+    return E, S

@@ -84,10 +84,10 @@ def _random_orbitals(N, seed):
     return C, eps
 
 
-@pytest.mark.parametrize("width", [1, 7, 12, 20])
+@pytest.mark.parametrize("width", [1, 7, 8, 12, 16, 20])
 def test_widths_against_the_independent_checker(engine, n2_tz, width):
-    """N2/cc-pVTZ, random orthonormal orbitals: one pair; 49 pairs (one partial batch of 64); 144 and 400 pairs (several batches of 64,
-    the last one partial)."""
+    """N2/cc-pVTZ, random orthonormal orbitals: one pair; 49 pairs (one partial batch of 64); 64 and 256 pairs (full batches only); 144
+    and 400 pairs (several batches of 64, the last one partial)."""
     aos, E = n2_tz
     engine.set_basis(aos).build_eri(True)
     C, eps = _random_orbitals(engine.N, 30 + width)
@@ -148,6 +148,36 @@ def test_repeatable_and_refusals(engine, mp3_golden):
     # the context stays usable
     r = engine.mp3_rhf(g["C"], g["eps"], 7)
     assert abs(r["E_MP3"] - float(g["E_MP3"])) < 1e-10
+    # the ladder probe: its refusals, each followed by a call that works
+    T = np.random.default_rng(5).standard_normal((2, N, N))
+    Z, out = engine.mp3_ladder_probe(T), np.zeros_like(T)
+    assert np.all(np.isfinite(Z)) and np.abs(Z).max() > 0
+    for args in ((0, p(T), p(out)), (-1, p(T), p(out)), (2, None, p(out)), (2, p(T), None)):
+        assert L.tf_mp3_ladder_probe(ctx, *args) == TF_EINVAL, args
+        assert np.array_equal(engine.mp3_ladder_probe(T), Z)
+    assert L.tf_mp3_ladder_probe(None, 2, p(T), p(out)) == TF_EINVAL
+    with Engine(0) as fresh:                                          # no tensor yet
+        fresh.set_basis(aos)
+        assert fresh._L.tf_mp3_ladder_probe(fresh._ctx, 2, p(T), p(out)) == TF_EINVAL
+        fresh.build_eri(True)
+        assert np.array_equal(fresh.mp3_ladder_probe(T), Z)
+    with Engine(0, 0, 2) as half:                                     # rank 0 of two
+        half.set_basis(aos).build_eri(True)
+        assert half._L.tf_mp3_ladder_probe(half._ctx, 2, p(T), p(out)) == TF_EINVAL
+    try:
+        for layout in ("rows", "tiles"):
+            engine.set_basis(aos).build_eri(True, layout=layout)
+            assert engine.eri_storage()["layout"] == layout
+            assert L.tf_mp3_ladder_probe(ctx, 2, p(T), p(out)) == TF_EINVAL
+            with pytest.raises(TunaError):
+                engine.mp3_ladder_probe(T)
+            r = engine.mp3_rhf(g["C"], g["eps"], 7)
+            assert abs(r["E_MP3"] - float(g["E_MP3"])) < 1e-10
+    finally:
+        _reset(engine)
+    engine.set_basis(aos).build_eri(True)
+    assert engine.eri_storage()["layout"] == "packed" and np.array_equal(engine.mp3_ladder_probe(T), Z)
+    assert not np.any(out)                                            # (no refused call wrote anything)
 
 
 def test_input_lines(engine, mp3_golden):

@@ -85,3 +85,37 @@ def test_spin_orbital_and_restricted_terms_agree_on_random_data():
     for nf in (0, 1):
         so, rt = mr.spin_orbital_terms(E, C, eps, 4, nf), mr.restricted_terms(E, C, eps, 4, nf)
         assert np.allclose(so, rt, rtol=1e-12, atol=1e-12 * max(abs(x) for x in so)), (nf, so, rt)
+
+
+def _blocks_and_terms(E, C, eps, n_occ, n_frozen):
+    """terms_from_blocks with every input made the way tests/test_gpu_mp3_large.py makes it: (ij|ab) and (ki|lj) from Coulomb matrices,
+    Z from the exchange matrix of the transposed argument (the reference strings "ijkl,kl->ij" and "ilkj,kl->ij")."""
+    Co, Cv, eo, ev = mr._windows(C, eps, n_occ, n_frozen)
+    ovov = mr.mo_tensor(E, Co, Cv, Co, Cv)
+    oovv, oooo = mr.blocks_from_coulomb(lambda D: np.einsum("ijkl,pkl->pij", E, D, optimize=True), Co, Cv, batch=5)
+    return mr.terms_from_blocks(ovov, oovv, oooo, lambda T: np.einsum("ilkj,pkl->pij", E, T.transpose(0, 2, 1), optimize=True), Cv, eo, ev,
+                                batch=4)
+
+
+@pytest.mark.parametrize("N, n_occ, n_frozen", [(9, 3, 0), (12, 5, 1), (14, 6, 2), (10, 1, 0), (11, 4, 3)])
+def test_terms_from_blocks_equal_restricted_terms_on_random_data(N, n_occ, n_frozen):
+    """the last two cases: one occupied orbital, without and by freezing the others"""
+    E, C, eps = _random_case(N, n_occ, 200 + N)
+    got, S = _blocks_and_terms(E, C, eps, n_occ, n_frozen)
+    want = mr.restricted_terms(E, C, eps, n_occ, n_frozen)
+    for g, w, s in zip(got, want, S):
+        assert abs(g - w) <= 1e-12 * abs(w), (got, want)
+        assert s >= abs(w) * (1 - 1e-12)                              # (sum |x| bounds |sum x|)
+
+
+@pytest.mark.parametrize("tag", ["n2_sto3g", "co_631g", "hf_ccpvdz", "ne_ccpvdz", "n2_ccpvdz"])
+def test_terms_from_blocks_equal_restricted_terms_on_the_golden_systems(mp3_golden, tag):
+    g = mp3_golden[tag]
+    E = dense(tag)
+    nocc = int(g["n_occ"])
+    for nf in (0, 1, nocc - 1):
+        got, S = _blocks_and_terms(E, g["C"], g["eps"], nocc, nf)
+        want = mr.restricted_terms(E, g["C"], g["eps"], nocc, nf)
+        assert np.all(np.abs(np.array(got) - np.array(want)) <= 1e-12 * np.abs(want)), (tag, nf, got, want)
+        if nf < 2:
+            assert abs(sum(got) - float(g[("", "fc1_")[nf] + "E_MP3"])) < 1e-10

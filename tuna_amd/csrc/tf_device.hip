@@ -3765,6 +3765,21 @@ int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_f
     return TF_OK;
 }
 
+// One batch of the AO-direct ladder on the packed layout (null stream): Zh[p][mu][nu] = the stored-triangle contraction of the tensor
+// with the pair matrices Tm[p] (tfmp3::mp3_ladder_kernel), p < nb <= TFL_W, everything [N][N] in the internal AO order; Tt [N][N][TFL_W] is
+// the work space of the pairs-last image.  The one body behind tf_mp3_rhf and tf_mp3_ladder_probe.  false: a launch failed.
+static bool mp3_ladder_batch(tf_ctx *ctx, const double *Tm, int nb, double *Tt, double *Zh)
+{
+    const int N = ctx->N;
+    const long long tot = (long long)N * N * TFL_W;
+    int csize[4];
+    for (int q = 0; q < 4; ++q) csize[q] = ctx->hl.csize[q];
+    hipLaunchKernelGGL(tfmp3::mp3_pairs_last_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb, Tt);
+    tfmp3::LadderArgs LA{ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, tfmp3::ladder_blocks(csize)};
+    tfmp3::launch_ladder(LA, ctx->bl, N, 0);
+    return hipGetLastError() == hipSuccess;
+}
+
 // Restricted MP3 (run_restricted_MP3, tuna_mp.py:1410-1470; tf_mp3.hip.h has the expressions).  Stages: the MO blocks (ia|jb),
 // (ij|ab), (ki|lj) through mo_transform_device; amplitudes and MP2 partials (mp3_amp_kernel); the particle-particle ladder in the AO
 // basis, batches of TFL_W pairs; the hole-hole and ring GEMMs; one energy reduction.
@@ -3853,9 +3868,6 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
         hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
         Cvl = d_Cvi;
     }
-    int csize[4];
-    for (int q = 0; q < 4; ++q) csize[q] = ctx->hl.csize[q];
-    const int lblk = tfmp3::ladder_blocks(csize);
 #define MP3_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp3_rhf: rocBLAS failed: " #call); } while (0)
     for (int p0 = 0; p0 < npair; p0 += W) {
         const int nb = std::min(W, npair - p0);
@@ -3864,11 +3876,7 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
         if (packed) {
-            const long long tot = nn * W;
-            hipLaunchKernelGGL(tfmp3::mp3_pairs_last_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb, Tt);
-            tfmp3::LadderArgs LA{ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, lblk};
-            tfmp3::launch_ladder(LA, ctx->bl, N, 0);
-            if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: ladder kernel launch failed");
+            if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zh)) return fail(TF_ENODEVICE, "tf_mp3_rhf: ladder kernel launch failed");
         } else {
             for (int d = 0; d < nb; d += chunk) {
                 const int nd = std::min(chunk, nb - d);
@@ -3916,6 +3924,48 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
         seconds[2] = std::chrono::duration<double>(t3 - t2).count();
         seconds[3] = std::chrono::duration<double>((t2 - t1) + (t4 - t3)).count();
     }
+    return TF_OK;
+}
+
+int tf_mp3_ladder_probe(tf_ctx *ctx, int n, const double *T, double *Zh)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: call tf_build_eri first");
+    if (n < 1 || !T || !Zh) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: bad arguments (needs n >= 1, T and Zh)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: a sharded tensor (world > 1) is not supported");
+    if (ctx->layout != 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: the ladder kernel runs on the packed layout only");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int N = ctx->N, W = TFL_W;
+    const size_t nn = (size_t)N * N, nT = (size_t)W * nn;
+    const int *oI = ctx->hl.origI.data();                     // internal -> caller's AO index
+    double *buf = nullptr;                                    // T [W][N][N] | Tt [N][N][W] | Zh [W][N][N]
+    if (tf_malloc(&buf, 3 * nT * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); TF_FAIL(ctx, TF_ENOMEM, "tf_mp3_ladder_probe: out of device memory"); }
+    auto fail = [&](int code, const char *m) { ctx->err = m; (void)tf_free(buf); return code; };
+    double *Tm = buf, *Tt = Tm + nT, *Zd = Tt + nT;
+    std::vector<double> h(nT);
+    for (int p0 = 0; p0 < n; p0 += W) {
+        const int nb = std::min(W, n - p0);
+        for (int p = 0; p < nb; ++p)
+            for (int x = 0; x < N; ++x) {
+                const double *src = T + (size_t)(p0 + p) * nn + (size_t)oI[x] * N;
+                double *dst = h.data() + (size_t)p * nn + (size_t)x * N;
+                for (int y = 0; y < N; ++y) dst[y] = src[oI[y]];
+            }
+        // every byte of the output 0xff first: an element the kernel does not write comes back as a NaN
+        if (hipMemcpy(Tm, h.data(), (size_t)nb * nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(Zd, 0xff, nT * sizeof(double)) != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: copy failed");
+        if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zd)) return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: ladder kernel launch failed");
+        if (hipMemcpy(h.data(), Zd, (size_t)nb * nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: the ladder kernel failed on the device");
+        for (int p = 0; p < nb; ++p)
+            for (int x = 0; x < N; ++x) {
+                const double *src = h.data() + (size_t)p * nn + (size_t)x * N;
+                double *dst = Zh + (size_t)(p0 + p) * nn + (size_t)oI[x] * N;
+                for (int y = 0; y < N; ++y) dst[oI[y]] = src[y];
+            }
+    }
+    (void)tf_free(buf);
     return TF_OK;
 }
 

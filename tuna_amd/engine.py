@@ -266,6 +266,16 @@ class Engine:
         return {"E_OS": E_OS, "E_SS": E_SS, "E_MP2": E_OS + E_SS, "E_pp": e3[0], "E_hh": e3[1], "E_ring": e3[2],
                 "E_MP3": e3[0] + e3[1] + e3[2], "seconds": list(t)}
 
+    def mp3_ladder_probe(self, T) -> np.ndarray:
+        """Zh[p] = the stored-triangle ladder contraction of the packed tensor with T[p] ([N,N] or [n,N,N], any matrices), by the kernel
+        and the batching of mp3_rhf (tunafock.h: tf_mp3_ladder_probe); Z[T] = Zh[T] + Zh[T^T]^T."""
+        T = f64(T)
+        if T.ndim not in (2, 3) or T.shape[-1] != self.N or T.shape[-2] != self.N:
+            raise ValueError(f"mp3_ladder_probe: matrices must be [{self.N},{self.N}] or [n,{self.N},{self.N}], got {T.shape}")
+        Zh = np.zeros_like(T)
+        self._check(self._L.tf_mp3_ladder_probe(self._ctx, 1 if T.ndim == 2 else T.shape[0], ptr(T), ptr(Zh)))
+        return Zh
+
     def diagonalise(self, F, X):
         """(epsilons, molecular_orbitals) = eigh(sym(X^T F X)), C = X C' on the device (scf:222-250)."""
         F, X = f64(F), f64(X)
