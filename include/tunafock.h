@@ -306,6 +306,41 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
  * TF_EINVAL (the context stays usable) without a tensor, with n < 1, on a NULL pointer, on the rows and tiles layouts, or with world > 1. */
 int tf_mp3_ladder_probe(tf_ctx *ctx, int n, const double *T, double *Zh);
 
+/* ---- coupled-cluster doubles: replaces calculate_coupled_cluster_energy (tuna_cc.py:2950-3175) for restricted LCCD and CCD ---- */
+
+typedef struct {
+    int32_t method;             /* 0 = LCCD (tuna_cc.py:830-864), 1 = CCD (tuna_cc.py:915-960) */
+    int32_t max_iter;           /* CORRMAXITER (100)                               */
+    int32_t use_diis;           /* DIIS / NODIIS                                   */
+    int32_t max_diis;           /* DIIS n (6): amplitude vectors kept              */
+    double conv_delta_E;        /* |dE| below this and ...                         */
+    double conv_amplitudes;     /* ... ||t - t_old||_2 below this: AMPCONV (1e-8)  */
+    double damping;             /* CORRDAMP (0): t <- damping t_old + (1 - damping) t */
+} tf_cc_opts;
+
+typedef struct {
+    double e_corr;              /* sum [2 (ia|jb) - (ib|ja)] t_ijab of the last step */
+    double e_mp2;               /* the same sum for the guess t = (ia|jb) / D: E_OS + E_SS of tf_mp2_rhf */
+    int32_t n_iter;
+    int32_t converged;
+    double *table;              /* [max_iter,3] caller-allocated, may be NULL: step, E_corr, dE */
+    double *t2;                 /* [o,o,v,v] caller-allocated, may be NULL: t_ijab of the last step */
+    double seconds[4];          /* wall time, MO blocks, ladder (all iterations), the rest */
+} tf_cc_result;
+
+/* Restricted LCCD / CCD from canonical RHF orbitals C [N,N] and eps [N]; windows as tf_mp3_rhf: occupied [n_frozen, n_occ), virtual
+ * [n_occ, N).  The MO blocks (ia|jb), (ij|ab), (ik|jl) are made once; every iteration is one pass of the AO-direct ladder of tf_mp3_rhf
+ * over the current amplitudes (the v^4 block is never formed), rocBLAS GEMMs for the hole-hole and ring terms -- CCD: on the
+ * intermediates F_ik, F_ca, W_ijkl, W_icak, W_ciak, which need the same three blocks only -- and one fused update kernel; amplitudes,
+ * blocks and the DIIS history stay on the device.  Order of a step (tuna_cc.py:3004-3161): new amplitudes; their energy and dE (the
+ * first dE is taken from zero); converged if |dE| < conv_delta_E and ||t - t_old||_2 < conv_amplitudes; otherwise the new amplitudes
+ * and t - t_old join the DIIS history (the oldest pair leaves once there are more than max_diis), from step 3 on the amplitudes are
+ * extrapolated (B matrix with -1 borders; a singular B clears the history and skips the extrapolation), then damping.
+ * TF_ENOTCONV after max_iter steps: table, n_iter, e_corr and t2 then hold the last step.  TF_EINVAL (the context stays usable) without a
+ * tensor, on a NULL opts, C, eps or out, unless 0 <= n_frozen < n_occ < N, with max_iter < 1, a method other than 0 and 1, or world > 1.
+ * TF_ENOMEM, with the size in the message, when the work space does not fit. */
+int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_cc_result *out);
+
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */
 int tf_diagonalise(tf_ctx *ctx, int n, const double *F, const double *X, double *eps, double *C);

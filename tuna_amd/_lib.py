@@ -38,13 +38,23 @@ class ScfUhfResult(C.Structure):                          # tf_scf_uhf_result
                 ("F_spin", C.c_void_p * 2)]
 
 
+class CcOpts(C.Structure):                                # tf_cc_opts
+    _fields_ = [("method", C.c_int32), ("max_iter", C.c_int32), ("use_diis", C.c_int32), ("max_diis", C.c_int32),
+                ("conv_delta_E", C.c_double), ("conv_amplitudes", C.c_double), ("damping", C.c_double)]
+
+
+class CcResult(C.Structure):                              # tf_cc_result
+    _fields_ = [("e_corr", C.c_double), ("e_mp2", C.c_double), ("n_iter", C.c_int32), ("converged", C.c_int32),
+                ("table", C.c_void_p), ("t2", C.c_void_p), ("seconds", C.c_double * 4)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)     # tf_allreduce_fn
 
 EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normalize", "tf_set_basis", "tf_get_norms",
            "tf_dims", "tf_get_sph_matrix", "tf_one_electron", "tf_cross_overlap", "tf_build_eri", "tf_eri_storage",
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
            "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_shard_plan", "tf_jk_profile",
-           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp3_ladder_probe", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
+           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
            "tf_dft_clear", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
 
@@ -113,6 +123,7 @@ def lib():
     L.tf_mp2_uhf.restype = ci; L.tf_mp2_uhf.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, dp, dp]
     L.tf_mp3_rhf.restype = ci; L.tf_mp3_rhf.argtypes = [vp, ci, ci, vp, vp, dp, dp, dp]
     L.tf_mp3_ladder_probe.restype = ci; L.tf_mp3_ladder_probe.argtypes = [vp, ci, vp, vp]
+    L.tf_ccd_rhf.restype = ci; L.tf_ccd_rhf.argtypes = [vp, C.POINTER(CcOpts), ci, ci, vp, vp, C.POINTER(CcResult)]
     L.tf_dft_setup.restype = ci; L.tf_dft_setup.argtypes = [vp, C.c_int64, vp, vp, ci, ci, cd, cd, cd]
     L.tf_dft_vxc.restype = ci; L.tf_dft_vxc.argtypes = [vp, vp, vp, dp, dp, dp]
     L.tf_dft_vxc_unrestricted.restype = ci; L.tf_dft_vxc_unrestricted.argtypes = [vp, vp, vp, vp, vp, dp, dp, dp]

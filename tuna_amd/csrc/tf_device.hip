@@ -33,6 +33,7 @@
 #include "tf_scf.hip.h"
 #include "tf_mp2.hip.h"
 #include "tf_mp3.hip.h"
+#include "tf_ccd.hip.h"
 #include "tf_dft.hip.h"
 
 // ---- small-block cache for THIS file's device allocations ------------------------------------------------------------------------
@@ -3780,6 +3781,91 @@ static bool mp3_ladder_batch(tf_ctx *ctx, const double *Tm, int nb, double *Tt, 
     return hipGetLastError() == hipSuccess;
 }
 
+// The MO blocks of tf_mp3_rhf and tf_ccd_rhf through mo_transform_device: (ia|jb) = g1[i][a][j][b], (ab|ij) = g2[a][b][i][j],
+// (ki|lj) = g3[k][i][l][j].  On failure ctx->err is set and the blocks made so far stay with the caller (who frees them).
+static int mp3_mo_blocks(tf_ctx *ctx, const char *who, const std::vector<double> &Co, const std::vector<double> &Cv, int o, int v, double **pg1,
+                         double **pg2, double **pg3)
+{
+    const int N = ctx->N;
+    const long long nn = (long long)N * N;
+    int rc;
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, pg1, nullptr))) return rc;
+    {
+        // (ab|ij) = g2[a][b][i][j], in slices of the first virtual index: on the packed and tiles layouts the transformation also forms
+        // the image with (ab) on the ket side, whose work space grows as N^2 v^2 (190 GB at N = 400); a slice of nc virtuals keeps it
+        // near 4 GB
+        if (tf_malloc(pg2, (size_t)v * v * o * o * sizeof(double)) != hipSuccess) { ctx->err = std::string(who) + ": out of device memory"; return TF_ENOMEM; }
+        double *g2 = *pg2;
+        const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
+        std::vector<double> Cs((size_t)N * nc);
+        for (int a0 = 0; a0 < v; a0 += nc) {
+            const int na = std::min(nc, v - a0);
+            for (int m = 0; m < N; ++m)
+                for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = Cv[(size_t)m * v + a0 + a];
+            double *d_s = nullptr;
+            if ((rc = mo_transform_device(ctx, Cs.data(), na, Cv.data(), v, Co.data(), o, Co.data(), o, &d_s, nullptr))) return rc;
+            const hipError_t ce = hipMemcpy(g2 + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
+            (void)tf_free(d_s);
+            if (ce != hipSuccess) { ctx->err = std::string(who) + ": copy failed"; return TF_ENODEVICE; }
+        }
+    }
+    return mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Co.data(), o, pg3, nullptr);
+}
+
+// Doubles of the ladder stage's batch work space: U [W][v][N] (later V [W][N][v]) | T [W][N][N] | Tt [N][N][W] (packed) or
+// J [chunk][N][N] (exchange route) | Zh [W][N][N]
+static size_t mp3_ladder_work_doubles(const tf_ctx *ctx, int v)
+{
+    const int N = ctx->N, W = TFL_W, chunk = ctx->layout == 2 ? 8 : 2;
+    const size_t nn = (size_t)N * N, nU = (size_t)W * v * N, nT = (size_t)W * nn;
+    return nU + nT + (ctx->layout == 1 ? nT : (size_t)chunk * nn) + nT;
+}
+
+// The particle-particle ladder stage of tf_mp3_rhf and tf_ccd_rhf: Y[ij][a][b] = 1/2 C_v^T Z C_v for the amplitudes too[ij][a][b], in
+// batches of TFL_W pairs (packed layout: Z's stored-triangle half through mp3_ladder_batch, the caller adds the transposed pair;
+// rows / tiles: the general-density exchange build).  Cvl = C_v in the AO order of T and Z (internal order on the packed layout),
+// batch = mp3_ladder_work_doubles of work space.  On failure ctx->err is set.
+static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const double *too, const double *Cvl, double *batch, double *Y)
+{
+    const int N = ctx->N;
+    const long long nn = (long long)N * N;
+    const bool packed = ctx->layout == 1;
+    rocblas_handle blas = ctx->scf.blas;
+    const int W = TFL_W, npair = o * o;
+    const size_t nU = (size_t)W * v * N, nT = (size_t)W * nn;
+    const int chunk = ctx->layout == 2 ? 8 : 2;
+    double *U = batch, *Tm = U + nU, *Tt = Tm + nT, *Jx = Tt, *Zh = Tt + (packed ? nT : (size_t)chunk * nn);
+    int rc;
+#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) { ctx->err = std::string(who) + ": rocBLAS failed: " #call; return TF_ELINALG; } } while (0)
+    for (int p0 = 0; p0 < npair; p0 += W) {
+        const int nb = std::min(W, npair - p0);
+        const double *tb = too + (size_t)p0 * v * v;
+        // U_p = t_p C_v^T (packed: Zh of T_p; exchange route: K of T_p^T, so t_p^T), T_p = C_v U_p
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
+        if (packed) {
+            if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zh)) { ctx->err = std::string(who) + ": ladder kernel launch failed"; return TF_ENODEVICE; }
+        } else {
+            for (int d = 0; d < nb; d += chunk) {
+                const int nd = std::min(chunk, nb - d);
+                const double *pp[8]; double *jj[8], *kk[8];
+                int nonsym[8];
+                for (int q = 0; q < 8; ++q) {
+                    const int dq = d + std::min(q, nd - 1);
+                    pp[q] = Tm + (size_t)dq * nn; jj[q] = Jx + (size_t)std::min(q, nd - 1) * nn; kk[q] = Zh + (size_t)dq * nn; nonsym[q] = 1;
+                }
+                if ((rc = launch_jk(ctx, nd, pp, jj, kk, 0, nonsym))) return rc;
+            }
+        }
+        // V_p = Z_p C_v, Y_p = 1/2 C_v^T V_p
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, v, N, 1.0, Zh, N, nn, Cvl, v, 0, 0.0, U, v, (long long)N * v, nb));
+        MP3_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, N, 0.5, Cvl, v, 0, U, v, (long long)N * v, 0.0, Y + (size_t)p0 * v * v, v,
+                                        (long long)v * v, nb));
+    }
+#undef MP3_BLAS
+    return TF_OK;
+}
+
 // Restricted MP3 (run_restricted_MP3, tuna_mp.py:1410-1470; tf_mp3.hip.h has the expressions).  Stages: the MO blocks (ia|jb),
 // (ij|ab), (ki|lj) through mo_transform_device; amplitudes and MP2 partials (mp3_amp_kernel); the particle-particle ladder in the AO
 // basis, batches of TFL_W pairs; the hole-hole and ring GEMMs; one energy reduction.
@@ -3797,7 +3883,7 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
     int rc = tfscf::ensure(ctx->scf, N, 6, msg);
     if (rc) { ctx->err = msg; return rc; }
     const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o, nn = (long long)N * N;
+    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o;
     if (ov > 0x7fffffffLL || (long long)v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: dimension overflow");
     const bool packed = ctx->layout == 1;                     // the AO-direct ladder kernel; rows / tiles: the exchange build
     std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
@@ -3810,26 +3896,7 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
     auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
     auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
     // ---- MO blocks: (ia|jb) = g1[i][a][j][b], (ab|ij) = g2[a][b][i][j], (ki|lj) = g3[k][i][l][j]
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, &g1, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-    {
-        // (ab|ij) = g2[a][b][i][j], in slices of the first virtual index: on the packed and tiles layouts the transformation also forms
-        // the image with (ab) on the ket side, whose work space grows as N^2 v^2 (190 GB at N = 400); a slice of nc virtuals keeps it
-        // near 4 GB
-        if (tf_malloc(&g2, (size_t)v * v * o * o * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory");
-        const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
-        std::vector<double> Cs((size_t)N * nc);
-        for (int a0 = 0; a0 < v; a0 += nc) {
-            const int na = std::min(nc, v - a0);
-            for (int m = 0; m < N; ++m)
-                for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = Cv[(size_t)m * v + a0 + a];
-            double *d_s = nullptr;
-            if ((rc = mo_transform_device(ctx, Cs.data(), na, Cv.data(), v, Co.data(), o, Co.data(), o, &d_s, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-            const hipError_t ce = hipMemcpy(g2 + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
-            (void)tf_free(d_s);
-            if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
-        }
-    }
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Co.data(), o, &g3, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    if ((rc = mp3_mo_blocks(ctx, "tf_mp3_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
     const auto t1 = stamp();
     // ---- work space: tov | too | tp | tsw | Moo | M1 | M2 | S13 | S2 | Xhh | Y
     const size_t nwork = (size_t)10 * B2 + (size_t)o4;
@@ -3856,46 +3923,16 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
     const auto t2 = stamp();
     // ---- particle-particle ladder: Y[ij][a][b] = 1/2 C_v^T Z C_v, in batches of TFL_W pairs
     rocblas_handle blas = ctx->scf.blas;
-    const int W = TFL_W, npair = o * o;
-    const size_t nU = (size_t)W * v * N, nT = (size_t)W * nn;
-    // batch work space: U [W][v][N] (later V [W][N][v]) | T [W][N][N] | Tt [N][N][W] (packed) or J [chunk][N][N] (exchange route) | Zh [W][N][N]
-    const int chunk = ctx->layout == 2 ? 8 : 2;
-    const size_t nbatch = nU + nT + (packed ? nT : (size_t)chunk * nn) + nT;
-    if (tf_malloc(&batch, nbatch * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory for the ladder work space");
-    double *U = batch, *Tm = U + nU, *Tt = Tm + nT, *Jx = Tt, *Zh = Tt + (packed ? nT : (size_t)chunk * nn);
+    if (tf_malloc(&batch, mp3_ladder_work_doubles(ctx, v) * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory for the ladder work space");
     const double *Cvl = d_Cv;                                 // C_v in the AO order of T and Z (internal order on the packed layout)
     if (packed) {
         hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
         Cvl = d_Cvi;
     }
-#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp3_rhf: rocBLAS failed: " #call); } while (0)
-    for (int p0 = 0; p0 < npair; p0 += W) {
-        const int nb = std::min(W, npair - p0);
-        const double *tb = too + (size_t)p0 * v * v;
-        // U_p = t_p C_v^T (packed: Zh of T_p; exchange route: K of T_p^T, so t_p^T), T_p = C_v U_p
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
-        if (packed) {
-            if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zh)) return fail(TF_ENODEVICE, "tf_mp3_rhf: ladder kernel launch failed");
-        } else {
-            for (int d = 0; d < nb; d += chunk) {
-                const int nd = std::min(chunk, nb - d);
-                const double *pp[8]; double *jj[8], *kk[8];
-                int nonsym[8];
-                for (int q = 0; q < 8; ++q) {
-                    const int dq = d + std::min(q, nd - 1);
-                    pp[q] = Tm + (size_t)dq * nn; jj[q] = Jx + (size_t)std::min(q, nd - 1) * nn; kk[q] = Zh + (size_t)dq * nn; nonsym[q] = 1;
-                }
-                if ((rc = launch_jk(ctx, nd, pp, jj, kk, 0, nonsym))) { const std::string m = ctx->err; return fail(rc, m); }
-            }
-        }
-        // V_p = Z_p C_v, Y_p = 1/2 C_v^T V_p
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, v, N, 1.0, Zh, N, nn, Cvl, v, 0, 0.0, U, v, (long long)N * v, nb));
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, N, 0.5, Cvl, v, 0, U, v, (long long)N * v, 0.0, Y + (size_t)p0 * v * v, v,
-                                        (long long)v * v, nb));
-    }
+    if ((rc = mp3_ladder_stage(ctx, "tf_mp3_rhf", o, v, too, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
     const auto t3 = stamp();
     // ---- hole-hole and ring terms
+#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp3_rhf: rocBLAS failed: " #call); } while (0)
     {
         const long long tot = std::max(B2, o4);
         hipLaunchKernelGGL(tfmp3::mp3_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3, o, v, Moo, M1, M2);
@@ -3924,6 +3961,206 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
         seconds[2] = std::chrono::duration<double>(t3 - t2).count();
         seconds[3] = std::chrono::duration<double>((t2 - t1) + (t4 - t3)).count();
     }
+    return TF_OK;
+}
+
+// Restricted LCCD / CCD (tuna_cc.py:830-864, :915-960, the loop of :3004-3161; tf_ccd.hip.h has the expressions and the operands).
+// Stages: the MO blocks of tf_mp3_rhf, once; per step the amplitude operands, the ladder stage of tf_mp3_rhf on the current amplitudes,
+// CCD's intermediates, the hole-hole and ring GEMMs, the fused update; then convergence, DIIS and damping.  Only dE, ||dt|| and the new
+// row of the DIIS matrix come back to the host per step.
+int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_cc_result *out)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
+    if (opts->max_iter < 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: max_iter must be at least 1");
+    if (opts->method != 0 && opts->method != 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: method must be 0 (LCCD) or 1 (CCD)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: a sharded tensor (world > 1) is not supported");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o;
+    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: dimension overflow");
+    const bool packed = ctx->layout == 1, ccd = opts->method == 1, diis = opts->use_diis != 0;
+    const int keep = std::max(1, std::min(opts->max_diis, 32));   // vectors of the history after the oldest has left (at most 32 here)
+    const int nslot = diis ? std::max(keep, 2) + 1 : 0;       // (steps 1 and 2 store without dropping: tuna_cc.py:482)
+    out->e_corr = out->e_mp2 = 0.0; out->n_iter = 0; out->converged = 0;
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *work = nullptr, *hist = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *batch = nullptr;
+    int *d_slot = nullptr;
+    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
+    bool blas_mode_set = false;
+    auto cleanup = [&]() {
+        for (double *p : {g1, g2, g3, work, hist, d_small, d_Cv, d_Cvi, batch}) if (p) (void)tf_free(p);
+        if (d_slot) (void)tf_free(d_slot);
+        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
+    };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- MO blocks, as tf_mp3_rhf makes them
+    if ((rc = mp3_mo_blocks(ctx, "tf_ccd_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t1 = stamp();
+    // ---- work space, in arrays of o^2 v^2: t | t_new | dt | Tn | Tx | Tm | S1 | S2 | X | Y | H  (CCD: | A1 | A2 | Gx | Gw | Goo), then
+    //      Moo, W (o^4 each), F_ik, F_ca; the DIIS history: nslot amplitude vectors, then nslot error vectors
+    const int nblk = 1024;
+    const size_t narr = ccd ? 16 : 11;
+    const size_t nwork = narr * (size_t)B2 + 2 * (size_t)o4 + (size_t)o * o + (size_t)v * v;
+    const size_t nsmall = (size_t)nblk * std::max(2, nslot) + 2 * (size_t)std::max(2, nslot) + (size_t)N;
+    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
+    {
+        const double gb = (double)(nwork + 2 * (size_t)nslot * B2 + nladder) * sizeof(double) / 1e9;
+        char text[160];
+        snprintf(text, sizeof text, "tf_ccd_rhf: out of device memory for %.2f GB of work space (%zu arrays of o^2 v^2 values)", gb, narr + 2 * (size_t)nslot);
+        if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || (nslot && tf_malloc(&hist, 2 * (size_t)nslot * B2 * sizeof(double)) != hipSuccess) ||
+            tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_slot, (size_t)std::max(1, nslot) * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    double *t = work, *t_new = t + B2, *dt = t_new + B2, *Tn = dt + B2, *Tx = Tn + B2, *Tm = Tx + B2, *S1 = Tm + B2, *S2 = S1 + B2, *X = S2 + B2,
+           *Y = X + B2, *H = Y + B2, *A1 = g1, *A2 = H, *Gx = nullptr, *Gw = nullptr, *Goo = nullptr, *tail = H + B2;
+    if (ccd) { A1 = tail; A2 = A1 + B2; Gx = A2 + B2; Gw = Gx + B2; Goo = Gw + B2; tail = Goo + B2; }
+    double *Moo = tail, *Woo = Moo + o4, *Fik = Woo + o4, *Fca = Fik + (size_t)o * o;
+    double *d_part = d_small, *d_sum = d_part + (size_t)nblk * std::max(2, nslot), *d_coef = d_sum + std::max(2, nslot), *d_eps = d_coef + std::max(2, nslot);
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+    const double *Cvl = d_Cv;                                 // C_v in the AO order of the ladder (internal order on the packed layout)
+    if (packed) {
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
+        Cvl = d_Cvi;
+    }
+    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
+    // ---- the integral operands, the guess amplitudes and their MP2 energy
+    {
+        const long long tot = std::max(B2, o4);
+        hipLaunchKernelGGL(tfccd::cc_integral_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3,
+                           o, v, H, Moo, Gx, Gw, Goo);
+    }
+    hipLaunchKernelGGL(tfccd::cc_guess_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, t, d_part);
+    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
+    {
+        double e2[2];
+        if (hipMemcpy(e2, d_sum, sizeof e2, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the guess kernels failed on the device");
+        out->e_mp2 = e2[0] + e2[1];
+    }
+    (void)tf_free(g2); g2 = nullptr;                          // (ab|ij) lives on in H
+    (void)tf_free(g3); g3 = nullptr;
+    rocblas_handle blas = ctx->scf.blas;
+    // the iteration's GEMMs run without atomics (the skinny ones -- F_ik, W_ijkl -- would otherwise take rocBLAS's split-K kernels, whose
+    // sums change from run to run); the AO->MO transformation above keeps them, as everywhere else
+    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
+        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
+        blas_mode_set = true;
+    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
+    std::vector<int> order;                                   // slots of the history, oldest first
+    std::vector<double> Bee((size_t)std::max(1, nslot) * std::max(1, nslot), 0.0);   // error dots by slot
+    double E = 0.0, ladder_seconds = 0.0;
+    int step = 0, code = TF_ENOTCONV;
+#define CCD_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_ccd_rhf: rocBLAS failed: " #call); } while (0)
+    for (step = 1; step <= opts->max_iter; ++step) {
+        const double E_old = E;
+        hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, t, o, v, Tn, Tx, Tm);
+        // ---- particle-particle ladder on the bare (ac|bd): Y[ij][a][b]
+        const auto l0 = stamp();
+        if ((rc = mp3_ladder_stage(ctx, "tf_ccd_rhf", o, v, t, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
+        const auto l1 = stamp();
+        ladder_seconds += std::chrono::duration<double>(l1 - l0).count();
+        const double *W = Moo;
+        if (ccd) {
+            // F_ik = Tn [i][(cld)] Gw [k][(cld)]^T;  F_ca = -sum_k Gw_k [c][(ld)] Tn_k [a][(ld)]^T
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, Tn, ovv, Gw, ovv, 0.0, Fik, o));
+            for (int k = 0; k < o; ++k)
+                CCD_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, -1.0, Gw + (size_t)k * v * ov, iov, Tn + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fca, v));
+            // W_ijkl = Moo + t [(ij)][(cd)] Goo [(kl)][(cd)]^T
+            if (hipMemcpyAsync(Woo, Moo, (size_t)o4 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(A1, g1, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(A2, H, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, t, vv, Goo, vv, 1.0, Woo, oo));
+            W = Woo;
+            // A1 = G + 1/2 Tn Gw - 1/2 Tx G;  A2 = H - 1/2 Tx Gx
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 0.5, Tn, iov, Gw, iov, 1.0, A1, iov));
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, g1, iov, 1.0, A1, iov));
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, Gx, iov, 1.0, A2, iov));
+        }
+        // X[(ij)][(ab)] = 1/2 W [(ij)][(kl)] t [(kl)][(ab)]  (CCD: + F_ca^T t_ij - F_ik t)
+        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, W, oo, t, vv, 0.0, X, vv));
+        if (ccd) {
+            CCD_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, v, 1.0, Fca, v, 0, t, v, (long long)vv, 1.0, X, v, (long long)vv, oo));
+            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fik, o, t, ovv, 1.0, X, ovv));
+        }
+        // S1 = A1 Tm - A2 Tn;  S2 = A2 Tx   (all [(ov)][(ov)])
+        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A1, iov, Tm, iov, 0.0, S1, iov));
+        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, A2, iov, Tn, iov, 1.0, S1, iov));
+        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A2, iov, Tx, iov, 0.0, S2, iov));
+        // ---- the fused update: t_new, dt, E and ||dt||^2
+        hipLaunchKernelGGL(tfccd::cc_update_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, n_occ, o, v, t, Y, packed ? 1 : 0, X, S1, S2, t_new, dt,
+                           d_part);
+        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
+        double red[2];
+        if (hipMemcpy(red, d_sum, sizeof red, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the iteration kernels failed on the device");
+        E = red[0];
+        const double dE = E - E_old, dnorm = std::sqrt(red[1]);
+        out->e_corr = E; out->n_iter = step;
+        if (out->table) { double *row = out->table + 3 * (size_t)(step - 1); row[0] = step; row[1] = E; row[2] = dE; }
+        if (!std::isfinite(E) || !std::isfinite(dnorm) || E > 1000.0) { code = TF_ELINALG; break; }     // tuna_cc.py:3129
+        if (std::fabs(dE) < opts->conv_delta_E && dnorm < opts->conv_amplitudes) { code = TF_OK; out->converged = 1; break; }
+        if (step == opts->max_iter) break;
+        // ---- DIIS: store (t_new, dt); from step 3 on drop the oldest beyond max_diis and extrapolate
+        int n_ex = 0;
+        if (diis) {
+            int s = 0;
+            while (std::find(order.begin(), order.end(), s) != order.end()) ++s;
+            order.push_back(s);
+            if (hipMemcpyAsync(hist + (size_t)s * B2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(hist + (size_t)(nslot + s) * B2, dt, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+            if (step > 2 && (int)order.size() > keep) order.erase(order.begin());
+            const int n = (int)order.size();
+            if (hipMemcpy(d_slot, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+            hipLaunchKernelGGL(tfccd::cc_diis_dots_kernel, dim3(nblk, (unsigned)n), dim3(256), 0, 0, hist + (size_t)nslot * B2, B2, d_slot, n, n - 1, B2, d_part);
+            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, n, d_sum);
+            std::vector<double> row(n);
+            if (hipMemcpy(row.data(), d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the DIIS kernels failed on the device");
+            for (int m = 0; m < n; ++m) Bee[(size_t)order[m] * nslot + s] = Bee[(size_t)s * nslot + order[m]] = row[m];
+            if (step > 2) {
+                std::vector<double> B((size_t)n * n), coef(n);
+                for (int p = 0; p < n; ++p)
+                    for (int q = 0; q < n; ++q) B[(size_t)p * n + q] = Bee[(size_t)order[p] * nslot + order[q]];
+                if (tfccd::diis_solve(n, B.data(), coef.data())) {
+                    if (hipMemcpy(d_coef, coef.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+                    n_ex = n;
+                } else {
+                    order.clear();                            // "(Resetting DIIS)", tuna_cc.py:398-408
+                }
+            }
+        }
+        hipLaunchKernelGGL(tfccd::cc_mix_kernel, grid_e, dim3(256), 0, 0, t, t_new, hist, B2, d_slot, d_coef, n_ex, opts->damping, B2);
+    }
+#undef CCD_BLAS
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: a kernel launch failed");
+    if (out->t2 && hipMemcpy(out->t2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
+    const auto t4 = stamp();
+    cleanup();
+    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
+    out->seconds[1] = std::chrono::duration<double>(t1 - t0).count();
+    out->seconds[2] = ladder_seconds;
+    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
+    if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
+    if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
     return TF_OK;
 }
 

@@ -7,7 +7,9 @@ Input line format `TYPE : A B R : METHOD BASIS : KEYWORDS` (tuna.py:87-99).  Sup
 (restricted) or UHF / any multiplicity via ML (unrestricted), a functional of tuna_amd.dft.FUNCTIONALS (restricted Kohn-Sham; unrestricted
 with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tuna_amd/data, and the SCF keywords of SURVEY.md section 5
 (LOOSE/MEDIUM/TIGHT/EXTREME, MAXITER n, DIIS [n]/NODIIS, DAMP x/NODAMP/MAXDAMP x, SLOWCONV/VERYSLOWCONV, HFX x,
-CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  Everything numerical runs on the GPU through the C ABI.  The initial
+CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, and the coupled-cluster doubles
+methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
+iterations too).  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
 """
 from __future__ import annotations
@@ -59,6 +61,10 @@ class Calculation:
     opposite_spin_scaling: float = 6 / 5               # OSS, calc:209
     mp3: bool = False                                  # MP3 / SCS-MP3 after the MP2 step (tuna_mp.py:1814-1828)
     MP3_scaling: float = 1 / 4                         # MP3S / MP3SCALING / MP3SCAL, calc:183 (applied by SCS-MP3 only)
+    coupled_cluster: str | None = None                 # "LCCD" or "CCD" after the SCF (tuna_cc.py:830-864, :915-960)
+    amp_conv: float = 1e-8                             # AMPCONV, calc:184
+    correlated_max_iter: int = 100                     # CORRMAXITER, calc:191
+    correlated_damping_parameter: float = 0.0          # CORRDAMP [x], calc:201 (without a number: the default, no damping)
 
 
 @dataclass
@@ -161,6 +167,20 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.opposite_spin_scaling = float(value())
         elif p in ("MP3S", "MP3SCALING", "MP3SCAL"):
             calc.MP3_scaling = float(value())
+        elif p == "AMPCONV":
+            calc.amp_conv = float(value())
+        elif p == "CORRMAXITER":
+            calc.correlated_max_iter = int(value())
+        elif p == "CORRDAMP":                                # a boolean with an optional value (calc:201, as DIIS above)
+            calc.correlated_damping_parameter = 0.0
+            if k + 1 < len(params):
+                try:
+                    x = float(params[k + 1])
+                except ValueError:
+                    x = None
+                if x is not None:
+                    calc.correlated_damping_parameter = x
+                    next(it)
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -332,12 +352,14 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(f"\n Correlation energy from {tag}MP2:  {' ' * (4 - len(tag))}" + f"{r['E_MP2']:16.10f}")
                     log(f" Correlation energy from {tag}MP3:  {' ' * (4 - len(tag))}" + f"{E_MP3:16.10f}\n")
                     log(" Total correlation energy:         " + f"{r['E_MP2'] + E_MP3:16.10f}\n")
+        if calc.coupled_cluster:
+            run_coupled_cluster_doubles(calc, molecule, out, engine, silent, log)
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
         if calc.dipole or calc.polarisability or calc.hyperpolarisability:
             # finite-field properties (energy:941-957): the cycles of a property run in lockstep on the resident tensor
             from . import properties as props
-            if calc.method == "MP2":
+            if calc.method == "MP2" or calc.coupled_cluster:
                 raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
             t0 = time.perf_counter()
             fe = props.FieldEnergies(molecule, calc, integrals, V_NN, X, guess)
@@ -356,6 +378,44 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             engine.close()
 
 
+def run_coupled_cluster_doubles(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """Restricted LCCD / CCD on the device-resident tensor (all-electron), tf_ccd_rhf: the iteration of calculate_coupled_cluster_energy
+    (tuna_cc.py:2950-3175) with its log lines (tuna_cc.py:163-199, :3139, :3164-3170; kernel:1282).  The energy threshold is the chosen
+    SCF set's delta_E, or ECONV (calc:518)."""
+    name = calc.coupled_cluster
+    conv_E = calc.SCF_conv["delta_E"]
+    t0 = time.perf_counter()
+    r = engine.ccd_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, method=name, max_iter=calc.correlated_max_iter,
+                       conv_delta_E=conv_E, conv_amplitudes=calc.amp_conv, use_diis=calc.DIIS, max_diis=calc.max_DIIS_matrices,
+                       damping=calc.correlated_damping_parameter, allow_unconverged=True)
+    out.timings[f"{name} energy"] = time.perf_counter() - t0
+    if not silent:
+        log(f"              {name:>5} Energy and Density ")
+        log(f"  Energy convergence tolerance:        {conv_E:.10f}")
+        log(f"  Amplitude convergence tolerance:     {calc.amp_conv:.10f}")
+        log(f"\n  Guess t-amplitude MP2 energy:       {r['E_MP2']:.10f}\n")
+        if calc.correlated_damping_parameter != 0:
+            log(f"  Using damping parameter of {calc.correlated_damping_parameter:.2f} for convergence.")
+        if calc.DIIS:
+            log(f"  Using DIIS, storing {calc.max_DIIS_matrices} matrices, for convergence.")
+        log(f"\n  Starting {name} iterations...\n")
+        log("  Step          Correlation E               DE")
+        for step, E, dE in r["table"]:
+            log(f"  {step:3.0f}           {E:13.10f}         {dE:13.10f}")
+    if not r["converged"]:
+        raise TunaError(f"The {name} iterations failed to converge! Try increasing the maximum iterations with CORRMAXITER?", -4)
+    E_CC = r["E_corr"]
+    if not silent:
+        log(f"\n  Singles contribution:               {0.0:13.10f}")
+        log(f"  Connected doubles contribution:     {E_CC:13.10f}")
+        log(f"  Disconnected doubles contribution:  {0.0:13.10f}")
+        log(f"\n  {name} correlation energy:  {' ' * (10 - len(name))}    {E_CC:.10f}")
+        log(f" Correlation energy from {name}:{' ' * max(0, 8 - len(name))} " + f"{E_CC:16.10f}\n")
+    out.cc = r
+    out.correlation_energy_cc = E_CC
+    out.energy += E_CC
+
+
 def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=print):
     """tuna.py:345 `run(input_line, suppress_output)` for single-point restricted Hartree-Fock."""
     ctype, method, basis, symbols, R, params = parse_input(input_line)
@@ -372,10 +432,18 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         method = method[1:]
     if method in ("UMP3", "USCS-MP3"):
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP3 runs on a closed-shell restricted reference.")
+    if method in ("UCCD", "ULCCD"):
+        raise TunaError(f"Unrestricted {method[1:]} is not available in this build: {method[1:]} runs on a closed-shell restricted reference.")
     mp3 = method in ("MP3", "SCS-MP3")
-    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3") and method not in dft_mod.FUNCTIONALS:
+    cc = method if method in ("CCD", "LCCD") else None       # coupled-cluster doubles; every other CC name stays unsupported
+    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3", "CCD", "LCCD") and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP" in method else "HF"), basis))
+    calc.coupled_cluster = cc
+    if cc and calc.multiplicity != 1:
+        raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
+    if cc and (calc.dipole or calc.polarisability or calc.hyperpolarisability):
+        raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
     calc.spin_component_scaling = method in ("SCS-MP2", "SCS-MP3")      # tuna_mp.py:872: "SCS" in the name scales the MP2 part too
     calc.mp3 = mp3
     if mp3 and calc.multiplicity != 1:

@@ -266,6 +266,35 @@ class Engine:
         return {"E_OS": E_OS, "E_SS": E_SS, "E_MP2": E_OS + E_SS, "E_pp": e3[0], "E_hh": e3[1], "E_ring": e3[2],
                 "E_MP3": e3[0] + e3[1] + e3[2], "seconds": list(t)}
 
+    def ccd_rhf(self, C, eps, n_occ, n_frozen=0, method="CCD", max_iter=100, conv_delta_E=1e-6, conv_amplitudes=1e-8, use_diis=True,
+                max_diis=6, damping=0.0, return_t2=False, allow_unconverged=False) -> dict:
+        """Restricted LCCD or CCD from canonical RHF orbitals, iterated on the resident tensor (tunafock.h: tf_ccd_rhf; tuna_cc.py:830-864,
+        :915-960, :3004-3161): {"E_corr", "E_MP2", "n_iter", "converged", "table" [n_iter, 3] = step, E_corr, dE, "t2" [o, o, v, v] with
+        return_t2, "seconds" = [wall, MO blocks, ladder, rest]}.  Raises TunaError with the code when the iterations do not converge,
+        unless allow_unconverged: the dict then holds the last step."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"ccd_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if method not in ("LCCD", "CCD"):
+            raise TunaError(f"ccd_rhf: method must be \"LCCD\" or \"CCD\", got {method!r}")
+        import ctypes
+        from ._lib import CcOpts, CcResult
+        o, v = int(n_occ) - int(n_frozen), self.N - int(n_occ)
+        opts = CcOpts(1 if method == "CCD" else 0, int(max_iter), int(bool(use_diis)), int(max_diis), float(conv_delta_E), float(conv_amplitudes),
+                      float(damping))
+        table = np.zeros((max(1, int(max_iter)), 3))
+        t2 = np.zeros((o, o, v, v)) if return_t2 and o > 0 and v > 0 else None
+        res = CcResult()
+        res.table, res.t2 = ptr(table), ptr(t2)
+        rc = self._L.tf_ccd_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ctypes.byref(res))
+        if rc != 0 and not (rc == -4 and allow_unconverged):     # TF_ENOTCONV
+            self._check(rc)
+        out = {"E_corr": res.e_corr, "E_MP2": res.e_mp2, "n_iter": int(res.n_iter), "converged": bool(res.converged),
+               "table": table[:int(res.n_iter)].copy(), "seconds": list(res.seconds)}
+        if return_t2:
+            out["t2"] = t2
+        return out
+
     def mp3_ladder_probe(self, T) -> np.ndarray:
         """Zh[p] = the stored-triangle ladder contraction of the packed tensor with T[p] ([N,N] or [n,N,N], any matrices), by the kernel
         and the batching of mp3_rhf (tunafock.h: tf_mp3_ladder_probe); Z[T] = Zh[T] + Zh[T^T]^T."""
