@@ -296,6 +296,20 @@ int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_f
  * the general-density exchange build.  seconds (may be NULL): [0] wall time, [1] MO blocks, [2] ladder, [3] the rest.
  * TF_EINVAL (the context stays usable) without a tensor, on a NULL pointer, unless 0 <= n_frozen < n_occ < N, or with world > 1. */
 int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double *seconds);
+/* Restricted MP4(SDQ) (level 1) or MP4(DQ) (level 0) from canonical RHF orbitals (run_restricted_MP4, tuna_mp.py:1552-1685, without the
+ * triples); windows, D, t, t' and X[.] (MP3's operator: 1/2 pp + 1/2 hh + ring) as tf_mp3_rhf, L_pqrs = 2 (pq|rs) - (ps|rq):
+ *   e_mp2, e_mp3 = bit for bit what tf_mp3_rhf returns for the same arguments (the same kernels in the same order);
+ *   e_mp4 = {E_S, E_D, E_Q}, E_MP4 their sum:
+ *     E_D = sum t' X[t2],  t2_ijab = (X[t]_ijab + X[t]_jiba) / D: a second pass of the ladder, hole-hole and ring stages;
+ *     E_S = sum t' S,  S_ijab = sum_c t1_jc (ai|bc) - sum_k t1_kb (ai|kj),  t1_ia = -[sum_kld t_klad L_kild - sum_kcd t_kicd L_adkc] / (e_i - e_a)
+ *           (exactly 0.0 at level 0).  The integrals with three virtual indices are never formed: the first ladder pass is
+ *           back-transformed with C_o as well, [C_o^T Z_ij C_v]_ka = sum_cd (kc|ad) t_ijcd, of which the singles need o^2 v sums;
+ *     E_Q = sum t' Q, the six products of t, t and (kc|ld) of tuna_mp.py:1645-1650, as rocBLAS GEMMs.
+ * Work space: 13 arrays of o^2 v^2 values (tf_mp3_rhf: 10) and the ladder's batch; nothing with three or four virtual indices.
+ * seconds (may be NULL): [0] wall time, [1] MO blocks, [2] ladder (both passes), [3] the rest.
+ * TF_EINVAL (the context stays usable) as tf_mp3_rhf, and with a level outside {0, 1}; TF_ENOMEM with the size in the message. */
+int tf_mp4_rhf(tf_ctx *ctx, int level, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double e_mp4[3],
+               double *seconds);
 /* The particle-particle ladder contraction of tf_mp3_rhf on its own (instrumentation, tests): T = n matrices [n][N][N] and
  * Zh [n][N][N], host buffers in the caller's AO order,
  *   Zh[p][mu][nu] = sum_{lambda sigma} R_(mu lambda)[nu][sigma] T[p][lambda][sigma],

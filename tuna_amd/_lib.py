@@ -54,7 +54,7 @@ EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normali
            "tf_dims", "tf_get_sph_matrix", "tf_one_electron", "tf_cross_overlap", "tf_build_eri", "tf_eri_storage",
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
            "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_shard_plan", "tf_jk_profile",
-           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
+           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
            "tf_dft_clear", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
 
@@ -122,6 +122,7 @@ def lib():
     L.tf_mp2_rhf.restype = ci; L.tf_mp2_rhf.argtypes = [vp, ci, ci, vp, vp, dp, dp, dp]
     L.tf_mp2_uhf.restype = ci; L.tf_mp2_uhf.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, dp, dp]
     L.tf_mp3_rhf.restype = ci; L.tf_mp3_rhf.argtypes = [vp, ci, ci, vp, vp, dp, dp, dp]
+    L.tf_mp4_rhf.restype = ci; L.tf_mp4_rhf.argtypes = [vp, ci, ci, ci, vp, vp, dp, dp, dp, dp]
     L.tf_mp3_ladder_probe.restype = ci; L.tf_mp3_ladder_probe.argtypes = [vp, ci, vp, vp]
     L.tf_ccd_rhf.restype = ci; L.tf_ccd_rhf.argtypes = [vp, C.POINTER(CcOpts), ci, ci, vp, vp, C.POINTER(CcResult)]
     L.tf_dft_setup.restype = ci; L.tf_dft_setup.argtypes = [vp, C.c_int64, vp, vp, ci, ci, cd, cd, cd]

@@ -34,6 +34,7 @@
 #include "tf_mp2.hip.h"
 #include "tf_mp3.hip.h"
 #include "tf_ccd.hip.h"
+#include "tf_mp4.hip.h"
 #include "tf_dft.hip.h"
 
 // ---- small-block cache for THIS file's device allocations ------------------------------------------------------------------------
@@ -3825,7 +3826,11 @@ static size_t mp3_ladder_work_doubles(const tf_ctx *ctx, int v)
 // batches of TFL_W pairs (packed layout: Z's stored-triangle half through mp3_ladder_batch, the caller adds the transposed pair;
 // rows / tiles: the general-density exchange build).  Cvl = C_v in the AO order of T and Z (internal order on the packed layout),
 // batch = mp3_ladder_work_doubles of work space.  On failure ctx->err is set.
-static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const double *too, const double *Cvl, double *batch, double *Y)
+// With Col (C_o in that AO order; tf_mp4_rhf's singles) every batch is back-transformed with the occupied coefficients as well:
+// OA[ij][k][a] = C_o^T Zh_ij C_v and, on the packed layout, OB[ij][a][k] = C_v^T Zh_ij C_o (the other stored-triangle half of
+// C_o^T Z_ji C_v); Vo = TFL_W N o doubles of work space.  These GEMMs are skinny and run without rocBLAS's atomics (split-K sums).
+static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const double *too, const double *Cvl, double *batch, double *Y,
+                            const double *Col = nullptr, double *Vo = nullptr, double *OA = nullptr, double *OB = nullptr)
 {
     const int N = ctx->N;
     const long long nn = (long long)N * N;
@@ -3861,6 +3866,21 @@ static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const do
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, v, N, 1.0, Zh, N, nn, Cvl, v, 0, 0.0, U, v, (long long)N * v, nb));
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, N, 0.5, Cvl, v, 0, U, v, (long long)N * v, 0.0, Y + (size_t)p0 * v * v, v,
                                         (long long)v * v, nb));
+        if (Col) {
+            rocblas_atomics_mode mode = rocblas_atomics_allowed;
+            const bool mode_set = rocblas_get_atomics_mode(blas, &mode) == rocblas_status_success &&
+                                  rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success;
+            rocblas_status st = tfmp3::gemm_rm_batched(blas, true, false, o, v, N, 1.0, Col, o, 0, U, v, (long long)N * v, 0.0,
+                                                       OA + (size_t)p0 * o * v, v, (long long)o * v, nb);
+            if (st == rocblas_status_success && packed) {
+                st = tfmp3::gemm_rm_batched(blas, false, false, N, o, N, 1.0, Zh, N, nn, Col, o, 0, 0.0, Vo, o, (long long)N * o, nb);
+                if (st == rocblas_status_success)
+                    st = tfmp3::gemm_rm_batched(blas, true, false, v, o, N, 1.0, Cvl, v, 0, Vo, o, (long long)N * o, 0.0, OB + (size_t)p0 * v * o, o,
+                                                (long long)v * o, nb);
+            }
+            if (mode_set) (void)rocblas_set_atomics_mode(blas, mode);
+            if (st != rocblas_status_success) { ctx->err = std::string(who) + ": rocBLAS failed in the occupied back-transformation"; return TF_ELINALG; }
+        }
     }
 #undef MP3_BLAS
     return TF_OK;
@@ -3960,6 +3980,172 @@ int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const doub
         seconds[1] = std::chrono::duration<double>(t1 - t0).count();
         seconds[2] = std::chrono::duration<double>(t3 - t2).count();
         seconds[3] = std::chrono::duration<double>((t2 - t1) + (t4 - t3)).count();
+    }
+    return TF_OK;
+}
+
+// Restricted MP4(SDQ) / MP4(DQ) (run_restricted_MP4, tuna_mp.py:1552-1685, without the triples; tf_mp4.hip.h has the expressions).
+// Stages: tf_mp3_rhf's own, in its order and with its kernels (so that e_mp2 and e_mp3 are bit for bit its values), the first ladder
+// pass also back-transforming with C_o for the singles; the singles from those o^3 v values and the block (ki|ld); t2 and a second pass
+// of the ladder, hole-hole and ring stages on it; the quadruples' GEMMs.
+int tf_mp4_rhf(tf_ctx *ctx, int level, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double e_mp4[3],
+               double *seconds)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!C || !eps || !e_mp2 || !e_mp3 || !e_mp4 || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: bad arguments (needs C, eps, outputs and 0 <= n_frozen < n_occ < N)");
+    if (level != 0 && level != 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: level must be 0 (DQ) or 1 (SDQ)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: a sharded tensor (world > 1) is not supported");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o, o3v = (long long)o * o * ov;
+    if (ov > 0x7fffffffLL || (long long)v * v > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: dimension overflow");
+    const bool packed = ctx->layout == 1, singles = level == 1;
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *g4 = nullptr, *work = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *d_Co = nullptr,
+           *d_Coi = nullptr, *batch = nullptr;
+    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
+    bool blas_mode_set = false;
+    auto cleanup = [&]() {
+        for (double *p : {g1, g2, g3, g4, work, d_small, d_Cv, d_Cvi, d_Co, d_Coi, batch}) if (p) (void)tf_free(p);
+        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
+    };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- MO blocks: tf_mp3_rhf's, and for the singles (ki|ld) = g4[k][i][l][d]
+    if ((rc = mp3_mo_blocks(ctx, "tf_mp4_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
+    if (singles && (rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t1 = stamp();
+    // ---- work space: tf_mp3_rhf's tov | too | tp | tsw | M1 | M2 | S13 | S2 | Xhh | Y, then t2's tov2 | too2 | tsw2, then Moo | Ioo (o^4);
+    //      small: partials [3 nblk] | sums [4] | eps [N] | F [o^2] | Fv [v^2] | t1 [ov] | singles' partials [ov] | OA [o^3 v] | OB [o^3 v] |
+    //      Vo [TFL_W N o]
+    const int nblk = 1024;
+    const size_t nwork = (size_t)13 * B2 + 2 * (size_t)o4;
+    const size_t nsmall = (size_t)3 * nblk + 4 + (size_t)N + (size_t)o * o + (size_t)v * v + 2 * (size_t)ov + 2 * (size_t)o3v + (size_t)TFL_W * N * o;
+    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
+    if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
+        tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess ||
+        tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Co, (size_t)N * o * sizeof(double)) != hipSuccess ||
+        tf_malloc(&d_Coi, (size_t)N * o * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        char text[160];
+        snprintf(text, sizeof text, "tf_mp4_rhf: out of device memory for %.2f GB of work space (13 arrays of o^2 v^2 values and the ladder's batch)",
+                 (double)(nwork + nsmall + nladder) * sizeof(double) / 1e9);
+        return fail(TF_ENOMEM, text);
+    }
+    double *tov = work, *too = tov + B2, *tp = too + B2, *tsw = tp + B2, *M1 = tsw + B2, *M2 = M1 + B2, *S13 = M2 + B2, *S2 = S13 + B2, *Xhh = S2 + B2,
+           *Y = Xhh + B2, *tov2 = Y + B2, *too2 = tov2 + B2, *tsw2 = too2 + B2, *Moo = tsw2 + B2, *Ioo = Moo + o4;
+    double *d_part = d_small, *d_sum = d_part + (size_t)3 * nblk, *d_eps = d_sum + 4, *Fjk = d_eps + N, *Fv = Fjk + (size_t)o * o, *d_t1 = Fv + (size_t)v * v,
+           *d_spart = d_t1 + ov, *OA = d_spart + ov, *OB = OA + o3v, *Vo = OB + o3v;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_mp4_rhf: copy failed");
+    // ---- amplitudes and the MP2 partials
+    hipLaunchKernelGGL(tfmp3::mp3_amp_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, tov, too, tp, tsw, d_part);
+    {
+        std::vector<double> part(2 * nblk);
+        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: copy failed");
+        double os = 0.0, ss = 0.0;
+        for (int b = 0; b < nblk; ++b) { os += part[2 * b]; ss += part[2 * b + 1]; }
+        e_mp2[0] = os; e_mp2[1] = ss;
+    }
+    const auto t2 = stamp();
+    // ---- first ladder pass, on t: Y and (singles) the occupied-virtual blocks OA, OB
+    rocblas_handle blas = ctx->scf.blas;
+    const double *Cvl = d_Cv, *Col = d_Co;                    // in the AO order of T and Z (internal order on the packed layout)
+    if (packed) {
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * o + 255) / 256)), dim3(256), 0, 0, d_Co, ctx->bl.origI, N, o, d_Coi);
+        Cvl = d_Cvi; Col = d_Coi;
+    }
+    if ((rc = mp3_ladder_stage(ctx, "tf_mp4_rhf", o, v, too, Cvl, batch, Y, singles ? Col : nullptr, Vo, OA, OB))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t3 = stamp();
+#define MP4_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp4_rhf: rocBLAS failed: " #call); } while (0)
+    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
+    // the hole-hole and ring GEMMs of X[.] on amplitudes in the three layouts (tf_mp3_rhf's, in its order), then its energy kernel
+    auto hh_ring_energy = [&](const double *a_ov, const double *a_oo, const double *a_sw, double e[3]) -> int {
+        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, Moo, oo, a_oo, vv, 0.0, Xhh, vv));
+        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, a_ov, iov, M1, iov, 0.0, S13, iov));
+        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, a_sw, iov, g1, iov, 1.0, S13, iov));
+        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, a_sw, iov, M2, iov, 0.0, S2, iov));
+        hipLaunchKernelGGL(tfmp3::mp3_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, Y, packed ? 1 : 0, Xhh, S13, S2, o, v, d_part);
+        std::vector<double> part(3 * nblk);
+        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the energy kernels failed on the device");
+        e[0] = e[1] = e[2] = 0.0;
+        for (int b = 0; b < nblk; ++b)
+            for (int q = 0; q < 3; ++q) e[q] += part[3 * b + q];
+        return TF_OK;
+    };
+    // ---- X[t]: E_MP3
+    {
+        const long long tot = std::max(B2, o4);
+        hipLaunchKernelGGL(tfmp3::mp3_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3, o, v, Moo, M1, M2);
+    }
+    if ((rc = hh_ring_energy(tov, too, tsw, e_mp3))) return rc;
+    // ---- singles
+    e_mp4[0] = 0.0;
+    if (singles) {
+        hipLaunchKernelGGL(tfmp4::mp4_singles_kernel, dim3((unsigned)ov), dim3(256), 0, 0, too, tp, g4, OA, OB, packed ? 1 : 0, d_eps, n_frozen, n_occ, o, v, d_t1,
+                           d_spart);
+        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_spart, (int)ov, 1, d_sum);
+        if (hipMemcpy(&e_mp4[0], d_sum, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the singles kernels failed on the device");
+    }
+    // ---- t2 = (X[t]_ijab + X[t]_jiba) / D, then X[t2]: E_D
+    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
+    hipLaunchKernelGGL(tfmp4::mp4_t2_kernel, grid_e, dim3(256), 0, 0, Y, packed ? 1 : 0, Xhh, S13, S2, d_eps, n_frozen, n_occ, o, v, tov2, too2, tsw2);
+    const auto t4 = stamp();
+    if ((rc = mp3_ladder_stage(ctx, "tf_mp4_rhf", o, v, too2, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t5 = stamp();
+    double eD[3];
+    if ((rc = hh_ring_energy(tov2, too2, tsw2, eD))) return rc;
+    e_mp4[1] = eD[0] + eD[1] + eD[2];
+    // ---- quadruples, in the buffers the doubles have left: Gx | Gw | Goo | Tmp | QA | QB | QC.  The skinny GEMMs (F, Fv, Ioo) would
+    //      otherwise take rocBLAS's split-K kernels, whose sums change from run to run
+    double *Gx = M1, *Gw = M2, *Goo = S13, *Tmp = S2, *QA = Xhh, *QB = Y, *QC = tov2;
+    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
+        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
+        blas_mode_set = true;
+    hipLaunchKernelGGL(tfmp4::mp4_integral_operands_kernel, grid_e, dim3(256), 0, 0, g1, o, v, Gx, Gw, Goo);
+    // QA = 1/2 (t Goo^T) t - F t - t_ij Fv^T
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, too, vv, Goo, vv, 0.0, Ioo, oo));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, Ioo, oo, too, vv, 0.0, QA, vv));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, tov, ovv, Gw, ovv, 0.0, Fjk, o));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fjk, o, too, ovv, 1.0, QA, ovv));
+    for (int k = 0; k < o; ++k)
+        MP4_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, 1.0, tov + (size_t)k * v * ov, iov, Gw + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fv, v));
+    MP4_BLAS(tfmp3::gemm_rm_batched(blas, false, true, v, v, v, -1.0, too, v, (long long)vv, Fv, v, 0, 1.0, QA, v, (long long)vv, oo));
+    // QB = Tn ((Tn - Tx) Gw)^T + 1/2 Tx (Tx G)^T
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tov, iov, Gw, iov, 0.0, Tmp, iov));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, tsw, iov, Gw, iov, 1.0, Tmp, iov));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 1.0, tov, iov, Tmp, iov, 0.0, QB, iov));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tsw, iov, g1, iov, 0.0, Tmp, iov));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 0.5, tsw, iov, Tmp, iov, 1.0, QB, iov));
+    // QC = 1/2 Tx (Tx Gx)^T
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tsw, iov, Gx, iov, 0.0, Tmp, iov));
+    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 0.5, tsw, iov, Tmp, iov, 0.0, QC, iov));
+#undef MP4_BLAS
+    hipLaunchKernelGGL(tfmp4::mp4_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, QA, QB, QC, o, v, d_part);
+    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 1, d_sum);
+    if (hipMemcpy(&e_mp4[2], d_sum, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the quadruples kernels failed on the device");
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: a kernel launch failed");
+    const auto t6 = stamp();
+    cleanup();
+    if (seconds) {
+        seconds[0] = std::chrono::duration<double>(t6 - t0).count();
+        seconds[1] = std::chrono::duration<double>(t1 - t0).count();
+        seconds[2] = std::chrono::duration<double>((t3 - t2) + (t5 - t4)).count();
+        seconds[3] = seconds[0] - seconds[1] - seconds[2];
     }
     return TF_OK;
 }

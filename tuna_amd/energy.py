@@ -7,7 +7,8 @@ Input line format `TYPE : A B R : METHOD BASIS : KEYWORDS` (tuna.py:87-99).  Sup
 (restricted) or UHF / any multiplicity via ML (unrestricted), a functional of tuna_amd.dft.FUNCTIONALS (restricted Kohn-Sham; unrestricted
 with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tuna_amd/data, and the SCF keywords of SURVEY.md section 5
 (LOOSE/MEDIUM/TIGHT/EXTREME, MAXITER n, DIIS [n]/NODIIS, DAMP x/NODAMP/MAXDAMP x, SLOWCONV/VERYSLOWCONV, HFX x,
-CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, and the coupled-cluster doubles
+CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, MP4(SDQ) / MP4(DQ) (also written
+MP4[SDQ] / MP4[DQ]; full MP4 with triples is not available), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
 iterations too).  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
@@ -61,6 +62,7 @@ class Calculation:
     opposite_spin_scaling: float = 6 / 5               # OSS, calc:209
     mp3: bool = False                                  # MP3 / SCS-MP3 after the MP2 step (tuna_mp.py:1814-1828)
     MP3_scaling: float = 1 / 4                         # MP3S / MP3SCALING / MP3SCAL, calc:183 (applied by SCS-MP3 only)
+    mp4: str | None = None                             # "SDQ" or "DQ": MP4(SDQ) / MP4(DQ) after MP2 and MP3 (tuna_mp.py:1552-1685)
     coupled_cluster: str | None = None                 # "LCCD" or "CCD" after the SCF (tuna_cc.py:830-864, :915-960)
     amp_conv: float = 1e-8                             # AMPCONV, calc:184
     correlated_max_iter: int = 100                     # CORRMAXITER, calc:191
@@ -298,7 +300,9 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             else:
                 label = "\n Unrestricted Hartree-Fock energy: " if calc.reference == "UHF" else "\n Restricted Hartree-Fock energy:   "
                 log(label + f"{out.energy:16.10f}")                                      # kernel:846-850
-        if calc.method == "MP2":
+        if calc.method == "MP2" and calc.mp4:
+            run_restricted_mp4(calc, molecule, out, engine, silent, log)
+        elif calc.method == "MP2":
             # second-order Moller-Plesset correlation energy on the device-resident tensor (all-electron, SURVEY.md section 8d
             # config 5): restricted, AO->MO of the (ia|jb) block + the energy sums, tf_mp2_rhf (tuna_mp.py:834-906); unrestricted, the
             # three spin blocks, tf_mp2_uhf (tuna_mp.py:987-1117)
@@ -378,6 +382,41 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             engine.close()
 
 
+def run_restricted_mp4(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """Restricted MP4(SDQ) / MP4(DQ) on the device-resident tensor (all-electron), tf_mp4_rhf, which returns the MP2 and MP3 parts of the
+    same orbitals as well: the log lines of run_restricted_MP2 (tuna_mp.py:904-906), run_restricted_MP3 (:1472), run_restricted_MP4
+    (:1576-1682) and the summary of tuna_kernel.py:1245-1262.  Nothing is scaled: out.energy = E_SCF + E_MP2 + E_MP3 + E_MP4."""
+    level = calc.mp4
+    t0 = time.perf_counter()
+    r = engine.mp4_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, level=level)
+    out.timings[f"MP4({level}) energy"] = time.perf_counter() - t0
+    E_MP2, E_MP3, E_MP4 = r["E_MP2"], r["E_MP3"], r["E_MP4"]
+    if not silent:
+        log(f"\n  Same spin contribution:             {r['E_SS']:13.10f}")              # mp:904-906
+        log(f"  Opposite spin contribution:         {r['E_OS']:13.10f}")
+        log(f"\n  MP2 correlation energy:             {E_MP2:13.10f}")
+        log(f"\n  MP3 correlation energy:             {E_MP3:13.10f}")                  # mp:1472
+        log("                      MP4 Energy  ")                                       # mp:1577
+        if level == "SDQ":                                                              # mp:1665-1671
+            log("  Triples are not included in MP4(SDQ).\n")
+        else:
+            log("  Singles and triples are not included in MP4(DQ).\n")
+        log(f"  Singles correlation energy:         {r['E_S']:13.10f}")                 # mp:1677-1682
+        log(f"  Doubles correlation energy:         {r['E_D']:13.10f}")
+        log(f"  Triples correlation energy:         {0.0:13.10f}")
+        log(f"  Quadruples correlation energy:      {r['E_Q']:13.10f}")
+        log(f"\n  MP4 correlation energy:             {E_MP4:13.10f}")
+        log("\n Correlation energy from MP2:      " + f"{E_MP2:16.10f}")                # kernel:1247-1262
+        log(" Correlation energy from MP3:      " + f"{E_MP3:16.10f}")
+        log(f" Correlation energy from MP4({level}):{' ' * (4 - len(level))}" + f"{E_MP4:16.10f}\n")
+        log(" Total correlation energy:         " + f"{E_MP2 + E_MP3 + E_MP4:16.10f}\n")
+    out.mp2 = {k: r[k] for k in ("E_OS", "E_SS", "E_MP2", "seconds")}
+    out.mp3 = dict({k: r[k] for k in ("E_OS", "E_SS", "E_MP2", "E_pp", "E_hh", "E_ring", "E_MP3", "seconds")}, E_MP3_scaled=E_MP3)
+    out.mp4 = r
+    out.correlation_energy_mp2, out.correlation_energy_mp3, out.correlation_energy_mp4 = E_MP2, E_MP3, E_MP4
+    out.energy += E_MP2 + E_MP3 + E_MP4
+
+
 def run_coupled_cluster_doubles(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
     """Restricted LCCD / CCD on the device-resident tensor (all-electron), tf_ccd_rhf: the iteration of calculate_coupled_cluster_energy
     (tuna_cc.py:2950-3175) with its log lines (tuna_cc.py:163-199, :3139, :3164-3170; kernel:1282).  The energy threshold is the chosen
@@ -434,9 +473,15 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP3 runs on a closed-shell restricted reference.")
     if method in ("UCCD", "ULCCD"):
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: {method[1:]} runs on a closed-shell restricted reference.")
+    if method in ("MP4", "MP4[SDTQ]", "MP4(SDTQ)"):
+        raise TunaError(f"{method} is not available in this build: the triples of full fourth order need the (ov|vv) integrals and an "
+                        "o^3 v^4 step this build does not have.  MP4(SDQ) is the fourth-order energy without them.")
+    if method.startswith("UMP4"):
+        raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP4 runs on a closed-shell restricted reference.")
+    mp4 = {"MP4(SDQ)": "SDQ", "MP4[SDQ]": "SDQ", "MP4(DQ)": "DQ", "MP4[DQ]": "DQ"}.get(method)
     mp3 = method in ("MP3", "SCS-MP3")
     cc = method if method in ("CCD", "LCCD") else None       # coupled-cluster doubles; every other CC name stays unsupported
-    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3", "CCD", "LCCD") and method not in dft_mod.FUNCTIONALS:
+    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3", "CCD", "LCCD") and not mp4 and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP" in method else "HF"), basis))
     calc.coupled_cluster = cc
@@ -446,6 +491,11 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
     calc.spin_component_scaling = method in ("SCS-MP2", "SCS-MP3")      # tuna_mp.py:872: "SCS" in the name scales the MP2 part too
     calc.mp3 = mp3
+    calc.mp4 = mp4
+    if mp4 and calc.multiplicity != 1:
+        raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
+    if mp4 and (calc.dipole or calc.polarisability or calc.hyperpolarisability):
+        raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
     if mp3 and calc.multiplicity != 1:
         raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
     if mp3 and (calc.dipole or calc.polarisability or calc.hyperpolarisability):

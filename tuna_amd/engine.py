@@ -266,6 +266,25 @@ class Engine:
         return {"E_OS": E_OS, "E_SS": E_SS, "E_MP2": E_OS + E_SS, "E_pp": e3[0], "E_hh": e3[1], "E_ring": e3[2],
                 "E_MP3": e3[0] + e3[1] + e3[2], "seconds": list(t)}
 
+    def mp4_rhf(self, C, eps, n_occ, n_frozen=0, level="SDQ") -> dict:
+        """Restricted MP4(SDQ) or MP4(DQ) from canonical RHF orbitals (tunafock.h: tf_mp4_rhf; tuna_mp.py:1552-1685 without the triples):
+        the keys of mp3_rhf, bit for bit its values, plus {"E_S", "E_D", "E_Q", "E_MP4"}, E_MP4 = E_S + E_D + E_Q (E_S is exactly 0.0 for
+        level "DQ"); seconds = [wall, MO blocks, ladder (both passes), rest]."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"mp4_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if level not in ("SDQ", "DQ"):
+            raise TunaError(f"mp4_rhf: level must be \"SDQ\" or \"DQ\", got {level!r}")
+        import ctypes
+        e2 = (ctypes.c_double * 2)()
+        e3 = (ctypes.c_double * 3)()
+        e4 = (ctypes.c_double * 3)()
+        t = (ctypes.c_double * 4)()
+        self._check(self._L.tf_mp4_rhf(self._ctx, 1 if level == "SDQ" else 0, int(n_occ), int(n_frozen), ptr(C), ptr(eps), e2, e3, e4, t))
+        E_OS, E_SS = e2[0], e2[1]
+        return {"E_OS": E_OS, "E_SS": E_SS, "E_MP2": E_OS + E_SS, "E_pp": e3[0], "E_hh": e3[1], "E_ring": e3[2],
+                "E_MP3": e3[0] + e3[1] + e3[2], "E_S": e4[0], "E_D": e4[1], "E_Q": e4[2], "E_MP4": e4[0] + e4[1] + e4[2], "seconds": list(t)}
+
     def ccd_rhf(self, C, eps, n_occ, n_frozen=0, method="CCD", max_iter=100, conv_delta_E=1e-6, conv_amplitudes=1e-8, use_diis=True,
                 max_diis=6, damping=0.0, return_t2=False, allow_unconverged=False) -> dict:
         """Restricted LCCD or CCD from canonical RHF orbitals, iterated on the resident tensor (tunafock.h: tf_ccd_rhf; tuna_cc.py:830-864,
