@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE: a NumPy model of the parity-blocked packed tensor layout and of the Fock-build algebra that
-tuna_amd/csrc/tf_jkpacked.hip.h runs on it (tables, tasks, partial sums, validity rules of the reductions).  It mirrors the
-host-side table construction of tf_build_eri (tuna_amd/csrc/tf_device.hip: build_blocked_layout / build_jk_tables) so that the
-index algebra can be checked on a CPU against the reference einsums (scf:55-72, scf:27-44); nothing in the product imports it.
+tuna_amd/csrc/tf_jkpacked.hip.h runs on it (tables, tasks, partial sums, validity rules of the reductions).  It restates the
+host-side table construction of the library (tuna_amd/csrc/tf_packed_host.h: build_layout / pack_rows / build_jk_work) independently, so
+that the index algebra can be checked on a CPU against the reference einsums (scf:55-72, scf:27-44) and the library's own tables against
+this model (tests/test_packed_tables.py; rpoff and RS are laid out differently here on purpose); nothing in the product imports it.
 
 Layout in one paragraph.  On a z-axis diatomic every AO has a definite parity under x -> -x and y -> -y: class 0..3 =
 (x parity) | (y parity) << 1.  (ij|kl) vanishes unless class(i) ^ class(j) == class(k) ^ class(l) (the rule the reference uses to

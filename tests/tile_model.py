@@ -42,7 +42,8 @@ def lib():
     if _LIB is None:
         so = os.path.join(HERE, "tile_model", "_build", "libtiletables.so")
         src = [os.path.join(HERE, "tile_model", "tile_tables.cpp"), os.path.join(HERE, "..", "tuna_amd", "csrc", "tf_tiles.h"),
-               os.path.join(HERE, "..", "tuna_amd", "csrc", "tf_tiles_host.h")]
+               os.path.join(HERE, "..", "tuna_amd", "csrc", "tf_tiles_host.h"), os.path.join(HERE, "..", "tuna_amd", "csrc", "tf_packed.h"),
+               os.path.join(HERE, "..", "tuna_amd", "csrc", "tf_packed_host.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
             subprocess.check_call(["sh", os.path.join(HERE, "tile_model", "build.sh")])
         L = C.CDLL(so)

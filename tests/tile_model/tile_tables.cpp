@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE: exposes the host table builder of the "tiles" tensor layout (tuna_amd/csrc/tf_tiles_host.h) to the NumPy
 // model tests/tile_model.py.  Built by tests/tile_model/build.sh with g++ (no HIP, no GPU); nothing in the product links it.
 #include <cstring>
+#include "../../tuna_amd/csrc/tf_packed_host.h"
 #include "../../tuna_amd/csrc/tf_tiles_host.h"
 
 struct Handle {
@@ -16,23 +17,13 @@ extern "C" {
 void *ttm_build(int N, const int *cls, int n_rows, const int *rows_ij /* original (i >= j) pairs */, int ksub, int part_steps)
 {
     Handle *h = new Handle();
-    tft::ClassInfo &C = h->C;
-    C.N = N;
-    for (int k = 0; k < N; ++k) ++C.csize[cls[k]];
-    int order[4] = {0, 1, 2, 3};
-    std::stable_sort(order, order + 4, [&](int x, int y) { return C.csize[x] > C.csize[y]; });
-    for (int t = 0, s0 = 0; t < 4; ++t) { C.cstart[order[t]] = s0; s0 += C.csize[order[t]]; }
-    h->sigma.assign(N, 0); C.clsI.assign(N, 0); C.origI.assign(N, 0); C.cntA.assign((size_t)4 * N, 0);
-    std::vector<int> cnt((size_t)4 * N, 0);
-    int seen[4] = {0, 0, 0, 0};
-    for (int k = 0; k < N; ++k) {
-        const int loc = seen[cls[k]]++;
-        h->sigma[k] = C.cstart[cls[k]] + loc;
-        C.origI[h->sigma[k]] = k; C.clsI[h->sigma[k]] = cls[k];
-        for (int b = 0; b < 4; ++b) cnt[(size_t)b * N + k] = seen[b];
-    }
-    for (int a = 0; a < 4; ++a)
-        for (int x = 0; x < N; ++x) C.cntA[(size_t)a * N + x] = cnt[(size_t)a * N + C.origI[x]];
+    // class ordering: the library's own (tf_packed_host.h), as tf_build_eri hands it to the tiles builder
+    tfp::HostLayout H;
+    h->err = tfp::build_layout(std::vector<int>(cls, cls + N), 1, H);
+    if (!h->err.empty()) return h;
+    h->C = tfp::class_info(H);
+    h->sigma = H.sigma;
+    const tft::ClassInfo &C = h->C;
     std::vector<std::pair<int, int>> rows;
     for (int r = 0; r < n_rows; ++r) rows.push_back({h->sigma[rows_ij[2 * r]], h->sigma[rows_ij[2 * r + 1]]});
     std::sort(rows.begin(), rows.end());

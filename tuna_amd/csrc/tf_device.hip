@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <array>
@@ -23,6 +24,7 @@
 #include "tf_internal.h"
 #include "tf_kernels.hip.h"
 #include "tf_jkpacked.hip.h"
+#include "tf_packed_host.h"
 #include "tf_tiles_host.h"
 #include "tf_jktile.hip.h"
 #include "tf_eri.hip.h"
@@ -175,24 +177,8 @@ struct tf_ctx {
     int2 *d_jrows = nullptr;                     // (local row, ORIGINAL first index of the row)
     int *d_xorder = nullptr;                     // output rows of the exchange reduction, most partial vectors first
     int *d_rowsec = nullptr;            // [n_rows][6]: start of section a inside local row r; position in its storage unit, rows of the unit
-    // parity-blocked layout tables (tf_layout.hip.h), host mirror and device view
-    struct HostLayout {
-        int N = 0, NW = 0, RS = 0, MC = 1;
-        int KS = 1 << 30, MP = 1;                                  // steps per part and parts of a cut walk (several ranks: shorter tasks)
-        int cstart[4] = {}, csize[4] = {}, corder[4] = {}, wfirst[5] = {}, fullsec[4][4] = {}, gbase[4] = {};
-        long long cbase[4] = {}, NP[4] = {}, NPtot = 0, RLS = 0;
-        std::vector<int> cls, loc, sigma, ao, origI, clsI, cntA, kap0, kapF, rpoff, chunk_c0, chunk_width, chunk_cls, chunk_of, gk;
-        std::vector<KInfo> kinfo;                                   // [4][N]
-        std::vector<int> offE;                                      // [4][N]: offA + padded segment length
-        int ke(int a, int xI) const { return cntA[(size_t)a * N + xI]; }
-        int seclen(int c, int a, int iI) const { const int k = ke(a, iI); return k == 0 ? 0 : offE[(size_t)c * N + cstart[a] + k - 1]; }
-        int row_shape(int c, int iI, int *secoff) const {           // section starts and the length of a class-c row with first index iI
-            int tot = 0;
-            for (int t = 0; t < 4; ++t) { const int a = corder[t]; secoff[a] = tot; tot += seclen(c, a, iI); }
-            return tot;
-        }
-        bool task_exists(int c, int w, int iI) const { return kap0[(size_t)c * NW + w] < ke(chunk_cls[w] ^ c, iI); }
-    } hl;
+    // parity-blocked layout tables (tf_layout.hip.h), host mirror (tf_packed_host.h) and device view
+    tfp::HostLayout hl;
     BLayout bl{};
     std::vector<void *> layout_allocs;
     // work tables of jk_packed_kernel: set 0 for one density per pass (groups of 8 rows), set 1 for two (groups of 4 rows)
@@ -427,112 +413,17 @@ static void free_basis(tf_ctx *ctx)
     ctx->have_basis = false;
 }
 
-// Tables of the parity-blocked layout for the output AOs of this build (tf_layout.hip.h; the NumPy model tests/layout_model.py
-// builds the same tables).  cls[k]: x/y parity class of output AO k (original order).
+// Tables of the parity-blocked layout for the output AOs of this build (tf_packed_host.h: build_layout) and their device copy.
+// cls[k]: x/y parity class of output AO k (original order).
 static int build_blocked_layout(tf_ctx *ctx, const std::vector<int> &cls)
 {
-    tf_ctx::HostLayout &H = ctx->hl;
-    H = tf_ctx::HostLayout();
-    const int N = (int)cls.size(), PAD = TF_SEG_PAD;
-    H.N = N; H.cls = cls;
-    for (int k = 0; k < N; ++k) ++H.csize[cls[k]];
-    int order[4] = {0, 1, 2, 3};
-    std::stable_sort(order, order + 4, [&](int x, int y) { return H.csize[x] > H.csize[y]; });   // larger classes first (ties: class id)
-    for (int t = 0, s0 = 0; t < 4; ++t) { H.corder[t] = order[t]; H.cstart[order[t]] = s0; s0 += H.csize[order[t]]; }
-    H.loc.assign(N, 0); H.sigma.assign(N, 0); H.ao.assign(N, 0); H.origI.assign(N, 0); H.clsI.assign(N, 0);
-    std::vector<int> cnt((size_t)4 * N, 0);                          // cnt[b][k]: class-b AOs with original index <= k
-    {
-        int seen[4] = {0, 0, 0, 0};
-        for (int k = 0; k < N; ++k) {
-            H.loc[k] = seen[cls[k]]++;
-            H.sigma[k] = H.cstart[cls[k]] + H.loc[k];
-            H.ao[k] = cls[k] | (H.loc[k] << 2);
-            H.origI[H.sigma[k]] = k;
-            H.clsI[H.sigma[k]] = cls[k];
-            for (int b = 0; b < 4; ++b) cnt[(size_t)b * N + k] = seen[b];
-        }
-    }
-    H.cntA.assign((size_t)4 * N, 0);
-    for (int a = 0; a < 4; ++a)
-        for (int x = 0; x < N; ++x) H.cntA[(size_t)a * N + x] = cnt[(size_t)a * N + H.origI[x]];
-    H.kinfo.assign((size_t)4 * N, KInfo{0, 0});
-    H.offE.assign((size_t)4 * N, 0);
-    for (int c = 0; c < 4; ++c) {
-        long long tot = 0;
-        for (int t = 0; t < 4; ++t) {
-            const int a = H.corder[t];
-            H.fullsec[c][a] = (int)tot;
-            long long off = 0;
-            for (int kk = 0; kk < H.csize[a]; ++kk) {
-                const int kI = H.cstart[a] + kk;
-                const int n = cnt[(size_t)(a ^ c) * N + H.origI[kI]];
-                H.kinfo[(size_t)c * N + kI] = KInfo{(int)off, n};
-                off += (n + PAD - 1) / PAD * PAD;
-                H.offE[(size_t)c * N + kI] = (int)off;
-            }
-            tot += off;
-        }
-        if (tot > 0x7fffffffLL / 8) TF_FAIL(ctx, TF_EINVAL, "basis too large for the packed layout's 32-bit row offsets");
-        H.NP[c] = tot;
-    }
-    H.NPtot = 0; H.RLS = 0;
-    for (int c = 0; c < 4; ++c) { H.cbase[c] = H.NPtot; H.NPtot += H.NP[c]; H.RLS = std::max(H.RLS, H.NP[c]); }
-    // granule table: AO k of the segment that holds granule g of class c's pair index space
-    {
-        int gb = 0;
-        for (int c = 0; c < 4; ++c) { H.gbase[c] = gb; gb += (int)(H.NP[c] / PAD); }
-        H.gk.assign((size_t)std::max(gb, 1), 0);
-        for (int c = 0; c < 4; ++c)
-            for (int kI = 0; kI < N; ++kI) {
-                const int a = H.clsI[kI];
-                const int g0 = (H.fullsec[c][a] + H.kinfo[(size_t)c * N + kI].offA) / PAD, g1 = (H.fullsec[c][a] + H.offE[(size_t)c * N + kI]) / PAD;
-                for (int g = g0; g < g1; ++g) H.gk[(size_t)H.gbase[c] + g] = kI;
-            }
-    }
-    // column chunks: the internal columns cut at class boundaries and every TF_JKP_CW columns
-    H.chunk_of.assign(N, 0);
-    for (int b = 0; b < 4; ++b) {
-        H.wfirst[b] = (int)H.chunk_cls.size();
-        for (int lam0 = 0; lam0 < H.csize[b]; lam0 += TF_JKP_CW) {
-            const int wd = std::min(TF_JKP_CW, H.csize[b] - lam0);
-            for (int u = 0; u < wd; ++u) H.chunk_of[H.cstart[b] + lam0 + u] = (int)H.chunk_cls.size();
-            H.chunk_cls.push_back(b); H.chunk_c0.push_back(H.cstart[b] + lam0); H.chunk_width.push_back(wd);
-        }
-    }
-    H.wfirst[4] = (int)H.chunk_cls.size();
-    H.NW = (int)H.chunk_cls.size();
-    const int NW = H.NW;
-    H.kap0.assign((size_t)4 * std::max(NW, 1), 0); H.kapF.assign((size_t)4 * std::max(NW, 1), 0); H.rpoff.assign((size_t)4 * std::max(NW, 1), 0);
-    // row parts of a group / row: a dense [MC][N] block, MC = most chunks of one class; the task of chunk number s of its class writes
-    // slot s at the internal index of k: rpoff[c][w] = s N + cstart[class of k] (+ kappa)
-    H.MC = 1;
-    for (int b = 0; b < 4; ++b) H.MC = std::max(H.MC, H.wfirst[b + 1] - H.wfirst[b]);
-    H.RS = H.MC * N;
-    {
-        // Several ranks: a rank has 1/world of the tasks but every task walks as long as before, so the longest walks bound the pass
-        // (N = 400, 8 ranks: 0.58 ms against 0.24 ms at perfect balance).  The walks are cut into MP parts of KS steps; the price is one
-        // plane of column parts (and of Jd) per part.
-        int parts = ctx->world >= 4 ? 4 : (ctx->world >= 2 ? 2 : 1);
-        if (const char *e = getenv("TF_JK_PARTS")) parts = std::max(1, std::min(8, atoi(e)));
-        int longest = 1;
-        for (int a = 0; a < 4; ++a) longest = std::max(longest, H.csize[a]);
-        H.MP = std::max(1, std::min(parts, longest));
-        H.KS = (longest + H.MP - 1) / H.MP;
-    }
-    for (int c = 0; c < 4; ++c) {
-        for (int w = 0; w < NW; ++w) {
-            const int b = H.chunk_cls[w], a = b ^ c, lam0 = H.chunk_c0[w] - H.cstart[b];
-            const int cm = (c == 0) ? 1 : 0;
-            int k0 = H.csize[a], kF = H.csize[a];
-            for (int kk = H.csize[a] - 1; kk >= 0; --kk) {           // the counts are non-decreasing along a class
-                const int n = H.kinfo[(size_t)c * N + H.cstart[a] + kk].cnt;
-                if (n > lam0) k0 = kk;
-                if (H.chunk_width[w] == TF_JKP_CW && n - cm >= lam0 + TF_JKP_CW) kF = kk;
-            }
-            H.kap0[(size_t)c * NW + w] = k0; H.kapF[(size_t)c * NW + w] = kF;
-            H.rpoff[(size_t)c * NW + w] = (w - H.wfirst[b]) * N + H.cstart[a];
-        }
-    }
+    tfp::HostLayout &H = ctx->hl;
+    // (several ranks: the walks of the Fock kernel are cut into parts -- tf_packed_host.h)
+    int parts = ctx->world >= 4 ? 4 : (ctx->world >= 2 ? 2 : 1);
+    if (const char *e = getenv("TF_JK_PARTS")) parts = std::max(1, std::min(8, atoi(e)));
+    const std::string msg = tfp::build_layout(cls, parts, H);
+    if (!msg.empty()) TF_FAIL(ctx, TF_EINVAL, "%s", msg.c_str());
+    const int N = H.N, NW = H.NW;
     // device copy
     BLayout L{};
     L.N = N; L.NW = NW; L.RS = H.RS; L.NPtot = H.NPtot;
@@ -916,6 +807,40 @@ static int upload_csr(tf_ctx *ctx, int spherical)
     return TF_OK;
 }
 
+// work tables of the J/K kernel for groups of RB rows (8: one density per pass; 4: two), built by tf_packed_host.h
+static int upload_jk_tables(tf_ctx *ctx, const tfp::RowTables &rows, int RB, tf_ctx::JKTables &T)
+{
+    const tfp::HostLayout &H = ctx->hl;
+    tfp::JKWork W;
+    tfp::build_jk_work(H, rows, RB, W);
+    if (g_dbg) {
+        long long st_all = 0, st_cd = 0;                       // wave steps of the two lists (what a pass costs)
+        for (const JKTask &t : W.tasks) {
+            const JKSuper &sg = W.supers[t.super];
+            const long long stp = (long long)tfp::task_steps(H, sg, t) * ((sg.ng + TF_JKP_GPW - 1) / TF_JKP_GPW);
+            st_all += stp;
+            if (tfp::task_class_diagonal(H, sg, t)) st_cd += stp;
+        }
+        DBG("J/K tasks: %zu (class-diagonal list: %zu), wave steps %lld (%lld)", W.tasks.size(), W.tasks_cd.size(), st_all, st_cd);
+    }
+    int rc2;
+    if ((rc2 = upload(ctx, W.groups, &T.d_groups, false)) || (rc2 = upload(ctx, W.gfirst, &T.d_gfirst, false)) ||
+        (rc2 = upload(ctx, W.tasks, &T.d_tasks, false)) || (rc2 = upload(ctx, W.supers, &T.d_supers, false)) ||
+        (rc2 = upload(ctx, W.tasks_cd, &T.d_tasks_cd, false)))
+        return rc2;
+    T.n_groups = (int)W.groups.size(); T.n_tasks = (int)W.tasks.size(); T.n_supers = (int)W.supers.size();
+    T.n_tasks_cd = (int)W.tasks_cd.size();
+    std::copy(W.bucket, W.bucket + 4, T.bucket); std::copy(W.bucket_cd, W.bucket_cd + 4, T.bucket_cd);
+    T.nseg = W.nseg;
+    T.ypart_len = W.ypart_len;
+    T.jp = W.jp;
+    return TF_OK;
+}
+
+// the device reads (i, j) pairs as int2
+static_assert(sizeof(TFInt2) == sizeof(int2) && offsetof(TFInt2, y) == offsetof(int2, y), "TFInt2 must have the layout of int2");
+static int upload_int2(tf_ctx *ctx, const std::vector<TFInt2> &h, int2 **d) { return upload(ctx, h, reinterpret_cast<TFInt2 **>(d), false); }
+
 static double seconds_between(hipEvent_t a, hipEvent_t b)
 {
     float ms = 0.f;
@@ -923,27 +848,187 @@ static double seconds_between(hipEvent_t a, hipEvent_t b)
     return ms * 1e-3;
 }
 
-int tf_build_eri(tf_ctx *ctx, int spherical)
+extern "C++" {
+// ---- the tensor build: tf_build_eri is a short sequence of units over one plan -----------------------------
+// The device lists and timing events that live for ONE build.  release() is what the end of a successful build does (the device is
+// drained by then); the destructor covers every other way out: launches may still be in flight, so it drains the device first.
+struct EriBuildMem {
+    tf_ctx *ctx;
+    std::vector<void *> blocks;
+    std::vector<hipEvent_t> events;
+    explicit EriBuildMem(tf_ctx *c) : ctx(c) {}
+    EriBuildMem(const EriBuildMem &) = delete;
+    template <class T> int alloc(T **p, size_t bytes)
+    {
+        HIPCHK(ctx, tf_malloc((void **)p, bytes));
+        blocks.push_back(*p);
+        return TF_OK;
+    }
+    template <class T> int up(const std::vector<T> &h, T **d)
+    {
+        *d = nullptr;
+        const int rc = upload(ctx, h, d, false);
+        if (*d) blocks.push_back(*d);
+        return rc;
+    }
+    void drop(void *p)                                              // a list that is replaced by a larger one
+    {
+        if (!p) return;
+        blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end());
+        (void)tf_free(p);
+    }
+    int event(hipEvent_t *e)
+    {
+        HIPCHK(ctx, hipEventCreate(e));
+        events.push_back(*e);
+        return TF_OK;
+    }
+    void release()
+    {
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void *p : blocks) (void)tf_free(p);
+        events.clear(); blocks.clear();
+        ctx->db.kq_ptr = ctx->db.kq_off = ctx->db.kt_ptr = ctx->db.kt_k = nullptr; ctx->db.kt_c = nullptr;
+    }
+    ~EriBuildMem()
+    {
+        if (blocks.empty() && events.empty()) return;
+        (void)hipDeviceSynchronize();
+        release();
+    }
+};
+
+// The plan of one build: what the units below share.  plan_storage and plan_generation fill it, run_slab walks it.
+struct EriBuild {
+    tf_ctx *ctx;
+    const tf::Basis &bs;
+    const tfp::HostLayout &H;
+    const int spherical;
+    EriBuildMem mem;
+    EriBuild(tf_ctx *c, int sph) : ctx(c), bs(c->bs), H(c->hl), spherical(sph), mem(c) {}
+
+    // storage
+    int Nc = 0, N = 0, ld = 0, npairs = 0, nsh = 0, ncls = 0;
+    bool packed = false, tiles = false;
+    long long row_len = 0;
+    std::vector<long long> pair_rows;
+    std::vector<int> owner;
+    tfp::RowTables rows;
+    // slab size, work counters
+    bool per_class = false;
+    double *d_C = nullptr, *d_T2 = nullptr;
+    long long max_rows_c = 1;
+    double t_stage[4] = {0, 0, 0, 0};
+    long long n_quart = 0, n_primq = 0, n_compq = 0;
+    std::vector<long long> cum_pairs, cum_pp, cum_comp;
+    std::vector<std::array<double, 4>> pairW, pairNc, cumW;
+    std::vector<std::array<double, 44>> cumNL;
+    double nominal_flops = 0.0;
+    std::chrono::steady_clock::time_point t_wall0;
+    // ket lists, groups and families
+    static constexpr int NLPG = 7, NGRP = 2 * NLPG;
+    static constexpr int FAM_MM = 9, FAM_MA_CC = 3;
+    std::vector<int> ket_sorted, ket_off, cls_maxnpp;
+    int kets_goff[NGRP + 1] = {};
+    int *d_kets = nullptr, *d_kets_all = nullptr;
+    std::vector<int> kets_all_host;                              // same order as d_kets_all
+    bool fam_off = false, cc_fam_off = false, bra_fam_on = false, fam_any = false;
+    std::vector<int> fam_heads, fam_ptr{0}, fam_mem;
+    int fam_goff[NGRP + 1] = {};
+    int *d_fam_heads = nullptr, *d_fam_ptr = nullptr, *d_fam_mem = nullptr;
+    std::vector<int> psid;
+    std::vector<int> mine_sorted;
+    // streams
+    int NSTREAM = 1;
+    hipStream_t *streams = nullptr;
+    hipEvent_t *sev = nullptr;
+    int launch_count = 0;
+    // launch tables
+    std::vector<LRec> lrecs_host;                              // per (La, Lb | Lc, Ld), filled by make_lrecs
+    hipError_t team_error = hipSuccess;                        // first failed launch of a team kernel
+    bool use_team_pc = false, use_teamc = false, use_team = false;
+    int teamc_pqmax = 700;
+    struct KClassTab { int pS[5] = {0, 0, 0, 0, 0}; int nkap = 0, nnzT = 0, tp_off = 0, te_off = 0; };
+    std::vector<KClassTab> kct;
+    int *d_kq_ptr = nullptr, *d_kq_off = nullptr, *d_kt_ptr = nullptr, *d_kt_k = nullptr, *d_kcnt = nullptr;
+    double *d_kt_c = nullptr;
+    KetRec *d_ketrec = nullptr;                                // parallel to d_kets (class-sorted ket list)
+    int *d_tflat = nullptr;                                    // flat component / output lists of the class pairs (TClass::flat_off)
+    std::vector<int> flat_off;
+    BraRec *d_brarec = nullptr;                                // parallel to the slab's bra list d_bra
+    const int *d_bra_base = nullptr;
+    struct GroupStat { int maxLp = 0, maxT = 1, maxLp1 = 1, maxE = 0, maxcomp = 1, maxnpp = 1; };
+    CFCaps gcaps[NGRP][NGRP];
+    bool gcaps_fit[NGRP][NGRP], gcaps_gtab[NGRP][NGRP];
+    struct BraFam { int *d_ptr = nullptr, *d_mem = nullptr; unsigned n = 0; };
+    typedef std::map<std::pair<size_t, int>, BraFam> BraFams;  // by (first position of the run of bra pairs, largest family)
+    // the slabs' index lists (two sets) and timing events
+    size_t cap_bra = 0, cap_out = 0, out_bytes = 0, rowcls_bytes = 0;
+    int *d_bra = nullptr, *d_bra_alloc = nullptr;
+    long long *d_braoff = nullptr, *d_braoff_alloc = nullptr;
+    void *d_out = nullptr, *d_out_alloc = nullptr;
+    BraRec *d_brarec_alloc = nullptr;
+    signed char *d_rowcls = nullptr, *d_rowcls_alloc = nullptr;  // parity class of every slab row (small-problem mode, packed layout)
+    long long slab_no = 0;
+    std::vector<hipEvent_t> tev;                                   // 4 timing events per slab, read at the end
+    std::vector<hipEvent_t> tev2;                                  // 2 per slab around the task-list team kernels (they count as ERI kernels)
+    size_t cursor = 0;
+    // small-problem mode with team kernels
+    std::vector<TClass> tcs_host;
+    std::vector<int> tc_of, tc_team;                               // -2: not made yet, -1: not eligible
+    std::vector<size_t> tc_lds;
+    bool any_wide_pair = false;                                    // a pair sum beyond the team kernels' instantiations
+    int max_npp_all = 1;
+    TClass *d_tcs = nullptr; TeamTask *d_tasks = nullptr;
+    size_t d_tcs_cap = 0, d_tasks_cap = 0;
+    struct TcLaunch { int LAB, LCD, team; size_t lds; std::vector<TeamTask> tasks; std::vector<double> cost; };
+
+    int out_dim(const tf::Shell &s) const { return spherical ? s.nsph : s.ncomp; }
+    int out_off(const tf::Shell &s) const { return spherical ? s.sph_off : s.cart_off; }
+    long long pair_cost(int p) const {                             // primitive pairs x components: what a quartet with this pair costs
+        return (long long)bs.pairs[p].npp * bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp;
+    }
+    // groups of shell pairs: by La + Lb (0-1, 2-3, 4-5, 6-7, 8, 9, 10: the table sizes grow with the fourth power of L, and only the
+    // very top -- (hh|hh), (hh|gh), ... -- exceeds LDS and falls back to the component-per-lane kernel) and by contracted / uncontracted
+    static int lp_group(int lp) { return lp <= 1 ? 0 : (lp <= 3 ? 1 : (lp <= 5 ? 2 : (lp <= 7 ? 3 : std::min(lp - 4, 6)))); }
+    int pair_group(int p) const { return 2 * lp_group(bs.pairs[p].La + bs.pairs[p].Lb) + (bs.pairs[p].npp > 1 ? 1 : 0); }
+
+    int plan_storage();
+    int upload_consumer_tables();
+    int plan_generation();
+    int plan_slab_size();
+    void plan_work_counters();
+    int plan_ket_lists();
+    int plan_ket_families();
+    int setup_streams();
+    int plan_team_tables();
+    int plan_index_buffers();
+    TClass tclass_common(int bcls, int kcls, int &maxblk, int &maxK, int &nnzc) const;
+    void launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra, const int *d_bra, const long long *d_braoff, int bra_Amax);
+    void launch_generic_old(unsigned n_bra, const int *d_bra, const long long *d_braoff, unsigned n_ket, const int *d_ket, hipStream_t st);
+    GroupStat group_stat(const int *pairs_host, size_t n) const;
+    void make_caps();
+    int make_lrecs(bool with_caps);
+    const BraFam *bra_families(BraFams &bra_fams, const std::vector<int> &bra_host, size_t b0, size_t b1, int most);
+    int launch_generic(const std::vector<int> &bra_host, const int *d_bra, const long long *d_braoff);
+    int teamc_class(int bcls, int kcls);
+    int teamc_tasks(const std::vector<int> &bra, const std::vector<long long> &braoff, std::vector<TcLaunch> &tcl, bool &old_needed);
+    int launch_teamc(const std::vector<TcLaunch> &tcl);
+    int run_slab();
+    int finish();
+    int alloc_jk_scratch();
+};
+
+// Storage: layout choice, owners of the bra shell pairs, host tables (tf_packed_host.h / tf_tiles_host.h), tensor buffer, table uploads
+int EriBuild::plan_storage()
 {
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_basis) TF_FAIL(ctx, TF_EINVAL, "tf_build_eri: call tf_set_basis first");
-    const tf::Basis &bs = ctx->bs;
-    if (spherical && !bs.all_full)
-        TF_FAIL(ctx, TF_EINVAL, "spherical output needs complete shells in canonical Cartesian order (use CARTHARM / spherical=0)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    free_eri(ctx);
-    DBG("build_eri start");
-    int rc = upload_csr(ctx, spherical);
-    if (rc) return rc;
-    DBG("csr uploaded");
-    const int Nc = bs.n_cart, N = spherical ? bs.n_sph : bs.n_cart, ld = (N + 1) & ~1;
+    int rc;
+    Nc = bs.n_cart; N = spherical ? bs.n_sph : bs.n_cart; ld = (N + 1) & ~1;
     if (ctx->grid.G > 0 && ctx->grid.N != N) tfdft::release(ctx->grid);   // (a grid of the other AO representation)
     ctx->spherical = spherical; ctx->N = N; ctx->ld = ld;
-    const int npairs = (int)bs.pairs.size();
+    npairs = (int)bs.pairs.size();
 
     // ---- which bra shell pairs (= row blocks) belong to this rank: longest-processing-time on row counts
-    auto out_dim = [&](const tf::Shell &s) { return spherical ? s.nsph : s.ncomp; };
-    auto out_off = [&](const tf::Shell &s) { return spherical ? s.sph_off : s.cart_off; };
     for (int p = 0; p < npairs; ++p) {
         ctx->host_pairs[p].outoff_a = out_off(bs.shells[bs.pairs[p].A]);
         ctx->host_pairs[p].outoff_b = out_off(bs.shells[bs.pairs[p].B]);
@@ -956,21 +1041,13 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
     ctx->layout = layout;
     // packed: the symmetry-unique, parity-allowed values (layouts 1 and 2: the generation and its slab are the same); tiles: stored
     // j-innermost in (i, class pair, strip, chunk) regions (tf_tiles.h) instead of row by row (tf_jkpacked.hip.h)
-    const bool packed = layout >= 1, tiles = layout == 2;
-    std::vector<long long> pair_rows(npairs), pair_weight(npairs);
+    packed = layout >= 1; tiles = layout == 2;
+    pair_rows.assign(npairs, 0);
     for (int p = 0; p < npairs; ++p) {
         const tf::Shell &a = bs.shells[bs.pairs[p].A], &b = bs.shells[bs.pairs[p].B];
         pair_rows[p] = (bs.pairs[p].A == bs.pairs[p].B) ? (long long)out_dim(a) * (out_dim(a) + 1) / 2
                                                         : (long long)out_dim(a) * out_dim(b);
-        long long w = 0;                                         // stored elements of the block's rows
-        for (int x = 0; x < out_dim(a); ++x)
-            for (int y = 0; y < out_dim(b); ++y) {
-                const long long i = out_off(a) + x, j = out_off(b) + y;
-                if (i >= j) w += packed ? packed_row_len(i, j) : 1;
-            }
-        pair_weight[p] = w;
     }
-    std::vector<int> owner;
     {
         std::vector<int> dims(bs.shells.size());
         for (size_t q = 0; q < dims.size(); ++q) dims[q] = out_dim(bs.shells[q]);
@@ -982,75 +1059,22 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
 
     // ---- parity classes of the output AOs and the layout tables (packed layout)
     if (packed) {
-        std::vector<int> cls(N);
-        // every Cartesian component of a real spherical AO has the AO's x/y parity: the first one decides
-        {
-            std::vector<double> blk;
-            int o = 0;
-            for (const auto &sh : bs.shells) {
-                const int nout = out_dim(sh);
-                if (spherical) tf::sph_block(sh.L, blk);
-                for (int r = 0; r < nout; ++r) {
-                    int cc = r;
-                    if (spherical) {
-                        cc = 0;
-                        while (cc < sh.ncomp && blk[(size_t)r * sh.ncomp + cc] == 0.0) ++cc;
-                    }
-                    const int ca = sh.cart_off + cc;
-                    cls[o++] = (bs.ao_lmn[3 * ca] & 1) | ((bs.ao_lmn[3 * ca + 1] & 1) << 1);
-                }
-            }
-        }
+        std::vector<int> cls;
+        tfp::ao_classes(bs, spherical != 0, cls);
         if ((rc = build_blocked_layout(ctx, cls))) return rc;
     }
-    const tf_ctx::HostLayout &H = ctx->hl;
     // ---- row tables
-    std::vector<int2> row_ij;                                       // original (i >= j) of every local row
-    std::vector<int> rowmap((size_t)N * (N + 1) / 2, -1);
-    std::vector<long long> pair_first_row(npairs, -1);
-    for (int p : ctx->my_pairs) {
-        const tf::Shell &a = bs.shells[bs.pairs[p].A], &b = bs.shells[bs.pairs[p].B];
-        pair_first_row[p] = (long long)row_ij.size();
-        for (int x = 0; x < out_dim(a); ++x)
-            for (int y = 0; y < out_dim(b); ++y) {
-                const int i = out_off(a) + x, j = out_off(b) + y;
-                if (i < j) continue;
-                rowmap[(size_t)i * (i + 1) / 2 + j] = (int)row_ij.size();
-                row_ij.push_back(make_int2(i, j));
-            }
+    {
+        std::vector<int> ooff(bs.shells.size()), odim(bs.shells.size());
+        for (size_t q = 0; q < odim.size(); ++q) { ooff[q] = out_off(bs.shells[q]); odim[q] = out_dim(bs.shells[q]); }
+        tfp::list_rows(bs.pairs, ooff, odim, ctx->my_pairs, N, rows);
     }
-    std::vector<long long> rowoff;
-    std::vector<int> rowsec, rowlen;
-    auto ikey = [](int x, int y) { const int hi = std::max(x, y), lo = std::min(x, y); return (size_t)hi * (hi + 1) / 2 + lo; };
-    if (packed) {
-        // owned rows in ascending internal (sigma(i), sigma(j)): rows that share i and the class of j are adjacent (the row groups of the
-        // J/K kernel); rowmap is keyed by the unordered pair of internal indices
-        {
-            // (the keys sigma(i) N + sigma(j) are distinct: one pass over the N^2 key space instead of a comparison sort -- 3 ms at N = 400)
-            std::vector<int> slot((size_t)N * N, -1);
-            for (size_t r = 0; r < row_ij.size(); ++r) slot[(size_t)H.sigma[row_ij[r].x] * N + H.sigma[row_ij[r].y]] = (int)r;
-            std::vector<int2> sorted;
-            sorted.reserve(row_ij.size());
-            for (size_t k = 0; k < slot.size(); ++k)
-                if (slot[k] >= 0) sorted.push_back(row_ij[(size_t)slot[k]]);
-            row_ij.swap(sorted);
-        }
-        std::fill(rowmap.begin(), rowmap.end(), -1);
-        rowoff.assign(row_ij.size() + 1, 0);
-        rowsec.assign(6 * row_ij.size() + 6, 0);
-        rowlen.assign(row_ij.size() + 1, 0);
-        for (size_t r = 0; r < row_ij.size(); ++r) {
-            const int i = row_ij[r].x, j = row_ij[r].y;
-            rowmap[ikey(H.sigma[i], H.sigma[j])] = (int)r;
-            if (!tiles) rowlen[r] = H.row_shape(H.cls[i] ^ H.cls[j], H.sigma[i], &rowsec[6 * r]);
-        }
-    }
+    if (packed) tfp::pack_rows(H, tiles, rows);
+    const std::vector<TFInt2> &row_ij = rows.row_ij;
+    if (packed && !tiles) ctx->n_elems = rows.n_elems;
     if (tiles) {
         // regions of the stored tensor and the task list of the Fock kernel (tf_tiles_host.h)
-        tft::ClassInfo C;
-        C.N = N;
-        for (int q = 0; q < 4; ++q) { C.cstart[q] = H.cstart[q]; C.csize[q] = H.csize[q]; }
-        C.clsI = H.clsI; C.origI = H.origI; C.cntA = H.cntA;
+        const tft::ClassInfo C = tfp::class_info(H);
         std::vector<std::pair<int, int>> rows_ij(row_ij.size());
         for (size_t r = 0; r < row_ij.size(); ++r) rows_ij[r] = {H.sigma[row_ij[r].x], H.sigma[row_ij[r].y]};
         static const int part_steps = std::min(TT_STEPS_MAX, getenv("TF_TILE_PART_STEPS") ? std::max(1, atoi(getenv("TF_TILE_PART_STEPS"))) : TT_STEPS_MAX);
@@ -1084,146 +1108,8 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         ctx->tv = V;
         ctx->tl1.d_pairs = d_pp; ctx->tl1.d_runs = d_rr;
     }
-    if (packed && !tiles) {
-        // storage units: runs of up to 8 consecutive j of one class with the same i, cut from the top (the row groups of the kernel; its
-        // groups of 4 for two densities are halves of them); the rows of a unit are interleaved segment by segment
-        long long off = 0;
-        for (long long r = (long long)row_ij.size() - 1; r >= 0;) {
-            long long r0 = r;
-            auto sI = [&](long long q) { return H.sigma[row_ij[q].x]; };
-            auto sJ = [&](long long q) { return H.sigma[row_ij[q].y]; };
-            while (r0 > 0 && sI(r0 - 1) == sI(r) && sJ(r0 - 1) == sJ(r0) - 1 && H.clsI[sJ(r0 - 1)] == H.clsI[sJ(r)] && r - r0 + 1 < TF_JKP_JBB) --r0;
-            const int nr = (int)(r - r0 + 1);
-            for (long long q = r0; q <= r; ++q) { rowoff[q] = off; rowsec[6 * q + 4] = (int)(q - r0); rowsec[6 * q + 5] = nr; }
-            off += (long long)nr * rowlen[r0];
-            r = r0 - 1;
-        }
-        rowoff[row_ij.size()] = off;
-        ctx->n_elems = off;
-    }
-    // work tables of the J/K kernel for groups of RB rows (8: one density per pass; 4: two)
-    auto build_jk_tables = [&](int RB, tf_ctx::JKTables &T) -> int {
-        std::vector<JKGroup> groups;
-        std::vector<JKTask> tasks;
-        std::vector<JKSuper> supers;
-        std::vector<int> gfirst(2 * (size_t)N, 0);
-        long long ypart_len = 0;
-        auto sI = [&](long long r) { return H.sigma[row_ij[r].x]; };
-        auto sJ = [&](long long r) { return H.sigma[row_ij[r].y]; };
-        // groups: runs of consecutive internal j of one class with the same i, largest j first
-        for (long long r = (long long)row_ij.size() - 1; r >= 0;) {
-            long long r0 = r;
-            while (r0 > 0 && sI(r0 - 1) == sI(r) && sJ(r0 - 1) == sJ(r0) - 1 && H.clsI[sJ(r0 - 1)] == H.clsI[sJ(r)] && r - r0 + 1 < RB) --r0;
-            JKGroup g{};
-            g.i = sI(r); g.j0 = sJ(r0); g.nr = (int)(r - r0 + 1); g.r0 = (int)r0;
-            g.c = H.clsI[g.i] ^ H.clsI[g.j0]; g.lamj0 = g.j0 - H.cstart[H.clsI[g.j0]];
-            g.ub = rowoff[r0]; g.p0 = rowsec[6 * (size_t)r0 + 4]; g.unr = rowsec[6 * (size_t)r0 + 5];
-            for (int a = 0; a < 4; ++a) g.secoff[a] = rowsec[6 * (size_t)r0 + a];
-            groups.push_back(g);
-            r = r0 - 1;
-        }
-        // (the reductions want the groups of one i contiguous: they are, the rows being sorted by i)
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const int a = groups[gi].i;
-            if (gfirst[N + a] == gfirst[a]) gfirst[a] = (int)gi;
-            gfirst[N + a] = (int)gi + 1;
-        }
-        // super-groups: up to TF_JKP_GPW * TF_JKP_W adjacent groups (TF_JKP_GPW per wave) with the same i and class share a workgroup and one Jt partial.  The kernel's
-        // groups index into `groups`, so the super list may be reordered freely: by class, then by descending original i (the Jt
-        // reduction needs those that reach an AO k to be a prefix of their class's list)
-        for (size_t gi = 0; gi < groups.size();) {
-            size_t ge = gi + 1;
-            while (ge < groups.size() && groups[ge].i == groups[gi].i && groups[ge].c == groups[gi].c && ge - gi < TF_JKP_GPW * TF_JKP_W) ++ge;
-            JKSuper sg{};
-            sg.g0 = (int)gi; sg.ng = (int)(ge - gi); sg.c = groups[gi].c; sg.i = groups[gi].i;
-            for (int a = 0; a < 4; ++a) sg.ke[a] = H.ke(a, sg.i);
-            supers.push_back(sg);
-            gi = ge;
-        }
-        std::stable_sort(supers.begin(), supers.end(), [&](const JKSuper &u, const JKSuper &v) {
-            return u.c != v.c ? u.c < v.c : H.origI[u.i] > H.origI[v.i];
-        });
-        JKJtPlan jp{};
-        for (size_t si = 0; si < supers.size(); ++si) {
-            supers[si].yoff = ypart_len;
-            ypart_len += H.NP[supers[si].c];
-            ++jp.sfirst[supers[si].c + 1];
-        }
-        for (int c = 0; c < 4; ++c) {
-            jp.sfirst[c + 1] += jp.sfirst[c];
-            jp.bfirst[c + 1] = jp.bfirst[c] + (int)((H.NP[c] + TF_JKR_THREADS - 1) / TF_JKR_THREADS);
-        }
-        // tasks (super-group, chunk) that have at least one step, longest first: the hardware dispatches workgroups in this order
-        std::vector<int> steps;
-        for (size_t si = 0; si < supers.size(); ++si)
-            for (int w = 0; w < H.NW; ++w)
-                if (H.task_exists(supers[si].c, w, supers[si].i)) {
-                    const int walk = H.ke(H.chunk_cls[w] ^ supers[si].c, supers[si].i) - H.kap0[(size_t)supers[si].c * H.NW + w];
-                    for (int part = 0; part * H.KS < walk; ++part) {
-                        tasks.push_back(JKTask{(int)si, w, part, 0});
-                        steps.push_back(std::min(H.KS, walk - part * H.KS));
-                    }
-                }
-        {
-            // workgroups of 4, 2 or 1 waves (two groups per wave): a rank of several holds few groups per (i, class), and a wave without
-            // a group would only sit in the barriers of its workgroup and occupy a SIMD slot.  One launch per workgroup size; inside
-            // a launch longest first.
-            auto waves = [&](int t) {                                  // workgroup sizes TF_JKP_W, TF_JKP_W / 2, TF_JKP_W / 4 waves (at least one)
-                const int nwv = (supers[tasks[t].super].ng + TF_JKP_GPW - 1) / TF_JKP_GPW;
-                for (int b = 2; b >= 0; --b) if ((TF_JKP_W >> b) >= 1 && nwv <= (TF_JKP_W >> b)) return TF_JKP_W >> b;
-                return TF_JKP_W;
-            };
-            std::vector<int> ord(tasks.size());
-            std::iota(ord.begin(), ord.end(), 0);
-            std::stable_sort(ord.begin(), ord.end(), [&](int u, int v) { return waves(u) != waves(v) ? waves(u) > waves(v) : steps[u] > steps[v]; });
-            std::vector<JKTask> sorted(tasks.size());
-            T.bucket[0] = 0; T.bucket[1] = T.bucket[2] = T.bucket[3] = (int)tasks.size();
-            for (size_t t = 0; t < ord.size(); ++t) {
-                sorted[t] = tasks[ord[t]];
-                const int wv = waves(ord[t]);
-                if (wv <= TF_JKP_W / 2 && T.bucket[1] == (int)tasks.size()) T.bucket[1] = (int)t;
-                if (wv <= TF_JKP_W / 4 && T.bucket[2] == (int)tasks.size()) T.bucket[2] = (int)t;
-            }
-            if (T.bucket[2] < T.bucket[1]) T.bucket[1] = T.bucket[2];
-            tasks.swap(sorted);
-        }
-        // the class-diagonal list: the same tasks in the same order without those whose column class is neither i's nor j's
-        std::vector<JKTask> tasks_cd;
-        tasks_cd.reserve(tasks.size());
-        for (int b = 0; b < 4; ++b) T.bucket_cd[b] = 0;
-        for (size_t t = 0; t < tasks.size(); ++t) {
-            for (int b = 1; b < 4; ++b) if ((int)t == T.bucket[b]) T.bucket_cd[b] = (int)tasks_cd.size();
-            const JKSuper &sg = supers[tasks[t].super];
-            const int ci = H.clsI[sg.i], cj = ci ^ sg.c, cb = H.chunk_cls[tasks[t].w];
-            if (sg.c == 0 || cb == ci || cb == cj) tasks_cd.push_back(tasks[t]);
-        }
-        for (int b = 1; b < 4; ++b) if (T.bucket[b] == (int)tasks.size()) T.bucket_cd[b] = (int)tasks_cd.size();
-        T.n_tasks_cd = (int)tasks_cd.size();
-        if (g_dbg) {
-            long long st_all = 0, st_cd = 0;                       // wave steps of the two lists (what a pass costs)
-            for (size_t t = 0; t < tasks.size(); ++t) {
-                const JKSuper &sg = supers[tasks[t].super];
-                const int ci = H.clsI[sg.i], cj = ci ^ sg.c, cb = H.chunk_cls[tasks[t].w];
-                const int walk = H.ke(cb ^ sg.c, sg.i) - H.kap0[(size_t)sg.c * H.NW + tasks[t].w];
-                const long long stp = (long long)std::min(H.KS, walk - tasks[t].part * H.KS) * ((sg.ng + TF_JKP_GPW - 1) / TF_JKP_GPW);
-                st_all += stp;
-                if (sg.c == 0 || cb == ci || cb == cj) st_cd += stp;
-            }
-            DBG("J/K tasks: %zu (class-diagonal list: %zu), wave steps %lld (%lld)", tasks.size(), tasks_cd.size(), st_all, st_cd);
-        }
-        int rc2;
-        if ((rc2 = upload(ctx, groups, &T.d_groups, false)) || (rc2 = upload(ctx, gfirst, &T.d_gfirst, false)) ||
-            (rc2 = upload(ctx, tasks, &T.d_tasks, false)) || (rc2 = upload(ctx, supers, &T.d_supers, false)) ||
-            (rc2 = upload(ctx, tasks_cd, &T.d_tasks_cd, false)))
-            return rc2;
-        T.n_groups = (int)groups.size(); T.n_tasks = (int)tasks.size(); T.n_supers = (int)supers.size();
-        T.nseg = std::max(1, std::min(TF_JKP_SEG, T.n_supers / 128));
-        T.ypart_len = ypart_len;
-        T.jp = jp;
-        return TF_OK;
-    };
     ctx->n_rows = (long long)row_ij.size();
-    const long long row_len = (long long)N * ld;
+    row_len = (long long)N * ld;
     if (!packed) ctx->n_elems = ctx->n_rows * row_len;
     if (ctx->n_rows > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "too many tensor rows for this build");
     {
@@ -1243,78 +1129,51 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
             ctx->eri_cap = need;
         }
     }
-    if ((rc = upload(ctx, row_ij, &ctx->d_row_ij, false)) || (rc = upload(ctx, rowmap, &ctx->d_rowmap, false))) return rc;
+    if ((rc = upload_int2(ctx, row_ij, &ctx->d_row_ij)) || (rc = upload(ctx, rows.rowmap, &ctx->d_rowmap, false))) return rc;
     if (packed) {
-        if (!tiles && ((rc = upload(ctx, rowoff, &ctx->d_rowoff, false)) || (rc = upload(ctx, rowsec, &ctx->d_rowsec, false)))) return rc;
+        if (!tiles && ((rc = upload(ctx, rows.rowoff, &ctx->d_rowoff, false)) || (rc = upload(ctx, rows.rowsec, &ctx->d_rowsec, false)))) return rc;
         ctx->db.bl = ctx->bl;
         ctx->db.RLS = H.RLS;
     }
     if (tiles) HIPCHK(ctx, hipMemsetAsync(ctx->d_eri, 0, (size_t)ctx->n_elems * sizeof(double), 0));   // the pad slots of the rows and pieces stay zero
-    // The tables only the CONSUMERS of the tensor need (work tables of the J/K kernel, reduction lists, rows by class) are built on the
-    // host while the generation kernels run: called behind the launches of the last slab (7 ms of host time at N = 400).
-    auto consumer_tables = [&]() -> int {
-        if (!packed) return TF_OK;
-        int rc2;
-        {
-            // rows listed class by class (the AO->MO transformation works on one class at a time: a row of class c is nonzero only in
-            // the blocks (k of class a) x (l of class a ^ c))
-            std::vector<int> class_rows, row_pos(row_ij.size(), 0);
-            class_rows.reserve(row_ij.size());
-            for (int c = 0; c < 4; ++c) {
-                ctx->class_row_off[c] = (long long)class_rows.size();
-                for (size_t r = 0; r < row_ij.size(); ++r)
-                    if ((H.cls[row_ij[r].x] ^ H.cls[row_ij[r].y]) == c) { row_pos[r] = (int)class_rows.size(); class_rows.push_back((int)r); }
-            }
-            ctx->class_row_off[4] = (long long)class_rows.size();
-            if ((rc2 = upload(ctx, class_rows, &ctx->d_class_rows, false)) || (rc2 = upload(ctx, row_pos, &ctx->d_row_pos, false))) return rc2;
-        }
-        if (tiles) {
-            const tft::Tables &TT = ctx->tiles;
-            const tft::TaskList &TL = ctx->ksub1 == TT_KS ? TT.primary : ctx->tsub1;
-            auto up_t = [&](const auto &h, auto **d) -> int {
-                int rc3 = upload(ctx, h, d, false);
-                if (!rc3) ctx->tile_allocs.push_back(*d);
-                return rc3;
-            };
-            if ((rc2 = tile_list_upload(ctx, TL, ctx->ksub1 != TT_KS, ctx->tl1)) || (rc2 = up_t(TT.jlist_ptr, &ctx->d_jlist_ptr)) || (rc2 = up_t(TT.jlist, &ctx->d_jlist)))
-                return rc2;
-            return TF_OK;
-        }
-        if ((rc2 = build_jk_tables(JKShape<1>::RB, ctx->jkt[0])) || (rc2 = build_jk_tables(JKShape<2>::RB, ctx->jkt[1]))) return rc2;
-        // reduction table: the rows (z, x), z != x, listed by their second index x (internal)
-        std::vector<int> jptr((size_t)N + 1, 0);
-        std::vector<int2> jrows;
-        for (size_t r = 0; r < row_ij.size(); ++r) {
-            const int iI = H.sigma[row_ij[r].x], jI = H.sigma[row_ij[r].y];
-            if (iI != jI) ++jptr[jI + 1];
-        }
-        for (int x = 0; x < N; ++x) jptr[x + 1] += jptr[x];
-        jrows.assign((size_t)std::max(1, jptr[N]), make_int2(0, 0));
-        {
-            std::vector<int> fill(jptr.begin(), jptr.end() - 1);
-            for (size_t r = 0; r < row_ij.size(); ++r) {            // (ascending local row: a fixed summation order)
-                const int iI = H.sigma[row_ij[r].x], jI = H.sigma[row_ij[r].y];
-                if (iI != jI) jrows[fill[jI]++] = make_int2((int)r, row_ij[r].x);
-            }
-        }
-        if ((rc2 = upload(ctx, jptr, &ctx->d_jptr, false)) || (rc2 = upload(ctx, jrows, &ctx->d_jrows, false))) return rc2;
-        {
-            // dispatch order of the exchange reduction: the output rows with the most partial vectors (rows listed under x + groups of x) first
-            std::vector<long long> work((size_t)N, 0);
-            for (int x = 0; x < N; ++x) work[x] = jptr[x + 1] - jptr[x];
-            for (const int2 &ij : row_ij) work[H.sigma[ij.x]] += 1;          // (8 rows of a group: weight 1/8 each would do; the order is what counts)
-            std::vector<int> xorder((size_t)N);
-            std::iota(xorder.begin(), xorder.end(), 0);
-            std::stable_sort(xorder.begin(), xorder.end(), [&](int a, int b) { return work[a] > work[b]; });
-            if ((rc2 = upload(ctx, xorder, &ctx->d_xorder, false))) return rc2;
-        }
-        return TF_OK;
-    };
+    return TF_OK;
+}
 
-    DBG("rows=%lld N=%d ld=%d (tensor + row tables allocated)", ctx->n_rows, N, ld);
-    // ---- slabs of bra pairs: Cartesian block -> ket transform -> bra transform -> tensor rows
+// The tables only the CONSUMERS of the tensor need (work tables of the J/K kernel, reduction lists, rows by class) are built on the
+// host while the generation kernels run: called behind the launches of the last slab (7 ms of host time at N = 400).
+int EriBuild::upload_consumer_tables()
+{
+    if (!packed) return TF_OK;
+    int rc2;
+    tfp::ConsumerTables CT;
+    tfp::build_class_rows(H, rows, CT);
+    std::copy(CT.class_row_off, CT.class_row_off + 5, ctx->class_row_off);
+    if ((rc2 = upload(ctx, CT.class_rows, &ctx->d_class_rows, false)) || (rc2 = upload(ctx, CT.row_pos, &ctx->d_row_pos, false))) return rc2;
+    if (tiles) {
+        const tft::Tables &TT = ctx->tiles;
+        const tft::TaskList &TL = ctx->ksub1 == TT_KS ? TT.primary : ctx->tsub1;
+        auto up_t = [&](const auto &h, auto **d) -> int {
+            int rc3 = upload(ctx, h, d, false);
+            if (!rc3) ctx->tile_allocs.push_back(*d);
+            return rc3;
+        };
+        if ((rc2 = tile_list_upload(ctx, TL, ctx->ksub1 != TT_KS, ctx->tl1)) || (rc2 = up_t(TT.jlist_ptr, &ctx->d_jlist_ptr)) || (rc2 = up_t(TT.jlist, &ctx->d_jlist)))
+            return rc2;
+        return TF_OK;
+    }
+    if ((rc2 = upload_jk_tables(ctx, rows, JKShape<1>::RB, ctx->jkt[0])) || (rc2 = upload_jk_tables(ctx, rows, JKShape<2>::RB, ctx->jkt[1]))) return rc2;
+    tfp::build_reduction_lists(H, rows, CT);
+    if ((rc2 = upload(ctx, CT.jptr, &ctx->d_jptr, false)) || (rc2 = upload_int2(ctx, CT.jrows, &ctx->d_jrows))) return rc2;
+    if ((rc2 = upload(ctx, CT.xorder, &ctx->d_xorder, false))) return rc2;
+    return TF_OK;
+}
+
+// ---- slabs of bra pairs: Cartesian block -> ket transform -> bra transform -> tensor rows
+int EriBuild::plan_slab_size()
+{
+    int rc;
     // Large problems launch per (bra class, ket class) with the ket transform fused into the ERI kernels: no Cartesian slab at all.
-    bool per_class = (long long)ctx->my_pairs.size() * npairs >= 2000000LL;
+    per_class = (long long)ctx->my_pairs.size() * npairs >= 2000000LL;
     if (const char *m = getenv("TF_ERI_MODE")) per_class = (m[0] == 'c');
     // A slab row is one Cartesian bra component pair: Nc^2 Cartesian ket values (small-problem mode only) and the ket-transformed
     // row -- N x ld (rows layout) or the complete-row shape of the packed layout (RLS doubles, ~ N^2 / 8).  1 GiB of slab, more (up
@@ -1326,7 +1185,7 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
     for (int p : ctx->my_pairs) slab_total += (size_t)bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp * slab_row_bytes;
     size_t slab_bytes = std::min<size_t>((size_t)4 << 30, std::max<size_t>((size_t)1 << 30, std::max((size_t)ctx->n_elems, slab_total)));
     if (const char *e = getenv("TF_SLAB_MB")) slab_bytes = (size_t)std::max(1, atoi(e)) << 20;
-    long long max_rows_c = std::max<long long>(1, (long long)(slab_bytes / slab_row_bytes));
+    max_rows_c = std::max<long long>(1, (long long)(slab_bytes / slab_row_bytes));
     long long biggest = 1;
     for (int p : ctx->my_pairs)
         biggest = std::max<long long>(biggest, (long long)bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp);
@@ -1339,13 +1198,16 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
     if ((rc = ensure_scratch(ctx, 0, per_class ? 8 : (size_t)max_rows_c * cart_row_bytes)) ||
         (rc = ensure_scratch(ctx, 2, (size_t)max_rows_c * t2_row_bytes)))
         return rc;
-    double *d_C = ctx->scr[0], *d_T2 = ctx->scr[2];
-    double t_stage[4] = {0, 0, 0, 0};
-    long long n_quart = 0, n_primq = 0, n_compq = 0;
+    d_C = ctx->scr[0]; d_T2 = ctx->scr[2];
+    return TF_OK;
+}
+
+void EriBuild::plan_work_counters()
+{
     // work counters: ket pairs / primitive pairs / component pairs with first shell <= A (the pair list is A-major).  The packed
     // layout computes exactly the kets whose first shell does not exceed the bra's; the rows layout all of them.
-    const int nsh = (int)bs.shells.size();
-    std::vector<long long> cum_pairs(nsh + 1, 0), cum_pp(nsh + 1, 0), cum_comp(nsh + 1, 0);
+    nsh = (int)bs.shells.size();
+    cum_pairs.assign(nsh + 1, 0); cum_pp.assign(nsh + 1, 0); cum_comp.assign(nsh + 1, 0);
     for (int p = 0; p < npairs; ++p) {
         const int A = bs.pairs[p].A;
         cum_pairs[A + 1] += 1;
@@ -1357,7 +1219,7 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
     // AO quartet that passes the parity test (pyx:1324-1327), 8 x the inner terms of the loop nest pyx:1179-1217 -- (lx12/2+1)(lx34/2+1)
     // (ly12/2+1)(ly34/2+1)(lz12+1)(lz34+1), a product of a bra and a ket factor -- plus the Boys / R table cost 6 (L+1) + 3 (L+1)^2 / 2 + 60.
     // Per shell pair and parity class c: W = sum of its factor over the component pairs of the class, n = their number.
-    std::vector<std::array<double, 4>> pairW(npairs), pairNc(npairs);
+    pairW.resize(npairs); pairNc.resize(npairs);
     for (int p = 0; p < npairs; ++p) {
         const tf::Shell &sa = bs.shells[bs.pairs[p].A], &sb = bs.shells[bs.pairs[p].B];
         pairW[p] = {0, 0, 0, 0}; pairNc[p] = {0, 0, 0, 0};
@@ -1371,8 +1233,8 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
             }
     }
     // prefix sums over the first shell A of the ket pairs (the pair list is A-major): npp x W per class, and npp x n per class and Lc + Ld
-    std::vector<std::array<double, 4>> cumW(nsh + 1, std::array<double, 4>{0, 0, 0, 0});
-    std::vector<std::array<double, 44>> cumNL(nsh + 1);
+    cumW.assign(nsh + 1, std::array<double, 4>{0, 0, 0, 0});
+    cumNL.resize(nsh + 1);
     for (auto &x : cumNL) x.fill(0.0);
     for (int p = 0; p < npairs; ++p) {
         const int A = bs.pairs[p].A, lcd = std::min(10, bs.pairs[p].La + bs.pairs[p].Lb);
@@ -1385,29 +1247,20 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         for (int c = 0; c < 4; ++c) cumW[a + 1][c] += cumW[a][c];
         for (int x = 0; x < 44; ++x) cumNL[a + 1][x] += cumNL[a][x];
     }
-    double nominal_flops = 0.0;
-    DBG("slab buffers allocated");
-    auto t_wall0 = std::chrono::steady_clock::now();
+}
+
+int EriBuild::plan_ket_lists()
+{
+    int rc;
     // class-sorted ket lists on the device (one contiguous range per class)
-    const int ncls = (int)ctx->class_pairs.size();
-    std::vector<int> ket_sorted, ket_off(ncls + 1, 0), cls_maxnpp(ncls, 1);
+    ncls = (int)ctx->class_pairs.size();
+    ket_off.assign(ncls + 1, 0); cls_maxnpp.assign(ncls, 1);
     for (int c = 0; c < ncls; ++c) {
         ket_sorted.insert(ket_sorted.end(), ctx->class_pairs[c].begin(), ctx->class_pairs[c].end());
         ket_off[c + 1] = (int)ket_sorted.size();
         for (int p : ctx->class_pairs[c]) cls_maxnpp[c] = std::max(cls_maxnpp[c], bs.pairs[p].npp);
     }
-    auto pair_cost = [&](int p) {                                  // primitive pairs x components: what a quartet with this pair costs
-        return (long long)bs.pairs[p].npp * bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp;
-    };
-    // groups of shell pairs: by La + Lb (0-1, 2-3, 4-5, 6-7, 8, 9, 10: the table sizes grow with the fourth power of L, and only the
-    // very top -- (hh|hh), (hh|gh), ... -- exceeds LDS and falls back to the component-per-lane kernel) and by contracted / uncontracted
-    constexpr int NLPG = 7, NGRP = 2 * NLPG;
-    auto lp_group = [](int lp) { return lp <= 1 ? 0 : (lp <= 3 ? 1 : (lp <= 5 ? 2 : (lp <= 7 ? 3 : std::min(lp - 4, 6)))); };
-    auto pair_group = [&](int p) { return 2 * lp_group(bs.pairs[p].La + bs.pairs[p].Lb) + (bs.pairs[p].npp > 1 ? 1 : 0); };
-    int kets_goff[NGRP + 1] = {};
-    int *d_kets = nullptr, *d_kets_all = nullptr;
-    std::vector<int> kets_all_host;                              // same order as d_kets_all
-    if ((rc = upload(ctx, ket_sorted, &d_kets, false))) return rc;
+    if ((rc = mem.up(ket_sorted, &d_kets))) return rc;
     {
         // generic (single-launch) mode: heaviest ket pairs first -- workgroups are dispatched in index order, and a deeply contracted
         // (pp|pp) quartet of Ar2/cc-pVQZ runs for 12 ms: it has to start early, not at the tail of the launch
@@ -1421,25 +1274,25 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         });
         for (int p : all) ++kets_goff[pair_group(p) + 1];
         for (int g = 0; g < NGRP; ++g) kets_goff[g + 1] += kets_goff[g];
-        if ((rc = upload(ctx, all, &d_kets_all, false))) return rc;
+        if ((rc = mem.up(all, &d_kets_all))) return rc;
         kets_all_host = all;
     }
-    // Families of ket pairs (general contractions, eri_cfact_kernel<.., MM>): shells with identical primitives -- same centre, L, exponents,
-    // components -- get the same primitive-set id; the contracted pairs of a group with the same (id, id) differ only in their primitive-pair
-    // weights and in the AOs they write.  Per contracted group: heads (first member, the group's cost order kept), members of each head.
-    constexpr int FAM_MM = 9, FAM_MA_CC = 3;
+    return TF_OK;
+}
+
+// Families of ket pairs (general contractions, eri_cfact_kernel<.., MM>): shells with identical primitives -- same centre, L, exponents,
+// components -- get the same primitive-set id; the contracted pairs of a group with the same (id, id) differ only in their primitive-pair
+// weights and in the AOs they write.  Per contracted group: heads (first member, the group's cost order kept), members of each head.
+int EriBuild::plan_ket_families()
+{
+    int rc;
     // (on when the build has the work to fill the chip with fewer, longer workgroups: Ar2/cc-pVQZ -- 5.0e7 primitive shell quartets -- gains
     // 20 %, N2/cc-pVTZ -- 1.2e6 -- loses 20 %; TF_ERI_FAMILIES=0 / 1 forces)
     const double prim_quartets_est = 0.5 * (double)cum_pp[nsh] * (double)cum_pp[nsh];
-    const bool fam_off = getenv("TF_ERI_FAMILIES") ? getenv("TF_ERI_FAMILIES")[0] == '0' : prim_quartets_est < 8.0e6;
-    const bool cc_fam_off = getenv("TF_ERI_CC_FAMILIES") && getenv("TF_ERI_CC_FAMILIES")[0] == '0';
-    const bool bra_fam_on = !fam_off && getenv("TF_ERI_BRA_FAMILIES") && getenv("TF_ERI_BRA_FAMILIES")[0] == '1';
-    std::vector<int> fam_heads, fam_ptr{0}, fam_mem;
-    int fam_goff[NGRP + 1] = {};
-    int *d_fam_heads = nullptr, *d_fam_ptr = nullptr, *d_fam_mem = nullptr;
-    bool fam_any = false;
-    std::vector<int> psid(bs.shells.size(), -1);
-    std::vector<void *> fam_allocs;                              // per-slab lists of the bra families (freed with the other lists of the build)
+    fam_off = getenv("TF_ERI_FAMILIES") ? getenv("TF_ERI_FAMILIES")[0] == '0' : prim_quartets_est < 8.0e6;
+    cc_fam_off = getenv("TF_ERI_CC_FAMILIES") && getenv("TF_ERI_CC_FAMILIES")[0] == '0';
+    bra_fam_on = !fam_off && getenv("TF_ERI_BRA_FAMILIES") && getenv("TF_ERI_BRA_FAMILIES")[0] == '1';
+    psid.assign(bs.shells.size(), -1);
     {
         int nid = 0;
         for (size_t a = 0; a < bs.shells.size(); ++a) {
@@ -1483,19 +1336,19 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         }
         fam_goff[NGRP] = (int)fam_heads.size();
         if (fam_any) {
-            if ((rc = upload(ctx, fam_heads, &d_fam_heads, false)) || (rc = upload(ctx, fam_ptr, &d_fam_ptr, false)) ||
-                (rc = upload(ctx, fam_mem, &d_fam_mem, false)))
+            if ((rc = mem.up(fam_heads, &d_fam_heads)) || (rc = mem.up(fam_ptr, &d_fam_ptr)) ||
+                (rc = mem.up(fam_mem, &d_fam_mem)))
                 return rc;
         }
     }
-    // my bra pairs ordered by class: a slab is a run of that list, launches go per (bra class run, ket class)
-    std::vector<int> mine_sorted;
-    for (int c = 0; c < ncls; ++c)
-        for (int p : ctx->class_pairs[c])
-            if (owner[p] == ctx->rank) mine_sorted.push_back(p);
-    // streams so that the many small class launches of a slab overlap
+    return TF_OK;
+}
+
+// streams so that the many small class launches of a slab overlap
+int EriBuild::setup_streams()
+{
     const int NSTREAM_MAX = tf_ctx::NSTREAM_MAX;
-    const int NSTREAM = getenv("TF_ERI_NSTREAM") ? std::max(1, std::min(NSTREAM_MAX, atoi(getenv("TF_ERI_NSTREAM")))) : NSTREAM_MAX;
+    NSTREAM = getenv("TF_ERI_NSTREAM") ? std::max(1, std::min(NSTREAM_MAX, atoi(getenv("TF_ERI_NSTREAM")))) : NSTREAM_MAX;
     if (!ctx->have_streams) {
         for (int k = 0; k < NSTREAM_MAX; ++k) {
             HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[k], hipStreamNonBlocking));
@@ -1506,955 +1359,990 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         for (auto &e : ctx->slab_lists) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ctx->have_streams = true;
     }
-    hipStream_t *streams = ctx->streams;
-    hipEvent_t *sev = ctx->sev;
-    int launch_count = 0;
-    DBG("streams created");
+    streams = ctx->streams;
+    sev = ctx->sev;
+    return TF_OK;
+}
 
-    std::vector<LRec> lrecs_host;                              // per (La, Lb | Lc, Ld), filled by make_lrecs below
-    hipError_t team_error = hipSuccess;                        // first failed launch of a team kernel
-    static const bool team_off = getenv("TF_ERI_TEAM") && getenv("TF_ERI_TEAM")[0] == '0';
-    const bool team_ok = packed && !team_off && bs.epool.size() < 0xffffffffull;
-    const bool use_team_pc = team_ok && per_class;                                        // per-class mode: eri_team_kernel for the uncontracted classes
-    // (off by default: on the BASELINE basis sets eri_cfact_kernel is faster -- N2/cc-pVTZ 1.2 ms against 3.3-4.2 ms, Ar2/cc-pVQZ 18 ms against
-    // 22-25 ms of ERI kernels: a team walks the primitive quartets of its shell quartet one after the other, a chain of dependent phases
-    // with nothing else on the chip to hide it; TF_ERI_TEAMC=1 switches it on for experiments and for the parity tests)
-    static const bool teamc_off = !(getenv("TF_ERI_TEAMC") && getenv("TF_ERI_TEAMC")[0] == '1');
-    const bool use_teamc = team_ok && !per_class && !teamc_off;                          // small-problem mode: eri_teamc_kernel over task lists
-    const bool use_team = use_team_pc || use_teamc;                                       // the team kernels' tables are needed
-    static const int teamc_pqmax = getenv("TF_TEAMC_PQMAX") ? atoi(getenv("TF_TEAMC_PQMAX")) : 700;
-    struct KClassTab { int pS[5] = {0, 0, 0, 0, 0}; int nkap = 0, nnzT = 0, tp_off = 0, te_off = 0; };
-    std::vector<KClassTab> kct(ncls);
-    int *d_kq_ptr = nullptr, *d_kq_off = nullptr, *d_kt_ptr = nullptr, *d_kt_k = nullptr, *d_kcnt = nullptr;
-    double *d_kt_c = nullptr;
-    KetRec *d_ketrec = nullptr;                                // parallel to d_kets (class-sorted ket list)
-    int *d_tflat = nullptr;                                    // flat component / output lists of the class pairs (TClass::flat_off)
-    std::vector<int> flat_off;
-    BraRec *d_brarec = nullptr;                                // parallel to the slab's bra list d_bra
-    const int *d_bra_base = nullptr;
-    // the class-wide part of a team kernel's class record (tf_eri_team.hip.h) for (bra pair class, ket pair class)
-    auto tclass_common = [&](int bcls, int kcls, int &maxblk, int &maxK, int &nnzc) {
-        const DPair &hb = ctx->host_pairs[ctx->class_pairs[bcls][0]], &hk = ctx->host_pairs[ctx->class_pairs[kcls][0]];
-        const KClassTab &kt = kct[kcls];
-        TClass t{};
-        t.La = hb.La; t.Lb = hb.Lb; t.Lc = hk.La; t.Ld = hk.Lb;
-        t.nTab = (t.La + 1) * (t.Lb + 1); t.nTcd = (t.Lc + 1) * (t.Ld + 1); t.nT = t.nTab * t.nTcd;
-        t.inv_nTcd = 1.0f / (float)t.nTcd;
-        t.nab = hb.nca * hb.ncb; t.ncd = hk.nca * hk.ncb;
-        maxblk = 1; maxK = 1; nnzc = 0;
-        for (int i = 0; i < 5; ++i) { t.pA[i] = hb.pcls[i]; t.pK[i] = hk.pcls[i]; t.pS[i] = kt.pS[i]; }
-        for (int i = 0; i < 4; ++i) {
-            maxK = std::max(maxK, t.pK[i + 1] - t.pK[i]);
-            maxblk = std::max(maxblk, (t.pA[i + 1] - t.pA[i]) * (t.pK[i + 1] - t.pK[i]));
-            nnzc += (t.pA[i + 1] - t.pA[i]) * (t.pK[i + 1] - t.pK[i]);
-        }
-        t.nkap = kt.nkap; t.nnzT = kt.nnzT; t.tabA = hb.tab_off; t.tabK = hk.tab_off; t.ktp_off = kt.tp_off; t.kte_off = kt.te_off;
-        t.nEab = hb.nE; t.nEcd = hk.nE; t.RLS = H.RLS; t.nacc = nnzc;
-        t.nout = 0;
-        for (int i = 0; i < 4; ++i) {
-            t.invK[i] = 1.0f / (float)std::max(1, t.pK[i + 1] - t.pK[i]);
-            t.invS[i] = 1.0f / (float)std::max(1, t.pS[i + 1] - t.pS[i]);
-            t.nout += (t.pA[i + 1] - t.pA[i]) * (t.pS[i + 1] - t.pS[i]);
-        }
-        return t;
-    };
-    // bra_Amax: largest first shell among the bra pairs of the run -- in the packed layout only kets with first shell <= it are needed
-    // (the class ket lists ascend in the first shell, so that is a prefix: workgroups beyond it are not even launched)
-    auto class_launch = [&](int bcls, int kcls, int max_npp_bra, unsigned n_bra, const int *d_bra, const long long *d_braoff, int bra_Amax) {
-        const tf::Pair &pb = bs.pairs[ctx->class_pairs[bcls][0]], &pk = bs.pairs[ctx->class_pairs[kcls][0]];
-        const tf::Shell &sa = bs.shells[pb.A], &sb = bs.shells[pb.B], &sc = bs.shells[pk.A], &sd = bs.shells[pk.B];
-        QClass q{};
-        q.La = pb.La; q.Lb = pb.Lb; q.Lc = pk.La; q.Ld = pk.Lb;
-        q.L = q.La + q.Lb + q.Lc + q.Ld;
-        q.tsize = (q.L + 1) * (q.L + 2) / 2;
-        q.nca = sa.ncomp; q.ncb = sb.ncomp; q.ncc = sc.ncomp; q.ncd = sd.ncomp;
-        q.ncomp = q.nca * q.ncb * q.ncc * q.ncd;
-        q.npp_ab = max_npp_bra; q.npp_cd = cls_maxnpp[kcls]; q.npq = q.npp_ab * q.npp_cd;      // class maxima (LDS sizing)
-        q.nEab = pb.nE; q.nEcd = pk.nE;
-        q.n_ket = ket_off[kcls + 1] - ket_off[kcls];
-        if (packed) {
-            const std::vector<int> &kl = ctx->class_pairs[kcls];
-            q.n_ket = (int)(std::upper_bound(kl.begin(), kl.end(), bra_Amax, [&](int a, int p) { return a < bs.pairs[p].A; }) - kl.begin());
-            if (q.n_ket == 0) return;
-        }
-        q.fused = 1; q.spherical = spherical ? 1 : 0;
-        q.nsc = spherical ? sc.nsph : sc.ncomp; q.nsd = spherical ? sd.nsph : sd.ncomp;
-        q.Nout = N; q.ld = ld;
-        q.tri = packed ? 1 : 0;
-        double *d_out_slab = d_T2;                               // fused kernels write the half-transformed slab directly
-        const int *d_ket = d_kets + ket_off[kcls];
-        hipStream_t st = streams[launch_count++ % NSTREAM];
-        // TF_ERI_CLASS_TIMES=1 (diagnostic): every class launch alone on the device, its time printed with the class
-        static const bool class_times = getenv("TF_ERI_CLASS_TIMES") != nullptr;
-        struct ClassTimer {
-            bool on; const QClass &q; unsigned nb; std::chrono::steady_clock::time_point t0;
-            ClassTimer(bool o, const QClass &qq, unsigned n) : on(o), q(qq), nb(n) { if (on) { (void)hipDeviceSynchronize(); t0 = std::chrono::steady_clock::now(); } }
-            ~ClassTimer() {
-                if (!on) return;
-                (void)hipDeviceSynchronize();
-                const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                fprintf(stderr, "[tf eri class] (%d %d|%d %d) npq %d bra %u ket %d quartets %.0f: %.3f ms, %.1f ns per quartet\n", q.La, q.Lb, q.Lc, q.Ld,
-                        q.npq, nb, q.n_ket, (double)nb * q.n_ket, ms, 1e6 * ms / ((double)nb * q.n_ket));
-            }
-        } class_timer(class_times, q, n_bra);
-        if (use_team_pc && q.npq == 1 && q.La + q.Lb <= TF_TEAM_LMAX && q.Lc + q.Ld <= TF_TEAM_LMAX) {
-            // one shell quartet per team of lanes, tables private to the team (tf_eri_team.hip.h)
-            int maxblk = 1, maxK = 1, nnzc = 0;
-            TClass t = tclass_common(bcls, kcls, maxblk, maxK, nnzc);
-            t.n_ket = q.n_ket;
-            const int LAB = q.La + q.Lb, LCD = q.Lc + q.Ld, NM = q.L / 2 + 1, XS = NM | 1, RSr = q.L + 2;
-            auto even = [](int x) { return (x + 1) & ~1; };
-            int o = 0;
-            t.oE12 = o; o += even(2 * t.nEab);
-            t.oOffA = o; o += 2 * t.nab;
-            t.oScA = o; o += even(t.nab);
-            t.oOffK = o; o += 2 * t.ncd;
-            t.oTp = o; o += even((t.nkap + 2) / 2);
-            t.oTk = o; o += even((t.nnzT + 1) / 2);
-            t.oTc = o; o += even(t.nnzT);
-            t.oRowOff = o; o += t.nab;
-            const int foff = flat_off.empty() ? -1 : flat_off[(size_t)bcls * ncls + kcls];
-            auto vmax_of = [](int tm) { return tm == 256 ? 2048 : (tm == 64 ? 512 : 96); };
-            const int nacc_pad = even(nnzc);
-            t.oCompW = o; t.oOutW = o + nacc_pad / 2; t.flat_off = std::max(0, foff); t.nflat = nacc_pad + 2 * t.nout;
-            const int flat_doubles = even((t.nflat + 1) / 2);
-            const int shared_noflat = o;
-            t.shared_doubles = o;
-            const int nG = t.nTcd * (LAB + 1) * NM, scr1 = 2 * t.nEcd + (q.L + 1) * RSr + nG;
-            // (a class whose parity-allowed components fit the team's block runs the flat lists: one loop over all components)
-            auto flat_for = [&](int tm) { return foff >= 0 && nnzc <= vmax_of(tm); };
-            auto vcap_of = [&](int tm) { return flat_for(tm) ? even(std::max(scr1, nnzc)) : even(std::max(scr1, std::max(maxK, std::min(maxblk, vmax_of(tm))))); };
-            auto team_doubles_of = [&](int tm) { return 2 * t.nT * XS + vcap_of(tm) + even((t.nkap + 1) / 2); };
-            auto bytes_of = [&](int tm) { return ((size_t)shared_noflat + (flat_for(tm) ? flat_doubles : 0) + (size_t)(256 / tm) * team_doubles_of(tm)) * sizeof(double); };
-            // lanes per quartet: 16 for the smallest classes; a wave while four quartets' tables fit about half of the LDS (two workgroups per
-            // CU); the whole workgroup beyond.  (Measured at N = 400, ERI kernels: 36 / 52 / 76 / 100 KB limit: 35.3 / 32.8 / 31.9 / 33 ms.)
-            static const int force_team = getenv("TF_ERI_TEAM_SIZE") ? atoi(getenv("TF_ERI_TEAM_SIZE")) : 0;
-            static const int lds_kb = getenv("TF_TEAM_LDS_KB") ? atoi(getenv("TF_TEAM_LDS_KB")) : 76;
-            static const int t16_nnz = getenv("TF_TEAM16_NNZ") ? atoi(getenv("TF_TEAM16_NNZ")) : 96;
-            static const long long kpw_div = getenv("TF_TEAM_KPW_DIV") ? atoll(getenv("TF_TEAM_KPW_DIV")) : 2048;
-            static const long long kpw_max = getenv("TF_TEAM_KPW_MAX") ? atoll(getenv("TF_TEAM_KPW_MAX")) : 16;
-            int team = 0;
-            if (t.nT <= 16 && nnzc <= t16_nnz && eri_team_available(LAB, LCD, 16)) team = 16;
-            else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= (size_t)lds_kb * 1024) team = 64;
-            else if (eri_team_available(LAB, LCD, 256) && bytes_of(256) <= 160 * 1024 - 256) team = 256;
-            else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= 160 * 1024 - 256) team = 64;
-            if (force_team && eri_team_available(LAB, LCD, force_team) && bytes_of(force_team) <= 160 * 1024 - 256) team = force_team;
-            if (team) {
-                const int NT = 256 / team;
-                t.vcap = vcap_of(team); t.team_doubles = team_doubles_of(team);
-                t.flat = flat_for(team) ? 1 : 0;
-                t.shared_doubles = shared_noflat + (t.flat ? flat_doubles : 0);
-                // a workgroup walks over several ket groups (shared staging once): enough workgroups to fill the chip, at most 16 groups each
-                // (measured at N = 400, ERI kernels: >= 65536 / 16384 / 4096 / 2048 / 1024 / 512 workgroups per launch aimed at:
-                // 36.0 / 32.8 / 28.3 / 26.8 / 26.5-27.1 / 27.9 ms)
-                const long long groups = (q.n_ket + NT - 1) / NT;
-                const long long kpw = std::max<long long>(1, std::min<long long>(kpw_max, groups * n_bra / kpw_div));
-                TeamLaunch a{LAB, LCD, team, dim3((unsigned)((groups + kpw - 1) / kpw), n_bra), bytes_of(team), st, &ctx->db, &t,
-                             d_brarec + (d_bra - d_bra_base), d_ketrec + ket_off[kcls], d_kcnt + (size_t)kcls * nsh, d_out_slab};
-                const hipError_t e = eri_team_launch(a);
-                if (e != hipSuccess) { team_error = e; }
-                return;
-            }
-        }
-        if (q.npq == 1 && q.ncomp <= 128) {
-            // several uncontracted shell quartets per workgroup
-            int ncp = 1;
-            while (ncp < q.ncomp) ncp <<= 1;
-            q.ncp = ncp;
-            q.G = std::max(1, std::min(TF_ERI_THREADS / ncp, TF_ERI_THREADS / (q.L + 1)));
-            q.PB = q.G; q.stride = q.G | 1;
-            const int kc = q.ncc + q.ncd;
-            int o = 0;
-            q.offR = o; o += q.stride * q.tsize;
-            q.offPref = o; o += q.G;
-            q.offPQ = o; o += q.G;
-            q.offRed = o;
-            q.offEab = o; o += 2 * q.nEab;
-            q.offEcd = o; o += q.G * 2 * q.nEcd;
-            q.offScale = o; o += 42 + kc * q.G;
-            q.offLmn = o; o += (42 + kc * q.G + q.G + 1) / 2;
-            q.offBlk = o; o += q.G * q.ncomp;
-            q.offCsr = o; o += TF_CSR_DOUBLES;
-            q.lds_doubles = o;
-            const dim3 grid((q.n_ket + q.G - 1) / q.G, n_bra);
-            hipLaunchKernelGGL(eri_multi_kernel, grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q, d_bra, d_braoff,
-                               d_ket, Nc, d_out_slab);
-        } else if (q.npq == 1 && (q.La + 1) * (q.Lb + 1) * (q.Lc + 1) * (q.Ld + 1) * 2 * (q.L / 2 + 1) <= 7000 && !getenv("TF_ERI_NOFACT")) {
-            // uncontracted, many components: per-axis factor tables in LDS
-            const int nT = (q.La + 1) * (q.Lb + 1) * (q.Lc + 1) * (q.Ld + 1), nM = q.L / 2 + 1;
-            q.PB = 1; q.stride = 1; q.G = 1; q.ncp = 0;
-            const LRec &lr = lrecs_host[((q.La * 6 + q.Lb) * 6 + q.Lc) * 6 + q.Ld];
-            q.tupG_off = lr.tupG_off; q.tupXZ_off = lr.tupXZ_off;
-            int o = 0;
-            q.offR = o; o += q.tsize;
-            q.offPref = o; o += 2;
-            q.offPQ = o; o += 2;
-            q.offEab = o; o += 2 * q.nEab;
-            q.offEcd = o; o += 2 * q.nEcd;
-            const int tables_end = o;                            // R, prefactors and E tables: dead once X and Z are built
-            q.offScale = o; o += 84;
-            q.offLmn = o; o += 42;
-            q.offRed = o; o += 2 * nT * nM;                      // X and Z tables
-            const int nG = (q.Lc + 1) * (q.Ld + 1) * (q.La + q.Lb + 1) * nM;
-            q.offBlk = o; o += std::max((int)TF_BLK_DOUBLES, nG);   // the ket half of the z tables lives here until the components start
-            q.offG = q.offBlk;
-            q.offTab = o; o += 2 * (q.nca * q.ncb + q.ncc * q.ncd) + 2;
-            if (tables_end >= TF_CSR_DOUBLES) q.offCsr = 0;      // staged over the dead tables (after the X/Z barrier)
-            else { q.offCsr = o; o += TF_CSR_DOUBLES; }
-            q.lds_doubles = o;
-            // (TF_ERI_FACT_THREADS=64|128: smaller workgroups for experiments -- measured slower at N = 400, 127 / 159 ms against 113-127 ms:
-            // the LDS of a quartet limits the workgroups per CU, so fewer waves per workgroup are fewer waves per CU)
-            static const int force_thr = getenv("TF_ERI_FACT_THREADS") ? atoi(getenv("TF_ERI_FACT_THREADS")) : 0;
-            const int fact_threads = (force_thr == 64 || force_thr == 128) ? force_thr : TF_ERI_THREADS;
-            hipLaunchKernelGGL(eri_fact_kernel, dim3(q.n_ket, n_bra), dim3(fact_threads), (size_t)o * sizeof(double), st, ctx->db, q, d_bra,
-                               d_braoff, d_ket, Nc, d_out_slab);
-        } else {
-            const int RB = 3584, EB = 3072;                     // LDS doubles for R tables / staged E tables
-            int PB = RB / q.tsize - 1;
-            PB = std::max(1, std::min(std::min(PB, TF_ERI_THREADS), q.npq));
-            q.PB = PB; q.stride = PB | 1; q.G = 1; q.ncp = 0;
-            const int needE = q.npp_ab * 2 * q.nEab + q.npp_cd * 2 * q.nEcd;
-            const bool stage = needE <= EB;
-            int o = 0;
-            q.offR = o; o += q.stride * q.tsize;
-            q.offPref = o; o += TF_ERI_THREADS;
-            q.offPQ = o; o += TF_ERI_THREADS;
-            q.offRed = o; o += TF_ERI_THREADS;
-            q.offEab = o; o += stage ? q.npp_ab * 2 * q.nEab : 0;
-            q.offEcd = o; o += stage ? q.npp_cd * 2 * q.nEcd : 0;
-            q.offScale = o; o += 84;
-            q.offLmn = o; o += 42;
-            q.offBlk = o; o += TF_BLK_DOUBLES;
-            q.offCsr = o; o += TF_CSR_DOUBLES;
-            q.lds_doubles = o;
-            const dim3 grid(q.n_ket, n_bra);
-            if (stage)
-                hipLaunchKernelGGL((eri_class_kernel<true, false>), grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q,
-                                   d_bra, d_braoff, d_ket, Nc, d_out_slab);
-            else
-                hipLaunchKernelGGL((eri_class_kernel<false, false>), grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q,
-                                   d_bra, d_braoff, d_ket, Nc, d_out_slab);
-        }
-    };
-
-    DBG("stage: small-problem groups");
-    // Small problems: per slab one launch per (bra group, ket group), each mixing the classes of its groups (LDS carved by the
-    // capacities the groups need).  bra_host: the slab's bra pairs (sorted by group).
-    static const bool old_generic = getenv("TF_ERI_GENERIC_OLD") != nullptr;
-    auto generic_launch_old = [&](unsigned n_bra, const int *d_bra, const long long *d_braoff, unsigned n_ket, const int *d_ket, hipStream_t st) {
-        QClass q{};
-        const int RB = 2048, EBa = 1024, EBc = 1024;       // (doubling the E capacities halves the occupancy: Ar2 build 0.084 -> 0.18 s)
-        int o = 0;
-        q.offR = o; o += RB;
-        q.offPref = o; o += TF_ERI_THREADS;
-        q.offPQ = o; o += TF_ERI_THREADS;
-        q.offRed = o; o += TF_ERI_THREADS;
-        q.offEab = o; o += EBa;
-        q.offEcd = o; o += EBc;
-        q.offScale = o; o += 84;
-        q.offLmn = o; o += 42;
-        q.lds_doubles = o;
-        q.offBlk = o;                                            // unused (unfused)
-        q.G = 1; q.n_ket = (int)n_ket; q.fused = 0;
-        q.tri = packed ? 1 : 0;
-        hipLaunchKernelGGL((eri_class_kernel<true, true>), dim3(n_ket, n_bra), dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st,
-                           ctx->db, q, d_bra, d_braoff, d_ket, Nc, d_C);
-    };
-    struct GroupStat { int maxLp = 0, maxT = 1, maxLp1 = 1, maxE = 0, maxcomp = 1, maxnpp = 1; };
-    auto group_stat = [&](const int *pairs_host, size_t n) {
-        GroupStat g;
-        for (size_t k = 0; k < n; ++k) {
-            const tf::Pair &pr = bs.pairs[pairs_host[k]];
-            g.maxLp = std::max(g.maxLp, pr.La + pr.Lb);
-            g.maxT = std::max(g.maxT, (pr.La + 1) * (pr.Lb + 1));
-            g.maxE = std::max(g.maxE, pr.npp * 2 * pr.nE);
-            g.maxcomp = std::max(g.maxcomp, bs.shells[pr.A].ncomp * bs.shells[pr.B].ncomp);
-            g.maxnpp = std::max(g.maxnpp, pr.npp);
-        }
-        g.maxLp1 = g.maxLp + 1;
-        return g;
-    };
-    DBG("stage: carve-outs");
-    // LDS carve-out of the launch (bra group gb, ket group gk), from the largest angular momenta / contraction depths of the groups
-    CFCaps gcaps[NGRP][NGRP];
-    bool gcaps_fit[NGRP][NGRP], gcaps_gtab[NGRP][NGRP];
-    auto make_caps = [&]() {
-        GroupStat gs[NGRP];
-        for (int g = 0; g < NGRP; ++g) gs[g] = group_stat(kets_all_host.data() + kets_goff[g], (size_t)(kets_goff[g + 1] - kets_goff[g]));
-        for (int gb = 0; gb < NGRP; ++gb)
-            for (int gk = 0; gk < NGRP; ++gk) {
-                const GroupStat &sb = gs[gb], &sk = gs[gk];
-                const int Lmax = sb.maxLp + sk.maxLp, nM = Lmax / 2 + 1, tsize = (Lmax + 1) * (Lmax + 2) / 2;
-                const int xz = sb.maxT * sk.maxT * nM, gsz = sk.maxT * sb.maxLp1 * nM;
-                const bool deep = sb.maxnpp > 1 || sk.maxnpp > 1;
-                // batch size aimed at and LDS doubles for the X / Z tables and the staged Hermite tables (tuning knobs; smaller carve-outs
-                // mean more workgroups per CU: Ar2/cc-pVQZ ERI kernels 21.1 ms with 48 / 1536 / 1536, 18.3 ms with 24 / 768 / 1024)
-                static const int k_nbt = getenv("TF_CF_NBT") ? atoi(getenv("TF_CF_NBT")) : 24, k_xz = getenv("TF_CF_XZ") ? atoi(getenv("TF_CF_XZ")) : 768;
-                static const int k_e = getenv("TF_CF_E") ? atoi(getenv("TF_CF_E")) : 1024;
-                const int nbt = deep ? std::min(TF_ERI_THREADS / (Lmax + 1), k_nbt) : 1;       // primitive quartets per batch aimed at
-                CFCaps c{};
-                int o = 0;
-                c.offR = o; c.capR = std::max(2 * tsize, std::min((nbt + 1) * tsize, 2 * k_xz * 2 / 3)); o += c.capR;
-                c.offPref = o; o += TF_ERI_THREADS;
-                c.offPQ = o; o += TF_ERI_THREADS;
-                c.offPP = o; o += TF_ERI_THREADS;
-                c.offG = o; c.capG = std::max(gsz, std::min(nbt * gsz, k_xz * 2 / 3)); o += c.capG;
-                c.capXZ = std::max(xz, std::min(nbt * xz, k_xz));
-                c.offX = o; o += c.capXZ;
-                c.offZ = o; o += c.capXZ;
-                c.offTupG = o; o += (gsz + 3) / 4;
-                c.offTupXZ = o; o += (xz + 3) / 4;
-                c.offEab = o; c.capEab = std::min(sb.maxE, k_e); o += c.capEab;
-                c.offEcd = o; c.capEcd = std::min(sk.maxE, k_e); o += c.capEcd;
-                c.offRed = o; o += TF_ERI_THREADS;
-                c.offKm = o; c.capKm = fam_off ? 0 : FAM_MM * (((gk & 1) ? sk.maxnpp : 0) + ((gb & 1) ? sb.maxnpp : 0)); o += c.capKm;
-                c.lds_doubles = o;
-                c.tri = packed ? 1 : 0;
-                c.dbg_npq_lo = 0; c.dbg_npq_hi = 0x7fffffff;
-                c.team_lmax = use_teamc ? TF_TEAM_LMAX : -1; c.team_pqmax = teamc_pqmax;
-                if (const char *e = getenv("TF_ERI_DBG_NPQ")) (void)sscanf(e, "%d:%d", &c.dbg_npq_lo, &c.dbg_npq_hi);
-                gcaps[gb][gk] = c;
-                gcaps_fit[gb][gk] = (size_t)o * sizeof(double) <= 160 * 1024 - 256;
-                gcaps_gtab[gb][gk] = false;
-                if (!gcaps_fit[gb][gk] && !deep) {
-                    // (hh|hh)-sized tables: G, X and Z of a workgroup go to global memory, everything else stays in LDS
-                    CFCaps d = c;
-                    int q = 0;
-                    d.offR = q; q += d.capR;
-                    d.offPref = q; q += TF_ERI_THREADS;
-                    d.offPQ = q; q += TF_ERI_THREADS;
-                    d.offPP = q; q += TF_ERI_THREADS;
-                    d.offTupG = q; q += (gsz + 3) / 4;
-                    d.offTupXZ = q; q += (xz + 3) / 4;
-                    d.offEab = q; q += d.capEab;
-                    d.offEcd = q; q += d.capEcd;
-                    d.offRed = q; q += TF_ERI_THREADS;
-                    d.offKm = q; q += d.capKm;
-                    d.lds_doubles = q;
-                    d.capG = gsz; d.capXZ = xz;
-                    d.offG = 0; d.offX = gsz; d.offZ = gsz + xz;
-                    d.gtab_doubles = gsz + 2 * xz;
-                    if ((size_t)q * sizeof(double) <= 160 * 1024 - 256) { gcaps[gb][gk] = d; gcaps_fit[gb][gk] = true; gcaps_gtab[gb][gk] = true; }
-                }
-            }
-    };
-    // per (La, Lb | Lc, Ld): table sizes, index words of the table entries, batch capacity under the caps of its launch
-    auto make_lrecs = [&](bool with_caps) -> int {
-        std::vector<LRec> recs(6 * 6 * 6 * 6, LRec{});
-        std::vector<unsigned short> tup;
-        std::vector<char> seen_pair(36, 0);
-        for (const tf::Pair &pr : bs.pairs) seen_pair[pr.La * 6 + pr.Lb] = 1;
-        auto grp_of = [&](int lp) { return lp_group(lp); };
-        for (int ab = 0; ab < 36; ++ab)
-            for (int cd = 0; cd < 36; ++cd) {
-                if (!seen_pair[ab] || !seen_pair[cd]) continue;
-                const int La = ab / 6, Lb = ab % 6, Lc = cd / 6, Ld = cd % 6;
-                const int gb = grp_of(La + Lb), gk = grp_of(Lc + Ld);
-                LRec r{};
-                r.L = La + Lb + Lc + Ld; r.nM = r.L / 2 + 1; r.tsize = (r.L + 1) * (r.L + 2) / 2;
-                r.nT = (La + 1) * (Lb + 1) * (Lc + 1) * (Ld + 1); r.xz = r.nT * r.nM;
-                const int Lab1 = La + Lb + 1;
-                r.gsz = (Lc + 1) * (Ld + 1) * Lab1 * r.nM;
-                r.lgG = 0; while ((1 << r.lgG) < r.gsz && (1 << r.lgG) < TF_ERI_THREADS) ++r.lgG;
-                r.lgX = 0; while ((1 << r.lgX) < r.xz && (1 << r.lgX) < TF_ERI_THREADS) ++r.lgX;
-                // batch capacity: the smallest over the launches (contracted bra and / or ket group) this tuple can occur in
-                int nb = TF_ERI_THREADS / (r.L + 1);
-                for (int fb = 0; fb < 2 && with_caps; ++fb)
-                    for (int fk = 0; fk < 2; ++fk) {
-                        if (fb + fk == 0) continue;
-                        const CFCaps &c = gcaps[2 * gb + fb][2 * gk + fk];
-                        if (c.capR < 2 * r.tsize || c.capG < r.gsz || c.capXZ < r.xz) continue;   // (no such quartet in that launch)
-                        nb = std::min(nb, c.capR / r.tsize - 1);
-                        nb = std::min(nb, std::min(c.capG / r.gsz, c.capXZ / r.xz));
-                    }
-                r.nb_cap = std::max(nb, 1);
-                // entry e of the G table = ((cc (Ld + 1) + d) Lab1 + v) nM + n, of the X / Z tables = (((a2 (Lb + 1) + b2) (Lc + 1) + cc) (Ld + 1) + d) nM + m
-                // (nested loops in that order: a cc-pVQZ basis has 625 tuples and 6e5 entries -- with a division chain per entry this was
-                // 2 ms of every tensor build)
-                r.tupG_off = (int)tup.size();
-                tup.resize(tup.size() + (size_t)r.gsz + (size_t)r.xz);
-                unsigned short *tp = tup.data() + r.tupG_off;
-                for (int cc = 0; cc <= Lc; ++cc)
-                    for (int d = 0; d <= Ld; ++d)
-                        for (int v = 0; v < Lab1; ++v)
-                            for (int n = 0; n < r.nM; ++n) *tp++ = (unsigned short)(n | (v << 4) | (d << 8) | (cc << 11));
-                r.tupXZ_off = r.tupG_off + r.gsz;
-                for (int a2 = 0; a2 <= La; ++a2)
-                    for (int b2 = 0; b2 <= Lb; ++b2)
-                        for (int cc = 0; cc <= Lc; ++cc)
-                            for (int d = 0; d <= Ld; ++d)
-                                for (int m = 0; m < r.nM; ++m) *tp++ = (unsigned short)(m | (a2 << 4) | (b2 << 7) | (cc << 10) | (d << 13));
-                recs[ab * 36 + cd] = r;
-            }
-        if (ctx->d_lrec) { (void)tf_free(ctx->d_lrec); ctx->d_lrec = nullptr; }
-        if (ctx->d_tup) { (void)tf_free(ctx->d_tup); ctx->d_tup = nullptr; }
-        int rc2;
-        if ((rc2 = upload(ctx, recs, &ctx->d_lrec, false)) || (rc2 = upload(ctx, tup, &ctx->d_tup, false))) return rc2;
-        ctx->db.lrec = ctx->d_lrec; ctx->db.tup = ctx->d_tup;
-        lrecs_host = recs;
-        return TF_OK;
-    };
-    DBG("stage: launch lambda defined");
-    // One launch per (bra group, ket group) with work.  A process has few hardware queues (4 by default) and the launches of one
-    // queue run one after the other, each as long as its slowest workgroup: the launches are spread over NQ streams by estimated
-    // cost (heaviest first, always onto the least loaded stream) instead of round-robin over all of them.
-    auto generic_launch = [&](const std::vector<int> &bra_host, const int *d_bra, const long long *d_braoff) -> int {
-        struct Launch { size_t b0, b1; int gb, gk; double cost; };
-        std::vector<Launch> launches;
-        double ket_cost[NGRP];
-        for (int g = 0; g < NGRP; ++g) {
-            ket_cost[g] = 0.0;
-            for (int k = kets_goff[g]; k < kets_goff[g + 1]; ++k) ket_cost[g] += (double)pair_cost(kets_all_host[k]);
-        }
-        for (size_t b0 = 0; b0 < bra_host.size();) {
-            const int gb = pair_group(bra_host[b0]);
-            size_t b1 = b0;
-            double bc = 0.0;
-            while (b1 < bra_host.size() && pair_group(bra_host[b1]) == gb) { bc += (double)pair_cost(bra_host[b1]); ++b1; }
-            for (int gk = 0; gk < NGRP; ++gk)
-                if (kets_goff[gk + 1] > kets_goff[gk]) launches.push_back(Launch{b0, b1, gb, gk, bc * ket_cost[gk]});
-            b0 = b1;
-        }
-        std::stable_sort(launches.begin(), launches.end(), [](const Launch &x, const Launch &y) { return x.cost > y.cost; });
-        // (as many streams as the process has hardware queues: 4 unless GPU_MAX_HW_QUEUES says otherwise -- tuna_amd sets 16)
-        const int hwq = getenv("GPU_MAX_HW_QUEUES") ? std::max(1, atoi(getenv("GPU_MAX_HW_QUEUES"))) : 4;
-        const int NQ = std::min(NSTREAM, getenv("TF_ERI_NQ") ? std::max(1, atoi(getenv("TF_ERI_NQ"))) : std::max(4, std::min(8, hwq)));
-        std::vector<double> load(NQ, 0.0);
-        struct BraFam { int *d_ptr = nullptr, *d_mem = nullptr; unsigned n = 0; };
-        std::map<std::pair<size_t, int>, BraFam> bra_fams;       // by (first position of the run of bra pairs, largest family)
-        // families of the bra pairs [b0, b1) of the slab's list, at most `most` members each: built and uploaded once per (slab, bra group)
-        auto bra_families = [&](size_t b0, size_t b1, int most) -> const BraFam * {
-            auto bf = bra_fams.find(std::make_pair(b0, most));
-            if (bf != bra_fams.end()) return &bf->second;
-            BraFam nf;
-            std::vector<int> bptr{0}, bmem;
-            std::map<std::pair<int, int>, int> open_fam;
-            std::vector<std::vector<int>> fams;
-            for (size_t y = b0; y < b1; ++y) {
-                const tf::Pair &pr = bs.pairs[bra_host[y]];
-                const auto key = std::make_pair(psid[pr.A], psid[pr.B]);
-                auto it = open_fam.find(key);
-                if (it == open_fam.end() || (int)fams[it->second].size() >= most) {
-                    fams.emplace_back();
-                    open_fam[key] = (int)fams.size() - 1;
-                    it = open_fam.find(key);
-                }
-                fams[it->second].push_back((int)y);
-            }
-            for (const auto &f : fams) { bmem.insert(bmem.end(), f.begin(), f.end()); bptr.push_back((int)bmem.size()); }
-            if (upload(ctx, bptr, &nf.d_ptr, false) || upload(ctx, bmem, &nf.d_mem, false)) return nullptr;
-            fam_allocs.push_back(nf.d_ptr); fam_allocs.push_back(nf.d_mem);
-            nf.n = (unsigned)(bptr.size() - 1);
-            return &bra_fams.emplace(std::make_pair(b0, most), nf).first->second;
-        };
-        for (const Launch &l : launches) {
-            const int qi = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            load[qi] += l.cost;
-            hipStream_t st = streams[qi];
-            const int gb = l.gb, gk = l.gk, nk = kets_goff[gk + 1] - kets_goff[gk];
-            const size_t b0 = l.b0, b1 = l.b1;
-            const CFCaps &c = gcaps[gb][gk];
-            const size_t bytes = (size_t)c.lds_doubles * sizeof(double);
-            if (old_generic || !gcaps_fit[gb][gk]) {             // the component-per-lane kernel
-                generic_launch_old((unsigned)(b1 - b0), d_bra + b0, d_braoff + b0, (unsigned)nk, d_kets_all + kets_goff[gk], st);
-                continue;
-            }
-            if (bytes > 64 * 1024 && !ctx->cfact_lds_set) {
-                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                ctx->cfact_lds_set = 160 * 1024;
-            }
-            if (gcaps_gtab[gb][gk]) {
-                const size_t need = (size_t)nk * (b1 - b0) * (size_t)c.gtab_doubles * sizeof(double);
-                if (need > ctx->gtab_bytes) {
-                    HIPCHK(ctx, hipDeviceSynchronize());           // (earlier launches of this build may still use the old block)
-                    if (ctx->d_gtab) (void)tf_free(ctx->d_gtab);
-                    ctx->d_gtab = nullptr; ctx->gtab_bytes = 0;
-                    HIPCHK(ctx, tf_malloc((void **)&ctx->d_gtab, need));
-                    ctx->gtab_bytes = need;
-                }
-                // launches that share the block must not overlap: they all go to one stream
-                hipLaunchKernelGGL((eri_cfact_kernel<true, true>), dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, streams[0], ctx->db, c,
-                                   d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C, ctx->d_gtab);
-                load[qi] -= l.cost; load[0] += l.cost;
-            } else if (((gb | gk) & 1) == 0)                     // both groups uncontracted: one primitive quartet per shell quartet
-                hipLaunchKernelGGL(eri_cfact_kernel<true>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
-                                   d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
-            else if ((gb & 1) && !(gk & 1) && bra_fam_on) {       // contracted bras against uncontracted kets: (family of bra pairs, ket pair).
-                // Off by default (TF_ERI_BRA_FAMILIES=1): the packed layout evaluates the kets whose first shell does not exceed the bra's,
-                // and the contracted shells come first on each atom -- the contracted pairs sit on the ket side; measured on Ar2/cc-pVQZ these
-                // bra families cost 5 % (fewer, longer workgroups) where the ket families gain 24 %.
-                const BraFam *bf = bra_families(b0, b1, FAM_MM);
-                if (!bf) return TF_ENOMEM;
-                static bool bfam_attr_set = false;
-                if (bytes > 64 * 1024 && !bfam_attr_set) {
-                    HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MM, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                    bfam_attr_set = true;
-                }
-                hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MM, 1>), dim3((unsigned)nk, bf->n), dim3(TF_ERI_THREADS), bytes, st,
-                                   ctx->db, c, d_bra, d_braoff, d_kets_all + kets_goff[gk], Nc, d_C, (double *)nullptr, (const int *)nullptr,
-                                   (const int *)nullptr, bf->d_ptr, bf->d_mem);
-            }
-            else if ((gb & 1) && (gk & 1) && fam_any && !cc_fam_off) {
-                // contracted against contracted: families on both sides -- up to 3 bra pairs x up to 9 ket pairs per workgroup (27 accumulators
-                // per component: the deepest quartets, (s13 s13|s13 s13) and friends, spend their time in the tables of 28 561 primitive quartets)
-                const BraFam *bf = bra_families(b0, b1, FAM_MA_CC);
-                if (!bf) return TF_ENOMEM;
-                static bool ccfam_attr_set = false;
-                if (bytes > 64 * 1024 && !ccfam_attr_set) {
-                    HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                    ccfam_attr_set = true;
-                }
-                hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), bf->n),
-                                   dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra, d_braoff, d_fam_heads + fam_goff[gk], Nc, d_C, (double *)nullptr,
-                                   d_fam_ptr + fam_goff[gk], d_fam_mem, bf->d_ptr, bf->d_mem);
-            }
-            else if ((gk & 1) && fam_any) {                       // contracted kets: one workgroup per (bra pair, family of ket pairs)
-                static bool fam_attr_set = false;                 // (per process and device: the attribute belongs to the function)
-                if (bytes > 64 * 1024 && !fam_attr_set) {
-                    HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, 1, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                    fam_attr_set = true;
-                }
-                hipLaunchKernelGGL((eri_cfact_kernel<false, false, 1, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), (unsigned)(b1 - b0)),
-                                   dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra + b0, d_braoff + b0, d_fam_heads + fam_goff[gk], Nc, d_C,
-                                   (double *)nullptr, d_fam_ptr + fam_goff[gk], d_fam_mem);
-            } else
-                hipLaunchKernelGGL(eri_cfact_kernel<false>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
-                                   d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
-            ++launch_count;
-        }
-        return TF_OK;
-    };
-    if (!per_class) make_caps();
-    DBG("stage: index-word tables");
-    if ((rc = make_lrecs(!per_class))) return rc;
-    DBG("stage: team tables");
-    // ---- team kernels (tf_eri_team.hip.h): the uncontracted classes of the per-class mode, packed layout.  Per pair class the ket
-    // pair transform (Cartesian component pairs -> output pairs inside each x/y parity class, normalisation ratios folded in), per
-    // shell pair the slab offsets of its output pairs.
-    if (use_team) {
-        std::vector<int> kt_ptr, kt_k, kq_ptr(npairs, 0), kq_off;
-        std::vector<double> kt_c, blkC, blkD;
-        std::vector<std::vector<int>> kap_list(ncls);               // output pairs (sc << 8 | sd) of a pair class, sorted by parity class
-        auto rows_of = [&](const tf::Shell &sh, std::vector<double> &U) {   // transformation rows of a shell (identity: Cartesian output)
-            if (spherical) { tf::sph_block(sh.L, U); return; }
-            U.assign((size_t)sh.ncomp * sh.ncomp, 0.0);
-            for (int i = 0; i < sh.ncomp; ++i) U[(size_t)i * sh.ncomp + i] = 1.0;
-        };
-        auto cls_of = [&](const tf::Shell &sh, const std::vector<double> &U, int r) {   // parity class of an output function: its first component's
-            int cc = 0;
-            while (cc + 1 < sh.ncomp && U[(size_t)r * sh.ncomp + cc] == 0.0) ++cc;
-            const int a = sh.comp_off + cc;
-            return (bs.c_lx[a] & 1) | ((bs.c_ly[a] & 1) << 1);
-        };
-        for (int c = 0; c < ncls; ++c) {
-            const DPair &pr = ctx->host_pairs[ctx->class_pairs[c][0]];
-            const tf::Shell &sC = bs.shells[pr.A], &sD = bs.shells[pr.B];
-            const int nsc = out_dim(sC), nsd = out_dim(sD), ncc = sC.ncomp, ncd = sD.ncomp;
-            rows_of(sC, blkC); rows_of(sD, blkD);
-            std::vector<int> loc((size_t)ncc * ncd, 0);              // position of a component pair inside its parity class (inverse of ct_ord)
-            for (int cl = 0; cl < 4; ++cl)
-                for (int s2 = pr.pcls[cl]; s2 < pr.pcls[cl + 1]; ++s2) loc[ctx->h_ct_ord[pr.tab_off + s2]] = s2 - pr.pcls[cl];
-            KClassTab &kt = kct[c];
-            kt.tp_off = (int)kt_ptr.size(); kt.te_off = (int)kt_k.size();
-            for (int cl = 0; cl < 4; ++cl) {
-                kt.pS[cl] = (int)kap_list[c].size();
-                for (int sc = 0; sc < nsc; ++sc)
-                    for (int sd = 0; sd < nsd; ++sd) {
-                        if ((cls_of(sC, blkC, sc) ^ cls_of(sD, blkD, sd)) != cl) continue;
-                        kap_list[c].push_back((sc << 8) | sd);
-                        kt_ptr.push_back((int)kt_k.size() - kt.te_off);
-                        for (int cc = 0; cc < ncc; ++cc) {
-                            const double uc = blkC[(size_t)sc * ncc + cc];
-                            if (uc == 0.0) continue;
-                            for (int cd2 = 0; cd2 < ncd; ++cd2) {
-                                const double ud = blkD[(size_t)sd * ncd + cd2];
-                                if (ud == 0.0) continue;
-                                const int f = cc * ncd + cd2;
-                                kt_k.push_back(loc[f]);
-                                kt_c.push_back(uc * ud * ctx->h_ct_sc[pr.tab_off + f]);
-                            }
-                        }
-                    }
-            }
-            kt.pS[4] = kt.nkap = (int)kap_list[c].size();
-            kt_ptr.push_back((int)kt_k.size() - kt.te_off);
-            kt.nnzT = (int)kt_k.size() - kt.te_off;
-        }
-        for (int p = 0; p < npairs; ++p) {
-            const DPair &pr = ctx->host_pairs[p];
-            kq_ptr[p] = (int)kq_off.size();
-            for (int word : kap_list[ctx->pair_class[p]]) {
-                const int k = pr.outoff_a + (word >> 8), l = pr.outoff_b + (word & 255);
-                if (l > k) { kq_off.push_back(-1); continue; }
-                const int cb = H.cls[k] ^ H.cls[l];
-                kq_off.push_back(H.fullsec[cb][H.cls[k]] + H.kinfo[(size_t)cb * N + H.sigma[k]].offA + H.loc[l]);
-            }
-        }
-        if ((rc = upload(ctx, kq_ptr, &d_kq_ptr, false)) || (rc = upload(ctx, kq_off, &d_kq_off, false)) || (rc = upload(ctx, kt_ptr, &d_kt_ptr, false)) ||
-            (rc = upload(ctx, kt_k, &d_kt_k, false)) || (rc = upload(ctx, kt_c, &d_kt_c, false)))
-            return rc;
-        ctx->db.kq_ptr = d_kq_ptr; ctx->db.kq_off = d_kq_off; ctx->db.kt_ptr = d_kt_ptr; ctx->db.kt_k = d_kt_k; ctx->db.kt_c = d_kt_c;
-        // flat records of the class-sorted ket list (uncontracted pairs) and, per class and shell A, the kets with first shell <= A
-        std::vector<KetRec> krec(ket_sorted.size());
-        for (size_t k = 0; k < ket_sorted.size(); ++k) {
-            const tf::Pair &pr = bs.pairs[ket_sorted[k]];
-            const double qq = bs.pp_p[pr.pp_off];
-            krec[k] = KetRec{qq, bs.pp_Pz[pr.pp_off], bs.pp_K[pr.pp_off] / qq, (unsigned)pr.e_off, kq_ptr[ket_sorted[k]]};
-        }
-        std::vector<int> kcnt((size_t)ncls * nsh, 0);
-        for (int c = 0; c < ncls; ++c) {
-            for (int p2 : ctx->class_pairs[c]) ++kcnt[(size_t)c * nsh + bs.pairs[p2].A];
-            for (int a = 1; a < nsh; ++a) kcnt[(size_t)c * nsh + a] += kcnt[(size_t)c * nsh + a - 1];
-        }
-        if ((rc = upload(ctx, krec, &d_ketrec, false)) || (rc = upload(ctx, kcnt, &d_kcnt, false))) return rc;
-        if (use_team_pc) {
-            // flat lists of the parity-allowed components and of the outputs of every (bra class, ket class) of uncontracted pairs
-            std::vector<int> tflat;
-            flat_off.assign((size_t)ncls * ncls, -1);
-            for (int bc = 0; bc < ncls; ++bc)
-                for (int kc = 0; kc < ncls; ++kc) {
-                    const DPair &hb = ctx->host_pairs[ctx->class_pairs[bc][0]], &hk = ctx->host_pairs[ctx->class_pairs[kc][0]];
-                    if (hb.npp != 1 || hk.npp != 1 || hb.La + hb.Lb > TF_TEAM_LMAX || hk.La + hk.Lb > TF_TEAM_LMAX) continue;
-                    int mb, mk, nz;
-                    const TClass t = tclass_common(bc, kc, mb, mk, nz);
-                    if (nz > 2048) continue;                          // (chunked classes keep the loop per parity class)
-                    flat_off[(size_t)bc * ncls + kc] = (int)tflat.size();
-                    for (int c = 0; c < 4; ++c)
-                        for (int il = 0; il < t.pA[c + 1] - t.pA[c]; ++il)
-                            for (int kl = 0; kl < t.pK[c + 1] - t.pK[c]; ++kl) tflat.push_back((t.pA[c] + il) | ((t.pK[c] + kl) << 16));
-                    if (tflat.size() & 1) tflat.push_back(0);
-                    int vbase = 0;
-                    for (int c = 0; c < 4; ++c) {
-                        const int nA = t.pA[c + 1] - t.pA[c], nK = t.pK[c + 1] - t.pK[c], nS = t.pS[c + 1] - t.pS[c];
-                        for (int il = 0; il < nA; ++il)
-                            for (int ks = 0; ks < nS; ++ks) { tflat.push_back((t.pA[c] + il) | ((t.pS[c] + ks) << 16)); tflat.push_back(vbase + il * nK); }
-                        vbase += nA * nK;
-                    }
-                }
-            if ((rc = upload(ctx, tflat, &d_tflat, false))) return rc;
-            ctx->db.tflat = d_tflat;
-        }
+// the class-wide part of a team kernel's class record (tf_eri_team.hip.h) for (bra pair class, ket pair class)
+TClass EriBuild::tclass_common(int bcls, int kcls, int &maxblk, int &maxK, int &nnzc) const
+{
+    const DPair &hb = ctx->host_pairs[ctx->class_pairs[bcls][0]], &hk = ctx->host_pairs[ctx->class_pairs[kcls][0]];
+    const KClassTab &kt = kct[kcls];
+    TClass t{};
+    t.La = hb.La; t.Lb = hb.Lb; t.Lc = hk.La; t.Ld = hk.Lb;
+    t.nTab = (t.La + 1) * (t.Lb + 1); t.nTcd = (t.Lc + 1) * (t.Ld + 1); t.nT = t.nTab * t.nTcd;
+    t.inv_nTcd = 1.0f / (float)t.nTcd;
+    t.nab = hb.nca * hb.ncb; t.ncd = hk.nca * hk.ncb;
+    maxblk = 1; maxK = 1; nnzc = 0;
+    for (int i = 0; i < 5; ++i) { t.pA[i] = hb.pcls[i]; t.pK[i] = hk.pcls[i]; t.pS[i] = kt.pS[i]; }
+    for (int i = 0; i < 4; ++i) {
+        maxK = std::max(maxK, t.pK[i + 1] - t.pK[i]);
+        maxblk = std::max(maxblk, (t.pA[i + 1] - t.pA[i]) * (t.pK[i + 1] - t.pK[i]));
+        nnzc += (t.pA[i + 1] - t.pA[i]) * (t.pK[i + 1] - t.pK[i]);
     }
-    if (!per_class)
-        std::stable_sort(mine_sorted.begin(), mine_sorted.end(), [&](int x, int y) {
-            const int gx = pair_group(x), gy = pair_group(y);
-            return gx != gy ? gx < gy : pair_cost(x) > pair_cost(y);
-        });
+    t.nkap = kt.nkap; t.nnzT = kt.nnzT; t.tabA = hb.tab_off; t.tabK = hk.tab_off; t.ktp_off = kt.tp_off; t.kte_off = kt.te_off;
+    t.nEab = hb.nE; t.nEcd = hk.nE; t.RLS = H.RLS; t.nacc = nnzc;
+    t.nout = 0;
+    for (int i = 0; i < 4; ++i) {
+        t.invK[i] = 1.0f / (float)std::max(1, t.pK[i + 1] - t.pK[i]);
+        t.invS[i] = 1.0f / (float)std::max(1, t.pS[i + 1] - t.pS[i]);
+        t.nout += (t.pA[i + 1] - t.pA[i]) * (t.pS[i + 1] - t.pS[i]);
+    }
+    return t;
+}
 
-    // device index buffers sized for the largest possible slab, reused by every slab
-    size_t max_out = 0;
-    for (int p : mine_sorted) max_out = std::max<size_t>(max_out, (size_t)pair_rows[p]);
-    const size_t cap_bra = std::min<size_t>(mine_sorted.size(), 65535) + 1;
-    const size_t cap_out = (size_t)std::min<long long>(ctx->n_rows, max_rows_c * 2 + (long long)max_out) + 1;
-    int *d_bra = nullptr; long long *d_braoff = nullptr; void *d_out = nullptr;
-    signed char *d_rowcls = nullptr;                               // parity class of every slab row (small-problem mode, packed layout)
-    // two sets of a slab's index lists: the lists of slab k + 1 are uploaded (on a stream of their own) while the kernels of slab k run;
-    // the kernels themselves stay ordered by the streams (one half-transformed slab)
-    const size_t out_bytes = cap_out * std::max(std::max(sizeof(OutRow), sizeof(OutRowP)), sizeof(OutRowT)), rowcls_bytes = (size_t)max_rows_c + 1;
-    HIPCHK(ctx, tf_malloc((void **)&d_bra, 2 * cap_bra * sizeof(int)));
-    HIPCHK(ctx, tf_malloc((void **)&d_braoff, 2 * cap_bra * sizeof(long long)));
-    if (use_team_pc) HIPCHK(ctx, tf_malloc((void **)&d_brarec, 2 * cap_bra * sizeof(BraRec)));
-    HIPCHK(ctx, tf_malloc((void **)&d_out, 2 * out_bytes));
-    if (packed && !per_class) HIPCHK(ctx, tf_malloc((void **)&d_rowcls, 2 * rowcls_bytes));
-    int *const d_bra_alloc = d_bra; long long *const d_braoff_alloc = d_braoff; void *const d_out_alloc = d_out;
-    BraRec *const d_brarec_alloc = d_brarec; signed char *const d_rowcls_alloc = d_rowcls;
-    d_bra_base = d_bra;
-    long long slab_no = 0;
-    std::vector<hipEvent_t> tev;                                   // 4 timing events per slab, read at the end
-    std::vector<hipEvent_t> tev2;                                  // 2 per slab around the task-list team kernels (they count as ERI kernels)
-    DBG("stage: teamc tables");
-    // ---- small-problem mode with team kernels (eri_teamc_kernel): class records per (bra class, ket class), created on demand; tasks
-    // per slab.  A quartet belongs to that kernel when both pair sums are <= TF_TEAM_LMAX and it has <= teamc_pqmax primitive quartets;
-    // eri_cfact_kernel skips exactly those (CFCaps::team_lmax / team_pqmax).
-    std::vector<TClass> tcs_host;
-    std::vector<int> tc_of((size_t)ncls * ncls, -2), tc_team;                // -2: not made yet, -1: not eligible
-    std::vector<size_t> tc_lds;
-    auto teamc_class = [&](int bcls, int kcls) -> int {
-        int &slot = tc_of[(size_t)bcls * ncls + kcls];
-        if (slot != -2) return slot;
-        int maxblk, maxK, nnzc;
+// bra_Amax: largest first shell among the bra pairs of the run -- in the packed layout only kets with first shell <= it are needed
+// (the class ket lists ascend in the first shell, so that is a prefix: workgroups beyond it are not even launched)
+void EriBuild::launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra, const int *d_bra, const long long *d_braoff, int bra_Amax)
+{
+    const tf::Pair &pb = bs.pairs[ctx->class_pairs[bcls][0]], &pk = bs.pairs[ctx->class_pairs[kcls][0]];
+    const tf::Shell &sa = bs.shells[pb.A], &sb = bs.shells[pb.B], &sc = bs.shells[pk.A], &sd = bs.shells[pk.B];
+    QClass q{};
+    q.La = pb.La; q.Lb = pb.Lb; q.Lc = pk.La; q.Ld = pk.Lb;
+    q.L = q.La + q.Lb + q.Lc + q.Ld;
+    q.tsize = (q.L + 1) * (q.L + 2) / 2;
+    q.nca = sa.ncomp; q.ncb = sb.ncomp; q.ncc = sc.ncomp; q.ncd = sd.ncomp;
+    q.ncomp = q.nca * q.ncb * q.ncc * q.ncd;
+    q.npp_ab = max_npp_bra; q.npp_cd = cls_maxnpp[kcls]; q.npq = q.npp_ab * q.npp_cd;      // class maxima (LDS sizing)
+    q.nEab = pb.nE; q.nEcd = pk.nE;
+    q.n_ket = ket_off[kcls + 1] - ket_off[kcls];
+    if (packed) {
+        const std::vector<int> &kl = ctx->class_pairs[kcls];
+        q.n_ket = (int)(std::upper_bound(kl.begin(), kl.end(), bra_Amax, [&](int a, int p) { return a < bs.pairs[p].A; }) - kl.begin());
+        if (q.n_ket == 0) return;
+    }
+    q.fused = 1; q.spherical = spherical ? 1 : 0;
+    q.nsc = spherical ? sc.nsph : sc.ncomp; q.nsd = spherical ? sd.nsph : sd.ncomp;
+    q.Nout = N; q.ld = ld;
+    q.tri = packed ? 1 : 0;
+    double *d_out_slab = d_T2;                               // fused kernels write the half-transformed slab directly
+    const int *d_ket = d_kets + ket_off[kcls];
+    hipStream_t st = streams[launch_count++ % NSTREAM];
+    // TF_ERI_CLASS_TIMES=1 (diagnostic): every class launch alone on the device, its time printed with the class
+    static const bool class_times = getenv("TF_ERI_CLASS_TIMES") != nullptr;
+    struct ClassTimer {
+        bool on; const QClass &q; unsigned nb; std::chrono::steady_clock::time_point t0;
+        ClassTimer(bool o, const QClass &qq, unsigned n) : on(o), q(qq), nb(n) { if (on) { (void)hipDeviceSynchronize(); t0 = std::chrono::steady_clock::now(); } }
+        ~ClassTimer() {
+            if (!on) return;
+            (void)hipDeviceSynchronize();
+            const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            fprintf(stderr, "[tf eri class] (%d %d|%d %d) npq %d bra %u ket %d quartets %.0f: %.3f ms, %.1f ns per quartet\n", q.La, q.Lb, q.Lc, q.Ld,
+                    q.npq, nb, q.n_ket, (double)nb * q.n_ket, ms, 1e6 * ms / ((double)nb * q.n_ket));
+        }
+    } class_timer(class_times, q, n_bra);
+    if (use_team_pc && q.npq == 1 && q.La + q.Lb <= TF_TEAM_LMAX && q.Lc + q.Ld <= TF_TEAM_LMAX) {
+        // one shell quartet per team of lanes, tables private to the team (tf_eri_team.hip.h)
+        int maxblk = 1, maxK = 1, nnzc = 0;
         TClass t = tclass_common(bcls, kcls, maxblk, maxK, nnzc);
-        const int LAB = t.La + t.Lb, LCD = t.Lc + t.Ld, L = LAB + LCD, NM = L / 2 + 1, XS = NM | 1;
-        if (LAB > TF_TEAM_LMAX || LCD > TF_TEAM_LMAX) return slot = -1;
+        t.n_ket = q.n_ket;
+        const int LAB = q.La + q.Lb, LCD = q.Lc + q.Ld, NM = q.L / 2 + 1, XS = NM | 1, RSr = q.L + 2;
         auto even = [](int x) { return (x + 1) & ~1; };
         int o = 0;
-        t.oE12 = 0;
+        t.oE12 = o; o += even(2 * t.nEab);
         t.oOffA = o; o += 2 * t.nab;
         t.oScA = o; o += even(t.nab);
         t.oOffK = o; o += 2 * t.ncd;
         t.oTp = o; o += even((t.nkap + 2) / 2);
         t.oTk = o; o += even((t.nnzT + 1) / 2);
         t.oTc = o; o += even(t.nnzT);
+        t.oRowOff = o; o += t.nab;
+        const int foff = flat_off.empty() ? -1 : flat_off[(size_t)bcls * ncls + kcls];
+        auto vmax_of = [](int tm) { return tm == 256 ? 2048 : (tm == 64 ? 512 : 96); };
+        const int nacc_pad = even(nnzc);
+        t.oCompW = o; t.oOutW = o + nacc_pad / 2; t.flat_off = std::max(0, foff); t.nflat = nacc_pad + 2 * t.nout;
+        const int flat_doubles = even((t.nflat + 1) / 2);
+        const int shared_noflat = o;
         t.shared_doubles = o;
-        t.vcap = even(2 * t.nEab + 2 * t.nEcd + (L + 1) * (L + 2) + t.nTcd * (LAB + 1) * NM);      // E12, E34, R, G of one primitive quartet
-        t.team_doubles = 2 * t.nT * XS + t.vcap + even(t.nacc) + even((t.nkap + 1) / 2);
-        auto bytes_of = [&](int tm) { return ((size_t)t.shared_doubles + (size_t)(256 / tm) * t.team_doubles) * sizeof(double); };
+        const int nG = t.nTcd * (LAB + 1) * NM, scr1 = 2 * t.nEcd + (q.L + 1) * RSr + nG;
+        // (a class whose parity-allowed components fit the team's block runs the flat lists: one loop over all components)
+        auto flat_for = [&](int tm) { return foff >= 0 && nnzc <= vmax_of(tm); };
+        auto vcap_of = [&](int tm) { return flat_for(tm) ? even(std::max(scr1, nnzc)) : even(std::max(scr1, std::max(maxK, std::min(maxblk, vmax_of(tm))))); };
+        auto team_doubles_of = [&](int tm) { return 2 * t.nT * XS + vcap_of(tm) + even((t.nkap + 1) / 2); };
+        auto bytes_of = [&](int tm) { return ((size_t)shared_noflat + (flat_for(tm) ? flat_doubles : 0) + (size_t)(256 / tm) * team_doubles_of(tm)) * sizeof(double); };
+        // lanes per quartet: 16 for the smallest classes; a wave while four quartets' tables fit about half of the LDS (two workgroups per
+        // CU); the whole workgroup beyond.  (Measured at N = 400, ERI kernels: 36 / 52 / 76 / 100 KB limit: 35.3 / 32.8 / 31.9 / 33 ms.)
+        static const int force_team = getenv("TF_ERI_TEAM_SIZE") ? atoi(getenv("TF_ERI_TEAM_SIZE")) : 0;
+        static const int lds_kb = getenv("TF_TEAM_LDS_KB") ? atoi(getenv("TF_TEAM_LDS_KB")) : 76;
+        static const int t16_nnz = getenv("TF_TEAM16_NNZ") ? atoi(getenv("TF_TEAM16_NNZ")) : 96;
+        static const long long kpw_div = getenv("TF_TEAM_KPW_DIV") ? atoll(getenv("TF_TEAM_KPW_DIV")) : 2048;
+        static const long long kpw_max = getenv("TF_TEAM_KPW_MAX") ? atoll(getenv("TF_TEAM_KPW_MAX")) : 16;
         int team = 0;
-        if (t.nT <= 16 && nnzc <= 96 && eri_team_available(LAB, LCD, 16)) team = 16;
-        else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= 52 * 1024) team = 64;
+        if (t.nT <= 16 && nnzc <= t16_nnz && eri_team_available(LAB, LCD, 16)) team = 16;
+        else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= (size_t)lds_kb * 1024) team = 64;
         else if (eri_team_available(LAB, LCD, 256) && bytes_of(256) <= 160 * 1024 - 256) team = 256;
         else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= 160 * 1024 - 256) team = 64;
-        if (!team) return slot = -1;
-        tcs_host.push_back(t); tc_team.push_back(team); tc_lds.push_back(bytes_of(team));
-        return slot = (int)tcs_host.size() - 1;
+        if (force_team && eri_team_available(LAB, LCD, force_team) && bytes_of(force_team) <= 160 * 1024 - 256) team = force_team;
+        if (team) {
+            const int NT = 256 / team;
+            t.vcap = vcap_of(team); t.team_doubles = team_doubles_of(team);
+            t.flat = flat_for(team) ? 1 : 0;
+            t.shared_doubles = shared_noflat + (t.flat ? flat_doubles : 0);
+            // a workgroup walks over several ket groups (shared staging once): enough workgroups to fill the chip, at most 16 groups each
+            // (measured at N = 400, ERI kernels: >= 65536 / 16384 / 4096 / 2048 / 1024 / 512 workgroups per launch aimed at:
+            // 36.0 / 32.8 / 28.3 / 26.8 / 26.5-27.1 / 27.9 ms)
+            const long long groups = (q.n_ket + NT - 1) / NT;
+            const long long kpw = std::max<long long>(1, std::min<long long>(kpw_max, groups * n_bra / kpw_div));
+            TeamLaunch a{LAB, LCD, team, dim3((unsigned)((groups + kpw - 1) / kpw), n_bra), bytes_of(team), st, &ctx->db, &t,
+                         d_brarec + (d_bra - d_bra_base), d_ketrec + ket_off[kcls], d_kcnt + (size_t)kcls * nsh, d_out_slab};
+            const hipError_t e = eri_team_launch(a);
+            if (e != hipSuccess) { team_error = e; }
+            return;
+        }
+    }
+    if (q.npq == 1 && q.ncomp <= 128) {
+        // several uncontracted shell quartets per workgroup
+        int ncp = 1;
+        while (ncp < q.ncomp) ncp <<= 1;
+        q.ncp = ncp;
+        q.G = std::max(1, std::min(TF_ERI_THREADS / ncp, TF_ERI_THREADS / (q.L + 1)));
+        q.PB = q.G; q.stride = q.G | 1;
+        const int kc = q.ncc + q.ncd;
+        int o = 0;
+        q.offR = o; o += q.stride * q.tsize;
+        q.offPref = o; o += q.G;
+        q.offPQ = o; o += q.G;
+        q.offRed = o;
+        q.offEab = o; o += 2 * q.nEab;
+        q.offEcd = o; o += q.G * 2 * q.nEcd;
+        q.offScale = o; o += 42 + kc * q.G;
+        q.offLmn = o; o += (42 + kc * q.G + q.G + 1) / 2;
+        q.offBlk = o; o += q.G * q.ncomp;
+        q.offCsr = o; o += TF_CSR_DOUBLES;
+        q.lds_doubles = o;
+        const dim3 grid((q.n_ket + q.G - 1) / q.G, n_bra);
+        hipLaunchKernelGGL(eri_multi_kernel, grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q, d_bra, d_braoff,
+                           d_ket, Nc, d_out_slab);
+    } else if (q.npq == 1 && (q.La + 1) * (q.Lb + 1) * (q.Lc + 1) * (q.Ld + 1) * 2 * (q.L / 2 + 1) <= 7000 && !getenv("TF_ERI_NOFACT")) {
+        // uncontracted, many components: per-axis factor tables in LDS
+        const int nT = (q.La + 1) * (q.Lb + 1) * (q.Lc + 1) * (q.Ld + 1), nM = q.L / 2 + 1;
+        q.PB = 1; q.stride = 1; q.G = 1; q.ncp = 0;
+        const LRec &lr = lrecs_host[((q.La * 6 + q.Lb) * 6 + q.Lc) * 6 + q.Ld];
+        q.tupG_off = lr.tupG_off; q.tupXZ_off = lr.tupXZ_off;
+        int o = 0;
+        q.offR = o; o += q.tsize;
+        q.offPref = o; o += 2;
+        q.offPQ = o; o += 2;
+        q.offEab = o; o += 2 * q.nEab;
+        q.offEcd = o; o += 2 * q.nEcd;
+        const int tables_end = o;                            // R, prefactors and E tables: dead once X and Z are built
+        q.offScale = o; o += 84;
+        q.offLmn = o; o += 42;
+        q.offRed = o; o += 2 * nT * nM;                      // X and Z tables
+        const int nG = (q.Lc + 1) * (q.Ld + 1) * (q.La + q.Lb + 1) * nM;
+        q.offBlk = o; o += std::max((int)TF_BLK_DOUBLES, nG);   // the ket half of the z tables lives here until the components start
+        q.offG = q.offBlk;
+        q.offTab = o; o += 2 * (q.nca * q.ncb + q.ncc * q.ncd) + 2;
+        if (tables_end >= TF_CSR_DOUBLES) q.offCsr = 0;      // staged over the dead tables (after the X/Z barrier)
+        else { q.offCsr = o; o += TF_CSR_DOUBLES; }
+        q.lds_doubles = o;
+        // (TF_ERI_FACT_THREADS=64|128: smaller workgroups for experiments -- measured slower at N = 400, 127 / 159 ms against 113-127 ms:
+        // the LDS of a quartet limits the workgroups per CU, so fewer waves per workgroup are fewer waves per CU)
+        static const int force_thr = getenv("TF_ERI_FACT_THREADS") ? atoi(getenv("TF_ERI_FACT_THREADS")) : 0;
+        const int fact_threads = (force_thr == 64 || force_thr == 128) ? force_thr : TF_ERI_THREADS;
+        hipLaunchKernelGGL(eri_fact_kernel, dim3(q.n_ket, n_bra), dim3(fact_threads), (size_t)o * sizeof(double), st, ctx->db, q, d_bra,
+                           d_braoff, d_ket, Nc, d_out_slab);
+    } else {
+        const int RB = 3584, EB = 3072;                     // LDS doubles for R tables / staged E tables
+        int PB = RB / q.tsize - 1;
+        PB = std::max(1, std::min(std::min(PB, TF_ERI_THREADS), q.npq));
+        q.PB = PB; q.stride = PB | 1; q.G = 1; q.ncp = 0;
+        const int needE = q.npp_ab * 2 * q.nEab + q.npp_cd * 2 * q.nEcd;
+        const bool stage = needE <= EB;
+        int o = 0;
+        q.offR = o; o += q.stride * q.tsize;
+        q.offPref = o; o += TF_ERI_THREADS;
+        q.offPQ = o; o += TF_ERI_THREADS;
+        q.offRed = o; o += TF_ERI_THREADS;
+        q.offEab = o; o += stage ? q.npp_ab * 2 * q.nEab : 0;
+        q.offEcd = o; o += stage ? q.npp_cd * 2 * q.nEcd : 0;
+        q.offScale = o; o += 84;
+        q.offLmn = o; o += 42;
+        q.offBlk = o; o += TF_BLK_DOUBLES;
+        q.offCsr = o; o += TF_CSR_DOUBLES;
+        q.lds_doubles = o;
+        const dim3 grid(q.n_ket, n_bra);
+        if (stage)
+            hipLaunchKernelGGL((eri_class_kernel<true, false>), grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q,
+                               d_bra, d_braoff, d_ket, Nc, d_out_slab);
+        else
+            hipLaunchKernelGGL((eri_class_kernel<false, false>), grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q,
+                               d_bra, d_braoff, d_ket, Nc, d_out_slab);
+    }
+}
+
+// Small problems: per slab one launch per (bra group, ket group), each mixing the classes of its groups (LDS carved by the
+// capacities the groups need).  bra_host: the slab's bra pairs (sorted by group).
+void EriBuild::launch_generic_old(unsigned n_bra, const int *d_bra, const long long *d_braoff, unsigned n_ket, const int *d_ket, hipStream_t st)
+{
+    QClass q{};
+    const int RB = 2048, EBa = 1024, EBc = 1024;       // (doubling the E capacities halves the occupancy: Ar2 build 0.084 -> 0.18 s)
+    int o = 0;
+    q.offR = o; o += RB;
+    q.offPref = o; o += TF_ERI_THREADS;
+    q.offPQ = o; o += TF_ERI_THREADS;
+    q.offRed = o; o += TF_ERI_THREADS;
+    q.offEab = o; o += EBa;
+    q.offEcd = o; o += EBc;
+    q.offScale = o; o += 84;
+    q.offLmn = o; o += 42;
+    q.lds_doubles = o;
+    q.offBlk = o;                                            // unused (unfused)
+    q.G = 1; q.n_ket = (int)n_ket; q.fused = 0;
+    q.tri = packed ? 1 : 0;
+    hipLaunchKernelGGL((eri_class_kernel<true, true>), dim3(n_ket, n_bra), dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st,
+                       ctx->db, q, d_bra, d_braoff, d_ket, Nc, d_C);
+}
+
+EriBuild::GroupStat EriBuild::group_stat(const int *pairs_host, size_t n) const
+{
+    GroupStat g;
+    for (size_t k = 0; k < n; ++k) {
+        const tf::Pair &pr = bs.pairs[pairs_host[k]];
+        g.maxLp = std::max(g.maxLp, pr.La + pr.Lb);
+        g.maxT = std::max(g.maxT, (pr.La + 1) * (pr.Lb + 1));
+        g.maxE = std::max(g.maxE, pr.npp * 2 * pr.nE);
+        g.maxcomp = std::max(g.maxcomp, bs.shells[pr.A].ncomp * bs.shells[pr.B].ncomp);
+        g.maxnpp = std::max(g.maxnpp, pr.npp);
+    }
+    g.maxLp1 = g.maxLp + 1;
+    return g;
+}
+
+// LDS carve-out of the launch (bra group gb, ket group gk), from the largest angular momenta / contraction depths of the groups
+void EriBuild::make_caps()
+{
+    GroupStat gs[NGRP];
+    for (int g = 0; g < NGRP; ++g) gs[g] = group_stat(kets_all_host.data() + kets_goff[g], (size_t)(kets_goff[g + 1] - kets_goff[g]));
+    for (int gb = 0; gb < NGRP; ++gb)
+        for (int gk = 0; gk < NGRP; ++gk) {
+            const GroupStat &sb = gs[gb], &sk = gs[gk];
+            const int Lmax = sb.maxLp + sk.maxLp, nM = Lmax / 2 + 1, tsize = (Lmax + 1) * (Lmax + 2) / 2;
+            const int xz = sb.maxT * sk.maxT * nM, gsz = sk.maxT * sb.maxLp1 * nM;
+            const bool deep = sb.maxnpp > 1 || sk.maxnpp > 1;
+            // batch size aimed at and LDS doubles for the X / Z tables and the staged Hermite tables (tuning knobs; smaller carve-outs
+            // mean more workgroups per CU: Ar2/cc-pVQZ ERI kernels 21.1 ms with 48 / 1536 / 1536, 18.3 ms with 24 / 768 / 1024)
+            static const int k_nbt = getenv("TF_CF_NBT") ? atoi(getenv("TF_CF_NBT")) : 24, k_xz = getenv("TF_CF_XZ") ? atoi(getenv("TF_CF_XZ")) : 768;
+            static const int k_e = getenv("TF_CF_E") ? atoi(getenv("TF_CF_E")) : 1024;
+            const int nbt = deep ? std::min(TF_ERI_THREADS / (Lmax + 1), k_nbt) : 1;       // primitive quartets per batch aimed at
+            CFCaps c{};
+            int o = 0;
+            c.offR = o; c.capR = std::max(2 * tsize, std::min((nbt + 1) * tsize, 2 * k_xz * 2 / 3)); o += c.capR;
+            c.offPref = o; o += TF_ERI_THREADS;
+            c.offPQ = o; o += TF_ERI_THREADS;
+            c.offPP = o; o += TF_ERI_THREADS;
+            c.offG = o; c.capG = std::max(gsz, std::min(nbt * gsz, k_xz * 2 / 3)); o += c.capG;
+            c.capXZ = std::max(xz, std::min(nbt * xz, k_xz));
+            c.offX = o; o += c.capXZ;
+            c.offZ = o; o += c.capXZ;
+            c.offTupG = o; o += (gsz + 3) / 4;
+            c.offTupXZ = o; o += (xz + 3) / 4;
+            c.offEab = o; c.capEab = std::min(sb.maxE, k_e); o += c.capEab;
+            c.offEcd = o; c.capEcd = std::min(sk.maxE, k_e); o += c.capEcd;
+            c.offRed = o; o += TF_ERI_THREADS;
+            c.offKm = o; c.capKm = fam_off ? 0 : FAM_MM * (((gk & 1) ? sk.maxnpp : 0) + ((gb & 1) ? sb.maxnpp : 0)); o += c.capKm;
+            c.lds_doubles = o;
+            c.tri = packed ? 1 : 0;
+            c.dbg_npq_lo = 0; c.dbg_npq_hi = 0x7fffffff;
+            c.team_lmax = use_teamc ? TF_TEAM_LMAX : -1; c.team_pqmax = teamc_pqmax;
+            if (const char *e = getenv("TF_ERI_DBG_NPQ")) (void)sscanf(e, "%d:%d", &c.dbg_npq_lo, &c.dbg_npq_hi);
+            gcaps[gb][gk] = c;
+            gcaps_fit[gb][gk] = (size_t)o * sizeof(double) <= 160 * 1024 - 256;
+            gcaps_gtab[gb][gk] = false;
+            if (!gcaps_fit[gb][gk] && !deep) {
+                // (hh|hh)-sized tables: G, X and Z of a workgroup go to global memory, everything else stays in LDS
+                CFCaps d = c;
+                int q = 0;
+                d.offR = q; q += d.capR;
+                d.offPref = q; q += TF_ERI_THREADS;
+                d.offPQ = q; q += TF_ERI_THREADS;
+                d.offPP = q; q += TF_ERI_THREADS;
+                d.offTupG = q; q += (gsz + 3) / 4;
+                d.offTupXZ = q; q += (xz + 3) / 4;
+                d.offEab = q; q += d.capEab;
+                d.offEcd = q; q += d.capEcd;
+                d.offRed = q; q += TF_ERI_THREADS;
+                d.offKm = q; q += d.capKm;
+                d.lds_doubles = q;
+                d.capG = gsz; d.capXZ = xz;
+                d.offG = 0; d.offX = gsz; d.offZ = gsz + xz;
+                d.gtab_doubles = gsz + 2 * xz;
+                if ((size_t)q * sizeof(double) <= 160 * 1024 - 256) { gcaps[gb][gk] = d; gcaps_fit[gb][gk] = true; gcaps_gtab[gb][gk] = true; }
+            }
+        }
+}
+
+// per (La, Lb | Lc, Ld): table sizes, index words of the table entries, batch capacity under the caps of its launch
+int EriBuild::make_lrecs(bool with_caps)
+{
+    std::vector<LRec> recs(6 * 6 * 6 * 6, LRec{});
+    std::vector<unsigned short> tup;
+    std::vector<char> seen_pair(36, 0);
+    for (const tf::Pair &pr : bs.pairs) seen_pair[pr.La * 6 + pr.Lb] = 1;
+    auto grp_of = [&](int lp) { return lp_group(lp); };
+    for (int ab = 0; ab < 36; ++ab)
+        for (int cd = 0; cd < 36; ++cd) {
+            if (!seen_pair[ab] || !seen_pair[cd]) continue;
+            const int La = ab / 6, Lb = ab % 6, Lc = cd / 6, Ld = cd % 6;
+            const int gb = grp_of(La + Lb), gk = grp_of(Lc + Ld);
+            LRec r{};
+            r.L = La + Lb + Lc + Ld; r.nM = r.L / 2 + 1; r.tsize = (r.L + 1) * (r.L + 2) / 2;
+            r.nT = (La + 1) * (Lb + 1) * (Lc + 1) * (Ld + 1); r.xz = r.nT * r.nM;
+            const int Lab1 = La + Lb + 1;
+            r.gsz = (Lc + 1) * (Ld + 1) * Lab1 * r.nM;
+            r.lgG = 0; while ((1 << r.lgG) < r.gsz && (1 << r.lgG) < TF_ERI_THREADS) ++r.lgG;
+            r.lgX = 0; while ((1 << r.lgX) < r.xz && (1 << r.lgX) < TF_ERI_THREADS) ++r.lgX;
+            // batch capacity: the smallest over the launches (contracted bra and / or ket group) this tuple can occur in
+            int nb = TF_ERI_THREADS / (r.L + 1);
+            for (int fb = 0; fb < 2 && with_caps; ++fb)
+                for (int fk = 0; fk < 2; ++fk) {
+                    if (fb + fk == 0) continue;
+                    const CFCaps &c = gcaps[2 * gb + fb][2 * gk + fk];
+                    if (c.capR < 2 * r.tsize || c.capG < r.gsz || c.capXZ < r.xz) continue;   // (no such quartet in that launch)
+                    nb = std::min(nb, c.capR / r.tsize - 1);
+                    nb = std::min(nb, std::min(c.capG / r.gsz, c.capXZ / r.xz));
+                }
+            r.nb_cap = std::max(nb, 1);
+            // entry e of the G table = ((cc (Ld + 1) + d) Lab1 + v) nM + n, of the X / Z tables = (((a2 (Lb + 1) + b2) (Lc + 1) + cc) (Ld + 1) + d) nM + m
+            // (nested loops in that order: a cc-pVQZ basis has 625 tuples and 6e5 entries -- with a division chain per entry this was
+            // 2 ms of every tensor build)
+            r.tupG_off = (int)tup.size();
+            tup.resize(tup.size() + (size_t)r.gsz + (size_t)r.xz);
+            unsigned short *tp = tup.data() + r.tupG_off;
+            for (int cc = 0; cc <= Lc; ++cc)
+                for (int d = 0; d <= Ld; ++d)
+                    for (int v = 0; v < Lab1; ++v)
+                        for (int n = 0; n < r.nM; ++n) *tp++ = (unsigned short)(n | (v << 4) | (d << 8) | (cc << 11));
+            r.tupXZ_off = r.tupG_off + r.gsz;
+            for (int a2 = 0; a2 <= La; ++a2)
+                for (int b2 = 0; b2 <= Lb; ++b2)
+                    for (int cc = 0; cc <= Lc; ++cc)
+                        for (int d = 0; d <= Ld; ++d)
+                            for (int m = 0; m < r.nM; ++m) *tp++ = (unsigned short)(m | (a2 << 4) | (b2 << 7) | (cc << 10) | (d << 13));
+            recs[ab * 36 + cd] = r;
+        }
+    if (ctx->d_lrec) { (void)tf_free(ctx->d_lrec); ctx->d_lrec = nullptr; }
+    if (ctx->d_tup) { (void)tf_free(ctx->d_tup); ctx->d_tup = nullptr; }
+    int rc2;
+    if ((rc2 = upload(ctx, recs, &ctx->d_lrec, false)) || (rc2 = upload(ctx, tup, &ctx->d_tup, false))) return rc2;
+    ctx->db.lrec = ctx->d_lrec; ctx->db.tup = ctx->d_tup;
+    lrecs_host = recs;
+    return TF_OK;
+}
+
+// families of the bra pairs [b0, b1) of the slab's list, at most `most` members each: built and uploaded once per (slab, bra group)
+const EriBuild::BraFam *EriBuild::bra_families(BraFams &bra_fams, const std::vector<int> &bra_host, size_t b0, size_t b1, int most)
+{
+    auto bf = bra_fams.find(std::make_pair(b0, most));
+    if (bf != bra_fams.end()) return &bf->second;
+    BraFam nf;
+    std::vector<int> bptr{0}, bmem;
+    std::map<std::pair<int, int>, int> open_fam;
+    std::vector<std::vector<int>> fams;
+    for (size_t y = b0; y < b1; ++y) {
+        const tf::Pair &pr = bs.pairs[bra_host[y]];
+        const auto key = std::make_pair(psid[pr.A], psid[pr.B]);
+        auto it = open_fam.find(key);
+        if (it == open_fam.end() || (int)fams[it->second].size() >= most) {
+            fams.emplace_back();
+            open_fam[key] = (int)fams.size() - 1;
+            it = open_fam.find(key);
+        }
+        fams[it->second].push_back((int)y);
+    }
+    for (const auto &f : fams) { bmem.insert(bmem.end(), f.begin(), f.end()); bptr.push_back((int)bmem.size()); }
+    if (mem.up(bptr, &nf.d_ptr) || mem.up(bmem, &nf.d_mem)) return nullptr;
+    nf.n = (unsigned)(bptr.size() - 1);
+    return &bra_fams.emplace(std::make_pair(b0, most), nf).first->second;
+}
+
+// One launch per (bra group, ket group) with work.  A process has few hardware queues (4 by default) and the launches of one
+// queue run one after the other, each as long as its slowest workgroup: the launches are spread over NQ streams by estimated
+// cost (heaviest first, always onto the least loaded stream) instead of round-robin over all of them.
+int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra, const long long *d_braoff)
+{
+    static const bool old_generic = getenv("TF_ERI_GENERIC_OLD") != nullptr;
+    struct Launch { size_t b0, b1; int gb, gk; double cost; };
+    std::vector<Launch> launches;
+    double ket_cost[NGRP];
+    for (int g = 0; g < NGRP; ++g) {
+        ket_cost[g] = 0.0;
+        for (int k = kets_goff[g]; k < kets_goff[g + 1]; ++k) ket_cost[g] += (double)pair_cost(kets_all_host[k]);
+    }
+    for (size_t b0 = 0; b0 < bra_host.size();) {
+        const int gb = pair_group(bra_host[b0]);
+        size_t b1 = b0;
+        double bc = 0.0;
+        while (b1 < bra_host.size() && pair_group(bra_host[b1]) == gb) { bc += (double)pair_cost(bra_host[b1]); ++b1; }
+        for (int gk = 0; gk < NGRP; ++gk)
+            if (kets_goff[gk + 1] > kets_goff[gk]) launches.push_back(Launch{b0, b1, gb, gk, bc * ket_cost[gk]});
+        b0 = b1;
+    }
+    std::stable_sort(launches.begin(), launches.end(), [](const Launch &x, const Launch &y) { return x.cost > y.cost; });
+    // (as many streams as the process has hardware queues: 4 unless GPU_MAX_HW_QUEUES says otherwise -- tuna_amd sets 16)
+    const int hwq = getenv("GPU_MAX_HW_QUEUES") ? std::max(1, atoi(getenv("GPU_MAX_HW_QUEUES"))) : 4;
+    const int NQ = std::min(NSTREAM, getenv("TF_ERI_NQ") ? std::max(1, atoi(getenv("TF_ERI_NQ"))) : std::max(4, std::min(8, hwq)));
+    std::vector<double> load(NQ, 0.0);
+    BraFams bra_fams;
+    for (const Launch &l : launches) {
+        const int qi = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        load[qi] += l.cost;
+        hipStream_t st = streams[qi];
+        const int gb = l.gb, gk = l.gk, nk = kets_goff[gk + 1] - kets_goff[gk];
+        const size_t b0 = l.b0, b1 = l.b1;
+        const CFCaps &c = gcaps[gb][gk];
+        const size_t bytes = (size_t)c.lds_doubles * sizeof(double);
+        if (old_generic || !gcaps_fit[gb][gk]) {             // the component-per-lane kernel
+            launch_generic_old((unsigned)(b1 - b0), d_bra + b0, d_braoff + b0, (unsigned)nk, d_kets_all + kets_goff[gk], st);
+            continue;
+        }
+        if (bytes > 64 * 1024 && !ctx->cfact_lds_set) {
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+            ctx->cfact_lds_set = 160 * 1024;
+        }
+        if (gcaps_gtab[gb][gk]) {
+            const size_t need = (size_t)nk * (b1 - b0) * (size_t)c.gtab_doubles * sizeof(double);
+            if (need > ctx->gtab_bytes) {
+                HIPCHK(ctx, hipDeviceSynchronize());           // (earlier launches of this build may still use the old block)
+                if (ctx->d_gtab) (void)tf_free(ctx->d_gtab);
+                ctx->d_gtab = nullptr; ctx->gtab_bytes = 0;
+                HIPCHK(ctx, tf_malloc((void **)&ctx->d_gtab, need));
+                ctx->gtab_bytes = need;
+            }
+            // launches that share the block must not overlap: they all go to one stream
+            hipLaunchKernelGGL((eri_cfact_kernel<true, true>), dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, streams[0], ctx->db, c,
+                               d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C, ctx->d_gtab);
+            load[qi] -= l.cost; load[0] += l.cost;
+        } else if (((gb | gk) & 1) == 0)                     // both groups uncontracted: one primitive quartet per shell quartet
+            hipLaunchKernelGGL(eri_cfact_kernel<true>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
+                               d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
+        else if ((gb & 1) && !(gk & 1) && bra_fam_on) {       // contracted bras against uncontracted kets: (family of bra pairs, ket pair).
+            // Off by default (TF_ERI_BRA_FAMILIES=1): the packed layout evaluates the kets whose first shell does not exceed the bra's,
+            // and the contracted shells come first on each atom -- the contracted pairs sit on the ket side; measured on Ar2/cc-pVQZ these
+            // bra families cost 5 % (fewer, longer workgroups) where the ket families gain 24 %.
+            const BraFam *bf = bra_families(bra_fams, bra_host, b0, b1, FAM_MM);
+            if (!bf) return TF_ENOMEM;
+            static bool bfam_attr_set = false;
+            if (bytes > 64 * 1024 && !bfam_attr_set) {
+                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MM, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+                bfam_attr_set = true;
+            }
+            hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MM, 1>), dim3((unsigned)nk, bf->n), dim3(TF_ERI_THREADS), bytes, st,
+                               ctx->db, c, d_bra, d_braoff, d_kets_all + kets_goff[gk], Nc, d_C, (double *)nullptr, (const int *)nullptr,
+                               (const int *)nullptr, bf->d_ptr, bf->d_mem);
+        }
+        else if ((gb & 1) && (gk & 1) && fam_any && !cc_fam_off) {
+            // contracted against contracted: families on both sides -- up to 3 bra pairs x up to 9 ket pairs per workgroup (27 accumulators
+            // per component: the deepest quartets, (s13 s13|s13 s13) and friends, spend their time in the tables of 28 561 primitive quartets)
+            const BraFam *bf = bra_families(bra_fams, bra_host, b0, b1, FAM_MA_CC);
+            if (!bf) return TF_ENOMEM;
+            static bool ccfam_attr_set = false;
+            if (bytes > 64 * 1024 && !ccfam_attr_set) {
+                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+                ccfam_attr_set = true;
+            }
+            hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), bf->n),
+                               dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra, d_braoff, d_fam_heads + fam_goff[gk], Nc, d_C, (double *)nullptr,
+                               d_fam_ptr + fam_goff[gk], d_fam_mem, bf->d_ptr, bf->d_mem);
+        }
+        else if ((gk & 1) && fam_any) {                       // contracted kets: one workgroup per (bra pair, family of ket pairs)
+            static bool fam_attr_set = false;                 // (per process and device: the attribute belongs to the function)
+            if (bytes > 64 * 1024 && !fam_attr_set) {
+                HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, 1, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+                fam_attr_set = true;
+            }
+            hipLaunchKernelGGL((eri_cfact_kernel<false, false, 1, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), (unsigned)(b1 - b0)),
+                               dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra + b0, d_braoff + b0, d_fam_heads + fam_goff[gk], Nc, d_C,
+                               (double *)nullptr, d_fam_ptr + fam_goff[gk], d_fam_mem);
+        } else
+            hipLaunchKernelGGL(eri_cfact_kernel<false>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
+                               d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
+        ++launch_count;
+    }
+    return TF_OK;
+}
+
+// ---- team kernels (tf_eri_team.hip.h): the uncontracted classes of the per-class mode, packed layout.  Per pair class the ket
+// pair transform (Cartesian component pairs -> output pairs inside each x/y parity class, normalisation ratios folded in), per
+// shell pair the slab offsets of its output pairs.
+int EriBuild::plan_team_tables()
+{
+    int rc;
+    if (!use_team) return TF_OK;
+    std::vector<int> kt_ptr, kt_k, kq_ptr(npairs, 0), kq_off;
+    std::vector<double> kt_c, blkC, blkD;
+    std::vector<std::vector<int>> kap_list(ncls);               // output pairs (sc << 8 | sd) of a pair class, sorted by parity class
+    auto rows_of = [&](const tf::Shell &sh, std::vector<double> &U) {   // transformation rows of a shell (identity: Cartesian output)
+        if (spherical) { tf::sph_block(sh.L, U); return; }
+        U.assign((size_t)sh.ncomp * sh.ncomp, 0.0);
+        for (int i = 0; i < sh.ncomp; ++i) U[(size_t)i * sh.ncomp + i] = 1.0;
     };
-    bool any_wide_pair = false;                                    // a pair sum beyond the team kernels' instantiations
-    int max_npp_all = 1;
+    auto cls_of = [&](const tf::Shell &sh, const std::vector<double> &U, int r) {   // parity class of an output function: its first component's
+        int cc = 0;
+        while (cc + 1 < sh.ncomp && U[(size_t)r * sh.ncomp + cc] == 0.0) ++cc;
+        const int a = sh.comp_off + cc;
+        return (bs.c_lx[a] & 1) | ((bs.c_ly[a] & 1) << 1);
+    };
+    for (int c = 0; c < ncls; ++c) {
+        const DPair &pr = ctx->host_pairs[ctx->class_pairs[c][0]];
+        const tf::Shell &sC = bs.shells[pr.A], &sD = bs.shells[pr.B];
+        const int nsc = out_dim(sC), nsd = out_dim(sD), ncc = sC.ncomp, ncd = sD.ncomp;
+        rows_of(sC, blkC); rows_of(sD, blkD);
+        std::vector<int> loc((size_t)ncc * ncd, 0);              // position of a component pair inside its parity class (inverse of ct_ord)
+        for (int cl = 0; cl < 4; ++cl)
+            for (int s2 = pr.pcls[cl]; s2 < pr.pcls[cl + 1]; ++s2) loc[ctx->h_ct_ord[pr.tab_off + s2]] = s2 - pr.pcls[cl];
+        KClassTab &kt = kct[c];
+        kt.tp_off = (int)kt_ptr.size(); kt.te_off = (int)kt_k.size();
+        for (int cl = 0; cl < 4; ++cl) {
+            kt.pS[cl] = (int)kap_list[c].size();
+            for (int sc = 0; sc < nsc; ++sc)
+                for (int sd = 0; sd < nsd; ++sd) {
+                    if ((cls_of(sC, blkC, sc) ^ cls_of(sD, blkD, sd)) != cl) continue;
+                    kap_list[c].push_back((sc << 8) | sd);
+                    kt_ptr.push_back((int)kt_k.size() - kt.te_off);
+                    for (int cc = 0; cc < ncc; ++cc) {
+                        const double uc = blkC[(size_t)sc * ncc + cc];
+                        if (uc == 0.0) continue;
+                        for (int cd2 = 0; cd2 < ncd; ++cd2) {
+                            const double ud = blkD[(size_t)sd * ncd + cd2];
+                            if (ud == 0.0) continue;
+                            const int f = cc * ncd + cd2;
+                            kt_k.push_back(loc[f]);
+                            kt_c.push_back(uc * ud * ctx->h_ct_sc[pr.tab_off + f]);
+                        }
+                    }
+                }
+        }
+        kt.pS[4] = kt.nkap = (int)kap_list[c].size();
+        kt_ptr.push_back((int)kt_k.size() - kt.te_off);
+        kt.nnzT = (int)kt_k.size() - kt.te_off;
+    }
+    for (int p = 0; p < npairs; ++p) {
+        const DPair &pr = ctx->host_pairs[p];
+        kq_ptr[p] = (int)kq_off.size();
+        for (int word : kap_list[ctx->pair_class[p]]) {
+            const int k = pr.outoff_a + (word >> 8), l = pr.outoff_b + (word & 255);
+            if (l > k) { kq_off.push_back(-1); continue; }
+            const int cb = H.cls[k] ^ H.cls[l];
+            kq_off.push_back(H.fullsec[cb][H.cls[k]] + H.kinfo[(size_t)cb * N + H.sigma[k]].offA + H.loc[l]);
+        }
+    }
+    if ((rc = mem.up(kq_ptr, &d_kq_ptr)) || (rc = mem.up(kq_off, &d_kq_off)) || (rc = mem.up(kt_ptr, &d_kt_ptr)) ||
+        (rc = mem.up(kt_k, &d_kt_k)) || (rc = mem.up(kt_c, &d_kt_c)))
+        return rc;
+    ctx->db.kq_ptr = d_kq_ptr; ctx->db.kq_off = d_kq_off; ctx->db.kt_ptr = d_kt_ptr; ctx->db.kt_k = d_kt_k; ctx->db.kt_c = d_kt_c;
+    // flat records of the class-sorted ket list (uncontracted pairs) and, per class and shell A, the kets with first shell <= A
+    std::vector<KetRec> krec(ket_sorted.size());
+    for (size_t k = 0; k < ket_sorted.size(); ++k) {
+        const tf::Pair &pr = bs.pairs[ket_sorted[k]];
+        const double qq = bs.pp_p[pr.pp_off];
+        krec[k] = KetRec{qq, bs.pp_Pz[pr.pp_off], bs.pp_K[pr.pp_off] / qq, (unsigned)pr.e_off, kq_ptr[ket_sorted[k]]};
+    }
+    std::vector<int> kcnt((size_t)ncls * nsh, 0);
+    for (int c = 0; c < ncls; ++c) {
+        for (int p2 : ctx->class_pairs[c]) ++kcnt[(size_t)c * nsh + bs.pairs[p2].A];
+        for (int a = 1; a < nsh; ++a) kcnt[(size_t)c * nsh + a] += kcnt[(size_t)c * nsh + a - 1];
+    }
+    if ((rc = mem.up(krec, &d_ketrec)) || (rc = mem.up(kcnt, &d_kcnt))) return rc;
+    if (use_team_pc) {
+        // flat lists of the parity-allowed components and of the outputs of every (bra class, ket class) of uncontracted pairs
+        std::vector<int> tflat;
+        flat_off.assign((size_t)ncls * ncls, -1);
+        for (int bc = 0; bc < ncls; ++bc)
+            for (int kc = 0; kc < ncls; ++kc) {
+                const DPair &hb = ctx->host_pairs[ctx->class_pairs[bc][0]], &hk = ctx->host_pairs[ctx->class_pairs[kc][0]];
+                if (hb.npp != 1 || hk.npp != 1 || hb.La + hb.Lb > TF_TEAM_LMAX || hk.La + hk.Lb > TF_TEAM_LMAX) continue;
+                int mb, mk, nz;
+                const TClass t = tclass_common(bc, kc, mb, mk, nz);
+                if (nz > 2048) continue;                          // (chunked classes keep the loop per parity class)
+                flat_off[(size_t)bc * ncls + kc] = (int)tflat.size();
+                for (int c = 0; c < 4; ++c)
+                    for (int il = 0; il < t.pA[c + 1] - t.pA[c]; ++il)
+                        for (int kl = 0; kl < t.pK[c + 1] - t.pK[c]; ++kl) tflat.push_back((t.pA[c] + il) | ((t.pK[c] + kl) << 16));
+                if (tflat.size() & 1) tflat.push_back(0);
+                int vbase = 0;
+                for (int c = 0; c < 4; ++c) {
+                    const int nA = t.pA[c + 1] - t.pA[c], nK = t.pK[c + 1] - t.pK[c], nS = t.pS[c + 1] - t.pS[c];
+                    for (int il = 0; il < nA; ++il)
+                        for (int ks = 0; ks < nS; ++ks) { tflat.push_back((t.pA[c] + il) | ((t.pS[c] + ks) << 16)); tflat.push_back(vbase + il * nK); }
+                    vbase += nA * nK;
+                }
+            }
+        if ((rc = mem.up(tflat, &d_tflat))) return rc;
+        ctx->db.tflat = d_tflat;
+    }
+    return TF_OK;
+}
+
+// device index buffers sized for the largest possible slab, reused by every slab
+int EriBuild::plan_index_buffers()
+{
+    int rc;
+    size_t max_out = 0;
+    for (int p : mine_sorted) max_out = std::max<size_t>(max_out, (size_t)pair_rows[p]);
+    cap_bra = std::min<size_t>(mine_sorted.size(), 65535) + 1;
+    cap_out = (size_t)std::min<long long>(ctx->n_rows, max_rows_c * 2 + (long long)max_out) + 1;
+    // two sets of a slab's index lists: the lists of slab k + 1 are uploaded (on a stream of their own) while the kernels of slab k run;
+    // the kernels themselves stay ordered by the streams (one half-transformed slab)
+    out_bytes = cap_out * std::max(std::max(sizeof(OutRow), sizeof(OutRowP)), sizeof(OutRowT)); rowcls_bytes = (size_t)max_rows_c + 1;
+    if ((rc = mem.alloc(&d_bra, 2 * cap_bra * sizeof(int)))) return rc;
+    if ((rc = mem.alloc(&d_braoff, 2 * cap_bra * sizeof(long long)))) return rc;
+    if (use_team_pc) if ((rc = mem.alloc(&d_brarec, 2 * cap_bra * sizeof(BraRec)))) return rc;
+    if ((rc = mem.alloc(&d_out, 2 * out_bytes))) return rc;
+    if (packed && !per_class) if ((rc = mem.alloc(&d_rowcls, 2 * rowcls_bytes))) return rc;
+    d_bra_alloc = d_bra; d_braoff_alloc = d_braoff; d_out_alloc = d_out;
+    d_brarec_alloc = d_brarec; d_rowcls_alloc = d_rowcls;
+    d_bra_base = d_bra;
+    return TF_OK;
+}
+
+// Generation: slab size, work counters, ket lists and families, streams, the launch tables of the mode, the slabs' index lists
+int EriBuild::plan_generation()
+{
+    int rc;
+    if ((rc = plan_slab_size())) return rc;
+    plan_work_counters();
+    DBG("slab buffers allocated");
+    t_wall0 = std::chrono::steady_clock::now();
+    if ((rc = plan_ket_lists()) || (rc = plan_ket_families())) return rc;
+    // my bra pairs ordered by class: a slab is a run of that list, launches go per (bra class run, ket class)
+    mine_sorted.clear();
+    for (int c = 0; c < ncls; ++c)
+        for (int p : ctx->class_pairs[c])
+            if (owner[p] == ctx->rank) mine_sorted.push_back(p);
+    if ((rc = setup_streams())) return rc;
+    DBG("streams created");
+    static const bool team_off = getenv("TF_ERI_TEAM") && getenv("TF_ERI_TEAM")[0] == '0';
+    const bool team_ok = packed && !team_off && bs.epool.size() < 0xffffffffull;
+    use_team_pc = team_ok && per_class;                                        // per-class mode: eri_team_kernel for the uncontracted classes
+    // (off by default: on the BASELINE basis sets eri_cfact_kernel is faster -- N2/cc-pVTZ 1.2 ms against 3.3-4.2 ms, Ar2/cc-pVQZ 18 ms against
+    // 22-25 ms of ERI kernels: a team walks the primitive quartets of its shell quartet one after the other, a chain of dependent phases
+    // with nothing else on the chip to hide it; TF_ERI_TEAMC=1 switches it on for experiments and for the parity tests)
+    static const bool teamc_off = !(getenv("TF_ERI_TEAMC") && getenv("TF_ERI_TEAMC")[0] == '1');
+    use_teamc = team_ok && !per_class && !teamc_off;                          // small-problem mode: eri_teamc_kernel over task lists
+    use_team = use_team_pc || use_teamc;                                       // the team kernels' tables are needed
+    static const int teamc_pqmax_env = getenv("TF_TEAMC_PQMAX") ? atoi(getenv("TF_TEAMC_PQMAX")) : 700;
+    teamc_pqmax = teamc_pqmax_env;
+    kct.assign(ncls, KClassTab());
+    DBG("stage: small-problem groups");
+    DBG("stage: carve-outs");
+    DBG("stage: launch lambda defined");
+    if (!per_class) make_caps();
+    DBG("stage: index-word tables");
+    if ((rc = make_lrecs(!per_class))) return rc;
+    DBG("stage: team tables");
+    if ((rc = plan_team_tables())) return rc;
+    if (!per_class)
+        std::stable_sort(mine_sorted.begin(), mine_sorted.end(), [&](int x, int y) {
+            const int gx = pair_group(x), gy = pair_group(y);
+            return gx != gy ? gx < gy : pair_cost(x) > pair_cost(y);
+        });
+    if ((rc = plan_index_buffers())) return rc;
+    DBG("stage: teamc tables");
+    tc_of.assign((size_t)ncls * ncls, -2);
     for (int p2 = 0; p2 < npairs; ++p2) {
         any_wide_pair = any_wide_pair || bs.pairs[p2].La + bs.pairs[p2].Lb > TF_TEAM_LMAX;
         max_npp_all = std::max(max_npp_all, bs.pairs[p2].npp);
     }
-    TClass *d_tcs = nullptr; TeamTask *d_tasks = nullptr;
-    size_t d_tcs_cap = 0, d_tasks_cap = 0;
-    size_t cursor = 0;
-    DBG("stage: slab loop");
-    while (cursor < mine_sorted.size()) {
-        std::vector<int> bra; std::vector<long long> braoff; std::vector<OutRow> outs;
-        std::vector<OutRowP> outsP;
-        std::vector<OutRowT> outsT;
-        std::vector<signed char> rowcls;
-        long long rows_c = 0;
-        while (cursor < mine_sorted.size()) {
-            const int p = mine_sorted[cursor];
-            const tf::Shell &a = bs.shells[bs.pairs[p].A], &b = bs.shells[bs.pairs[p].B];
-            const long long nr = (long long)a.ncomp * b.ncomp;
-            if (!bra.empty() && (rows_c + nr > max_rows_c || bra.size() >= 65535 || outs.size() + outsP.size() + outsT.size() + (size_t)pair_rows[p] >= cap_out)) break;
-            bra.push_back(p); braoff.push_back(rows_c);
-            long long r = pair_first_row[p];
-            for (int x = 0; x < out_dim(a); ++x)
-                for (int y = 0; y < out_dim(b); ++y) {
-                    const int i = out_off(a) + x, j = out_off(b) + y;
-                    if (i < j) continue;
-                    if (!packed) { outs.push_back(OutRow{i, j, a.cart_off, b.cart_off, b.ncomp, 0, rows_c, r++}); continue; }
-                    if (tiles) { outsT.push_back(OutRowT{i, j, H.sigma[i], H.sigma[j], H.cls[i] ^ H.cls[j], b.ncomp, a.cart_off, b.cart_off, rows_c}); continue; }
-                    const int lr = rowmap[ikey(H.sigma[i], H.sigma[j])];
-                    OutRowP o{};
-                    o.i = i; o.j = j; o.iI = H.sigma[i]; o.lamj = H.loc[j]; o.c = H.cls[i] ^ H.cls[j]; o.ncb = b.ncomp;
-                    o.cartA = a.cart_off; o.cartB = b.cart_off;
-                    for (int t = 0; t < 4; ++t) o.secoff[t] = rowsec[6 * (size_t)lr + t];
-                    o.len = rowlen[lr]; o.slab_off = rows_c; o.ubase = rowoff[lr]; o.upos = rowsec[6 * (size_t)lr + 4]; o.unr = rowsec[6 * (size_t)lr + 5];
-                    outsP.push_back(o);
+    return TF_OK;
+}
+
+// ---- small-problem mode with team kernels (eri_teamc_kernel): class records per (bra class, ket class), created on demand; tasks
+// per slab.  A quartet belongs to that kernel when both pair sums are <= TF_TEAM_LMAX and it has <= teamc_pqmax primitive quartets;
+// eri_cfact_kernel skips exactly those (CFCaps::team_lmax / team_pqmax).
+int EriBuild::teamc_class(int bcls, int kcls)
+{
+    int &slot = tc_of[(size_t)bcls * ncls + kcls];
+    if (slot != -2) return slot;
+    int maxblk, maxK, nnzc;
+    TClass t = tclass_common(bcls, kcls, maxblk, maxK, nnzc);
+    const int LAB = t.La + t.Lb, LCD = t.Lc + t.Ld, L = LAB + LCD, NM = L / 2 + 1, XS = NM | 1;
+    if (LAB > TF_TEAM_LMAX || LCD > TF_TEAM_LMAX) return slot = -1;
+    auto even = [](int x) { return (x + 1) & ~1; };
+    int o = 0;
+    t.oE12 = 0;
+    t.oOffA = o; o += 2 * t.nab;
+    t.oScA = o; o += even(t.nab);
+    t.oOffK = o; o += 2 * t.ncd;
+    t.oTp = o; o += even((t.nkap + 2) / 2);
+    t.oTk = o; o += even((t.nnzT + 1) / 2);
+    t.oTc = o; o += even(t.nnzT);
+    t.shared_doubles = o;
+    t.vcap = even(2 * t.nEab + 2 * t.nEcd + (L + 1) * (L + 2) + t.nTcd * (LAB + 1) * NM);      // E12, E34, R, G of one primitive quartet
+    t.team_doubles = 2 * t.nT * XS + t.vcap + even(t.nacc) + even((t.nkap + 1) / 2);
+    auto bytes_of = [&](int tm) { return ((size_t)t.shared_doubles + (size_t)(256 / tm) * t.team_doubles) * sizeof(double); };
+    int team = 0;
+    if (t.nT <= 16 && nnzc <= 96 && eri_team_available(LAB, LCD, 16)) team = 16;
+    else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= 52 * 1024) team = 64;
+    else if (eri_team_available(LAB, LCD, 256) && bytes_of(256) <= 160 * 1024 - 256) team = 256;
+    else if (eri_team_available(LAB, LCD, 64) && bytes_of(64) <= 160 * 1024 - 256) team = 64;
+    if (!team) return slot = -1;
+    tcs_host.push_back(t); tc_team.push_back(team); tc_lds.push_back(bytes_of(team));
+    return slot = (int)tcs_host.size() - 1;
+}
+
+// small-problem mode with team kernels: the slab's tasks, one launch per (LAB, LCD, team, LDS size class)
+int EriBuild::teamc_tasks(const std::vector<int> &bra, const std::vector<long long> &braoff, std::vector<TcLaunch> &tcl, bool &old_needed)
+{
+    int rc;
+    std::map<std::array<int, 4>, int> lidx;
+    int max_npp_bra = 1;
+    for (size_t b = 0; b < bra.size(); ++b) {
+        const int pb = bra[b], A = bs.pairs[pb].A, bcls = ctx->pair_class[pb];
+        max_npp_bra = std::max(max_npp_bra, bs.pairs[pb].npp);
+        for (int kc = 0; kc < ncls; ++kc) {
+            const std::vector<int> &kl = ctx->class_pairs[kc];
+            const int nk_all = (int)(std::upper_bound(kl.begin(), kl.end(), A, [&](int a, int p2) { return a < bs.pairs[p2].A; }) - kl.begin());
+            if (nk_all == 0) continue;
+            const int id = teamc_class(bcls, kc);
+            if (id < 0) continue;
+            const int team = tc_team[(size_t)id], NT = 256 / team;
+            int lg = 10;
+            while (((size_t)1 << lg) < tc_lds[(size_t)id]) ++lg;
+            const std::array<int, 4> key{tcs_host[(size_t)id].La + tcs_host[(size_t)id].Lb, tcs_host[(size_t)id].Lc + tcs_host[(size_t)id].Ld, team, lg};
+            auto it = lidx.find(key);
+            if (it == lidx.end()) { it = lidx.emplace(key, (int)tcl.size()).first; tcl.push_back(TcLaunch{key[0], key[1], team, 0, {}, {}}); }
+            TcLaunch &TL = tcl[(size_t)it->second];
+            TL.lds = std::max(TL.lds, tc_lds[(size_t)id]);
+            for (int g0 = 0; g0 < nk_all; g0 += NT) {
+                const int nk = std::min(NT, nk_all - g0);
+                int npq_max = 0, todo = 0;
+                for (int u = 0; u < nk; ++u) {
+                    const int npq = bs.pairs[pb].npp * bs.pairs[kl[(size_t)(g0 + u)]].npp;
+                    if (npq <= teamc_pqmax) { ++todo; npq_max = std::max(npq_max, npq); }
                 }
-            if (packed && !per_class)
-                for (int ca = 0; ca < a.ncomp; ++ca)
-                    for (int cb = 0; cb < b.ncomp; ++cb) {
-                        const int u = a.comp_off + ca, v = b.comp_off + cb;
-                        rowcls.push_back((signed char)(((bs.c_lx[u] + bs.c_lx[v]) & 1) | (((bs.c_ly[u] + bs.c_ly[v]) & 1) << 1)));
-                    }
-            rows_c += nr;
-            const int Alim = packed ? bs.pairs[p].A + 1 : nsh;
-            n_quart += cum_pairs[Alim];
-            n_primq += (long long)bs.pairs[p].npp * cum_pp[Alim];
-            n_compq += nr * cum_comp[Alim];
-            {
-                const double npp_ab = (double)bs.pairs[p].npp;
-                const int lab = bs.pairs[p].La + bs.pairs[p].Lb;
-                for (int c = 0; c < 4; ++c) {
-                    nominal_flops += 8.0 * npp_ab * pairW[p][c] * cumW[Alim][c];
-                    for (int lcd = 0; lcd <= 10; ++lcd) {
-                        const double L1 = (double)(lab + lcd + 1);
-                        nominal_flops += npp_ab * pairNc[p][c] * cumNL[Alim][4 * lcd + c] * (6.0 * L1 + 1.5 * L1 * L1 + 60.0);
-                    }
-                }
-            }
-            ++cursor;
-        }
-        // this set of index lists was last read by the kernels of the slab before the previous one: wait for that slab only
-        const int set = (int)(slab_no & 1);
-        if (slab_no >= 2) HIPCHK(ctx, hipEventSynchronize(ctx->slab_done[set]));
-        d_bra = d_bra_alloc + (size_t)set * cap_bra; d_braoff = d_braoff_alloc + (size_t)set * cap_bra;
-        d_out = (char *)d_out_alloc + (size_t)set * out_bytes;
-        if (d_brarec_alloc) d_brarec = d_brarec_alloc + (size_t)set * cap_bra;
-        if (d_rowcls_alloc) d_rowcls = d_rowcls_alloc + (size_t)set * rowcls_bytes;
-        d_bra_base = d_bra;
-        ++slab_no;
-        const hipStream_t cst = ctx->cstream;
-        HIPCHK(ctx, hipMemcpyAsync(d_bra, bra.data(), bra.size() * sizeof(int), hipMemcpyHostToDevice, cst));
-        HIPCHK(ctx, hipMemcpyAsync(d_braoff, braoff.data(), braoff.size() * sizeof(long long), hipMemcpyHostToDevice, cst));
-        std::vector<BraRec> brec;
-        if (use_team_pc) {
-            brec.resize(bra.size());
-            for (size_t k = 0; k < bra.size(); ++k) {
-                const tf::Pair &pr = bs.pairs[bra[k]];
-                const double pp = bs.pp_p[pr.pp_off];
-                brec[k] = BraRec{pp, bs.pp_Pz[pr.pp_off], bs.pp_K[pr.pp_off] / pp, (unsigned)pr.e_off, pr.A, braoff[k], 0};
-            }
-            HIPCHK(ctx, hipMemcpyAsync(d_brarec, brec.data(), brec.size() * sizeof(BraRec), hipMemcpyHostToDevice, cst));
-        }
-        if (!outs.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outs.data(), outs.size() * sizeof(OutRow), hipMemcpyHostToDevice, cst));
-        if (!outsP.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outsP.data(), outsP.size() * sizeof(OutRowP), hipMemcpyHostToDevice, cst));
-        if (!outsT.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outsT.data(), outsT.size() * sizeof(OutRowT), hipMemcpyHostToDevice, cst));
-        if (!rowcls.empty()) HIPCHK(ctx, hipMemcpyAsync(d_rowcls, rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, cst));
-        HIPCHK(ctx, hipStreamSynchronize(cst));                // (pageable sources: the copies are complete; the host vectors may go)
-        DBG("slab: %zu bra pairs, %lld cart rows, %zu out rows", bra.size(), rows_c, outs.size() + outsP.size() + outsT.size());
-        hipEvent_t e4[4];
-        for (auto &e : e4) { HIPCHK(ctx, hipEventCreate(&e)); tev.push_back(e); }
-        if (per_class && !packed && ld != N) HIPCHK(ctx, hipMemsetAsync(d_T2, 0, (size_t)rows_c * N * ld * sizeof(double), 0));   // pad columns
-        // small-problem mode with team kernels: the slab's tasks, one launch per (LAB, LCD, team, LDS size class)
-        struct TcLaunch { int LAB, LCD, team; size_t lds; std::vector<TeamTask> tasks; std::vector<double> cost; };
-        std::vector<TcLaunch> tcl;
-        bool old_needed = !use_teamc;
-        if (use_teamc) {
-            std::map<std::array<int, 4>, int> lidx;
-            int max_npp_bra = 1;
-            for (size_t b = 0; b < bra.size(); ++b) {
-                const int pb = bra[b], A = bs.pairs[pb].A, bcls = ctx->pair_class[pb];
-                max_npp_bra = std::max(max_npp_bra, bs.pairs[pb].npp);
-                for (int kc = 0; kc < ncls; ++kc) {
-                    const std::vector<int> &kl = ctx->class_pairs[kc];
-                    const int nk_all = (int)(std::upper_bound(kl.begin(), kl.end(), A, [&](int a, int p2) { return a < bs.pairs[p2].A; }) - kl.begin());
-                    if (nk_all == 0) continue;
-                    const int id = teamc_class(bcls, kc);
-                    if (id < 0) continue;
-                    const int team = tc_team[(size_t)id], NT = 256 / team;
-                    int lg = 10;
-                    while (((size_t)1 << lg) < tc_lds[(size_t)id]) ++lg;
-                    const std::array<int, 4> key{tcs_host[(size_t)id].La + tcs_host[(size_t)id].Lb, tcs_host[(size_t)id].Lc + tcs_host[(size_t)id].Ld, team, lg};
-                    auto it = lidx.find(key);
-                    if (it == lidx.end()) { it = lidx.emplace(key, (int)tcl.size()).first; tcl.push_back(TcLaunch{key[0], key[1], team, 0, {}, {}}); }
-                    TcLaunch &TL = tcl[(size_t)it->second];
-                    TL.lds = std::max(TL.lds, tc_lds[(size_t)id]);
-                    for (int g0 = 0; g0 < nk_all; g0 += NT) {
-                        const int nk = std::min(NT, nk_all - g0);
-                        int npq_max = 0, todo = 0;
-                        for (int u = 0; u < nk; ++u) {
-                            const int npq = bs.pairs[pb].npp * bs.pairs[kl[(size_t)(g0 + u)]].npp;
-                            if (npq <= teamc_pqmax) { ++todo; npq_max = std::max(npq_max, npq); }
-                        }
-                        if (!todo) continue;                       // (every quartet of the group goes to eri_cfact_kernel)
-                        TL.tasks.push_back(TeamTask{id, pb, ket_off[kc] + g0, nk, braoff[b]});
-                        TL.cost.push_back((double)npq_max * (tcs_host[(size_t)id].nT + tcs_host[(size_t)id].nacc));
-                    }
-                }
-            }
-            old_needed = any_wide_pair || (long long)max_npp_bra * max_npp_all > teamc_pqmax;
-            // heaviest tasks first inside a launch (workgroups are dispatched in index order), all tasks in one device array
-            std::vector<TeamTask> all;
-            for (TcLaunch &TL : tcl) {
-                std::vector<int> ord(TL.tasks.size());
-                std::iota(ord.begin(), ord.end(), 0);
-                std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return TL.cost[(size_t)x] > TL.cost[(size_t)y]; });
-                std::vector<TeamTask> sorted(TL.tasks.size());
-                for (size_t k = 0; k < ord.size(); ++k) sorted[k] = TL.tasks[(size_t)ord[k]];
-                TL.tasks.swap(sorted);
-                all.insert(all.end(), TL.tasks.begin(), TL.tasks.end());
-            }
-            if (tcs_host.size() > d_tcs_cap) {
-                if (d_tcs) (void)tf_free(d_tcs);
-                d_tcs_cap = tcs_host.size() + 64;
-                HIPCHK(ctx, tf_malloc((void **)&d_tcs, d_tcs_cap * sizeof(TClass)));
-            }
-            if (all.size() > d_tasks_cap) {
-                if (d_tasks) (void)tf_free(d_tasks);
-                d_tasks_cap = all.size() + 1024;
-                HIPCHK(ctx, tf_malloc((void **)&d_tasks, d_tasks_cap * sizeof(TeamTask)));
-            }
-            if (!tcs_host.empty()) HIPCHK(ctx, hipMemcpy(d_tcs, tcs_host.data(), tcs_host.size() * sizeof(TClass), hipMemcpyHostToDevice));
-            if (!all.empty()) HIPCHK(ctx, hipMemcpy(d_tasks, all.data(), all.size() * sizeof(TeamTask), hipMemcpyHostToDevice));
-        }
-        // generic mode: eri_cfact_kernel stores only the components that are not zero by x/y parity
-        if (!per_class && old_needed) HIPCHK(ctx, hipMemsetAsync(d_C, 0, (size_t)rows_c * Nc * Nc * sizeof(double), 0));
-        HIPCHK(ctx, hipEventRecord(e4[0], 0));
-        for (int k = 0; k < NSTREAM; ++k) HIPCHK(ctx, hipStreamWaitEvent(streams[k], e4[0], 0));
-        // runs of equal bra class inside the slab
-        size_t r0 = 0;
-        if (!per_class) { if (old_needed && (rc = generic_launch(bra, d_bra, d_braoff))) return rc; r0 = bra.size(); }
-        while (r0 < bra.size()) {
-            const int bcls = ctx->pair_class[bra[r0]];
-            size_t r1 = r0;
-            int max_npp = 1, Amax = 0;
-            while (r1 < bra.size() && ctx->pair_class[bra[r1]] == bcls) {
-                max_npp = std::max(max_npp, bs.pairs[bra[r1]].npp);
-                Amax = std::max(Amax, bs.pairs[bra[r1]].A);
-                ++r1;
-            }
-            for (int kcls = 0; kcls < ncls; ++kcls)
-                class_launch(bcls, kcls, max_npp, (unsigned)(r1 - r0), d_bra + r0, d_braoff + r0, Amax);
-            r0 = r1;
-        }
-        for (int k = 0; k < NSTREAM; ++k) {
-            HIPCHK(ctx, hipEventRecord(sev[k], streams[k]));
-            HIPCHK(ctx, hipStreamWaitEvent(0, sev[k], 0));
-        }
-        HIPCHK(ctx, hipEventRecord(e4[1], 0));
-        if (!per_class && old_needed) {
-            for (long long r0s = 0; r0s < rows_c; r0s += 65535) {      // both ket axes in one pass over the slab
-                const unsigned ny = (unsigned)std::min<long long>(65535, rows_c - r0s);
-                if (packed)
-                    hipLaunchKernelGGL(xform_ket_packed, dim3((unsigned)((N + 3) / 4), ny), dim3(256), 0, 0, d_C + (size_t)r0s * Nc * Nc,
-                                       d_T2 + (size_t)r0s * H.RLS, Nc, ctx->bl, (long long)H.RLS, d_rowcls + r0s, ctx->d_csr_ptr, ctx->d_csr_idx,
-                                       ctx->d_csr_val);
-                else
-                    hipLaunchKernelGGL(xform_ket_both, dim3((unsigned)((N + 3) / 4), ny), dim3(256), 0, 0, d_C + (size_t)r0s * Nc * Nc,
-                                       d_T2 + (size_t)r0s * N * ld, Nc, N, ld, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val, 0);
+                if (!todo) continue;                       // (every quartet of the group goes to eri_cfact_kernel)
+                TL.tasks.push_back(TeamTask{id, pb, ket_off[kc] + g0, nk, braoff[b]});
+                TL.cost.push_back((double)npq_max * (tcs_host[(size_t)id].nT + tcs_host[(size_t)id].nacc));
             }
         }
-        if (use_teamc && !tcl.empty()) {
-            // the team kernels write their quartets' part of the half-transformed slab (behind the ket transform of the others' part,
-            // which has left zeros there); heaviest launches first, spread over the streams
-            std::vector<size_t> first(tcl.size(), 0), order(tcl.size());
-            for (size_t k = 1; k < tcl.size(); ++k) first[k] = first[k - 1] + tcl[k - 1].tasks.size();
-            std::iota(order.begin(), order.end(), 0);
-            auto total = [&](size_t k) { double c = 0; for (double x : tcl[k].cost) c += x; return c; };
-            std::vector<double> tot(tcl.size());
-            for (size_t k = 0; k < tcl.size(); ++k) tot[k] = total(k);
-            std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return tot[x] > tot[y]; });
-            hipEvent_t et[2];
-            for (auto &e : et) { HIPCHK(ctx, hipEventCreate(&e)); tev2.push_back(e); }
-            HIPCHK(ctx, hipEventRecord(et[0], 0));
-            HIPCHK(ctx, hipEventRecord(sev[0], 0));
-            for (int k = 0; k < NSTREAM; ++k) HIPCHK(ctx, hipStreamWaitEvent(streams[k], sev[0], 0));
-            int nl = 0;
-            for (size_t k : order) {
-                const TcLaunch &TL = tcl[k];
-                if (TL.tasks.empty()) continue;
-                TeamcLaunch a{TL.LAB, TL.LCD, TL.team, (unsigned)TL.tasks.size(), TL.lds, streams[nl++ % NSTREAM], &ctx->db, d_tcs, d_tasks + first[k], d_kets,
-                              teamc_pqmax, d_T2};
-                const hipError_t e = eri_teamc_launch(a);
-                if (e != hipSuccess && team_error == hipSuccess) team_error = e;
-                ++launch_count;
-            }
-            for (int k = 0; k < NSTREAM; ++k) {
-                HIPCHK(ctx, hipEventRecord(sev[k], streams[k]));
-                HIPCHK(ctx, hipStreamWaitEvent(0, sev[k], 0));
-            }
-            HIPCHK(ctx, hipEventRecord(et[1], 0));
-        }
-        HIPCHK(ctx, hipEventRecord(e4[2], 0));
-        if (!outs.empty()) {
-            const unsigned gx = (unsigned)std::min<long long>((row_len + 255) / 256, 4096);
-            for (size_t o0 = 0; o0 < outs.size(); o0 += 65535) {
-                const unsigned ny = (unsigned)std::min<size_t>(65535, outs.size() - o0);
-                hipLaunchKernelGGL(xform_bra_store, dim3(gx, ny), dim3(256), 0, 0, d_T2, ctx->d_eri, reinterpret_cast<const OutRow *>(d_out) + o0,
-                                   row_len, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val);
-            }
-        }
-        if (!outsP.empty()) {
-            int maxlen = 1;
-            for (const OutRowP &o : outsP) maxlen = std::max(maxlen, o.len);
-            for (size_t o0 = 0; o0 < outsP.size(); o0 += 65535) {
-                const unsigned ny = (unsigned)std::min<size_t>(65535, outsP.size() - o0);
-                hipLaunchKernelGGL(xform_bra_store_packed, dim3((unsigned)((maxlen + 255) / 256), ny), dim3(256), 0, 0, d_T2, ctx->d_eri,
-                                   reinterpret_cast<const OutRowP *>(d_out) + o0, (long long)H.RLS, ctx->bl, ctx->d_csr_ptr, ctx->d_csr_idx,
-                                   ctx->d_csr_val);
-            }
-        }
-        if (!outsT.empty()) {
-            for (size_t o0 = 0; o0 < outsT.size(); o0 += 65535) {
-                const unsigned ny = (unsigned)std::min<size_t>(65535, outsT.size() - o0);
-                hipLaunchKernelGGL(xform_bra_store_tiles, dim3((unsigned)((H.RLS + 255) / 256), ny), dim3(256), 0, 0, d_T2, ctx->d_eri,
-                                   reinterpret_cast<const OutRowT *>(d_out) + o0, (long long)H.RLS, ctx->bl, ctx->tv, ctx->d_csr_ptr, ctx->d_csr_idx,
-                                   ctx->d_csr_val);
-            }
-        }
-        HIPCHK(ctx, hipEventRecord(e4[3], 0));
-        HIPCHK(ctx, hipEventRecord(ctx->slab_done[set], 0));
     }
-    DBG("all slabs launched (%d class launches)", launch_count);
-    if ((rc = consumer_tables())) { (void)hipDeviceSynchronize(); return rc; }
-    DBG("consumer tables built");
+    old_needed = any_wide_pair || (long long)max_npp_bra * max_npp_all > teamc_pqmax;
+    // heaviest tasks first inside a launch (workgroups are dispatched in index order), all tasks in one device array
+    std::vector<TeamTask> all;
+    for (TcLaunch &TL : tcl) {
+        std::vector<int> ord(TL.tasks.size());
+        std::iota(ord.begin(), ord.end(), 0);
+        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return TL.cost[(size_t)x] > TL.cost[(size_t)y]; });
+        std::vector<TeamTask> sorted(TL.tasks.size());
+        for (size_t k = 0; k < ord.size(); ++k) sorted[k] = TL.tasks[(size_t)ord[k]];
+        TL.tasks.swap(sorted);
+        all.insert(all.end(), TL.tasks.begin(), TL.tasks.end());
+    }
+    if (tcs_host.size() > d_tcs_cap) {
+        mem.drop(d_tcs);
+        d_tcs_cap = tcs_host.size() + 64;
+        if ((rc = mem.alloc(&d_tcs, d_tcs_cap * sizeof(TClass)))) return rc;
+    }
+    if (all.size() > d_tasks_cap) {
+        mem.drop(d_tasks);
+        d_tasks_cap = all.size() + 1024;
+        if ((rc = mem.alloc(&d_tasks, d_tasks_cap * sizeof(TeamTask)))) return rc;
+    }
+    if (!tcs_host.empty()) HIPCHK(ctx, hipMemcpy(d_tcs, tcs_host.data(), tcs_host.size() * sizeof(TClass), hipMemcpyHostToDevice));
+    if (!all.empty()) HIPCHK(ctx, hipMemcpy(d_tasks, all.data(), all.size() * sizeof(TeamTask), hipMemcpyHostToDevice));
+    return TF_OK;
+}
+
+int EriBuild::launch_teamc(const std::vector<TcLaunch> &tcl)
+{
+    int rc;
+    // the team kernels write their quartets' part of the half-transformed slab (behind the ket transform of the others' part,
+    // which has left zeros there); heaviest launches first, spread over the streams
+    std::vector<size_t> first(tcl.size(), 0), order(tcl.size());
+    for (size_t k = 1; k < tcl.size(); ++k) first[k] = first[k - 1] + tcl[k - 1].tasks.size();
+    std::iota(order.begin(), order.end(), 0);
+    auto total = [&](size_t k) { double c = 0; for (double x : tcl[k].cost) c += x; return c; };
+    std::vector<double> tot(tcl.size());
+    for (size_t k = 0; k < tcl.size(); ++k) tot[k] = total(k);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return tot[x] > tot[y]; });
+    hipEvent_t et[2];
+    for (auto &e : et) { if ((rc = mem.event(&e))) return rc; tev2.push_back(e); }
+    HIPCHK(ctx, hipEventRecord(et[0], 0));
+    HIPCHK(ctx, hipEventRecord(sev[0], 0));
+    for (int k = 0; k < NSTREAM; ++k) HIPCHK(ctx, hipStreamWaitEvent(streams[k], sev[0], 0));
+    int nl = 0;
+    for (size_t k : order) {
+        const TcLaunch &TL = tcl[k];
+        if (TL.tasks.empty()) continue;
+        TeamcLaunch a{TL.LAB, TL.LCD, TL.team, (unsigned)TL.tasks.size(), TL.lds, streams[nl++ % NSTREAM], &ctx->db, d_tcs, d_tasks + first[k], d_kets,
+                      teamc_pqmax, d_T2};
+        const hipError_t e = eri_teamc_launch(a);
+        if (e != hipSuccess && team_error == hipSuccess) team_error = e;
+        ++launch_count;
+    }
+    for (int k = 0; k < NSTREAM; ++k) {
+        HIPCHK(ctx, hipEventRecord(sev[k], streams[k]));
+        HIPCHK(ctx, hipStreamWaitEvent(0, sev[k], 0));
+    }
+    HIPCHK(ctx, hipEventRecord(et[1], 0));
+    return TF_OK;
+}
+
+// One pass of the slab loop: the next run of bra pairs that fits the slab, its index lists, its launches and transforms
+int EriBuild::run_slab()
+{
+    int rc;
+    std::vector<int> bra; std::vector<long long> braoff; std::vector<OutRow> outs;
+    std::vector<OutRowP> outsP;
+    std::vector<OutRowT> outsT;
+    std::vector<signed char> rowcls;
+    long long rows_c = 0;
+    while (cursor < mine_sorted.size()) {
+        const int p = mine_sorted[cursor];
+        const tf::Shell &a = bs.shells[bs.pairs[p].A], &b = bs.shells[bs.pairs[p].B];
+        const long long nr = (long long)a.ncomp * b.ncomp;
+        if (!bra.empty() && (rows_c + nr > max_rows_c || bra.size() >= 65535 || outs.size() + outsP.size() + outsT.size() + (size_t)pair_rows[p] >= cap_out)) break;
+        bra.push_back(p); braoff.push_back(rows_c);
+        long long r = rows.pair_first_row[p];
+        for (int x = 0; x < out_dim(a); ++x)
+            for (int y = 0; y < out_dim(b); ++y) {
+                const int i = out_off(a) + x, j = out_off(b) + y;
+                if (i < j) continue;
+                if (!packed) { outs.push_back(OutRow{i, j, a.cart_off, b.cart_off, b.ncomp, 0, rows_c, r++}); continue; }
+                if (tiles) { outsT.push_back(OutRowT{i, j, H.sigma[i], H.sigma[j], H.cls[i] ^ H.cls[j], b.ncomp, a.cart_off, b.cart_off, rows_c}); continue; }
+                const int lr = rows.rowmap[tfp::ikey(H.sigma[i], H.sigma[j])];
+                OutRowP o{};
+                o.i = i; o.j = j; o.iI = H.sigma[i]; o.lamj = H.loc[j]; o.c = H.cls[i] ^ H.cls[j]; o.ncb = b.ncomp;
+                o.cartA = a.cart_off; o.cartB = b.cart_off;
+                for (int t = 0; t < 4; ++t) o.secoff[t] = rows.rowsec[6 * (size_t)lr + t];
+                o.len = rows.rowlen[lr]; o.slab_off = rows_c; o.ubase = rows.rowoff[lr]; o.upos = rows.rowsec[6 * (size_t)lr + 4]; o.unr = rows.rowsec[6 * (size_t)lr + 5];
+                outsP.push_back(o);
+            }
+        if (packed && !per_class)
+            for (int ca = 0; ca < a.ncomp; ++ca)
+                for (int cb = 0; cb < b.ncomp; ++cb) {
+                    const int u = a.comp_off + ca, v = b.comp_off + cb;
+                    rowcls.push_back((signed char)(((bs.c_lx[u] + bs.c_lx[v]) & 1) | (((bs.c_ly[u] + bs.c_ly[v]) & 1) << 1)));
+                }
+        rows_c += nr;
+        const int Alim = packed ? bs.pairs[p].A + 1 : nsh;
+        n_quart += cum_pairs[Alim];
+        n_primq += (long long)bs.pairs[p].npp * cum_pp[Alim];
+        n_compq += nr * cum_comp[Alim];
+        {
+            const double npp_ab = (double)bs.pairs[p].npp;
+            const int lab = bs.pairs[p].La + bs.pairs[p].Lb;
+            for (int c = 0; c < 4; ++c) {
+                nominal_flops += 8.0 * npp_ab * pairW[p][c] * cumW[Alim][c];
+                for (int lcd = 0; lcd <= 10; ++lcd) {
+                    const double L1 = (double)(lab + lcd + 1);
+                    nominal_flops += npp_ab * pairNc[p][c] * cumNL[Alim][4 * lcd + c] * (6.0 * L1 + 1.5 * L1 * L1 + 60.0);
+                }
+            }
+        }
+        ++cursor;
+    }
+    // this set of index lists was last read by the kernels of the slab before the previous one: wait for that slab only
+    const int set = (int)(slab_no & 1);
+    if (slab_no >= 2) HIPCHK(ctx, hipEventSynchronize(ctx->slab_done[set]));
+    d_bra = d_bra_alloc + (size_t)set * cap_bra; d_braoff = d_braoff_alloc + (size_t)set * cap_bra;
+    d_out = (char *)d_out_alloc + (size_t)set * out_bytes;
+    if (d_brarec_alloc) d_brarec = d_brarec_alloc + (size_t)set * cap_bra;
+    if (d_rowcls_alloc) d_rowcls = d_rowcls_alloc + (size_t)set * rowcls_bytes;
+    d_bra_base = d_bra;
+    ++slab_no;
+    const hipStream_t cst = ctx->cstream;
+    HIPCHK(ctx, hipMemcpyAsync(d_bra, bra.data(), bra.size() * sizeof(int), hipMemcpyHostToDevice, cst));
+    HIPCHK(ctx, hipMemcpyAsync(d_braoff, braoff.data(), braoff.size() * sizeof(long long), hipMemcpyHostToDevice, cst));
+    std::vector<BraRec> brec;
+    if (use_team_pc) {
+        brec.resize(bra.size());
+        for (size_t k = 0; k < bra.size(); ++k) {
+            const tf::Pair &pr = bs.pairs[bra[k]];
+            const double pp = bs.pp_p[pr.pp_off];
+            brec[k] = BraRec{pp, bs.pp_Pz[pr.pp_off], bs.pp_K[pr.pp_off] / pp, (unsigned)pr.e_off, pr.A, braoff[k], 0};
+        }
+        HIPCHK(ctx, hipMemcpyAsync(d_brarec, brec.data(), brec.size() * sizeof(BraRec), hipMemcpyHostToDevice, cst));
+    }
+    if (!outs.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outs.data(), outs.size() * sizeof(OutRow), hipMemcpyHostToDevice, cst));
+    if (!outsP.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outsP.data(), outsP.size() * sizeof(OutRowP), hipMemcpyHostToDevice, cst));
+    if (!outsT.empty()) HIPCHK(ctx, hipMemcpyAsync(d_out, outsT.data(), outsT.size() * sizeof(OutRowT), hipMemcpyHostToDevice, cst));
+    if (!rowcls.empty()) HIPCHK(ctx, hipMemcpyAsync(d_rowcls, rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, cst));
+    HIPCHK(ctx, hipStreamSynchronize(cst));                // (pageable sources: the copies are complete; the host vectors may go)
+    DBG("slab: %zu bra pairs, %lld cart rows, %zu out rows", bra.size(), rows_c, outs.size() + outsP.size() + outsT.size());
+    hipEvent_t e4[4];
+    for (auto &e : e4) { if ((rc = mem.event(&e))) return rc; tev.push_back(e); }
+    if (per_class && !packed && ld != N) HIPCHK(ctx, hipMemsetAsync(d_T2, 0, (size_t)rows_c * N * ld * sizeof(double), 0));   // pad columns
+    std::vector<TcLaunch> tcl;
+    bool old_needed = !use_teamc;
+    if (use_teamc && (rc = teamc_tasks(bra, braoff, tcl, old_needed))) return rc;
+    // generic mode: eri_cfact_kernel stores only the components that are not zero by x/y parity
+    if (!per_class && old_needed) HIPCHK(ctx, hipMemsetAsync(d_C, 0, (size_t)rows_c * Nc * Nc * sizeof(double), 0));
+    HIPCHK(ctx, hipEventRecord(e4[0], 0));
+    for (int k = 0; k < NSTREAM; ++k) HIPCHK(ctx, hipStreamWaitEvent(streams[k], e4[0], 0));
+    // runs of equal bra class inside the slab
+    size_t r0 = 0;
+    if (!per_class) { if (old_needed && (rc = launch_generic(bra, d_bra, d_braoff))) return rc; r0 = bra.size(); }
+    while (r0 < bra.size()) {
+        const int bcls = ctx->pair_class[bra[r0]];
+        size_t r1 = r0;
+        int max_npp = 1, Amax = 0;
+        while (r1 < bra.size() && ctx->pair_class[bra[r1]] == bcls) {
+            max_npp = std::max(max_npp, bs.pairs[bra[r1]].npp);
+            Amax = std::max(Amax, bs.pairs[bra[r1]].A);
+            ++r1;
+        }
+        for (int kcls = 0; kcls < ncls; ++kcls)
+            launch_class(bcls, kcls, max_npp, (unsigned)(r1 - r0), d_bra + r0, d_braoff + r0, Amax);
+        r0 = r1;
+    }
+    for (int k = 0; k < NSTREAM; ++k) {
+        HIPCHK(ctx, hipEventRecord(sev[k], streams[k]));
+        HIPCHK(ctx, hipStreamWaitEvent(0, sev[k], 0));
+    }
+    HIPCHK(ctx, hipEventRecord(e4[1], 0));
+    if (!per_class && old_needed) {
+        for (long long r0s = 0; r0s < rows_c; r0s += 65535) {      // both ket axes in one pass over the slab
+            const unsigned ny = (unsigned)std::min<long long>(65535, rows_c - r0s);
+            if (packed)
+                hipLaunchKernelGGL(xform_ket_packed, dim3((unsigned)((N + 3) / 4), ny), dim3(256), 0, 0, d_C + (size_t)r0s * Nc * Nc,
+                                   d_T2 + (size_t)r0s * H.RLS, Nc, ctx->bl, (long long)H.RLS, d_rowcls + r0s, ctx->d_csr_ptr, ctx->d_csr_idx,
+                                   ctx->d_csr_val);
+            else
+                hipLaunchKernelGGL(xform_ket_both, dim3((unsigned)((N + 3) / 4), ny), dim3(256), 0, 0, d_C + (size_t)r0s * Nc * Nc,
+                                   d_T2 + (size_t)r0s * N * ld, Nc, N, ld, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val, 0);
+        }
+    }
+    if (use_teamc && !tcl.empty() && (rc = launch_teamc(tcl))) return rc;
+    HIPCHK(ctx, hipEventRecord(e4[2], 0));
+    if (!outs.empty()) {
+        const unsigned gx = (unsigned)std::min<long long>((row_len + 255) / 256, 4096);
+        for (size_t o0 = 0; o0 < outs.size(); o0 += 65535) {
+            const unsigned ny = (unsigned)std::min<size_t>(65535, outs.size() - o0);
+            hipLaunchKernelGGL(xform_bra_store, dim3(gx, ny), dim3(256), 0, 0, d_T2, ctx->d_eri, reinterpret_cast<const OutRow *>(d_out) + o0,
+                               row_len, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val);
+        }
+    }
+    if (!outsP.empty()) {
+        int maxlen = 1;
+        for (const OutRowP &o : outsP) maxlen = std::max(maxlen, o.len);
+        for (size_t o0 = 0; o0 < outsP.size(); o0 += 65535) {
+            const unsigned ny = (unsigned)std::min<size_t>(65535, outsP.size() - o0);
+            hipLaunchKernelGGL(xform_bra_store_packed, dim3((unsigned)((maxlen + 255) / 256), ny), dim3(256), 0, 0, d_T2, ctx->d_eri,
+                               reinterpret_cast<const OutRowP *>(d_out) + o0, (long long)H.RLS, ctx->bl, ctx->d_csr_ptr, ctx->d_csr_idx,
+                               ctx->d_csr_val);
+        }
+    }
+    if (!outsT.empty()) {
+        for (size_t o0 = 0; o0 < outsT.size(); o0 += 65535) {
+            const unsigned ny = (unsigned)std::min<size_t>(65535, outsT.size() - o0);
+            hipLaunchKernelGGL(xform_bra_store_tiles, dim3((unsigned)((H.RLS + 255) / 256), ny), dim3(256), 0, 0, d_T2, ctx->d_eri,
+                               reinterpret_cast<const OutRowT *>(d_out) + o0, (long long)H.RLS, ctx->bl, ctx->tv, ctx->d_csr_ptr, ctx->d_csr_idx,
+                               ctx->d_csr_val);
+        }
+    }
+    HIPCHK(ctx, hipEventRecord(e4[3], 0));
+    HIPCHK(ctx, hipEventRecord(ctx->slab_done[set], 0));
+    return TF_OK;
+}
+
+// Behind the last launch: drain the device, read the timing events, release the lists of the build, publish timings and counters
+int EriBuild::finish()
+{
     HIPCHK(ctx, hipDeviceSynchronize());
     DBG("device drained");
     HIPCHK(ctx, hipGetLastError());
@@ -2467,27 +2355,19 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
         const double dt = seconds_between(tev2[k], tev2[k + 1]);
         t_stage[1] += dt; t_stage[2] -= dt;
     }
-    for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : tev2) (void)hipEventDestroy(e);
-    (void)tf_free(d_bra_alloc); (void)tf_free(d_braoff_alloc); (void)tf_free(d_out_alloc);
-    if (d_rowcls_alloc) (void)tf_free(d_rowcls_alloc);
-    d_brarec = d_brarec_alloc;
-    (void)tf_free(d_kets); (void)tf_free(d_kets_all);
-    for (void *pt : {(void *)d_fam_heads, (void *)d_fam_ptr, (void *)d_fam_mem})
-        if (pt) (void)tf_free(pt);
-    for (void *pt : fam_allocs) (void)tf_free(pt);
-    for (void *pt : {(void *)d_kq_ptr, (void *)d_kq_off, (void *)d_kt_ptr, (void *)d_kt_k, (void *)d_kt_c, (void *)d_ketrec, (void *)d_brarec, (void *)d_kcnt,
-                     (void *)d_tcs, (void *)d_tasks, (void *)d_tflat})
-        if (pt) (void)tf_free(pt);
-    ctx->db.kq_ptr = ctx->db.kq_off = ctx->db.kt_ptr = ctx->db.kt_k = nullptr; ctx->db.kt_c = nullptr;
+    mem.release();
     if (team_error != hipSuccess) TF_FAIL(ctx, TF_ENODEVICE, "launch of a team ERI kernel failed: %s", hipGetErrorString(team_error));
     t_stage[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wall0).count();
     std::copy(t_stage, t_stage + 4, ctx->eri_seconds);
     ctx->eri_counts[0] = n_quart; ctx->eri_counts[1] = n_primq; ctx->eri_counts[2] = n_compq;
     ctx->eri_nominal_flops = nominal_flops;
+    return TF_OK;
+}
 
-    DBG("scratch freed");
-    // ---- J/K scratch
+// ---- J/K scratch
+int EriBuild::alloc_jk_scratch()
+{
+    int rc;
     const size_t nn = (size_t)N * N;
     // (sized for two densities per pass)
     const int NWjk = packed ? std::max(1, H.NW) * H.MP : 1;         // column chunks of jk_packed_kernel x parts of a walk
@@ -2540,6 +2420,38 @@ int tf_build_eri(tf_ctx *ctx, int spherical)
     HIPCHK(ctx, tf_malloc((void **)&ctx->d_J, npass * nn * sizeof(double)));
     HIPCHK(ctx, tf_malloc((void **)&ctx->d_K, npass * nn * sizeof(double)));
     HIPCHK(ctx, tf_malloc((void **)&ctx->d_P, npass * nn * sizeof(double)));
+    return TF_OK;
+}
+
+}  // extern "C++"
+
+int tf_build_eri(tf_ctx *ctx, int spherical)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_basis) TF_FAIL(ctx, TF_EINVAL, "tf_build_eri: call tf_set_basis first");
+    const tf::Basis &bs = ctx->bs;
+    if (spherical && !bs.all_full)
+        TF_FAIL(ctx, TF_EINVAL, "spherical output needs complete shells in canonical Cartesian order (use CARTHARM / spherical=0)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    free_eri(ctx);
+    DBG("build_eri start");
+    int rc = upload_csr(ctx, spherical);
+    if (rc) return rc;
+    DBG("csr uploaded");
+    EriBuild B(ctx, spherical);
+    if ((rc = B.plan_storage())) return rc;
+    DBG("rows=%lld N=%d ld=%d (tensor + row tables allocated)", ctx->n_rows, B.N, B.ld);
+    if ((rc = B.plan_generation())) return rc;
+    DBG("stage: slab loop");
+    while (B.cursor < B.mine_sorted.size())
+        if ((rc = B.run_slab())) return rc;
+    DBG("all slabs launched (%d class launches)", B.launch_count);
+    // The tables only the CONSUMERS of the tensor need are built on the host while the generation kernels run
+    if ((rc = B.upload_consumer_tables())) { (void)hipDeviceSynchronize(); return rc; }
+    DBG("consumer tables built");
+    if ((rc = B.finish())) return rc;
+    DBG("scratch freed");
+    if ((rc = B.alloc_jk_scratch())) return rc;
     DBG("build_eri done");
     ctx->have_eri = true;
     return TF_OK;

@@ -38,24 +38,10 @@
 #include <hip/hip_runtime.h>
 #include "tf_layout.hip.h"
 
-#define TF_JKP_JBB 8               // rows of a storage unit (and the largest row group)
-#ifndef TF_JKP_VR1
-#define TF_JKP_VR1 8               // rows of a group in a one-density pass: 8 (251 VGPRs, 2 waves per SIMD) or 4 (151 VGPRs, 3 waves per
-                                   // SIMD, twice the steps: measured the same 2.1 ms at N = 400)
-#endif
+#include "tf_packed.h"             // row groups, super-groups, tasks and the shape constants TF_JKP_* that the host builders share
 #ifndef TF_JKP_OCC4
 #define TF_JKP_OCC4 3              // waves per SIMD the 4-row shape is compiled for (4: 128 VGPRs with 41 spilled, 2.4 ms)
 #endif
-template <int ND> struct JKShape {           // virtual rows v = d * RB + r of a pass: RB tensor rows times ND densities
-    static constexpr int VR = ND == 1 ? TF_JKP_VR1 : 8, RB = VR / ND;
-};
-#ifndef TF_JKP_GPW
-#define TF_JKP_GPW 2               // row groups a wave works on at once: 2 (half waves on 64 columns) or 4 (quarter waves on 32 columns:
-                                   // 20 % fewer wave steps at N = 400, but measured 8-15 % SLOWER -- DESIGN.md section 4.1)
-#endif
-#define TF_JKP_LG (64 / TF_JKP_GPW)   // lanes per group
-#define TF_JKP_CW (2 * TF_JKP_LG)  // columns per chunk (2 per lane of a group's lanes)
-#define TF_JKP_SEG 16            // segments of the super-group lists in the Jt reduction
 #ifndef TF_JKP_STAGES
 #define TF_JKP_STAGES 2           // register buffers of the load ring: the loads of STAGES - 1 steps are in flight (2 or 4)
 #endif
@@ -73,20 +59,7 @@ __host__ __device__ inline long long tri_off(long long k)
 }
 __host__ __device__ inline long long packed_row_len(long long i, long long j) { return (tri_off(i) + j + TF_TRI_PAD) & ~(long long)(TF_TRI_PAD - 1); }
 
-struct JKGroup {
-    int i, j0, nr, r0;           // rows r0..r0+nr-1 (local numbering) = pairs (i, j0..j0+nr-1), internal indices
-    int c, lamj0;                // class of the rows; loc of j0
-    int unr, p0;                 // rows of the storage unit that holds the group; position of the group's first row in it
-    long long ub;                // base of the unit in the tensor
-    int secoff[4];               // start of section a inside a row of this group
-};
-#ifndef TF_JKP_W
-#define TF_JKP_W 4                // waves per workgroup (TF_JKP_GPW groups each): their Jt partials are merged in LDS before they are written
-#endif
 #define TF_JKP_KB 4               // k steps per merge block
-// up to 2 TF_JKP_W adjacent groups with the same i and class share one Jt partial (complete-row shape: NP[c] doubles at yoff)
-struct JKSuper { int g0, ng, c, i; long long yoff; int ke[4]; };   // ke[a] = cntA[a][i]: the rows reach the members kappa < ke[a] of class a
-struct JKTask { int super, w, part, pad; };   // part: which stretch of KS steps of the walk (the walks are cut for several ranks: shorter tasks)
 
 __device__ __forceinline__ double ld_stream(const double *p) { return __builtin_nontemporal_load(p); }
 
@@ -791,10 +764,6 @@ __global__ __launch_bounds__(64 * TF_JKP_W, TF_JKP_STAGES > 2 ? 1 : (JKShape<ND>
 // Jt partial sums over the pair index q of class c: the super-groups of a class are sorted by descending original i, so those whose
 // rows reach the AO k of q are a prefix of the class's list (ke[a] is non-increasing along it).  Block (bx, by) of a
 // (sum_c ceil(NP[c] / 256), nseg) grid: segment by sums its slice of every class's list; out[by][q].
-#ifndef TF_JKR_THREADS
-#define TF_JKR_THREADS 256         // (measured: 1024-thread blocks, 16 slices, are slower: 0.41 against 0.34 ms of tail at N = 400) threads of a jk_reduce_kernel block: 64 lanes x TF_JKR_THREADS / 64 slices of the rows / groups of an index
-#endif
-struct JKJtPlan { int sfirst[5]; int bfirst[5]; };   // supers of class c: sfirst[c] .. sfirst[c + 1]; blocks of class c: bfirst[c] .. bfirst[c + 1]
 __device__ __forceinline__ void jt_reduce_block(int bx, int by, int nseg, const double *__restrict__ ypart, const JKSuper *__restrict__ supers,
                                                 const JKJtPlan &JP, const BLayout &L, double *__restrict__ out)
 {

@@ -3,13 +3,9 @@
 // transforms and the Fock-build kernels.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#ifndef TF_SEG_PAD
-#define TF_SEG_PAD 8             // segments start at multiples of this many doubles (even; 8 = 64 bytes, 16 = one 128-byte line)
-#endif
+#include "tf_packed.h"             // KInfo, TF_SEG_PAD
 
 // ---- device view of the layout tables (built by tf_build_eri; every index "internal" unless it says original) ---------------
-struct KInfo { int offA, cnt; };  // segment of AO k in a row of class c: offset inside the section of k's class, stored values
 // The small per-class tables live in device memory (itab / ltab), not in the by-value struct: kernels index them with run-time
 // class numbers, and a dynamically indexed kernel argument would be copied to scratch memory.
 enum { BL_CSTART = 0, BL_CSIZE = 4, BL_WFIRST = 8, BL_FULLSEC = 13, BL_GBASE = 29, BL_ITAB = 33 };   // itab offsets
