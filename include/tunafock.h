@@ -355,6 +355,51 @@ typedef struct {
  * TF_ENOMEM, with the size in the message, when the work space does not fit. */
 int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_cc_result *out);
 
+/* ---- excited states: replaces calculate_restricted_single_reference_excited_states and calculate_restricted_transition_dipoles
+ * (tuna_ci.py:1284-1366, :1466-1518) for closed-shell CIS and TDHF (RPA) ---- */
+
+typedef struct {
+    int32_t tda;                /* 1 = CIS (the matrix A alone), 0 = TDHF / RPA    */
+    int32_t singlets;           /* which multiplicities to solve; both 0 is TF_EINVAL */
+    int32_t triplets;
+    int32_t n_keep;             /* state vectors returned per multiplicity: the lowest n_keep (0 = none; clamped to dim) */
+} tf_cis_opts;
+
+typedef struct {
+    int32_t dim;                /* o v: states per multiplicity (set by the call; 4 bytes of padding follow) */
+    double *e_singlet;          /* [dim] ascending, caller-allocated, may be NULL (left untouched when the multiplicity is off) */
+    double *e_triplet;          /* [dim] likewise */
+    double *x_singlet;          /* [n_keep][o][v] caller-allocated, may be NULL: X of the lowest states */
+    double *y_singlet;          /* [n_keep][o][v] likewise: Y (zeros for CIS) */
+    double *x_triplet;
+    double *y_triplet;
+    double *tdm;                /* [dim][3] may be NULL: transition dipoles of the singlets, x y z; needs dip */
+    double *osc;                /* [dim] may be NULL: oscillator strengths of the singlets; needs dip */
+    double *m_plus_singlet;     /* [dim][dim] may be NULL: the assembled matrix, A + B (TDHF) or A (CIS), singlet -- tests */
+    double *m_plus_triplet;     /* [dim][dim] likewise, triplet */
+    double *m_minus;            /* [dim][dim] may be NULL: A - B (TDHF only; untouched for CIS) */
+    double seconds[4];          /* wall time, MO blocks, assembly, solves and transition moments */
+} tf_cis_result;
+
+/* Closed-shell CIS / TDHF excitation energies, state vectors and transition moments from canonical RHF orbitals C [N,N] and eps [N];
+ * windows as tf_mp3_rhf: occupied [n_frozen, n_occ), virtual [n_occ, N); dim = o v, compound index (ia) = i v + a.  With HFX = 1,
+ *     singlet: A = Delta + 2 (ia|jb) - (ij|ab), B = 2 (ia|jb) - (ib|ja);   triplet: A = Delta - (ij|ab), B = -(ib|ja),
+ * Delta = diag(e_a - e_i), each assembled matrix symmetrised as 1/2 (M + M^T) to the last bit.  The blocks (ia|jb) and (ab|ij) are
+ * those of tf_mp3_rhf, on every layout; one kernel pass writes all matrices of the call, then the blocks are freed.
+ * CIS: one dsyevd of A per multiplicity; negative eigenvalues are returned as they are.
+ * TDHF: A - B = L L^T (dpotrf, once for both multiplicities), the symmetric dim x dim problem [L^T (A + B) L] Z = w^2 Z (dsyevd),
+ *     X + Y = L Z / sqrt(w), X - Y = sqrt(w) L^-T Z, so that X.X - Y.Y = 1.  If dpotrf fails or any w^2 <= 0 the RHF reference is
+ *     unstable: TF_ELINALG, the message names the multiplicity and the value, no state of that call is valid; the context stays usable.
+ * Transition moments of the singlets (dip = the three AO dipole matrices [3][N][N], host): mu_n[c] = sqrt(2) sum_ia (C_o^T D^c C_v)_ia
+ *     (X + Y)^n_ia (CIS: the eigenvector), f_n = (2/3) w_n |mu_n|^2.  Triplets have none: the caller's zeros.
+ * Nothing is reduced with atomics: two calls give the same bits.
+ * Work space: the matrices of the call (CIS 1-2, TDHF 2-3 arrays of dim^2) plus one array of dim^2 ((ij|ab) reordered during the
+ * assembly, the triangular products during the TDHF solves), the two blocks until the assembly is done, and rocSOLVER's own.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL opts, C, eps or out, unless 0 <= n_frozen < n_occ < N, with both
+ * multiplicities off, n_keep < 0, tdm or osc without dip, or world > 1.  TF_ENOMEM, with the size in the message. */
+int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip,
+               tf_cis_result *out);
+
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */
 int tf_diagonalise(tf_ctx *ctx, int n, const double *F, const double *X, double *eps, double *C);

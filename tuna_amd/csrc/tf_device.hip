@@ -36,6 +36,7 @@
 #include "tf_mp2.hip.h"
 #include "tf_mp3.hip.h"
 #include "tf_ccd.hip.h"
+#include "tf_cis.hip.h"
 #include "tf_mp4.hip.h"
 #include "tf_dft.hip.h"
 
@@ -4259,6 +4260,208 @@ int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, con
     out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
     if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
     if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
+    return TF_OK;
+}
+
+// Closed-shell CIS / TDHF (tuna_ci.py:719-841, :1161-1211, :1284-1366, :1466-1518; tf_cis.hip.h has the matrices and the reduction).
+// Stages: the MO blocks of tf_mp3_rhf; (ab|ij) transposed to [(ij)][(ab)] and every matrix of the call assembled in one pass, after which
+// the blocks are freed; then per multiplicity one dsyevd (CIS), or dpotrf of A - B once and per multiplicity two dtrmm, one dsyevd, one
+// dtrmm and -- for the kept states -- one dtrsm (TDHF); the transition moments of the singlets as GEMMs.  All dim x dim arrays of the
+// solves are symmetric or read column by column (state n = column n = dim contiguous values), so rocSOLVER's column-major view needs no
+// transposition.
+int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip, tf_cis_result *out)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
+    if (!opts->singlets && !opts->triplets) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: neither singlets nor triplets asked for: there are no excited states to calculate");
+    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: n_keep must not be negative");
+    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: transition dipoles and oscillator strengths need the AO dipole matrices (dip)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: a sharded tensor (world > 1) is not supported");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov;
+    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: dimension overflow");   // (grids of 32-wide tiles)
+    const int dim = (int)ov, nk = std::min(opts->n_keep, dim);
+    const bool tda = opts->tda != 0, sing = opts->singlets != 0, trip = opts->triplets != 0, moments = sing && dip && (out->tdm || out->osc);
+    out->dim = dim;
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *Ht = nullptr, *Ms = nullptr, *Mt = nullptr, *Mm = nullptr, *T = nullptr, *kept = nullptr, *small = nullptr;
+    rocblas_int *d_info = nullptr;
+    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
+    bool blas_mode_set = false;
+    auto cleanup = [&]() {
+        for (double *p : {g1, g2, g3, Ht, Ms, Mt, Mm, T, kept, small}) if (p) (void)tf_free(p);
+        if (d_info) (void)tf_free(d_info);
+        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
+    };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- MO blocks, as tf_mp3_rhf makes them ((ki|lj) is not needed here)
+    if ((rc = mp3_mo_blocks(ctx, "tf_cis_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
+    (void)tf_free(g3); g3 = nullptr;
+    const auto t1 = stamp();
+    // ---- work space: the matrices (CIS: A per multiplicity; TDHF: A + B per multiplicity, A - B and one more dim^2 array for the
+    //      triangular products), the transposed (ij|ab) until the assembly is done, the kept vectors, and the small arrays:
+    //      w | w2 | e (dsyevd) | stat[2] | eps [N] | D_ia [3][dim] | mu [dim][3] | f [dim] | C_o | C_v | D C_v [N][v] | D [3][N][N]
+    const int n_mats = (sing ? 1 : 0) + (trip ? 1 : 0) + (tda ? 0 : 2);
+    const size_t nsmall = 3 * (size_t)dim + 2 + (size_t)N + 7 * (size_t)dim + (size_t)N * o + 2 * (size_t)N * v + 3 * (size_t)N * N;
+    const size_t nkept = (size_t)std::max(1, nk) * dim * (tda ? 0 : 3);
+    {
+        const double gb = (double)(((size_t)n_mats + 1) * (size_t)B2 + nkept + nsmall) * sizeof(double) / 1e9;
+        char text[200];
+        snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space (%d arrays of (o v)^2 = %lld^2 values)", gb, n_mats + 1, ov);
+        if (tf_malloc(&Ht, (size_t)B2 * sizeof(double)) != hipSuccess || (sing && tf_malloc(&Ms, (size_t)B2 * sizeof(double)) != hipSuccess) ||
+            (trip && tf_malloc(&Mt, (size_t)B2 * sizeof(double)) != hipSuccess) || (!tda && tf_malloc(&Mm, (size_t)B2 * sizeof(double)) != hipSuccess) ||
+            tf_malloc(&small, nsmall * sizeof(double)) != hipSuccess || tf_malloc((double **)&d_info, 4 * sizeof(rocblas_int)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    double *d_w = small, *d_w2 = d_w + dim, *d_e = d_w2 + dim, *d_stat = d_e + dim, *d_eps = d_stat + 2, *d_Dia = d_eps + N, *d_mu = d_Dia + 3 * (size_t)dim,
+           *d_f = d_mu + 3 * (size_t)dim, *d_Co = d_f + dim, *d_Cv = d_Co + (size_t)N * o, *d_T1 = d_Cv + (size_t)N * v, *d_dip = d_T1 + (size_t)N * v;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+    // ---- assembly
+    tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+    {
+        tfcis::AssembleArgs A{};
+        A.g1 = g1; A.Ht = Ht; A.eps = d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v;
+        if (sing) { A.kind[A.n_out] = tda ? 0 : 2; A.out[A.n_out++] = Ms; }
+        if (trip) { A.kind[A.n_out] = tda ? 1 : 3; A.out[A.n_out++] = Mt; }
+        if (!tda) { A.kind[A.n_out] = 4; A.out[A.n_out++] = Mm; }
+        tfcis::launch_assemble(A, 0);
+    }
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the assembly kernels failed on the device");
+    for (double **p : {&g1, &g2, &Ht}) { (void)tf_free(*p); *p = nullptr; }
+    {
+        const std::pair<double *, const double *> outs[3] = {{out->m_plus_singlet, Ms}, {out->m_plus_triplet, Mt}, {out->m_minus, Mm}};
+        for (const auto &pr : outs)
+            if (pr.first && pr.second && hipMemcpy(pr.first, pr.second, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+    }
+    const auto t2 = stamp();
+    // ---- solves
+    if (!tda) {
+        char text[200];
+        snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space for the TDHF reduction",
+                 (double)((size_t)B2 + nkept) * sizeof(double) / 1e9);
+        if (tf_malloc(&T, (size_t)B2 * sizeof(double)) != hipSuccess || tf_malloc(&kept, nkept * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    double *Q = kept, *Xk = kept ? kept + (size_t)std::max(1, nk) * dim : nullptr, *Yk = kept ? Xk + (size_t)std::max(1, nk) * dim : nullptr;
+    rocblas_handle blas = ctx->scf.blas;
+    // no atomics in the products: split-K sums would change from run to run
+    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
+        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
+        blas_mode_set = true;
+#define CIS_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_cis_rhf: rocBLAS / rocSOLVER failed: " #call); } while (0)
+    auto info = [&](int *h) { return hipMemcpy(h, d_info, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; };
+    const double one = 1.0;
+    if (moments) {
+        if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+        for (int c = 0; c < 3; ++c) {                             // D^c_ia = C_o^T D^c C_v
+            CIS_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, d_dip + (size_t)c * N * N, N, d_Cv, v, 0.0, d_T1, v));
+            CIS_BLAS(tfmp3::gemm_rm(blas, true, false, o, v, N, 1.0, d_Co, o, d_T1, v, 0.0, d_Dia + (size_t)c * dim, v));
+        }
+    }
+    // mu_n[c] = sqrt(2) sum_ia D^c_ia V[ia][n] over the states (columns) of V, and the oscillator strengths, to the host
+    auto transition_moments = [&](const double *V) -> int {
+        if (tfmp3::gemm_rm(blas, false, true, dim, 3, dim, std::sqrt(2.0), V, dim, d_Dia, dim, 0.0, d_mu, 3) != rocblas_status_success) return TF_ELINALG;
+        hipLaunchKernelGGL(tfcis::oscillator_kernel, dim3((unsigned)((dim + 255) / 256)), dim3(256), 0, 0, d_mu, d_w, dim, d_f);
+        if ((out->tdm && hipMemcpy(out->tdm, d_mu, 3 * (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+            (out->osc && hipMemcpy(out->osc, d_f, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+            return TF_ENODEVICE;
+        return TF_OK;
+    };
+    if (!tda) {
+        // A - B = L L^T, once for both multiplicities
+        CIS_BLAS(rocsolver_dpotrf(blas, rocblas_fill_lower, dim, Mm, dim, d_info));
+        int h = 0;
+        if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the Cholesky factorisation failed on the device");
+        if (h != 0) {
+            char text[300];
+            snprintf(text, sizeof text, "tf_cis_rhf: A - B is not positive definite (dpotrf stopped at the leading minor of order %d of %d): the RHF "
+                     "reference is unstable, and TDHF has no real excitation energies for singlets or triplets; the states are not returned", h, dim);
+            return fail(TF_ELINALG, text);
+        }
+    }
+    for (int mult = 0; mult < 2; ++mult) {
+        double *M = mult == 0 ? Ms : Mt;
+        if (!M) continue;
+        const char *name = mult == 0 ? "singlet" : "triplet";
+        double *e_out = mult == 0 ? out->e_singlet : out->e_triplet, *x_out = mult == 0 ? out->x_singlet : out->x_triplet,
+               *y_out = mult == 0 ? out->y_singlet : out->y_triplet;
+        const double *V = M;                                      // the transition vectors X + Y, state by state
+        int h = 0;
+        if (tda) {
+            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w, d_e, d_info));
+            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
+            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the ") + name + " CIS matrix did not converge (rocsolver_dsyevd)");
+            if (nk > 0 && x_out && hipMemcpy(x_out, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+            if (nk > 0 && y_out) std::fill(y_out, y_out + (size_t)nk * dim, 0.0);
+        } else {
+            // M <- L^T (A + B) L; its eigenpairs (w^2, Z)
+            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
+                                   dim, T, dim));
+            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim,
+                                   T, dim, M, dim));
+            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w2, d_e, d_info));
+            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
+            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the reduced ") + name + " TDHF matrix did not converge (rocsolver_dsyevd)");
+            hipLaunchKernelGGL(tfcis::tdhf_roots_kernel, dim3(1), dim3(256), 0, 0, d_w2, dim, d_w, d_stat);
+            double stat[2];
+            if (hipMemcpy(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the root kernel failed on the device");
+            if (stat[0] != 0.0) {
+                char text[300];
+                snprintf(text, sizeof text, "tf_cis_rhf: %d %s root(s) of the TDHF problem have w^2 <= 0 (smallest w^2 = %.10g): the RHF reference is "
+                         "unstable towards a %s perturbation, and the states are not returned (CIS on the same orbitals still runs)", (int)stat[0], name, stat[1], name);
+                return fail(TF_ELINALG, text);
+            }
+            // X + Y = L Z / sqrt(w) for every state; X - Y = sqrt(w) L^-T Z for the kept ones
+            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
+                                   dim, T, dim));
+            if (nk > 0) {
+                if (hipMemcpy(Q, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+                CIS_BLAS(rocblas_dtrsm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, nk, &one, Mm, dim,
+                                       Q, dim));
+            }
+            hipLaunchKernelGGL(tfcis::tdhf_backsub_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, T, Q, d_w, dim, nk, Xk,
+                               Yk);
+            if (nk > 0 && ((x_out && hipMemcpy(x_out, Xk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+                           (y_out && hipMemcpy(y_out, Yk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)))
+                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+            V = T;
+        }
+        if (e_out && hipMemcpy(e_out, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+        if (mult == 0 && moments) {
+            const int mrc = transition_moments(V);
+            if (mrc) return fail(mrc, "tf_cis_rhf: the transition moments failed on the device");
+        }
+    }
+#undef CIS_BLAS
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: a kernel launch failed");
+    const auto t3 = stamp();
+    cleanup();
+    out->seconds[0] = std::chrono::duration<double>(t3 - t0).count();
+    out->seconds[1] = std::chrono::duration<double>(t1 - t0).count();
+    out->seconds[2] = std::chrono::duration<double>(t2 - t1).count();
+    out->seconds[3] = std::chrono::duration<double>(t3 - t2).count();
     return TF_OK;
 }
 

@@ -10,7 +10,8 @@ with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tu
 CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, MP4(SDQ) / MP4(DQ) (also written
 MP4[SDQ] / MP4[DQ]; full MP4 with triples is not available), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
-iterations too).  Everything numerical runs on the GPU through the C ABI.  The initial
+iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, or TD on an HF line
+(TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x).  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
 """
 from __future__ import annotations
@@ -23,7 +24,7 @@ import numpy as np
 from . import molecule as mol
 from ._lib import TunaError
 from .engine import SCF_CONVERGENCE, Engine
-from .scf import DeviceERI, Integrals, construct_density_matrix, run_self_consistent_field_cycle
+from .scf import BIG_SPACER, SPACER, DeviceERI, Integrals, construct_density_matrix, run_self_consistent_field_cycle
 
 
 @dataclass
@@ -67,6 +68,14 @@ class Calculation:
     amp_conv: float = 1e-8                             # AMPCONV, calc:184
     correlated_max_iter: int = 100                     # CORRMAXITER, calc:191
     correlated_damping_parameter: float = 0.0          # CORRDAMP [x], calc:201 (without a number: the default, no damping)
+    excited_state: str | None = None                   # the printed name of an excited-state run: "CIS", "TDHF", "RPA" or "TD-HF"
+    time_dependent: bool = False                       # TD, calc:114
+    tamm_dancoff_approximation: bool = False           # TDA, calc:113 (always on for CIS, tuna_ci.py:1314)
+    calculate_no_singlets: bool = False                # NOSINGLETS, calc:120
+    calculate_no_triplets: bool = False                # NOTRIPLETS, calc:119
+    root: int = 1                                      # ROOT / STATE, calc:167
+    n_states: int = 10                                 # NSTATES, calc:169
+    excited_state_contribution_threshold: float = 1.0  # EXTHRESH (per cent), calc:168
 
 
 @dataclass
@@ -183,6 +192,20 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
                 if x is not None:
                     calc.correlated_damping_parameter = x
                     next(it)
+        elif p == "TD":
+            calc.time_dependent = True
+        elif p == "TDA":
+            calc.tamm_dancoff_approximation = True
+        elif p == "NOSINGLETS":
+            calc.calculate_no_singlets = True
+        elif p == "NOTRIPLETS":
+            calc.calculate_no_triplets = True
+        elif p in ("ROOT", "STATE"):
+            calc.root = int(value())
+        elif p == "NSTATES":
+            calc.n_states = int(value())
+        elif p == "EXTHRESH":
+            calc.excited_state_contribution_threshold = float(value())
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -358,6 +381,8 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(" Total correlation energy:         " + f"{r['E_MP2'] + E_MP3:16.10f}\n")
         if calc.coupled_cluster:
             run_coupled_cluster_doubles(calc, molecule, out, engine, silent, log)
+        if calc.excited_state:
+            run_excited_states(calc, molecule, integrals, out, engine, silent, log)
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
         if calc.dipole or calc.polarisability or calc.hyperpolarisability:
@@ -455,6 +480,113 @@ def run_coupled_cluster_doubles(calc: Calculation, molecule, out, engine: Engine
     out.energy += E_CC
 
 
+_HARTREE_IN_JOULES = (mol._hbar ** 2) / (mol._me * mol.BOHR_IN_METRES ** 2)                       # tuna_util.py:53
+PER_CM_IN_HARTREE = _HARTREE_IN_JOULES / (299792458 * mol._h * 10 ** 2)                          # tuna_util.py:60
+EV_IN_HARTREE = _HARTREE_IN_JOULES / mol._e                                                      # tuna_util.py:63
+
+
+def merge_excited_states(E_singlet, E_triplet, tdm_singlet=None, osc_singlet=None):
+    """The merged list of run_excited_state_calculation (tuna_ci.py:2209-2267): singlets then triplets, sorted by energy with a stable
+    sort.  Returns (energies, labels, source index within the multiplicity, |mu|, f); triplets have |mu| = f = 0."""
+    parts = [(np.asarray(e, dtype=float), label) for e, label in ((E_singlet, "singlet"), (E_triplet, "triplet")) if e is not None]
+    energies = np.concatenate([e for e, _ in parts])
+    labels = np.concatenate([np.full(len(e), label) for e, label in parts])
+    source = np.concatenate([np.arange(len(e)) for e, _ in parts])
+    ns = len(E_singlet) if E_singlet is not None else 0
+    mu, f = np.zeros(len(energies)), np.zeros(len(energies))
+    if ns and tdm_singlet is not None:
+        mu[:ns] = np.linalg.norm(np.asarray(tdm_singlet, dtype=float).reshape(ns, -1), axis=1)
+        f[:ns] = np.asarray(osc_singlet, dtype=float)
+    order = np.argsort(energies)                             # (the reference's own call: tuna_ci.py:2263)
+    return energies[order], labels[order], source[order], mu[order], f[order]
+
+
+def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engine, silent=True, log=print):
+    """Closed-shell CIS / TDHF on the device-resident tensor (all-electron), tf_cis_rhf: the flow of run_excited_state_calculation
+    (tuna_ci.py:2150-2290; kernel:1175-1190, :1289-1301) with its log lines (tuna_ci.py:1222-1273, :1324-1362, :1736-1863).  All states of
+    the requested multiplicities are merged and sorted; out.energy = E_SCF + the excitation energy of ROOT; out.excited holds the
+    merged energies, labels, |mu|, oscillator strengths, the root's X and Y and E_transition.  The root's difference density (P_diff of
+    determine_restricted_excited_state_energy_and_density) and properties on it are not formed in this build.  A TDHF run on an
+    unstable reference raises the library's TunaError (TF_ELINALG) where the reference warns and drops states."""
+    n_occ, N = molecule.n_doubly_occ, molecule.n_basis
+    v = N - n_occ
+    if calc.calculate_no_singlets and calc.calculate_no_triplets:
+        raise TunaError("There are no excited states to calculate!")                      # tuna_ci.py:2171
+    if v <= 0:
+        raise TunaError("Excited state calculation requested on system with no virtual orbitals!")   # kernel:1181
+    tda = calc.tamm_dancoff_approximation
+    if not silent:
+        log("\n Beginning excited state calculation...")                                  # kernel:1177
+        log("\n" + SPACER)                                                                # tuna_ci.py:1236-1271
+        log("          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
+        log(SPACER)
+        log(("  Using" if tda else "  Not using") + " the Tamm-Dancoff approximation...\n")
+        if not calc.calculate_no_triplets and not calc.calculate_no_singlets:
+            log("  Singlet and triplet states will be calculated.")
+        elif not calc.calculate_no_triplets:
+            log("  Only triplet states will be calculated.")
+        else:
+            log("  Only singlet states will be calculated.")
+    t0 = time.perf_counter()
+    n_keep = max(calc.n_states, calc.root, 0)
+    r = engine.cis_rhf(out.molecular_orbitals, out.epsilons, n_occ, 0, method="CIS" if tda else "TDHF", singlets=not calc.calculate_no_singlets,
+                       triplets=not calc.calculate_no_triplets, n_keep=n_keep, dip=integrals.D)
+    out.timings["Excited state calculation"] = time.perf_counter() - t0
+    if not silent:
+        log("\n  Building excited state Hamiltonian...      [Done]")                      # tuna_ci.py:1324-1362
+        log("  Diagonalising Hamiltonian...               [Done]")
+        log("\n  Calculating oscillator strengths...        [Done]")                      # tuna_ci.py:2243-2259
+    energies, labels, source, mu, f = merge_excited_states(r["E_singlet"], r["E_triplet"], r["tdm"], r["osc"])
+    state = calc.root - 1
+    if not 0 <= state < len(energies):
+        raise TunaError(f"Specified root ({state + 1}) does not exist!")                  # tuna_ci.py:1619
+    if not silent:
+        log("  Constructing density matrix...             [Done]")                        # tuna_ci.py:2269-2281 (the energy only, here)
+
+    def vectors(n):
+        k = int(source[n])
+        return r[f"X_{labels[n]}"][k], r[f"Y_{labels[n]}"][k]
+    o = n_occ
+    if not silent:
+        log("\n  Printing excited state information...")                                  # tuna_ci.py:1817-1861
+        log(f"  Only printing contributions larger than {calc.excited_state_contribution_threshold:.1f} %.")
+        for n in range(min(len(energies), calc.n_states)):
+            log(f"\n  ~~~~~ State {n + 1} ~~~~~  {str(labels[n]).capitalize()}")
+            log(f"\n  Excitation energy: {energies[n]:16.10f}\n")
+            X, Y = vectors(n)
+            contributions = 100 * (X ** 2 - Y ** 2)
+            for index in np.argsort(contributions, axis=None)[::-1]:
+                i, a = divmod(int(index), v)
+                if contributions[i, a] <= calc.excited_state_contribution_threshold:
+                    break
+                log(f"    {f'{i + 1}':>4}  ->  {f'{o + a + 1}':<4}  {contributions[i, a]:7.2f} %")
+        # print_excited_state_absorption_spectrum, tuna_ci.py:1754-1785
+        from . import guess as guess_mod
+        com = guess_mod.centre_of_mass(molecule.atoms) if len(molecule.atoms) == 2 else 0.0
+        with np.errstate(divide="ignore"):
+            wavelengths_nm = 1e7 / (energies * PER_CM_IN_HARTREE)
+        log("\n" + SPACER)
+        log(f"\n Transition dipole moment origin is the centre of mass, {com * mol.BOHR_RADIUS_IN_ANGSTROM:.4f} angstroms from the first atom.")
+        log("\n" + BIG_SPACER)
+        log("                                     Excited State Absorption Spectrum")
+        log(BIG_SPACER)
+        log("   State         Energy          Energy (eV)     Wavelength (nm)    Osc. Strength     Transition Dipole")
+        log(BIG_SPACER)
+        for n in range(min(len(energies), calc.n_states)):
+            log(f"  {(n + 1):2} - {str(labels[n])[0].upper()}  {energies[n]:16.10f}  {EV_IN_HARTREE * energies[n]:14.5f}   {wavelengths_nm[n]:16.5f}       "
+                f"{f[n]:10.5f}          {mu[n]:10.5f}")
+        log(BIG_SPACER)
+    X, Y = vectors(state) if state < n_keep else (None, None)
+    E_transition = float(energies[state])
+    out.excited = {"energies": energies, "state_types": labels, "transition_dipoles": mu, "oscillator_strengths": f, "X": X, "Y": Y,
+                   "E_transition": E_transition, "root": calc.root, "method": calc.excited_state, "seconds": r["seconds"],
+                   "E_singlet": r["E_singlet"], "E_triplet": r["E_triplet"], "tdm_singlet": r["tdm"]}
+    out.energy = out.energy + E_transition                                                # tuna_ci.py:1642
+    if not silent:                                                                        # kernel:1295-1299
+        log(f"\n Excitation energy is the energy difference to excited state {calc.root}.")
+        log(f"\n Excitation energy from {f'{calc.excited_state}:':<11} {E_transition:15.10f}")
+
+
 def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=print):
     """tuna.py:345 `run(input_line, suppress_output)` for single-point restricted Hartree-Fock."""
     ctype, method, basis, symbols, R, params = parse_input(input_line)
@@ -478,13 +610,33 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
                         "o^3 v^4 step this build does not have.  MP4(SDQ) is the fourth-order energy without them.")
     if method.startswith("UMP4"):
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP4 runs on a closed-shell restricted reference.")
+    if method in ("CIS(D)", "CIS[D]", "UCIS(D)", "UCIS[D]"):
+        raise TunaError(f"{method} is not available in this build: the perturbative doubles correction to CIS is not implemented.  CIS gives the "
+                        "uncorrected states.")
+    if method in ("UCIS", "UTDHF", "URPA"):
+        raise TunaError(f"Unrestricted {method[1:]} is not available in this build: {method[1:]} runs on a closed-shell restricted reference.")
+    excited = method if method in ("CIS", "TDHF", "RPA") else None
     mp4 = {"MP4(SDQ)": "SDQ", "MP4[SDQ]": "SDQ", "MP4(DQ)": "DQ", "MP4[DQ]": "DQ"}.get(method)
     mp3 = method in ("MP3", "SCS-MP3")
     cc = method if method in ("CCD", "LCCD") else None       # coupled-cluster doubles; every other CC name stays unsupported
-    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3", "CCD", "LCCD") and not mp4 and method not in dft_mod.FUNCTIONALS:
+    if method not in ("HF", "RHF", "UHF", "MP2", "RMP2", "SCS-MP2", "MP3", "SCS-MP3", "CCD", "LCCD") and not mp4 and not excited and method not in dft_mod.FUNCTIONALS:
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP" in method else "HF"), basis))
     calc.coupled_cluster = cc
+    if calc.time_dependent and not excited:                  # TD on an HF line: time-dependent Hartree-Fock (kernel:1175)
+        if method not in ("HF", "RHF"):
+            raise TunaError(f"The TD keyword is available on an HF or RHF line only in this build: excited states of {method} (time-dependent DFT, "
+                            "unrestricted or correlated references) are not implemented.")
+        excited = "TD-HF"
+    if excited:
+        if calc.multiplicity != 1:
+            raise TunaError(f"{excited} is available for a closed-shell restricted reference only in this build (ML 1).")
+        if calc.dipole or calc.polarisability or calc.hyperpolarisability:
+            raise TunaError("finite-field properties are available for Hartree-Fock energies in this build")
+        if calc.calculate_no_singlets and calc.calculate_no_triplets:
+            raise TunaError("There are no excited states to calculate!")                  # tuna_ci.py:2171
+        calc.excited_state = excited
+        calc.tamm_dancoff_approximation = calc.tamm_dancoff_approximation or excited == "CIS"      # tuna_ci.py:1314
     if cc and calc.multiplicity != 1:
         raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
     if cc and (calc.dipole or calc.polarisability or calc.hyperpolarisability):

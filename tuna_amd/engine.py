@@ -314,6 +314,50 @@ class Engine:
             out["t2"] = t2
         return out
 
+    def cis_rhf(self, C, eps, n_occ, n_frozen=0, method="CIS", singlets=True, triplets=True, n_keep=0, dip=None, return_matrices=False) -> dict:
+        """Closed-shell CIS or TDHF (RPA) excited states from canonical RHF orbitals on the resident tensor (tunafock.h: tf_cis_rhf;
+        tuna_ci.py:1284-1366, :1466-1518): {"dim", "E_singlet", "E_triplet" [dim] ascending (None for a multiplicity that is off),
+        "X_singlet", "Y_singlet", "X_triplet", "Y_triplet" [n_keep, o, v] for the lowest n_keep states (Y = 0 for CIS), "tdm" [dim, 3] and
+        "osc" [dim] of the singlets with dip = the AO dipole matrices [3, N, N] (None otherwise), "seconds" = [wall, MO blocks, assembly,
+        solves]; with return_matrices "M_plus_singlet", "M_plus_triplet" (A + B, or A for CIS) and "M_minus" (A - B, TDHF) [dim, dim]}.
+        Raises TunaError with the library's code and message; TF_ELINALG (-5) when TDHF meets an unstable reference."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"cis_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if method not in ("CIS", "TDHF", "RPA"):
+            raise TunaError(f"cis_rhf: method must be \"CIS\", \"TDHF\" or \"RPA\", got {method!r}")
+        if dip is not None:
+            dip = f64(dip)
+            if dip.shape != (3, self.N, self.N):
+                raise TunaError(f"cis_rhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        import ctypes
+        from ._lib import CisOpts, CisResult
+        tda = method == "CIS"
+        o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
+        dim = o * v
+        nk = max(0, min(int(n_keep), dim))
+        opts = CisOpts(int(tda), int(bool(singlets)), int(bool(triplets)), int(n_keep))
+        res = CisResult()
+        arrays = {}
+
+        def take(name, shape, wanted=True):
+            arrays[name] = np.zeros(shape) if wanted else None
+            return ptr(arrays[name])
+        res.e_singlet, res.e_triplet = take("E_singlet", dim, singlets), take("E_triplet", dim, triplets)
+        for mult, on in (("singlet", singlets), ("triplet", triplets)):
+            setattr(res, f"x_{mult}", take(f"X_{mult}", (nk, o, v), on and nk > 0))
+            setattr(res, f"y_{mult}", take(f"Y_{mult}", (nk, o, v), on and nk > 0))
+        res.tdm, res.osc = take("tdm", (dim, 3), singlets and dip is not None), take("osc", dim, singlets and dip is not None)
+        res.m_plus_singlet = take("M_plus_singlet", (dim, dim), return_matrices and singlets)
+        res.m_plus_triplet = take("M_plus_triplet", (dim, dim), return_matrices and triplets)
+        res.m_minus = take("M_minus", (dim, dim), return_matrices and not tda)
+        self._check(self._L.tf_cis_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(dip), ctypes.byref(res)))
+        out = {"dim": int(res.dim), "seconds": list(res.seconds)}
+        for name, a in arrays.items():
+            if return_matrices or not name.startswith("M_"):
+                out[name] = a
+        return out
+
     def mp3_ladder_probe(self, T) -> np.ndarray:
         """Zh[p] = the stored-triangle ladder contraction of the packed tensor with T[p] ([N,N] or [n,N,N], any matrices), by the kernel
         and the batching of mp3_rhf (tunafock.h: tf_mp3_ladder_probe); Z[T] = Zh[T] + Zh[T^T]^T."""
