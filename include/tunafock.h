@@ -417,6 +417,33 @@ int tf_eri_counts(const tf_ctx *ctx, int64_t *counts3);
  * Boys / R table cost 6 (L+1) + 3 (L+1)^2 / 2 + 60).  The device kernels factorise the sums and execute fewer operations; the
  * figure prices the build against the FP64 vector peak. */
 int tf_eri_flops(const tf_ctx *ctx, double *nominal_flops);
+/* Launch structure of the last tf_build_eri (instrumentation, tests): host counters incremented where the launches are made, no
+ * device work and no synchronisation.  out[i] for i < n gets counter i of the list below (0 beyond TF_ERI_STAT_COUNT); TF_EINVAL on a
+ * NULL pointer or n < 0.  A slab is one run of this rank's bra shell pairs through generation, ket and bra transform (TF_SLAB_MB,
+ * TF_SLAB_ROWS); the family counters count kernel launches and add up to TF_ERI_STAT_LAUNCHES (TF_ERI_STAT_TEAM_FLAT counts launches
+ * already counted under their team size). */
+enum {
+    TF_ERI_STAT_SLABS = 0,
+    TF_ERI_STAT_LAUNCHES,             /* launches of ERI generation kernels, every family below                                   */
+    TF_ERI_STAT_TEAM16,               /* eri_team_kernel, 16 / 64 / 256 lanes per shell quartet (per-class mode, packed or tiles)  */
+    TF_ERI_STAT_TEAM64,
+    TF_ERI_STAT_TEAM256,
+    TF_ERI_STAT_TEAM_FLAT,            /* ... of those, launches that walk the flat component lists                                 */
+    TF_ERI_STAT_TEAMC,                /* eri_teamc_kernel over task lists (small-problem mode, TF_ERI_TEAMC=1)                     */
+    TF_ERI_STAT_CFACT_UNCONTRACTED,   /* eri_cfact_kernel (small-problem mode): both groups uncontracted                           */
+    TF_ERI_STAT_CFACT_CONTRACTED,     /* ... a contracted group, no families                                                       */
+    TF_ERI_STAT_CFACT_GTAB,           /* ... G, X and Z tables in global memory ((hh|hh)-sized quartets)                           */
+    TF_ERI_STAT_CFACT_KET_FAMILIES,   /* ... families of ket pairs (general contractions)                                          */
+    TF_ERI_STAT_CFACT_BOTH_FAMILIES,  /* ... families on both sides                                                                */
+    TF_ERI_STAT_CFACT_BRA_FAMILIES,   /* ... families of bra pairs (TF_ERI_BRA_FAMILIES=1)                                         */
+    TF_ERI_STAT_COMPONENT_LANE,       /* the component-per-lane kernel of the small-problem mode (TF_ERI_GENERIC_OLD, oversized LDS) */
+    TF_ERI_STAT_MULTI,                /* eri_multi_kernel (per-class mode: several small uncontracted quartets per workgroup)      */
+    TF_ERI_STAT_FACT,                 /* eri_fact_kernel (per-class mode: uncontracted, factor tables in LDS)                      */
+    TF_ERI_STAT_CLASS_STAGED,         /* eri_class_kernel with the Hermite tables staged in LDS (per-class mode)                   */
+    TF_ERI_STAT_CLASS_UNSTAGED,       /* eri_class_kernel reading them from global memory                                          */
+    TF_ERI_STAT_COUNT
+};
+int tf_eri_build_stats(const tf_ctx *ctx, int64_t *out, int n);
 /* Alignment unit (in doubles) of the stored segments of the packed, parity-blocked tensor layout. */
 int tf_segment_pad(void);
 

@@ -63,7 +63,7 @@ class CisResult(C.Structure):                             # tf_cis_result
 EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normalize", "tf_set_basis", "tf_get_norms",
            "tf_dims", "tf_get_sph_matrix", "tf_one_electron", "tf_cross_overlap", "tf_build_eri", "tf_eri_storage",
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
-           "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_shard_plan", "tf_jk_profile",
+           "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_eri_build_stats", "tf_shard_plan", "tf_jk_profile",
            "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_cis_rhf", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
            "tf_dft_clear", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
@@ -125,6 +125,7 @@ def lib():
     L.tf_orthogonaliser.restype = ci; L.tf_orthogonaliser.argtypes = [vp, ci, vp, vp, vp, dp]
     L.tf_eri_timings.restype = ci; L.tf_eri_timings.argtypes = [vp, vp]
     L.tf_eri_counts.restype = ci; L.tf_eri_counts.argtypes = [vp, vp]
+    L.tf_eri_build_stats.restype = ci; L.tf_eri_build_stats.argtypes = [vp, C.POINTER(C.c_int64), ci]
     L.tf_shard_plan.restype = ci; L.tf_shard_plan.argtypes = [ci, vp, ci, vp]
     L.tf_shard_plan_pairs.restype = ci; L.tf_shard_plan_pairs.argtypes = [ci, vp, ci, ci, vp]
     L.tf_diagonalise.restype = ci; L.tf_diagonalise.argtypes = [vp, ci, vp, vp, vp, vp]

@@ -241,6 +241,7 @@ struct tf_ctx {
     size_t jkstage_doubles = 0;
     double eri_seconds[4] = {0, 0, 0, 0};
     long long eri_counts[3] = {0, 0, 0};
+    long long eri_stats[TF_ERI_STAT_COUNT] = {};   // launches of the last build by kernel family (tf_eri_build_stats)
     double eri_nominal_flops = 0.0;      // the reference algorithm's operation count for the quartets of the last build
     tfscf::Workspace scf;
     std::vector<std::unique_ptr<tfscf::Workspace>> scf_batch;   // one workspace per cycle of a lockstep batch (tf_scf_rhf_batch), kept across calls
@@ -918,7 +919,7 @@ struct EriBuild {
     // slab size, work counters
     bool per_class = false;
     double *d_C = nullptr, *d_T2 = nullptr;
-    long long max_rows_c = 1;
+    long long max_rows_c = 1, cut_rows = 1;                     // rows the slab buffers hold; rows at which run_slab cuts (<= max_rows_c)
     double t_stage[4] = {0, 0, 0, 0};
     long long n_quart = 0, n_primq = 0, n_compq = 0;
     std::vector<long long> cum_pairs, cum_pp, cum_comp;
@@ -944,6 +945,8 @@ struct EriBuild {
     hipStream_t *streams = nullptr;
     hipEvent_t *sev = nullptr;
     int launch_count = 0;
+    long long stats[TF_ERI_STAT_COUNT] = {};                   // host counters of tf_eri_build_stats: incremented where the launches are made
+    void count(int family) { ++stats[family]; ++stats[TF_ERI_STAT_LAUNCHES]; }
     // launch tables
     std::vector<LRec> lrecs_host;                              // per (La, Lb | Lc, Ld), filled by make_lrecs
     hipError_t team_error = hipSuccess;                        // first failed launch of a team kernel
@@ -1187,6 +1190,10 @@ int EriBuild::plan_slab_size()
     size_t slab_bytes = std::min<size_t>((size_t)4 << 30, std::max<size_t>((size_t)1 << 30, std::max((size_t)ctx->n_elems, slab_total)));
     if (const char *e = getenv("TF_SLAB_MB")) slab_bytes = (size_t)std::max(1, atoi(e)) << 20;
     max_rows_c = std::max<long long>(1, (long long)(slab_bytes / slab_row_bytes));
+    // TF_SLAB_ROWS=n: the slab in Cartesian bra rows (the 1 MiB floor of TF_SLAB_MB cannot cut a small basis); n = 1 gives one bra
+    // shell pair per slab, the finest cut there is
+    cut_rows = 0;
+    if (const char *e = getenv("TF_SLAB_ROWS")) max_rows_c = cut_rows = std::max<long long>(1, atoll(e));
     long long biggest = 1;
     for (int p : ctx->my_pairs)
         biggest = std::max<long long>(biggest, (long long)bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp);
@@ -1196,6 +1203,8 @@ int EriBuild::plan_slab_size()
         for (int p : ctx->my_pairs) need += (long long)bs.shells[bs.pairs[p].A].ncomp * bs.shells[bs.pairs[p].B].ncomp;
         max_rows_c = std::max<long long>(biggest, std::min(max_rows_c, need));
     }
+    // the buffers hold the largest pair; the cut itself stays at what TF_SLAB_ROWS asked for (a slab always takes its first pair whole)
+    cut_rows = cut_rows ? std::min(cut_rows, max_rows_c) : max_rows_c;
     if ((rc = ensure_scratch(ctx, 0, per_class ? 8 : (size_t)max_rows_c * cart_row_bytes)) ||
         (rc = ensure_scratch(ctx, 2, (size_t)max_rows_c * t2_row_bytes)))
         return rc;
@@ -1489,6 +1498,8 @@ void EriBuild::launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra,
                          d_brarec + (d_bra - d_bra_base), d_ketrec + ket_off[kcls], d_kcnt + (size_t)kcls * nsh, d_out_slab};
             const hipError_t e = eri_team_launch(a);
             if (e != hipSuccess) { team_error = e; }
+            count(team == 16 ? TF_ERI_STAT_TEAM16 : (team == 64 ? TF_ERI_STAT_TEAM64 : TF_ERI_STAT_TEAM256));
+            if (t.flat) ++stats[TF_ERI_STAT_TEAM_FLAT];
             return;
         }
     }
@@ -1513,6 +1524,7 @@ void EriBuild::launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra,
         q.offCsr = o; o += TF_CSR_DOUBLES;
         q.lds_doubles = o;
         const dim3 grid((q.n_ket + q.G - 1) / q.G, n_bra);
+        count(TF_ERI_STAT_MULTI);
         hipLaunchKernelGGL(eri_multi_kernel, grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q, d_bra, d_braoff,
                            d_ket, Nc, d_out_slab);
     } else if (q.npq == 1 && (q.La + 1) * (q.Lb + 1) * (q.Lc + 1) * (q.Ld + 1) * 2 * (q.L / 2 + 1) <= 7000 && !getenv("TF_ERI_NOFACT")) {
@@ -1542,6 +1554,7 @@ void EriBuild::launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra,
         // the LDS of a quartet limits the workgroups per CU, so fewer waves per workgroup are fewer waves per CU)
         static const int force_thr = getenv("TF_ERI_FACT_THREADS") ? atoi(getenv("TF_ERI_FACT_THREADS")) : 0;
         const int fact_threads = (force_thr == 64 || force_thr == 128) ? force_thr : TF_ERI_THREADS;
+        count(TF_ERI_STAT_FACT);
         hipLaunchKernelGGL(eri_fact_kernel, dim3(q.n_ket, n_bra), dim3(fact_threads), (size_t)o * sizeof(double), st, ctx->db, q, d_bra,
                            d_braoff, d_ket, Nc, d_out_slab);
     } else {
@@ -1564,6 +1577,7 @@ void EriBuild::launch_class(int bcls, int kcls, int max_npp_bra, unsigned n_bra,
         q.offCsr = o; o += TF_CSR_DOUBLES;
         q.lds_doubles = o;
         const dim3 grid(q.n_ket, n_bra);
+        count(stage ? TF_ERI_STAT_CLASS_STAGED : TF_ERI_STAT_CLASS_UNSTAGED);
         if (stage)
             hipLaunchKernelGGL((eri_class_kernel<true, false>), grid, dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st, ctx->db, q,
                                d_bra, d_braoff, d_ket, Nc, d_out_slab);
@@ -1592,6 +1606,7 @@ void EriBuild::launch_generic_old(unsigned n_bra, const int *d_bra, const long l
     q.offBlk = o;                                            // unused (unfused)
     q.G = 1; q.n_ket = (int)n_ket; q.fused = 0;
     q.tri = packed ? 1 : 0;
+    count(TF_ERI_STAT_COMPONENT_LANE);
     hipLaunchKernelGGL((eri_class_kernel<true, true>), dim3(n_ket, n_bra), dim3(TF_ERI_THREADS), (size_t)o * sizeof(double), st,
                        ctx->db, q, d_bra, d_braoff, d_ket, Nc, d_C);
 }
@@ -1814,13 +1829,15 @@ int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra,
                 ctx->gtab_bytes = need;
             }
             // launches that share the block must not overlap: they all go to one stream
+            count(TF_ERI_STAT_CFACT_GTAB);
             hipLaunchKernelGGL((eri_cfact_kernel<true, true>), dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, streams[0], ctx->db, c,
                                d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C, ctx->d_gtab);
             load[qi] -= l.cost; load[0] += l.cost;
-        } else if (((gb | gk) & 1) == 0)                     // both groups uncontracted: one primitive quartet per shell quartet
+        } else if (((gb | gk) & 1) == 0) {                   // both groups uncontracted: one primitive quartet per shell quartet
+            count(TF_ERI_STAT_CFACT_UNCONTRACTED);
             hipLaunchKernelGGL(eri_cfact_kernel<true>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
                                d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
-        else if ((gb & 1) && !(gk & 1) && bra_fam_on) {       // contracted bras against uncontracted kets: (family of bra pairs, ket pair).
+        } else if ((gb & 1) && !(gk & 1) && bra_fam_on) {       // contracted bras against uncontracted kets: (family of bra pairs, ket pair).
             // Off by default (TF_ERI_BRA_FAMILIES=1): the packed layout evaluates the kets whose first shell does not exceed the bra's,
             // and the contracted shells come first on each atom -- the contracted pairs sit on the ket side; measured on Ar2/cc-pVQZ these
             // bra families cost 5 % (fewer, longer workgroups) where the ket families gain 24 %.
@@ -1831,6 +1848,7 @@ int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra,
                 HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MM, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
                 bfam_attr_set = true;
             }
+            count(TF_ERI_STAT_CFACT_BRA_FAMILIES);
             hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MM, 1>), dim3((unsigned)nk, bf->n), dim3(TF_ERI_THREADS), bytes, st,
                                ctx->db, c, d_bra, d_braoff, d_kets_all + kets_goff[gk], Nc, d_C, (double *)nullptr, (const int *)nullptr,
                                (const int *)nullptr, bf->d_ptr, bf->d_mem);
@@ -1845,6 +1863,7 @@ int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra,
                 HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
                 ccfam_attr_set = true;
             }
+            count(TF_ERI_STAT_CFACT_BOTH_FAMILIES);
             hipLaunchKernelGGL((eri_cfact_kernel<false, false, FAM_MA_CC, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), bf->n),
                                dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra, d_braoff, d_fam_heads + fam_goff[gk], Nc, d_C, (double *)nullptr,
                                d_fam_ptr + fam_goff[gk], d_fam_mem, bf->d_ptr, bf->d_mem);
@@ -1855,12 +1874,15 @@ int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra,
                 HIPCHK(ctx, hipFuncSetAttribute((const void *)eri_cfact_kernel<false, false, 1, FAM_MM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
                 fam_attr_set = true;
             }
+            count(TF_ERI_STAT_CFACT_KET_FAMILIES);
             hipLaunchKernelGGL((eri_cfact_kernel<false, false, 1, FAM_MM>), dim3((unsigned)(fam_goff[gk + 1] - fam_goff[gk]), (unsigned)(b1 - b0)),
                                dim3(TF_ERI_THREADS), bytes, st, ctx->db, c, d_bra + b0, d_braoff + b0, d_fam_heads + fam_goff[gk], Nc, d_C,
                                (double *)nullptr, d_fam_ptr + fam_goff[gk], d_fam_mem);
-        } else
+        } else {
+            count(TF_ERI_STAT_CFACT_CONTRACTED);
             hipLaunchKernelGGL(eri_cfact_kernel<false>, dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, st, ctx->db, c,
                                d_bra + b0, d_braoff + b0, d_kets_all + kets_goff[gk], Nc, d_C);
+        }
         ++launch_count;
     }
     return TF_OK;
@@ -2173,6 +2195,7 @@ int EriBuild::launch_teamc(const std::vector<TcLaunch> &tcl)
                       teamc_pqmax, d_T2};
         const hipError_t e = eri_teamc_launch(a);
         if (e != hipSuccess && team_error == hipSuccess) team_error = e;
+        count(TF_ERI_STAT_TEAMC);
         ++launch_count;
     }
     for (int k = 0; k < NSTREAM; ++k) {
@@ -2196,7 +2219,7 @@ int EriBuild::run_slab()
         const int p = mine_sorted[cursor];
         const tf::Shell &a = bs.shells[bs.pairs[p].A], &b = bs.shells[bs.pairs[p].B];
         const long long nr = (long long)a.ncomp * b.ncomp;
-        if (!bra.empty() && (rows_c + nr > max_rows_c || bra.size() >= 65535 || outs.size() + outsP.size() + outsT.size() + (size_t)pair_rows[p] >= cap_out)) break;
+        if (!bra.empty() && (rows_c + nr > cut_rows || bra.size() >= 65535 || outs.size() + outsP.size() + outsT.size() + (size_t)pair_rows[p] >= cap_out)) break;
         bra.push_back(p); braoff.push_back(rows_c);
         long long r = rows.pair_first_row[p];
         for (int x = 0; x < out_dim(a); ++x)
@@ -2246,6 +2269,7 @@ int EriBuild::run_slab()
     if (d_rowcls_alloc) d_rowcls = d_rowcls_alloc + (size_t)set * rowcls_bytes;
     d_bra_base = d_bra;
     ++slab_no;
+    ++stats[TF_ERI_STAT_SLABS];
     const hipStream_t cst = ctx->cstream;
     HIPCHK(ctx, hipMemcpyAsync(d_bra, bra.data(), bra.size() * sizeof(int), hipMemcpyHostToDevice, cst));
     HIPCHK(ctx, hipMemcpyAsync(d_braoff, braoff.data(), braoff.size() * sizeof(long long), hipMemcpyHostToDevice, cst));
@@ -2362,6 +2386,7 @@ int EriBuild::finish()
     std::copy(t_stage, t_stage + 4, ctx->eri_seconds);
     ctx->eri_counts[0] = n_quart; ctx->eri_counts[1] = n_primq; ctx->eri_counts[2] = n_compq;
     ctx->eri_nominal_flops = nominal_flops;
+    std::copy(stats, stats + TF_ERI_STAT_COUNT, ctx->eri_stats);
     return TF_OK;
 }
 
@@ -2489,6 +2514,13 @@ int tf_eri_counts(const tf_ctx *ctx, int64_t *c3)
 {
     if (!ctx || !c3) return TF_EINVAL;
     for (int i = 0; i < 3; ++i) c3[i] = ctx->eri_counts[i];
+    return TF_OK;
+}
+
+int tf_eri_build_stats(const tf_ctx *ctx, int64_t *out, int n)
+{
+    if (!ctx || !out || n < 0) return TF_EINVAL;
+    for (int i = 0; i < n; ++i) out[i] = i < TF_ERI_STAT_COUNT ? ctx->eri_stats[i] : 0;
     return TF_OK;
 }
 

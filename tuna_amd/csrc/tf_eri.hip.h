@@ -579,6 +579,9 @@ __global__ __launch_bounds__(TF_ERI_THREADS) void eri_fact_kernel(DBasis B, QCla
     }
     coop_tables(B, L, 1, 1, sR, sPref, sPQ, [&](int, int &ppab, int &ppcd) { ppab = ab.pp_off; ppcd = cd.pp_off; }, tid);
     __syncthreads();
+    // read here, not where it is used: with offCsr == 0 the spherical CSR rows are staged over the R / prefactor / E tables below, and the
+    // 46 entries of an h shell reach past the 45 R entries of an (ss|hf) quartet (L = 8) into sPref[0]
+    const double pref = sPref[0];
     // ---- ket half of the z tables: G[c,d][v][n], v <= La + Lb, n <= L - v - (c + d) (zero beyond) ----
     double *sG = smem + qc.offG;
     const unsigned short *__restrict__ tupG = B.tup + qc.tupG_off, *__restrict__ tupXZ = B.tup + qc.tupXZ_off;   // entry index words (host)
@@ -635,7 +638,6 @@ __global__ __launch_bounds__(TF_ERI_THREADS) void eri_fact_kernel(DBasis B, QCla
     // The tables are staged as BYTE OFFSETS into the X / Z tables (16-bit fields, the class constants (Lc+1)(Ld+1) and nM multiplied in
     // once per entry) and the scale of a bra pair carries the quartet's prefactor: the component loop itself has no integer
     // multiplication (quarter rate on this hardware: nine of them cost as much as the 35 multiply-adds of an (ff|ff) component).
-    const double pref = sPref[0];
     double *sBlk = smem + qc.offBlk;
     const int nsubc = qc.ncc * qc.ncd, nab = qc.nca * qc.ncb;
     double *sScAB = smem + qc.offTab, *sScCD = sScAB + nab;

@@ -123,6 +123,17 @@ class Engine:
                 "shell_quartets": int(c[0]), "primitive_shell_quartets": int(c[1]), "component_quartets": int(c[2]),
                 "nominal_flops": float(f[0])}
 
+    # counters of tf_eri_build_stats, in the order of the TF_ERI_STAT_* list of tunafock.h
+    ERI_BUILD_STATS = ("slabs", "launches", "team16", "team64", "team256", "team_flat", "teamc", "cfact_uncontracted", "cfact_contracted",
+                       "cfact_gtab", "cfact_ket_families", "cfact_both_families", "cfact_bra_families", "component_lane", "multi", "fact",
+                       "class_staged", "class_unstaged")
+
+    def eri_build_stats(self) -> dict:
+        """Launch structure of the last build_eri: slabs and launches per kernel family (tunafock.h: tf_eri_build_stats)."""
+        out = (C.c_int64 * len(self.ERI_BUILD_STATS))()
+        self._check(self._L.tf_eri_build_stats(self._ctx, out, len(out)))
+        return dict(zip(self.ERI_BUILD_STATS, (int(v) for v in out)))
+
     def copy_eri(self, out: np.ndarray | None = None) -> np.ndarray:
         N = self.N
         if out is None:
