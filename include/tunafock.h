@@ -355,6 +355,47 @@ typedef struct {
  * TF_ENOMEM, with the size in the message, when the work space does not fit. */
 int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_cc_result *out);
 
+/* ---- coupled-cluster singles and doubles: the same loop for restricted LCCSD, QCISD and CCSD ---- */
+
+#define TF_CCSD_LCCSD 0         /* tuna_cc.py:1020-1063 (the reference's input names CEPA, CEPA0, CEPA(0), CEPA[0] too) */
+#define TF_CCSD_QCISD 1         /* tuna_cc.py:1503-1557 */
+#define TF_CCSD_CCSD  2         /* tuna_cc.py:1638-1718 */
+
+typedef struct {
+    double e_corr;              /* e_singles + e_connected + e_disconnected of the last step */
+    double e_mp2;               /* the energy of the guess t2 = (ia|jb) / D: E_OS + E_SS of tf_mp2_rhf */
+    double e_singles;           /* sum F_ia t_ia with F = diag(eps): exactly 0.0 */
+    double e_connected;         /* sum [2 (ia|jb) - (ib|ja)] t_ijab */
+    double e_disconnected;      /* sum [2 (ia|jb) - (ib|ja)] t_ia t_jb (CCSD); exactly 0.0 for LCCSD and QCISD */
+    double t1_norm;             /* ||t1||_2 of the last step */
+    int32_t n_iter;
+    int32_t converged;
+    int64_t ladder_batches;     /* batches of 64 pair matrices sent through the ladder stage over the whole call */
+    double *table;              /* [max_iter,3] caller-allocated, may be NULL: step, E_corr, dE */
+    double *t1;                 /* [o,v] caller-allocated, may be NULL: t_ia of the last step */
+    double *t2;                 /* [o,o,v,v] caller-allocated, may be NULL: t_ijab of the last step */
+    double seconds[4];          /* wall time, MO blocks, ladder (all iterations), the rest */
+} tf_ccsd_result;
+
+/* Restricted LCCSD / QCISD / CCSD from canonical RHF orbitals; opts->method is one of the three codes above, everything else in opts,
+ * the windows, the guess t2 = (ia|jb) / D and e_mp2 as tf_ccd_rhf; the guess t1 is zero.  One step is a Jacobi update (new t1 and new t2
+ * both from the old pair).  Per step: ONE pass of the AO-direct ladder over the o^2 dressed pair matrices
+ *     T_ij = C_v th_ij C_v^T + c_i (C_v t_j)^T + (C_v t_i) c_j^T,   th = t2 (LCCSD, QCISD) or t2 + t1 t1 (CCSD),
+ * back-transformed with C_v (the ladder and sum_c (ia|cb) t_jc with its image) and with C_o, C_v (sum_cd (kc|ad) th_ijcd and the t1 parts:
+ * the three-virtual terms of the singles, CCSD's t1 parts of W_cdab and its two t1 t1 (oo|vv) / (ov|ov) terms), so
+ * ladder_batches == n_iter * ceil(o^2 / 64); tf_ccd_rhf's GEMMs on o^2 v^2, o^3 v and o^4 blocks ((ik|ja) is the one new block, made once);
+ * CCSD alone adds per step two AO->MO transformations with t1-dressed coefficients (the t1 parts of W_icak and W_ciak as o^2 v^2 blocks)
+ * and one general-density J/K build on C_v t1^T C_o^T (the t1 parts of L_ik and L_ca); one fused singles and one fused doubles update.
+ * No array with three or four virtual indices exists, on the device or on the host.  t1 lies behind t2 in every amplitude buffer:
+ * the DIIS error vector is the concatenation of t2 - t2_old and t1 - t1_old, both blocks are extrapolated with the same coefficients
+ * and damped alike.  Converged if |dE| < conv_delta_E, ||t2 - t2_old||_2 < conv_amplitudes and ||t1 - t1_old||_2 < conv_amplitudes.
+ * Work space in arrays of o^2 v^2 values: 11 (LCCSD), 16 (QCISD), 18 (CCSD), three of them o v longer, plus 2 (max(max_diis, 2) + 1) DIIS
+ * slots of o^2 v^2 + o v with DIIS, the blocks (ia|jb) and (transiently) (ab|ij) and CCSD's dressed pair of them, three o^3 v and two o^4
+ * blocks, and the ladder's batch.  Reductions are per block and summed in block order: two identical calls give identical results.
+ * TF_ENOTCONV after max_iter steps: table, n_iter, the energies, t1 and t2 then hold the last step.  TF_EINVAL (the context stays usable),
+ * TF_ENOMEM as tf_ccd_rhf; a method outside the three codes is TF_EINVAL. */
+int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_ccsd_result *out);
+
 /* ---- excited states: replaces calculate_restricted_single_reference_excited_states and calculate_restricted_transition_dipoles
  * (tuna_ci.py:1284-1366, :1466-1518) for closed-shell CIS and TDHF (RPA) ---- */
 

@@ -36,6 +36,7 @@
 #include "tf_mp2.hip.h"
 #include "tf_mp3.hip.h"
 #include "tf_ccd.hip.h"
+#include "tf_ccsd.hip.h"
 #include "tf_cis.hip.h"
 #include "tf_mp4.hip.h"
 #include "tf_dft.hip.h"
@@ -3774,8 +3775,11 @@ static size_t mp3_ladder_work_doubles(const tf_ctx *ctx, int v)
 // With Col (C_o in that AO order; tf_mp4_rhf's singles) every batch is back-transformed with the occupied coefficients as well:
 // OA[ij][k][a] = C_o^T Zh_ij C_v and, on the packed layout, OB[ij][a][k] = C_v^T Zh_ij C_o (the other stored-triangle half of
 // C_o^T Z_ji C_v); Vo = TFL_W N o doubles of work space.  These GEMMs are skinny and run without rocBLAS's atomics (split-K sums).
+// With Bol as well (tf_ccsd_rhf; Bol = C_v t1^T in that AO order, [N][o]) every pair matrix is dressed with c_i b_j^T + b_i c_j^T before the
+// contraction (tfccsd::ccsd_dress_pairs_kernel); n_batches, if given, counts the batches.
 static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const double *too, const double *Cvl, double *batch, double *Y,
-                            const double *Col = nullptr, double *Vo = nullptr, double *OA = nullptr, double *OB = nullptr)
+                            const double *Col = nullptr, double *Vo = nullptr, double *OA = nullptr, double *OB = nullptr,
+                            const double *Bol = nullptr, long long *n_batches = nullptr)
 {
     const int N = ctx->N;
     const long long nn = (long long)N * N;
@@ -3793,6 +3797,12 @@ static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const do
         // U_p = t_p C_v^T (packed: Zh of T_p; exchange route: K of T_p^T, so t_p^T), T_p = C_v U_p
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
         MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
+        if (Bol) {
+            const long long tot = nn * nb;
+            hipLaunchKernelGGL(tfccsd::ccsd_dress_pairs_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb,
+                               p0, o, Col, Bol, packed ? 0 : 1);
+        }
+        if (n_batches) ++*n_batches;
         if (packed) {
             if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zh)) { ctx->err = std::string(who) + ": ladder kernel launch failed"; return TF_ENODEVICE; }
         } else {
@@ -4292,6 +4302,322 @@ int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, con
     out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
     if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
     if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
+    return TF_OK;
+}
+
+// out[a][b][i][j] = (C1_a C2_b|C3_i C4_j) into dst (v v o o doubles on the device), in slices of the first index as mp3_mo_blocks makes
+// (ab|ij): tf_ccsd_rhf's dressed W_ciak block.  On failure ctx->err is set.
+static int ccsd_vvoo_block(tf_ctx *ctx, const char *who, const std::vector<double> &C1, const std::vector<double> &C2, const std::vector<double> &C3,
+                           const std::vector<double> &C4, int o, int v, double *dst)
+{
+    const int N = ctx->N;
+    const long long nn = (long long)N * N;
+    const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
+    std::vector<double> Cs((size_t)N * nc);
+    for (int a0 = 0; a0 < v; a0 += nc) {
+        const int na = std::min(nc, v - a0);
+        for (int m = 0; m < N; ++m)
+            for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = C1[(size_t)m * v + a0 + a];
+        double *d_s = nullptr;
+        int rc = mo_transform_device(ctx, Cs.data(), na, C2.data(), v, C3.data(), o, C4.data(), o, &d_s, nullptr);
+        if (rc) return rc;
+        const hipError_t ce = hipMemcpy(dst + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
+        (void)tf_free(d_s);
+        if (ce != hipSuccess) { ctx->err = std::string(who) + ": copy failed"; return TF_ENODEVICE; }
+    }
+    return TF_OK;
+}
+
+// Restricted LCCSD / QCISD / CCSD (tuna_cc.py:1020-1063, :1503-1557, :1638-1718, the loop of :3004-3161; tf_ccsd.hip.h has the expressions).
+// tf_ccd_rhf's stages with t1 directly behind t2 in every amplitude buffer (o^2 v^2 + o v elements): per step the amplitude operands, ONE
+// ladder pass on the dressed pair matrices with the occupied back-transformation of tf_mp4_rhf, the intermediates (CCSD: two dressed
+// AO->MO transformations and one general-density J/K build), the GEMMs, the fused singles and doubles updates; then convergence, DIIS and
+// damping over both blocks.  Work space in arrays of o^2 v^2: t | t_new | dt (each o v longer) | Tn | Tx | Tm | S1 | S2 | X | Y | H
+// (QCISD, CCSD: | A1 | A2 | Gx | Gw | Goo) (CCSD: | th | Q) -- 11, 16, 18 -- then Moo, W (o^4), F_ik, F_ca, G2e, F_kc, OA, OB (o^3 v), the
+// stage's Vo, C_v t1^T and an N max(o, v) scratch; nothing with three or four virtual indices.
+int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_ccsd_result *out)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
+    if (opts->max_iter < 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: max_iter must be at least 1");
+    if (opts->method != TF_CCSD_LCCSD && opts->method != TF_CCSD_QCISD && opts->method != TF_CCSD_CCSD)
+        TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: method must be 0 (LCCSD), 1 (QCISD) or 2 (CCSD)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: a sharded tensor (world > 1) is not supported");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov, BT = B2 + ov, o4 = (long long)o * o * o * o, o3v = (long long)o * o * ov, nn = (long long)N * N;
+    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL || o4 > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: dimension overflow");
+    const int level = opts->method;
+    const bool packed = ctx->layout == 1, quad = level >= 1, full = level >= 2, diis = opts->use_diis != 0;
+    const int keep = std::max(1, std::min(opts->max_diis, 32));
+    const int nslot = diis ? std::max(keep, 2) + 1 : 0;
+    out->e_corr = out->e_mp2 = out->e_singles = out->e_connected = out->e_disconnected = out->t1_norm = 0.0;
+    out->n_iter = 0; out->converged = 0; out->ladder_batches = 0;
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *g4 = nullptr, *work = nullptr, *hist = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr,
+           *d_Co = nullptr, *d_Coi = nullptr, *batch = nullptr;
+    int *d_slot = nullptr;
+    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
+    bool blas_mode_set = false;
+    auto cleanup = [&]() {
+        for (double *p : {g1, g2, g3, g4, work, hist, d_small, d_Cv, d_Cvi, d_Co, d_Coi, batch}) if (p) (void)tf_free(p);
+        if (d_slot) (void)tf_free(d_slot);
+        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
+    };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- MO blocks: tf_mp3_rhf's, and (ik|ja) = g4[i][k][j][a]
+    if ((rc = mp3_mo_blocks(ctx, "tf_ccsd_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    const auto t1s = stamp();
+    const int nblk = 1024;
+    const size_t narr = full ? 18 : (quad ? 16 : 11);
+    const int ntmp = std::max(o, v);
+    const size_t nwork = narr * (size_t)B2 + 3 * (size_t)ov + 2 * (size_t)o4 + (size_t)o * o + 2 * (size_t)v * v + (size_t)ov + 2 * (size_t)o3v +
+                         (size_t)TFL_W * N * o + (size_t)N * o + (size_t)N * ntmp;
+    const int nsum = std::max(4, nslot), npart = std::max(2, nslot);
+    const size_t nsmall = (size_t)nblk * npart + (size_t)nblk + (size_t)ov + (size_t)nsum + (size_t)npart + (size_t)N;
+    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
+    {
+        const double gb = (double)(nwork + 2 * (size_t)nslot * BT + nladder) * sizeof(double) / 1e9;
+        char text[160];
+        snprintf(text, sizeof text, "tf_ccsd_rhf: out of device memory for %.2f GB of work space (%zu arrays of o^2 v^2 values)", gb, narr + 2 * (size_t)nslot);
+        if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || (nslot && tf_malloc(&hist, 2 * (size_t)nslot * BT * sizeof(double)) != hipSuccess) ||
+            tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_Co, (size_t)N * o * sizeof(double)) != hipSuccess || tf_malloc(&d_Coi, (size_t)N * o * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_slot, (size_t)std::max(1, nslot) * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    double *t = work, *t_new = t + BT, *dt = t_new + BT, *Tn = dt + BT, *Tx = Tn + B2, *Tm = Tx + B2, *S1 = Tm + B2, *S2 = S1 + B2, *X = S2 + B2,
+           *Y = X + B2, *H = Y + B2, *A1 = g1, *A2 = H, *Gx = nullptr, *Gw = nullptr, *Goo = nullptr, *th = t, *Q = nullptr, *tail = H + B2;
+    if (quad) { A1 = tail; A2 = A1 + B2; Gx = A2 + B2; Gw = Gx + B2; Goo = Gw + B2; tail = Goo + B2; }
+    if (full) { th = tail; Q = th + B2; tail = Q + B2; }
+    double *Moo = tail, *Woo = Moo + o4, *Fik = Woo + o4, *Fca = Fik + (size_t)o * o, *G2e = Fca + (size_t)v * v, *Fkc = G2e + (size_t)v * v,
+           *OA = Fkc + ov, *OB = OA + o3v, *Vo = OB + o3v, *Bol = Vo + (size_t)TFL_W * N * o, *d_tmp = Bol + (size_t)N * o;
+    double *d_part = d_small, *d_part2 = d_part + (size_t)nblk * npart, *d_spart = d_part2 + nblk, *d_sum = d_spart + ov, *d_coef = d_sum + nsum,
+           *d_eps = d_coef + npart;
+    double *t1 = t + B2, *t1_new = t_new + B2, *dt1 = dt + B2;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(t1, 0, (size_t)ov * sizeof(double)) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+    const double *Cvl = d_Cv, *Col = d_Co;                    // in the AO order of the ladder (internal order on the packed layout)
+    if (packed) {
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
+        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * o + 255) / 256)), dim3(256), 0, 0, d_Co, ctx->bl.origI, N, o, d_Coi);
+        Cvl = d_Cvi; Col = d_Coi;
+    }
+    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
+    const dim3 grid_t((unsigned)std::min<long long>((BT + 255) / 256, 1 << 16));
+    // ---- the integral operands, the guess amplitudes and their MP2 energy (tf_ccd_rhf's kernels: e_mp2 is bit for bit tf_mp2_rhf's)
+    {
+        const long long tot = std::max(B2, o4);
+        hipLaunchKernelGGL(tfccd::cc_integral_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3,
+                           o, v, H, Moo, Gx, Gw, Goo);
+    }
+    hipLaunchKernelGGL(tfccsd::ccsd_g2e_kernel, dim3((unsigned)((v * v + 255) / 256)), dim3(256), 0, 0, H, g1, o, v, G2e);
+    hipLaunchKernelGGL(tfccd::cc_guess_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, t, d_part);
+    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
+    {
+        double e2[2];
+        if (hipMemcpy(e2, d_sum, sizeof e2, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the guess kernels failed on the device");
+        out->e_mp2 = e2[0] + e2[1];
+    }
+    (void)tf_free(g2); g2 = nullptr;                          // (ab|ij) lives on in H
+    (void)tf_free(g3); g3 = nullptr;
+    rocblas_handle blas = ctx->scf.blas;
+    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
+        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
+        blas_mode_set = true;
+    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
+    std::vector<int> order;
+    std::vector<double> Bee((size_t)std::max(1, nslot) * std::max(1, nslot), 0.0);
+    std::vector<double> h_t1((size_t)ov), Lo, Xv, Bh, Ph;
+    if (full) { Lo.resize((size_t)N * o); Xv.resize((size_t)N * v); Bh.resize((size_t)N * o); Ph.resize((size_t)nn); }
+    double E = 0.0, ladder_seconds = 0.0;
+    long long batches = 0;
+    int step = 0, code = TF_ENOTCONV;
+#define CCSD_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_ccsd_rhf: rocBLAS failed: " #call); } while (0)
+    for (step = 1; step <= opts->max_iter; ++step) {
+        const double E_old = E;
+        hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, t, o, v, Tn, Tx, Tm);
+        if (full) hipLaunchKernelGGL(tfccsd::ccsd_tau_kernel, grid_e, dim3(256), 0, 0, t, t1, o, v, th);
+        // ---- the one ladder pass of the step, on the dressed pair matrices: Y, OA, OB
+        CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, N, o, v, 1.0, Cvl, v, t1, v, 0.0, Bol, o));
+        const auto l0 = stamp();
+        if ((rc = mp3_ladder_stage(ctx, "tf_ccsd_rhf", o, v, th, Cvl, batch, Y, Col, Vo, OA, OB, Bol, &batches))) { const std::string m = ctx->err; return fail(rc, m); }
+        const auto l1 = stamp();
+        ladder_seconds += std::chrono::duration<double>(l1 - l0).count();
+        const double *W = Moo;
+        if (quad) {
+            // F_ik, F_ca as tf_ccd_rhf's, on th (CCSD: its operand goes through S1, free until the ring GEMMs)
+            const double *Tnh = Tn;
+            if (full) {
+                hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, th, o, v, S1, S2, X);
+                Tnh = S1;
+            }
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, Tnh, ovv, Gw, ovv, 0.0, Fik, o));
+            for (int k = 0; k < o; ++k)
+                CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, -1.0, Gw + (size_t)k * v * ov, iov, Tnh + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fca, v));
+            hipLaunchKernelGGL(tfccsd::ccsd_fkc_kernel, dim3((unsigned)ov), dim3(256), 0, 0, Gw, t1, iov, Fkc);
+        }
+        // ---- the fused singles update, on F_ik and F_ca as they stand (CCSD dresses them to L_ik, L_ca for the doubles below)
+        hipLaunchKernelGGL(tfccsd::ccsd_singles_kernel, dim3((unsigned)ov), dim3(256), 0, 0, level, t, th, t1, g4, OA, OB, packed ? 1 : 0, G2e, Fik, Fca, Fkc, d_eps,
+                           n_frozen, n_occ, o, v, t1_new, dt1, d_spart);
+        if (quad) {
+            if (hipMemcpyAsync(Woo, Moo, (size_t)o4 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, th, vv, Goo, vv, 1.0, Woo, oo));
+            W = Woo;
+            if (!full) {
+                if (hipMemcpyAsync(A1, g1, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                    hipMemcpyAsync(A2, H, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                    return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+            } else {
+                hipLaunchKernelGGL(tfccsd::ccsd_woo_dress_kernel, dim3((unsigned)((o4 + 255) / 256)), dim3(256), 0, 0, g4, t1, o, v, Woo);
+                // the dressed coefficients L = C_o + C_v t1^T, X = C_v - C_o t1 and the density C_v t1^T C_o^T, on the host (N o v flops)
+                if (hipMemcpy(h_t1.data(), t1, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+                for (int m = 0; m < N; ++m) {
+                    for (int i = 0; i < o; ++i) {
+                        double b = 0.0;
+                        for (int a = 0; a < v; ++a) b += Cv[(size_t)m * v + a] * h_t1[(size_t)i * v + a];
+                        Bh[(size_t)m * o + i] = b;
+                        Lo[(size_t)m * o + i] = Co[(size_t)m * o + i] + b;
+                    }
+                    for (int a = 0; a < v; ++a) {
+                        double x = 0.0;
+                        for (int k = 0; k < o; ++k) x += Co[(size_t)m * o + k] * h_t1[(size_t)k * v + a];
+                        Xv[(size_t)m * v + a] = Cv[(size_t)m * v + a] - x;
+                    }
+                }
+                for (int m = 0; m < N; ++m)
+                    for (int n = 0; n < N; ++n) {
+                        double p = 0.0;
+                        for (int k = 0; k < o; ++k) p += Bh[(size_t)m * o + k] * Co[(size_t)n * o + k];
+                        Ph[(size_t)m * N + n] = p;
+                    }
+                // W_icak's t1 part (l_i x_a|kc) -> A1, W_ciak's (l_i k|x_a c) -> A2
+                double *d_a = nullptr;
+                if ((rc = mo_transform_device(ctx, Lo.data(), o, Xv.data(), v, Co.data(), o, Cv.data(), v, &d_a, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+                const hipError_t ce = hipMemcpy(A1, d_a, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice);
+                (void)tf_free(d_a);
+                if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+                if ((rc = ccsd_vvoo_block(ctx, "tf_ccsd_rhf", Xv, Cv, Lo, Co, o, v, Q))) { const std::string m = ctx->err; return fail(rc, m); }
+                hipLaunchKernelGGL(tfccsd::ccsd_vvoo_operand_kernel, grid_e, dim3(256), 0, 0, Q, o, v, A2);
+                // M = 2 J - K of that density; L_ca = F_ca + C_v^T M C_v, L_ik = F_ik + C_o^T M C_o
+                if (hipMemcpy(ctx->d_P, Ph.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+                {
+                    const double *pp[8]; double *jj[8], *kk[8];
+                    int nonsym[8];
+                    for (int q = 0; q < 8; ++q) { pp[q] = ctx->d_P; jj[q] = ctx->d_J; kk[q] = ctx->d_K; nonsym[q] = 1; }
+                    if ((rc = launch_jk(ctx, 1, pp, jj, kk, 0, nonsym))) { const std::string m = ctx->err; return fail(rc, m); }
+                }
+                hipLaunchKernelGGL(tfccsd::ccsd_m_kernel, dim3((unsigned)std::min<long long>((nn + 255) / 256, 1 << 16)), dim3(256), 0, 0, ctx->d_J, ctx->d_K, nn);
+                CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, ctx->d_J, N, d_Cv, v, 0.0, d_tmp, v));
+                CCSD_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, N, 1.0, d_Cv, v, d_tmp, v, 1.0, Fca, v));
+                CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, N, o, N, 1.0, ctx->d_J, N, d_Co, o, 0.0, d_tmp, o));
+                CCSD_BLAS(tfmp3::gemm_rm(blas, true, false, o, o, N, 1.0, d_Co, o, d_tmp, o, 1.0, Fik, o));
+            }
+            // A1 += 1/2 Tn Gw - 1/2 Tx G;  A2 -= 1/2 Tx Gx
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 0.5, Tn, iov, Gw, iov, 1.0, A1, iov));
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, g1, iov, 1.0, A1, iov));
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, Gx, iov, 1.0, A2, iov));
+        }
+        // X[(ij)][(ab)] = 1/2 W [(ij)][(kl)] th [(kl)][(ab)]  (QCISD, CCSD: + F_ca^T t_ij - F_ik t)
+        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, W, oo, th, vv, 0.0, X, vv));
+        if (quad) {
+            CCSD_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, v, 1.0, Fca, v, 0, t, v, (long long)vv, 1.0, X, v, (long long)vv, oo));
+            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fik, o, t, ovv, 1.0, X, ovv));
+        }
+        // S1 = A1 Tm - A2 Tn;  S2 = A2 Tx
+        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A1, iov, Tm, iov, 0.0, S1, iov));
+        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, A2, iov, Tn, iov, 1.0, S1, iov));
+        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A2, iov, Tx, iov, 0.0, S2, iov));
+        // ---- the fused doubles update, then the disconnected energy of the new singles
+        hipLaunchKernelGGL(tfccsd::ccsd_update_kernel, dim3(nblk), dim3(256), 0, 0, level, g1, d_eps, n_frozen, n_occ, o, v, t, Y, packed ? 1 : 0, X, S1, S2, g4, t1,
+                           OA, OB, t_new, dt, d_part);
+        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
+        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_spart, (int)ov, 1, d_sum + 2);
+        if (full) {
+            hipLaunchKernelGGL(tfccsd::ccsd_disconnected_kernel, dim3(nblk), dim3(256), 0, 0, g1, t1_new, o, v, d_part2);
+            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part2, nblk, 1, d_sum + 3);
+        }
+        double red[4] = {0.0, 0.0, 0.0, 0.0};
+        if (hipMemcpy(red, d_sum, (full ? 4 : 3) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the iteration kernels failed on the device");
+        out->e_connected = red[0];
+        out->e_disconnected = full ? red[3] : 0.0;
+        E = out->e_singles + out->e_connected + out->e_disconnected;
+        const double dE = E - E_old, dnorm2 = std::sqrt(red[1]), dnorm1 = std::sqrt(red[2]);
+        out->e_corr = E; out->n_iter = step;
+        if (out->table) { double *row = out->table + 3 * (size_t)(step - 1); row[0] = step; row[1] = E; row[2] = dE; }
+        if (!std::isfinite(E) || !std::isfinite(dnorm2) || !std::isfinite(dnorm1) || E > 1000.0) { code = TF_ELINALG; break; }
+        if (std::fabs(dE) < opts->conv_delta_E && dnorm2 < opts->conv_amplitudes && dnorm1 < opts->conv_amplitudes) { code = TF_OK; out->converged = 1; break; }
+        if (step == opts->max_iter) break;
+        // ---- DIIS and damping over (t2, t1): tf_ccd_rhf's, on o^2 v^2 + o v elements
+        int n_ex = 0;
+        if (diis) {
+            int s = 0;
+            while (std::find(order.begin(), order.end(), s) != order.end()) ++s;
+            order.push_back(s);
+            if (hipMemcpyAsync(hist + (size_t)s * BT, t_new, (size_t)BT * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
+                hipMemcpyAsync(hist + (size_t)(nslot + s) * BT, dt, (size_t)BT * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+            if (step > 2 && (int)order.size() > keep) order.erase(order.begin());
+            const int n = (int)order.size();
+            if (hipMemcpy(d_slot, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+            hipLaunchKernelGGL(tfccd::cc_diis_dots_kernel, dim3(nblk, (unsigned)n), dim3(256), 0, 0, hist + (size_t)nslot * BT, BT, d_slot, n, n - 1, BT, d_part);
+            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, n, d_sum);
+            std::vector<double> row(n);
+            if (hipMemcpy(row.data(), d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the DIIS kernels failed on the device");
+            for (int m = 0; m < n; ++m) Bee[(size_t)order[m] * nslot + s] = Bee[(size_t)s * nslot + order[m]] = row[m];
+            if (step > 2) {
+                std::vector<double> B((size_t)n * n), coef(n);
+                for (int p = 0; p < n; ++p)
+                    for (int q = 0; q < n; ++q) B[(size_t)p * n + q] = Bee[(size_t)order[p] * nslot + order[q]];
+                if (tfccd::diis_solve(n, B.data(), coef.data())) {
+                    if (hipMemcpy(d_coef, coef.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+                    n_ex = n;
+                } else {
+                    order.clear();
+                }
+            }
+        }
+        hipLaunchKernelGGL(tfccd::cc_mix_kernel, grid_t, dim3(256), 0, 0, t, t_new, hist, BT, d_slot, d_coef, n_ex, opts->damping, BT);
+    }
+#undef CCSD_BLAS
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: a kernel launch failed");
+    if (hipMemcpy(h_t1.data(), t1_new, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        (out->t2 && hipMemcpy(out->t2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+    {
+        double s = 0.0;
+        for (long long e = 0; e < ov; ++e) s += h_t1[(size_t)e] * h_t1[(size_t)e];
+        out->t1_norm = std::sqrt(s);
+        if (out->t1) std::memcpy(out->t1, h_t1.data(), (size_t)ov * sizeof(double));
+    }
+    out->ladder_batches = batches;
+    const auto t4 = stamp();
+    cleanup();
+    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
+    out->seconds[1] = std::chrono::duration<double>(t1s - t0).count();
+    out->seconds[2] = ladder_seconds;
+    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
+    if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccsd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
+    if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccsd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
     return TF_OK;
 }
 

@@ -64,7 +64,8 @@ class Calculation:
     mp3: bool = False                                  # MP3 / SCS-MP3 after the MP2 step (tuna_mp.py:1814-1828)
     MP3_scaling: float = 1 / 4                         # MP3S / MP3SCALING / MP3SCAL, calc:183 (applied by SCS-MP3 only)
     mp4: str | None = None                             # "SDQ" or "DQ": MP4(SDQ) / MP4(DQ) after MP2 and MP3 (tuna_mp.py:1552-1685)
-    coupled_cluster: str | None = None                 # "LCCD" or "CCD" after the SCF (tuna_cc.py:830-864, :915-960)
+    coupled_cluster: str | None = None                 # "LCCD" or "CCD" after the SCF (tuna_cc.py:830-864, :915-960), or "LCCSD",
+                                                       # "QCISD", "CCSD" (:1020-1063, :1503-1557, :1638-1718; not on the input line yet)
     amp_conv: float = 1e-8                             # AMPCONV, calc:184
     correlated_max_iter: int = 100                     # CORRMAXITER, calc:191
     correlated_damping_parameter: float = 0.0          # CORRDAMP [x], calc:201 (without a number: the default, no damping)
@@ -379,7 +380,9 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(f"\n Correlation energy from {tag}MP2:  {' ' * (4 - len(tag))}" + f"{r['E_MP2']:16.10f}")
                     log(f" Correlation energy from {tag}MP3:  {' ' * (4 - len(tag))}" + f"{E_MP3:16.10f}\n")
                     log(" Total correlation energy:         " + f"{r['E_MP2'] + E_MP3:16.10f}\n")
-        if calc.coupled_cluster:
+        if calc.coupled_cluster in CCSD_METHODS:
+            run_coupled_cluster_singles_doubles(calc, molecule, out, engine, silent, log)
+        elif calc.coupled_cluster:
             run_coupled_cluster_doubles(calc, molecule, out, engine, silent, log)
         if calc.excited_state:
             run_excited_states(calc, molecule, integrals, out, engine, silent, log)
@@ -474,6 +477,49 @@ def run_coupled_cluster_doubles(calc: Calculation, molecule, out, engine: Engine
         log(f"  Connected doubles contribution:     {E_CC:13.10f}")
         log(f"  Disconnected doubles contribution:  {0.0:13.10f}")
         log(f"\n  {name} correlation energy:  {' ' * (10 - len(name))}    {E_CC:.10f}")
+        log(f" Correlation energy from {name}:{' ' * max(0, 8 - len(name))} " + f"{E_CC:16.10f}\n")
+    out.cc = r
+    out.correlation_energy_cc = E_CC
+    out.energy += E_CC
+
+
+CCSD_METHODS = ("LCCSD", "QCISD", "CCSD")
+
+
+def run_coupled_cluster_singles_doubles(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """Restricted LCCSD / QCISD / CCSD on the device-resident tensor (all-electron), tf_ccsd_rhf: the iteration of
+    calculate_coupled_cluster_energy (tuna_cc.py:2950-3175) with its log lines (tuna_cc.py:163-199, :3139, :3164-3170), the T1 lines of
+    calculate_T1_diagnostic (:670-671) and the summary line of run_coupled_cluster_doubles.  Thresholds as there."""
+    name = calc.coupled_cluster
+    conv_E = calc.SCF_conv["delta_E"]
+    t0 = time.perf_counter()
+    r = engine.ccsd_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, method=name, max_iter=calc.correlated_max_iter,
+                        conv_delta_E=conv_E, conv_amplitudes=calc.amp_conv, use_diis=calc.DIIS, max_diis=calc.max_DIIS_matrices,
+                        damping=calc.correlated_damping_parameter, allow_unconverged=True)
+    out.timings[f"{name} energy"] = time.perf_counter() - t0
+    if not silent:
+        log(f"              {name:>5} Energy and Density ")
+        log(f"  Energy convergence tolerance:        {conv_E:.10f}")
+        log(f"  Amplitude convergence tolerance:     {calc.amp_conv:.10f}")
+        log(f"\n  Guess t-amplitude MP2 energy:       {r['E_MP2']:.10f}\n")
+        if calc.correlated_damping_parameter != 0:
+            log(f"  Using damping parameter of {calc.correlated_damping_parameter:.2f} for convergence.")
+        if calc.DIIS:
+            log(f"  Using DIIS, storing {calc.max_DIIS_matrices} matrices, for convergence.")
+        log(f"\n  Starting {name} iterations...\n")
+        log("  Step          Correlation E               DE")
+        for step, E, dE in r["table"]:
+            log(f"  {step:3.0f}           {E:13.10f}         {dE:13.10f}")
+    if not r["converged"]:
+        raise TunaError(f"The {name} iterations failed to converge! Try increasing the maximum iterations with CORRMAXITER?", -4)
+    E_CC = r["E_corr"]
+    if not silent:
+        log(f"\n  Singles contribution:               {r['E_singles']:13.10f}")
+        log(f"  Connected doubles contribution:     {r['E_connected']:13.10f}")
+        log(f"  Disconnected doubles contribution:  {r['E_disconnected']:13.10f}")
+        log(f"\n  {name} correlation energy:  {' ' * (10 - len(name))}    {E_CC:.10f}")
+        log(f"\n  Norm of singles amplitudes:         {r['t1_norm']:13.10f}")
+        log(f"  Value of T1 diagnostic:             {r['T1_diagnostic']:13.10f}")
         log(f" Correlation energy from {name}:{' ' * max(0, 8 - len(name))} " + f"{E_CC:16.10f}\n")
     out.cc = r
     out.correlation_energy_cc = E_CC

@@ -325,6 +325,43 @@ class Engine:
             out["t2"] = t2
         return out
 
+    CCSD_METHODS = {"LCCSD": 0, "QCISD": 1, "CCSD": 2}    # TF_CCSD_LCCSD, TF_CCSD_QCISD, TF_CCSD_CCSD
+
+    def ccsd_rhf(self, C, eps, n_occ, n_frozen=0, method="CCSD", max_iter=100, conv_delta_E=1e-6, conv_amplitudes=1e-8, use_diis=True,
+                 max_diis=6, damping=0.0, return_t1=False, return_t2=False, allow_unconverged=False) -> dict:
+        """Restricted LCCSD, QCISD or CCSD from canonical RHF orbitals, iterated on the resident tensor (tunafock.h: tf_ccsd_rhf;
+        tuna_cc.py:1020-1063, :1503-1557, :1638-1718, :3004-3161): the dict of ccd_rhf and "E_singles", "E_connected", "E_disconnected"
+        (E_corr is their sum; the first is 0.0, the last is 0.0 unless CCSD), "t1_norm" = ||t1||_2, "T1_diagnostic" = t1_norm /
+        sqrt(2 (n_occ - n_frozen)) (tuna_cc.py:656-668), "ladder_batches", "t1" [o, v] with return_t1, "t2" [o, o, v, v] with return_t2.
+        Raises TunaError with the code when the iterations do not converge, unless allow_unconverged: the dict then holds the last step."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"ccsd_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if method not in self.CCSD_METHODS:
+            raise TunaError(f"ccsd_rhf: method must be \"LCCSD\", \"QCISD\" or \"CCSD\", got {method!r}")
+        import ctypes
+        from ._lib import CcOpts, CcsdResult
+        o, v = int(n_occ) - int(n_frozen), self.N - int(n_occ)
+        opts = CcOpts(self.CCSD_METHODS[method], int(max_iter), int(bool(use_diis)), int(max_diis), float(conv_delta_E), float(conv_amplitudes),
+                      float(damping))
+        table = np.zeros((max(1, int(max_iter)), 3))
+        t1 = np.zeros((o, v)) if return_t1 and o > 0 and v > 0 else None
+        t2 = np.zeros((o, o, v, v)) if return_t2 and o > 0 and v > 0 else None
+        res = CcsdResult()
+        res.table, res.t1, res.t2 = ptr(table), ptr(t1), ptr(t2)
+        rc = self._L.tf_ccsd_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ctypes.byref(res))
+        if rc != 0 and not (rc == -4 and allow_unconverged):     # TF_ENOTCONV
+            self._check(rc)
+        out = {"E_corr": res.e_corr, "E_MP2": res.e_mp2, "E_singles": res.e_singles, "E_connected": res.e_connected,
+               "E_disconnected": res.e_disconnected, "t1_norm": res.t1_norm,
+               "T1_diagnostic": res.t1_norm / np.sqrt(2.0 * o) if o > 0 else 0.0, "n_iter": int(res.n_iter), "converged": bool(res.converged),
+               "ladder_batches": int(res.ladder_batches), "table": table[:int(res.n_iter)].copy(), "seconds": list(res.seconds)}
+        if return_t1:
+            out["t1"] = t1
+        if return_t2:
+            out["t2"] = t2
+        return out
+
     def cis_rhf(self, C, eps, n_occ, n_frozen=0, method="CIS", singlets=True, triplets=True, n_keep=0, dip=None, return_matrices=False) -> dict:
         """Closed-shell CIS or TDHF (RPA) excited states from canonical RHF orbitals on the resident tensor (tunafock.h: tf_cis_rhf;
         tuna_ci.py:1284-1366, :1466-1518): {"dim", "E_singlet", "E_triplet" [dim] ascending (None for a multiplicity that is off),
