@@ -396,6 +396,45 @@ typedef struct {
  * TF_ENOMEM as tf_ccd_rhf; a method outside the three codes is TF_EINVAL. */
 int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_ccsd_result *out);
 
+/* ---- perturbative triples: CCSD(T), QCISD(T) (calculate_restricted_CCSD_T_energy, tuna_cc.py:2688-2758) and the triples of full MP4
+ * (run_restricted_MP4, tuna_mp.py:403-428 and :1605-1637) ---- */
+
+#define TF_TRIPLES_CCSD_T  0
+#define TF_TRIPLES_QCISD_T 1
+#define TF_TRIPLES_MP4     2      /* t1 and t2 must be NULL: t2 = (ia|jb)/D is made inside, V = 0 */
+
+typedef struct {
+    double e_t;               /* e_connected + e_disconnected */
+    double e_connected;       /* the W·Y part ("[T]") */
+    double e_disconnected;    /* the V·Y part; exactly 0.0 for TF_TRIPLES_MP4 */
+    int64_t n_triples;        /* unordered triples i >= j >= k sent through the kernels (i = j = k skipped) */
+    double *e_ijk;            /* [o,o,o] caller-allocated, may be NULL: every ordered triple filled, e_iii exactly 0.0 */
+    double seconds[4];        /* wall, MO blocks incl. (ia|bc), the triples loop, the rest */
+} tf_triples_result;
+
+/* The non-iterative triples energy of a closed shell from canonical RHF orbitals and (kinds 0 and 1) converged amplitudes t1 [o,v] and
+ * t2 [o,o,v,v] as tf_ccsd_rhf returns them; windows as tf_ccsd_rhf.  In chemists' integrals
+ *     X_ijk^abc = sum_f (ia|bf) t2[k,j,c,f] - sum_m (ia|jm) t2[m,k,b,c],   W = the sum of X over the six simultaneous permutations of the
+ *     columns (i a), (j b), (k c),   V_ijk^abc = s [(jb|kc) t1[i,a] + (ia|kc) t1[j,b] + (ia|jb) t1[k,c]]  (s = 1, 2; V = 0 for MP4),
+ *     e_ijk = 1/3 sum_abc (W + V)^abc (4 W^abc + W^bca + W^cab - 2 W^cba - 2 W^acb - 2 W^bac) / (e_i + e_j + e_k - e_a - e_b - e_c),
+ * E_T = the sum of e_ijk over all ordered triples.  e_ijk is the average over the six orderings of the reference's per-triple term: it
+ * is symmetric in (i, j, k) (every value is computed once and scattered), the total is the reference's.  t2 need not be symmetric under
+ * (ij)(ab); only the equality of kind 2 with the reference's MP4 triples rests on that symmetry, which first-order amplitudes have.
+ * Data: (ia|bc) as [i][a][b][c], o v^3 values resident on the device (8.0 GB at N = 400, o = 18), made through the AO->MO transformation
+ * in slabs of occupied orbitals and slices of b sized from the free memory; TF_TRIPLES_SLAB=n and TF_TRIPLES_SLICE=n (read per call) allow
+ * at most n occupied orbitals per slab and n values of b per slice.  Per unordered triple i >= j >= k (i = j = k skipped: n_triples = o (o + 1) (o + 2) / 6 - o) twelve rocBLAS GEMMs write
+ * the six X_pqr of its orderings as [a][b][c], and one fused kernel over unordered triples of 8^3 tiles of (a, b, c) forms W at the six
+ * permuted tile positions in LDS (28 KB), applies V and D and leaves one pair of partial sums per workgroup: W never reaches HBM.
+ * Partials are summed in block order with a fixed association, triples in loop order with their number of distinct orderings (6 or 3):
+ * two identical calls give bit-identical results.  seconds: [0] wall, [1] MO blocks incl. (ia|bc), [2] the triples loop, [3] the rest.
+ * Measured on one MI355X, warm, o = 18: N = 200 1.0 s (0.83 ms per triple: the GEMMs 0.72, the fused kernel 0.12 = 2.5 TB/s of reads);
+ * N = 400 19 - 21 s = (ia|bc) and the other blocks 7 - 13 s + the loop 7.8 - 7.9 s (7.0 ms per triple, not split further).  Against an independent NumPy loop the
+ * largest |d| / S seen is 1.7e-15 at N2/cc-pVTZ (S = the sum of magnitudes of a triple's terms), against the reference program 9e-17 Eh.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL C, eps or out, unless 0 <= n_frozen < n_occ < N, on a kind outside the
+ * three, with world > 1, on a NULL t1 or t2 for kinds 0 and 1 and on a non-NULL t1 or t2 for kind 2.  TF_ENOMEM with the size in the message. */
+int tf_triples_rhf(tf_ctx *ctx, int kind, int n_occ, int n_frozen, const double *C, const double *eps, const double *t1 /* [o,v] */,
+                   const double *t2 /* [o,o,v,v] */, tf_triples_result *out);
+
 /* ---- excited states: replaces calculate_restricted_single_reference_excited_states and calculate_restricted_transition_dipoles
  * (tuna_ci.py:1284-1366, :1466-1518) for closed-shell CIS and TDHF (RPA) ---- */
 

@@ -39,6 +39,7 @@
 #include "tf_ccsd.hip.h"
 #include "tf_cis.hip.h"
 #include "tf_mp4.hip.h"
+#include "tf_triples.hip.h"
 #include "tf_dft.hip.h"
 
 // ---- small-block cache for THIS file's device allocations ------------------------------------------------------------------------
@@ -4618,6 +4619,190 @@ int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, co
     out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
     if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccsd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
     if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccsd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
+    return TF_OK;
+}
+
+// The perturbative triples of CCSD(T), QCISD(T) and full MP4 (tuna_cc.py:2688-2758, tuna_mp.py:403-428 and :1605-1637; tf_triples.hip.h has
+// the expressions and the fused kernel).  Stages: the blocks (ia|jb) and (ki|ld) as tf_ccsd_rhf makes them; (ia|bc) = [i][a][b][c], resident,
+// filled in slabs of occupied orbitals (TF_TRIPLES_SLAB bounds them) and slices of b (TF_TRIPLES_SLICE), both sized from the free memory: the transformation
+// holds N^2 values per element of its ket pair; then per unordered triple i >= j >= k (i = j = k skipped) twelve rocBLAS GEMMs write the
+// six X_pqr, one launch of triples_energy_kernel and one of triples_sum_partials_kernel leave two sums per triple on the device.  The host
+// reads them once after the loop and adds them in loop order with the number of distinct orderings of each triple.
+int tf_triples_rhf(tf_ctx *ctx, int kind, int n_occ, int n_frozen, const double *C, const double *eps, const double *t1, const double *t2,
+                   tf_triples_result *out)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: call tf_build_eri first");
+    const int N = ctx->N;
+    if (!C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
+        TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: bad arguments (needs C, eps, out and 0 <= n_frozen < n_occ < N)");
+    if (kind != TF_TRIPLES_CCSD_T && kind != TF_TRIPLES_QCISD_T && kind != TF_TRIPLES_MP4)
+        TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: kind must be 0 (CCSD(T)), 1 (QCISD(T)) or 2 (MP4)");
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: a sharded tensor (world > 1) is not supported");
+    if (kind == TF_TRIPLES_MP4 && (t1 || t2)) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: MP4 makes its own amplitudes: t1 and t2 must be NULL");
+    if (kind != TF_TRIPLES_MP4 && (!t1 || !t2)) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: CCSD(T) and QCISD(T) need t1 and t2");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    const int o = n_occ - n_frozen, v = N - n_occ;
+    const long long ov = (long long)o * v, B2 = ov * ov;
+    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: dimension overflow");
+    const size_t v2 = (size_t)v * v, v3 = v2 * v, o3 = (size_t)o * o * o;
+    const long long n_triples = (long long)o * (o + 1) * (o + 2) / 6 - o;
+    out->e_t = out->e_connected = out->e_disconnected = 0.0;
+    out->n_triples = n_triples;
+    for (int q = 0; q < 4; ++q) out->seconds[q] = 0.0;
+    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
+    for (int m = 0; m < N; ++m) {
+        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
+        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
+    }
+    double *g1 = nullptr, *g4 = nullptr, *gv = nullptr, *X = nullptr, *d_t2 = nullptr, *d_small = nullptr;
+    int *d_tiles = nullptr;
+    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
+    bool blas_mode_set = false;
+    auto cleanup = [&]() {
+        for (double *p : {g1, g4, gv, X, d_t2, d_small}) if (p) (void)tf_free(p);
+        if (d_tiles) (void)tf_free(d_tiles);
+        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
+    };
+    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
+    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
+    // ---- the resident arrays: (ia|bc), the six X, t2; small: partials [2 n_blocks] | per-triple sums [2 n_triples] | eps [N] | t1 [ov]
+    const int nt = (v + tftriples::TT - 1) / tftriples::TT;
+    const long long n_blocks = (long long)nt * (nt + 1) * (nt + 2) / 6;
+    const size_t nsmall = 2 * (size_t)n_blocks + 2 * (size_t)std::max<long long>(1, n_triples) + (size_t)N + (size_t)ov;
+    {
+        char text[200];
+        snprintf(text, sizeof text, "tf_triples_rhf: out of device memory for %.2f GB of work space ((ia|bc): o v^3 values, six arrays of v^3 and t2)",
+                 (double)((size_t)o * v3 + 6 * v3 + (size_t)B2 + nsmall) * sizeof(double) / 1e9);
+        if (tf_malloc(&gv, (size_t)o * v3 * sizeof(double)) != hipSuccess || tf_malloc(&X, 6 * v3 * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_t2, (size_t)B2 * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
+            tf_malloc(&d_tiles, (size_t)3 * n_blocks * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    double *d_part = d_small, *d_e = d_part + 2 * (size_t)n_blocks, *d_eps = d_e + 2 * (size_t)std::max<long long>(1, n_triples), *d_t1 = d_eps + N;
+    // ---- MO blocks: (ia|jb) = g1[i][a][j][b], (ki|ld) = g4[k][i][l][d], (ia|bc) = gv[i][a][b][c]
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, &g1, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+    {
+        // the transformation's scratch is about 1.5 N^2 values per element of the ket pair, for both images of a packed tensor: (slab, v) and
+        // (slice of b, v).  A quarter of the free memory, 32 GB at the most, bounds either.
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: hipMemGetInfo failed");
+        const size_t budget = std::min<size_t>((free_b + tfcache::cached()) / 4, (size_t)32 << 30);
+        const long long cap = std::max<long long>(1, (long long)(budget / ((size_t)12 * N * N * v)));
+        long long slab = std::min<long long>(o, cap);
+        if (const char *env = getenv("TF_TRIPLES_SLAB")) { const long long n = atoll(env); if (n >= 1) slab = std::min(slab, n); }
+        long long slice = std::min<long long>(v, cap);
+        if (const char *env = getenv("TF_TRIPLES_SLICE")) { const long long n = atoll(env); if (n >= 1) slice = std::min(slice, n); }
+        const int nb_max = (int)slice;
+        std::vector<double> Cos((size_t)N * slab), Cs((size_t)N * nb_max);
+        for (int i0 = 0; i0 < o; i0 += (int)slab) {
+            const int ns = (int)std::min<long long>(slab, o - i0);
+            for (int m = 0; m < N; ++m)
+                for (int i = 0; i < ns; ++i) Cos[(size_t)m * ns + i] = Co[(size_t)m * o + i0 + i];
+            for (int b0 = 0; b0 < v; b0 += nb_max) {
+                const int nb = std::min(nb_max, v - b0);
+                for (int m = 0; m < N; ++m)
+                    for (int b = 0; b < nb; ++b) Cs[(size_t)m * nb + b] = Cv[(size_t)m * v + b0 + b];
+                double *d_s = nullptr;
+                if ((rc = mo_transform_device(ctx, Cos.data(), ns, Cv.data(), v, Cs.data(), nb, Cv.data(), v, &d_s, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
+                // [is][a][b'][c] -> gv[i0 + is][a][b0 + b'][c]: ns v rows of nb v values, v^2 apart
+                const hipError_t ce = hipMemcpy2D(gv + (size_t)i0 * v3 + (size_t)b0 * v, v2 * sizeof(double), d_s, (size_t)nb * v * sizeof(double),
+                                                  (size_t)nb * v * sizeof(double), (size_t)ns * v, hipMemcpyDeviceToDevice);
+                (void)tf_free(d_s);
+                if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
+            }
+        }
+    }
+    const auto t1s = stamp();
+    // ---- amplitudes, orbital energies, the tile triples t0 <= t1 <= t2
+    {
+        std::vector<int> tiles((size_t)3 * n_blocks);
+        size_t n = 0;
+        for (int a = 0; a < nt; ++a)
+            for (int b = a; b < nt; ++b)
+                for (int c = b; c < nt; ++c) { tiles[n++] = a; tiles[n++] = b; tiles[n++] = c; }
+        if (hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
+    }
+    if (kind == TF_TRIPLES_MP4) {
+        hipLaunchKernelGGL(tftriples::triples_mp2_amplitudes_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, d_eps,
+                           n_frozen, n_occ, o, v, d_t2);
+    } else if (hipMemcpy(d_t2, t2, (size_t)B2 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(d_t1, t1, (size_t)ov * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
+    // ---- the loop over unordered triples.  Split-K GEMM kernels would change their sums from run to run
+    rocblas_handle blas = ctx->scf.blas;
+    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
+        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
+        blas_mode_set = true;
+    static const int P3[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};    // tftriples::perm3
+    const auto t2s = stamp();
+#define TRIPLES_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_triples_rhf: rocBLAS failed: " #call); } while (0)
+    {
+        tftriples::EnergyArgs A{};
+        for (int n = 0; n < 6; ++n) A.X[n] = X + (size_t)n * v3;
+        A.tiles = d_tiles; A.g1 = g1; A.t1 = d_t1; A.eps = d_eps;
+        A.vscale = kind == TF_TRIPLES_CCSD_T ? 1.0 : (kind == TF_TRIPLES_QCISD_T ? 2.0 : 0.0);
+        A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v; A.partial = d_part;
+        long long t = 0;
+        for (int i = 0; i < o; ++i)
+            for (int j = 0; j <= i; ++j)
+                for (int k = 0; k <= j; ++k) {
+                    if (i == k) continue;
+                    const int occ[3] = {i, j, k};
+                    for (int n = 0; n < 6; ++n) {
+                        const int p = occ[P3[n][0]], q = occ[P3[n][1]], r = occ[P3[n][2]];
+                        double *Xn = X + (size_t)n * v3;
+                        // X[(ab)][c] = (pa|b.) [v^2 x v] t2[r,q]^T;  X[a][(bc)] -= (pa|q.) [v x o] t2[.,r] [o x v^2]
+                        TRIPLES_BLAS(tfmp3::gemm_rm(blas, false, true, (int)v2, v, v, 1.0, gv + (size_t)p * v3, v, d_t2 + ((size_t)r * o + q) * v2, v, 0.0, Xn, v));
+                        TRIPLES_BLAS(tfmp3::gemm_rm(blas, true, false, v, (int)v2, o, -1.0, g4 + ((size_t)q * o * o + p) * v, (int)ov, d_t2 + (size_t)r * v2,
+                                                    (int)((size_t)o * v2), 1.0, Xn, (int)v2));
+                    }
+                    A.i = i; A.j = j; A.k = k;
+                    hipLaunchKernelGGL(tftriples::triples_energy_kernel, dim3((unsigned)n_blocks), dim3(tftriples::THREADS), 0, 0, A);
+                    hipLaunchKernelGGL(tftriples::triples_sum_partials_kernel, dim3(1), dim3(tftriples::THREADS), 0, 0, d_part, (int)n_blocks, d_e + 2 * t);
+                    ++t;
+                }
+    }
+#undef TRIPLES_BLAS
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: a kernel launch failed");
+    std::vector<double> e2(2 * (size_t)std::max<long long>(1, n_triples), 0.0);
+    if (n_triples > 0 && hipMemcpy(e2.data(), d_e, 2 * (size_t)n_triples * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_triples_rhf: the triples kernels failed on the device");
+    const auto t3s = stamp();
+    if (out->e_ijk) std::fill(out->e_ijk, out->e_ijk + o3, 0.0);
+    {
+        double ec = 0.0, ed = 0.0;
+        long long t = 0;
+        for (int i = 0; i < o; ++i)
+            for (int j = 0; j <= i; ++j)
+                for (int k = 0; k <= j; ++k) {
+                    if (i == k) continue;
+                    const double c = e2[2 * t] / 3.0, d = e2[2 * t + 1] / 3.0, w = (i == j || j == k) ? 3.0 : 6.0;
+                    ec += w * c; ed += w * d;
+                    if (out->e_ijk) {
+                        const int occ[3] = {i, j, k};
+                        for (int n = 0; n < 6; ++n)
+                            out->e_ijk[((size_t)occ[P3[n][0]] * o + occ[P3[n][1]]) * o + occ[P3[n][2]]] = c + d;
+                    }
+                    ++t;
+                }
+        out->e_connected = ec; out->e_disconnected = ed; out->e_t = ec + ed;
+    }
+    cleanup();
+    const auto t4 = std::chrono::steady_clock::now();
+    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
+    out->seconds[1] = std::chrono::duration<double>(t1s - t0).count();
+    out->seconds[2] = std::chrono::duration<double>(t3s - t2s).count();
+    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
     return TF_OK;
 }
 

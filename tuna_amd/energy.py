@@ -8,7 +8,7 @@ Input line format `TYPE : A B R : METHOD BASIS : KEYWORDS` (tuna.py:87-99).  Sup
 with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tuna_amd/data, and the SCF keywords of SURVEY.md section 5
 (LOOSE/MEDIUM/TIGHT/EXTREME, MAXITER n, DIIS [n]/NODIIS, DAMP x/NODAMP/MAXDAMP x, SLOWCONV/VERYSLOWCONV, HFX x,
 CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, MP4(SDQ) / MP4(DQ) (also written
-MP4[SDQ] / MP4[DQ]; full MP4 with triples is not available), and the coupled-cluster doubles
+MP4[SDQ] / MP4[DQ]; full MP4 with triples through Calculation.mp4 = "SDTQ", not on the input line), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
 iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, or TD on an HF line
 (TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x).  Everything numerical runs on the GPU through the C ABI.  The initial
@@ -63,9 +63,11 @@ class Calculation:
     opposite_spin_scaling: float = 6 / 5               # OSS, calc:209
     mp3: bool = False                                  # MP3 / SCS-MP3 after the MP2 step (tuna_mp.py:1814-1828)
     MP3_scaling: float = 1 / 4                         # MP3S / MP3SCALING / MP3SCAL, calc:183 (applied by SCS-MP3 only)
-    mp4: str | None = None                             # "SDQ" or "DQ": MP4(SDQ) / MP4(DQ) after MP2 and MP3 (tuna_mp.py:1552-1685)
+    mp4: str | None = None                             # "SDQ" or "DQ": MP4(SDQ) / MP4(DQ) after MP2 and MP3 (tuna_mp.py:1552-1685);
+                                                       # "SDTQ": full MP4 with the triples (not on the input line yet)
     coupled_cluster: str | None = None                 # "LCCD" or "CCD" after the SCF (tuna_cc.py:830-864, :915-960), or "LCCSD",
                                                        # "QCISD", "CCSD" (:1020-1063, :1503-1557, :1638-1718; not on the input line yet)
+    triples: bool = False                              # the perturbative triples after CCSD or QCISD: CCSD(T), QCISD(T) (tuna_cc.py:2688-2758)
     amp_conv: float = 1e-8                             # AMPCONV, calc:184
     correlated_max_iter: int = 100                     # CORRMAXITER, calc:191
     correlated_damping_parameter: float = 0.0          # CORRDAMP [x], calc:201 (without a number: the default, no damping)
@@ -296,6 +298,8 @@ def build_molecule_and_integrals(symbols, R_bohr, calc: Calculation, engine: Eng
 
 
 def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None = None, silent=True, log=print):
+    if calc.triples and calc.coupled_cluster not in ("CCSD", "QCISD"):
+        raise TunaError(f"Perturbative triples follow CCSD or QCISD only, not {calc.coupled_cluster or calc.method}!")
     own = engine is None
     engine = engine or Engine(0)
     try:
@@ -382,6 +386,8 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(" Total correlation energy:         " + f"{r['E_MP2'] + E_MP3:16.10f}\n")
         if calc.coupled_cluster in CCSD_METHODS:
             run_coupled_cluster_singles_doubles(calc, molecule, out, engine, silent, log)
+            if calc.triples:
+                run_perturbative_triples(calc, molecule, out, engine, silent, log)
         elif calc.coupled_cluster:
             run_coupled_cluster_doubles(calc, molecule, out, engine, silent, log)
         if calc.excited_state:
@@ -413,11 +419,17 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
 def run_restricted_mp4(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
     """Restricted MP4(SDQ) / MP4(DQ) on the device-resident tensor (all-electron), tf_mp4_rhf, which returns the MP2 and MP3 parts of the
     same orbitals as well: the log lines of run_restricted_MP2 (tuna_mp.py:904-906), run_restricted_MP3 (:1472), run_restricted_MP4
-    (:1576-1682) and the summary of tuna_kernel.py:1245-1262.  Nothing is scaled: out.energy = E_SCF + E_MP2 + E_MP3 + E_MP4."""
+    (:1576-1682) and the summary of tuna_kernel.py:1245-1262.  Nothing is scaled: out.energy = E_SCF + E_MP2 + E_MP3 + E_MP4.
+    Level "SDTQ" is full MP4: tf_mp4_rhf at level SDQ, then the triples of tf_triples_rhf (kind MP4), E_MP4 = E_S + E_D + E_T + E_Q."""
     level = calc.mp4
+    full = level == "SDTQ"
     t0 = time.perf_counter()
-    r = engine.mp4_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, level=level)
-    out.timings[f"MP4({level}) energy"] = time.perf_counter() - t0
+    r = engine.mp4_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, level="SDQ" if full else level)
+    if full:
+        out.triples = engine.triples_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, kind="MP4")
+        out.correlation_energy_triples = out.triples["E_T"]
+        r = dict(r, E_T=out.triples["E_T"], E_MP4=r["E_S"] + r["E_D"] + out.triples["E_T"] + r["E_Q"])
+    out.timings["MP4 energy" if full else f"MP4({level}) energy"] = time.perf_counter() - t0
     E_MP2, E_MP3, E_MP4 = r["E_MP2"], r["E_MP3"], r["E_MP4"]
     if not silent:
         log(f"\n  Same spin contribution:             {r['E_SS']:13.10f}")              # mp:904-906
@@ -425,18 +437,23 @@ def run_restricted_mp4(calc: Calculation, molecule, out, engine: Engine, silent=
         log(f"\n  MP2 correlation energy:             {E_MP2:13.10f}")
         log(f"\n  MP3 correlation energy:             {E_MP3:13.10f}")                  # mp:1472
         log("                      MP4 Energy  ")                                       # mp:1577
-        if level == "SDQ":                                                              # mp:1665-1671
+        if level == "SDQ":                                                              # mp:1665-1675
             log("  Triples are not included in MP4(SDQ).\n")
+        elif full:
+            log("  Triples are included in full MP4.\n")
         else:
             log("  Singles and triples are not included in MP4(DQ).\n")
         log(f"  Singles correlation energy:         {r['E_S']:13.10f}")                 # mp:1677-1682
         log(f"  Doubles correlation energy:         {r['E_D']:13.10f}")
-        log(f"  Triples correlation energy:         {0.0:13.10f}")
+        log(f"  Triples correlation energy:         {r['E_T'] if full else 0.0:13.10f}")
         log(f"  Quadruples correlation energy:      {r['E_Q']:13.10f}")
         log(f"\n  MP4 correlation energy:             {E_MP4:13.10f}")
         log("\n Correlation energy from MP2:      " + f"{E_MP2:16.10f}")                # kernel:1247-1262
         log(" Correlation energy from MP3:      " + f"{E_MP3:16.10f}")
-        log(f" Correlation energy from MP4({level}):{' ' * (4 - len(level))}" + f"{E_MP4:16.10f}\n")
+        if full:
+            log(" Correlation energy from MP4:      " + f"{E_MP4:16.10f}\n")
+        else:
+            log(f" Correlation energy from MP4({level}):{' ' * (4 - len(level))}" + f"{E_MP4:16.10f}\n")
         log(" Total correlation energy:         " + f"{E_MP2 + E_MP3 + E_MP4:16.10f}\n")
     out.mp2 = {k: r[k] for k in ("E_OS", "E_SS", "E_MP2", "seconds")}
     out.mp3 = dict({k: r[k] for k in ("E_OS", "E_SS", "E_MP2", "E_pp", "E_hh", "E_ring", "E_MP3", "seconds")}, E_MP3_scaled=E_MP3)
@@ -489,13 +506,15 @@ CCSD_METHODS = ("LCCSD", "QCISD", "CCSD")
 def run_coupled_cluster_singles_doubles(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
     """Restricted LCCSD / QCISD / CCSD on the device-resident tensor (all-electron), tf_ccsd_rhf: the iteration of
     calculate_coupled_cluster_energy (tuna_cc.py:2950-3175) with its log lines (tuna_cc.py:163-199, :3139, :3164-3170), the T1 lines of
-    calculate_T1_diagnostic (:670-671) and the summary line of run_coupled_cluster_doubles.  Thresholds as there."""
+    calculate_T1_diagnostic (:670-671) and the summary line of run_coupled_cluster_doubles.  Thresholds as there.  With calc.triples the
+    converged amplitudes come back as well, for run_perturbative_triples."""
     name = calc.coupled_cluster
     conv_E = calc.SCF_conv["delta_E"]
     t0 = time.perf_counter()
+    amplitudes = dict(return_t1=True, return_t2=True) if calc.triples else {}
     r = engine.ccsd_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, method=name, max_iter=calc.correlated_max_iter,
                         conv_delta_E=conv_E, conv_amplitudes=calc.amp_conv, use_diis=calc.DIIS, max_diis=calc.max_DIIS_matrices,
-                        damping=calc.correlated_damping_parameter, allow_unconverged=True)
+                        damping=calc.correlated_damping_parameter, allow_unconverged=True, **amplitudes)
     out.timings[f"{name} energy"] = time.perf_counter() - t0
     if not silent:
         log(f"              {name:>5} Energy and Density ")
@@ -524,6 +543,32 @@ def run_coupled_cluster_singles_doubles(calc: Calculation, molecule, out, engine
     out.cc = r
     out.correlation_energy_cc = E_CC
     out.energy += E_CC
+
+
+def run_perturbative_triples(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """CCSD(T) / QCISD(T) after run_coupled_cluster_singles_doubles (all-electron), tf_triples_rhf on the converged amplitudes of out.cc:
+    the section of calculate_restricted_CCSD_T_energy (tuna_cc.py:2713-2756; QCISD(T) prints one space less, as there) and the summary
+    lines of tuna_kernel.py:1276-1278.  The line " Correlation energy from CCSD:" of the singles-doubles step stays where that step prints
+    it, in front of this section; the summary repeats it in the reference's format.  out.energy grows by E_T."""
+    name = f"{calc.coupled_cluster}(T)"
+    t0 = time.perf_counter()
+    r = engine.triples_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, kind=name, t1=out.cc["t1"], t2=out.cc["t2"])
+    out.timings[f"{name} energy"] = time.perf_counter() - t0
+    E_CC, E_T = out.correlation_energy_cc, r["E_T"]
+    if not silent:
+        space = "" if "QCISD" in name else " "                                          # cc:2733-2740
+        log(f"                    {name} Energy ")                                       # cc:2714
+        log("  Forming disconnected amplitudes...         [Done]")                      # cc:2725, :2742
+        log("  Forming connected amplitudes...            [Done]")                      # cc:2744, :2750
+        log(f"\n  Calculating {name} correlation energy... {space}[Done]\n")           # cc:2752, :2756
+        log(f"  {name} correlation energy:       {space} {E_T:13.10f}")
+        space = " " * max(0, 8 - len(name))                                             # kernel:1272-1278
+        log(f" Correlation energy from {calc.coupled_cluster}:{space}    {E_CC:16.10f}")
+        log(f" Correlation energy from {name}: {space}{E_T:16.10f}\n")
+        log(f" Total correlation energy: {space}       {E_CC + E_T:16.10f}\n")
+    out.triples = r
+    out.correlation_energy_triples = E_T
+    out.energy += E_T
 
 
 _HARTREE_IN_JOULES = (mol._hbar ** 2) / (mol._me * mol.BOHR_IN_METRES ** 2)                       # tuna_util.py:53

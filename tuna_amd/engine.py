@@ -362,6 +362,39 @@ class Engine:
             out["t2"] = t2
         return out
 
+    TRIPLES_KINDS = {"CCSD(T)": 0, "QCISD(T)": 1, "MP4": 2}    # TF_TRIPLES_CCSD_T, TF_TRIPLES_QCISD_T, TF_TRIPLES_MP4
+
+    def triples_rhf(self, C, eps, n_occ, n_frozen=0, kind="CCSD(T)", t1=None, t2=None, return_e_ijk=False) -> dict:
+        """The perturbative triples of CCSD(T), QCISD(T) (with the converged t1 [o, v] and t2 [o, o, v, v] of ccsd_rhf) or of full MP4
+        (kind "MP4": no amplitudes, t2 = (ia|jb) / D is made inside) from canonical RHF orbitals on the resident tensor (tunafock.h:
+        tf_triples_rhf; tuna_cc.py:2688-2758, tuna_mp.py:403-428 and :1605-1637): {"E_T" = "E_connected" + "E_disconnected" (the last
+        exactly 0.0 for MP4), "n_triples" = unordered triples sent through the kernels, "e_ijk" [o, o, o] with return_e_ijk (None
+        otherwise; symmetric under permutations, E_T is its sum), "seconds" = [wall, MO blocks, triples loop, rest]}."""
+        C, eps = f64(C), f64(eps)
+        if kind not in self.TRIPLES_KINDS:
+            raise TunaError(f"triples_rhf: kind must be \"CCSD(T)\", \"QCISD(T)\" or \"MP4\", got {kind!r}")
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"triples_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
+        if kind == "MP4":
+            if t1 is not None or t2 is not None:
+                raise TunaError("triples_rhf: kind \"MP4\" makes its own amplitudes: t1 and t2 must be None")
+        else:
+            if t1 is None or t2 is None:
+                raise TunaError(f"triples_rhf: kind {kind!r} needs the amplitudes t1 [{o}, {v}] and t2 [{o}, {o}, {v}, {v}]")
+            t1, t2 = f64(t1), f64(t2)
+            if t1.shape != (o, v) or t2.shape != (o, o, v, v):
+                raise TunaError(f"triples_rhf: amplitudes must be t1 [{o}, {v}] and t2 [{o}, {o}, {v}, {v}], got {t1.shape} and {t2.shape}")
+        import ctypes
+        from ._lib import TriplesResult
+        e_ijk = np.zeros((o, o, o)) if return_e_ijk and o > 0 else None
+        res = TriplesResult()
+        res.e_ijk = ptr(e_ijk)
+        self._check(self._L.tf_triples_rhf(self._ctx, self.TRIPLES_KINDS[kind], int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(t1), ptr(t2),
+                                           ctypes.byref(res)))
+        return {"E_T": res.e_t, "E_connected": res.e_connected, "E_disconnected": res.e_disconnected, "n_triples": int(res.n_triples),
+                "e_ijk": e_ijk, "seconds": list(res.seconds)}
+
     def cis_rhf(self, C, eps, n_occ, n_frozen=0, method="CIS", singlets=True, triplets=True, n_keep=0, dip=None, return_matrices=False) -> dict:
         """Closed-shell CIS or TDHF (RPA) excited states from canonical RHF orbitals on the resident tensor (tunafock.h: tf_cis_rhf;
         tuna_ci.py:1284-1366, :1466-1518): {"dim", "E_singlet", "E_triplet" [dim] ascending (None for a multiplicity that is off),
