@@ -124,6 +124,37 @@ def test_fixed_steps_against_the_independent_checker(engine, n2_tz, width):
     assert not bad, bad
 
 
+def test_small_diis_depths(engine, mp3_golden):
+    """N2/cc-pVDZ (N = 28, o = 7, v = 21), golden orbitals, packed layout: ten fixed steps with damping 0.2 at max_diis 1, 2 and 3, where
+    the history drops a vector in every step from the third on (the fixed-step loops above never drop one, the golden runs keep six).
+    Against the checker's own loop at the same depth, element by element, with the tolerances of the test above; and the runs at depth 1
+    and 2 are the same loop (two vectors kept, one leaving per step), so they agree bit for bit.  The checker's two forms
+    (restricted_iterations, iterations_from_blocks) agree to 4e-15 in t and 4e-16 in E over these ten steps, max|t| = 0.076."""
+    m = mp3_golden["n2_ccpvdz"]
+    shells, aos = _system("n2_ccpvdz")
+    E = mr.dense_eri(aos, shells)
+    engine.set_basis(aos).build_eri(True)
+    assert engine.eri_storage()["layout"] == "packed"
+    bad = []
+    for method in METHODS:
+        runs = {}
+        for depth in (1, 2, 3):
+            r = engine.ccd_rhf(m["C"], m["eps"], 7, 0, method=method, max_iter=10, conv_delta_E=0.0, conv_amplitudes=0.0, return_t2=True,
+                               allow_unconverged=True, use_diis=True, max_diis=depth, damping=0.2)
+            ref = cr.restricted_iterations(E, m["C"], m["eps"], 7, 0, method, 10, diis=True, max_diis=depth, damping=0.2)
+            scale = np.abs(ref["t"]).max()
+            dt = np.abs(r["t2"] - ref["t"]).max() / scale
+            dE = np.abs(r["table"][:, 1] - np.array(ref["energies"])) / np.abs(ref["energies"])
+            print(f"\n[{method}, max_diis {depth}] max|t| {scale:.3f} max|dt|/max|t| {dt:.1e} rel dE per step {dE}")
+            assert scale < 1.0 and r["n_iter"] == 10 and not r["converged"]
+            if not (dt <= 1e-10 and np.all(dE <= 1e-11)):
+                bad.append((method, depth, dt, dE))
+            runs[depth] = r
+        assert np.array_equal(runs[1]["t2"], runs[2]["t2"]) and np.array_equal(runs[1]["table"], runs[2]["table"]), method
+        assert not np.array_equal(runs[2]["t2"], runs[3]["t2"]), method      # (the depth does reach the loop)
+    assert not bad, bad
+
+
 def test_layouts_agree(engine, mp3_golden, n2_tz):
     m = mp3_golden["n2_ccpvtz"]
     try:

@@ -138,6 +138,46 @@ def test_fixed_steps_against_the_independent_checker(engine, n2_tz, width):
     assert not bad, bad
 
 
+def test_small_diis_depths(engine, mp3_golden):
+    """tests/test_gpu_ccd.py's test of the same name for LCCSD and CCSD: N2/cc-pVDZ, golden orbitals, packed layout, ten fixed steps with
+    damping 0.2 at max_diis 1, 2 and 3 (a vector leaves the history in every step from the third on), t1 and t2 element by element against
+    the checker's loop at the same depth; depths 1 and 2 bit for bit.  At these settings the checker's two closed-shell forms
+    (restricted_iterations, iterations_from_blocks) agree over the ten steps to 3.5e-15 in t2 / max|t2|, 5.0e-15 in t1 / max|t1| and
+    3.7e-16 in E (max|t2| = 0.079, max|t1| = 0.023), so the tolerances are five orders above the checker's own noise.  (Its spin-orbital
+    form is no yardstick here: with DIIS on, its error dots run over the spin-orbital amplitudes, another metric, and its path leaves
+    the closed-shell one at the first extrapolation.)"""
+    m = mp3_golden["n2_ccpvdz"]
+    shells, aos = _system("n2_ccpvdz")
+    E = mr.dense_eri(aos, shells)
+    engine.set_basis(aos).build_eri(True)
+    assert engine.eri_storage()["layout"] == "packed"
+    C, eps = m["C"], m["eps"]
+    Co, Cv, eo, ev = mr._windows(C, eps, 7, 0)
+    blocks = (mr.mo_tensor(E, Co, Cv, Co, Cv), mr.mo_tensor(E, Co, Co, Cv, Cv), mr.mo_tensor(E, Co, Co, Co, Co), mr.mo_tensor(E, Co, Co, Co, Cv),
+              mr.mo_tensor(E, Co, Cv, Cv, Cv), mr.mo_tensor(E, Cv, Cv, Cv, Cv))          # once: sr.restricted_iterations makes the same six
+    t0 = blocks[0].transpose(0, 2, 1, 3) / sr._denominators(eo, ev)
+    bad = []
+    for method in ("LCCSD", "CCSD"):
+        step = sr.restricted_step(*blocks, eo, ev, method)
+        runs = {}
+        for depth in (1, 2, 3):
+            r = engine.ccsd_rhf(C, eps, 7, 0, method=method, max_iter=10, conv_delta_E=0.0, conv_amplitudes=0.0, return_t1=True, return_t2=True,
+                                allow_unconverged=True, use_diis=True, max_diis=depth, damping=0.2)
+            ref = sr._run(step, sr._energy_parts(blocks[0]), t0, (7, len(ev)), method, 10, diis=True, max_diis=depth, damping=0.2)
+            s2, s1 = np.abs(ref["t2"]).max(), np.abs(ref["t1"]).max()
+            d2, d1 = np.abs(r["t2"] - ref["t2"]).max() / s2, np.abs(r["t1"] - ref["t1"]).max() / s1
+            dE = np.abs(r["table"][:, 1] - np.array(ref["energies"])) / np.abs(ref["energies"])
+            print(f"\n[{method}, max_diis {depth}] max|t2| {s2:.3f} max|t1| {s1:.4f} max|dt2|/max|t2| {d2:.1e} max|dt1|/max|t1| {d1:.1e} rel dE per step {dE}")
+            assert s2 < 1.0 and 0.0 < s1 < 1.0 and r["n_iter"] == 10 and not r["converged"]
+            if not (d2 <= 1e-10 and d1 <= 1e-10 and np.all(dE <= 1e-11)):
+                bad.append((method, depth, d2, d1, dE))
+            runs[depth] = r
+        for key in ("t1", "t2", "table"):
+            assert np.array_equal(runs[1][key], runs[2][key]), (method, key)
+        assert not np.array_equal(runs[2]["t2"], runs[3]["t2"]), method      # (the depth does reach the loop)
+    assert not bad, bad
+
+
 def test_nesting_with_lccd(engine, mp3_golden, n2_tz):
     """t1 = 0 goes in, so the doubles of LCCSD's first step see no singles: LCCD's first step; its singles come out nonzero"""
     m = mp3_golden["n2_ccpvtz"]

@@ -35,7 +35,7 @@ def test_mirror_of_the_singles_path_constants():
     """The singles path adds no slicing of its own: the occupied rows are back-transformed per batch of TFL_W pairs of the ladder stage
     (work space TFL_W N o), and mp4_singles_kernel walks o^2 v products per (i, a) with SINGLES_THREADS threads.  If one of these changes
     in the library, this test fails instead of the others silently missing the edge."""
-    mp3, mp4, dev = (open(os.path.join(CSRC, f)).read() for f in ("tf_mp3.hip.h", "tf_mp4.hip.h", "tf_device.hip"))
+    mp3, mp4, dev = (open(os.path.join(CSRC, f)).read() for f in ("tf_mp3.hip.h", "tf_mp4.hip.h", "tf_corr_host.hip.h"))
     assert int(re.search(r"#define TFL_W (\d+)", mp3).group(1)) == TFL_W
     assert re.search(r"__shared__ double s_u\[(\d+)\], s_r\[(\d+)\];", mp4).groups() == (str(SINGLES_THREADS),) * 2
     assert re.search(r"mp4_singles_kernel, dim3\(\(unsigned\)ov\), dim3\((\d+)\)", dev).group(1) == str(SINGLES_THREADS)

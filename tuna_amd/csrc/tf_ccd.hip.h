@@ -6,7 +6,7 @@
 // LCCD: F = 0, W_ijkl = (ik|jl), W_icak = (ia|kc), W_ciak = (ik|ac).  CCD (w_cdkl = 2 (ck|dl) - (dk|cl)):
 //     F_ik = sum_lcd w_cdkl t_ilcd,   F_ca = -sum_kld w_cdkl t_klad,   W_ijkl = (ik|jl) + sum_cd (ck|dl) t_ijcd,
 //     W_icak = (ia|kc) - 1/2 sum_ld (dl|ck) t_ilda + 1/2 sum_ld w_dclk t_ilad,   W_ciak = (ik|ac) - 1/2 sum_ld (cl|dk) t_ilda
-// Everything but the particle-particle ladder is a GEMM over these operands (the caller, tf_device.hip), all [(ov)][(ov)] unless noted:
+// Everything but the particle-particle ladder is a GEMM over these operands (the caller, tf_corr_host.hip.h), all [(ov)][(ov)] unless noted:
 //     G [(ia)][(kc)] = (ia|kc) (the block itself)   Gx[(ld)][(kc)] = (lc|kd)   Gw = 2 G - Gx   H[(ia)][(kc)] = (ik|ac)
 //     Goo[(kl)][(cd)] = (kc|ld)   Moo[(ij)][(kl)] = (ik|jl)
 //     Tn[(kc)][(jb)] = t_kjcb   Tx[(kc)][(jb)] = t_kjbc   Tm = 2 Tn - Tx                    (from t[i][j][a][b] every step)
@@ -16,6 +16,7 @@
 // in block order by one thread: bitwise repeatable, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "tf_cc_diis.h"   // the host side of the DIIS: diis_solve, DiisHistory
 
 namespace tfccd {
 
@@ -190,38 +191,6 @@ __global__ void cc_mix_kernel(double *__restrict__ t, const double *__restrict__
         }
         t[e] = damping * t[e] + (1.0 - damping) * x;
     }
-}
-
-// The Pulay equations of update_DIIS (tuna_cc.py:363-381): B c = rhs with -1 borders, solved by elimination with partial pivoting.
-// false: an exactly singular (or non-finite) matrix -- numpy.linalg.solve's LinAlgError, where the reference clears its history.
-inline bool diis_solve(int n, const double *Bee /* [n][n] error dots */, double *coef /* [n] */)
-{
-    const int m = n + 1;
-    double A[33 * 34];
-    if (m > 33) return false;
-    for (int r = 0; r < m; ++r) {
-        for (int c = 0; c < m; ++c) A[r * (m + 1) + c] = (r < n && c < n) ? Bee[r * n + c] : ((r == n && c == n) ? 0.0 : -1.0);
-        A[r * (m + 1) + m] = r == n ? -1.0 : 0.0;
-    }
-    for (int c = 0; c < m; ++c) {
-        int p = c;
-        for (int r = c + 1; r < m; ++r) if (fabs(A[r * (m + 1) + c]) > fabs(A[p * (m + 1) + c])) p = r;
-        const double piv = A[p * (m + 1) + c];
-        if (!(fabs(piv) > 0.0) || !std::isfinite(piv)) return false;
-        if (p != c) for (int q = 0; q <= m; ++q) std::swap(A[p * (m + 1) + q], A[c * (m + 1) + q]);
-        for (int r = c + 1; r < m; ++r) {
-            const double f = A[r * (m + 1) + c] / piv;
-            if (f != 0.0) for (int q = c; q <= m; ++q) A[r * (m + 1) + q] -= f * A[c * (m + 1) + q];
-        }
-    }
-    double x[33];
-    for (int r = m - 1; r >= 0; --r) {
-        double s = A[r * (m + 1) + m];
-        for (int q = r + 1; q < m; ++q) s -= A[r * (m + 1) + q] * x[q];
-        x[r] = s / A[r * (m + 1) + r];
-    }
-    for (int r = 0; r < n; ++r) { if (!std::isfinite(x[r])) return false; coef[r] = x[r]; }
-    return true;
 }
 
 }  // namespace tfccd

@@ -3422,1633 +3422,8 @@ int tf_dft_vxc_unrestricted(tf_ctx *ctx, const double *P_alpha, const double *P_
     return TF_OK;
 }
 
-// ---- AO->MO transformation and RMP2 (next row of the hot path: consumers of the resident tensor) ----------------------
-
-static int mo_transform_device(tf_ctx *ctx, const double *C1, int n1, const double *C2, int n2, const double *C3, int n3, const double *C4,
-                               int n4, double **d_out, double *seconds)
-{
-    const int N = ctx->N;
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    if (ctx->world > 1 && !ctx->allreduce && !ctx->comm)
-        TF_FAIL(ctx, TF_EINVAL, "AO->MO transformation of a sharded tensor (world > 1) needs an RCCL communicator (tf_comm_init) or the all-reduce hook (tf_set_allreduce)");
-    const bool packed = ctx->layout >= 1, tiles = ctx->layout == 2;
-    double *dC[4] = {nullptr, nullptr, nullptr, nullptr}, *dG[2] = {nullptr, nullptr};
-    const double *hC[4] = {C1, C2, C3, C4};
-    const int nk[4] = {n1, n2, n3, n4};
-    const size_t total = (size_t)n1 * n2 * n3 * n4;
-    // packed rows hold the pairs (kl) <= (ij): out[pq][rs] = G(C1 C2 C3 C4)[pq][rs] + G(C3 C4 C1 C2)[rs][pq]; one transformation
-    // serves both terms when the two coefficient pairs are the same matrices ((ia|jb), (pq|rs) with one C)
-    const bool same_pairs = n1 == n3 && n2 == n4 && std::memcmp(C1, C3, (size_t)N * n1 * sizeof(double)) == 0 &&
-                            std::memcmp(C2, C4, (size_t)N * n2 * sizeof(double)) == 0;
-    double secs = 0.0;
-    auto cleanup = [&]() { for (int k = 0; k < 4; ++k) if (dC[k]) (void)tf_free(dC[k]); for (int k = 0; k < 2; ++k) if (dG[k]) (void)tf_free(dG[k]); };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); if (*d_out) { (void)tf_free(*d_out); *d_out = nullptr; } return code; };
-    *d_out = nullptr;
-    for (int k = 0; k < 4; ++k) {
-        if (tf_malloc((void **)&dC[k], (size_t)N * nk[k] * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "AO->MO transformation: out of device memory");
-        if (hipMemcpy(dC[k], hC[k], (size_t)N * nk[k] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation: copy failed");
-    }
-    if (tf_malloc((void **)d_out, (total + 1) * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "AO->MO transformation: out of device memory");   // (+ 1: the status word of the hook's exchange)
-    // the short index first: a ket coefficient matrix of at most 32 columns (the occupied orbitals of (ia|jb)) goes through the hand-written
-    // first quarter on the packed segments (tfmp2::mo_q1_kernel); TF_MO_Q1=0 keeps the expanded-block path (A/B, tests)
-    const char *q1env = getenv("TF_MO_Q1");
-    const bool q1_allowed = packed && !tiles && !(q1env && q1env[0] == '0');
-    auto run = [&](int a, int b, int c, int d, double *dst) {
-        double s1 = 0.0;
-        if (q1_allowed && nk[c] <= 32 && nk[a] <= 32 && (size_t)N * ((nk[a] + 1) & ~1) * sizeof(double) + (size_t)N * sizeof(int) <= ((size_t)150 << 10)) {
-            const size_t need = tfmp2::q1_pool_doubles(N, ctx->n_rows, nk[a], nk[b], nk[c], nk[d]) * sizeof(double);
-            size_t free_b = 0, total_b = 0;
-            const bool fits = need <= ctx->mo_pool_bytes || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + ((size_t)2 << 30) <= free_b + ctx->mo_pool_bytes + tfcache::cached());
-            if (fits) {
-                if (need > ctx->mo_pool_bytes) {
-                    if (ctx->mo_pool) { (void)tf_free(ctx->mo_pool); ctx->mo_pool = nullptr; ctx->mo_pool_bytes = 0; }
-                    if (tf_malloc((void **)&ctx->mo_pool, need) == hipSuccess) ctx->mo_pool_bytes = need;
-                    else { ctx->mo_pool = nullptr; (void)hipGetLastError(); }
-                }
-                if (ctx->mo_pool) {
-                    int r = tfmp2::transform_q1(ctx->scf.blas, ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
-                                                dC[a], nk[a], dC[b], nk[b], dC[c], nk[c], dC[d], nk[d], dst, ctx->mo_pool, &s1, msg);
-                    secs += s1;
-                    return r;
-                }
-            }
-        }
-        tfmp2::PackedRows pr{};
-        if (packed) {
-            for (int q = 0; q < 4; ++q) { pr.csize[q] = ctx->hl.csize[q]; pr.cstart[q] = ctx->hl.cstart[q]; pr.NP[q] = ctx->hl.NP[q]; }
-            for (int q = 0; q < 5; ++q) pr.class_row_off[q] = ctx->class_row_off[q];
-            pr.d_class_rows = ctx->d_class_rows; pr.d_row_pos = ctx->d_row_pos;
-        }
-        int r = tfmp2::transform(ctx->scf.blas, ctx->d_eri, ctx->d_rowmap, (packed && !tiles) ? ctx->d_rowoff : nullptr, ctx->d_rowsec, ctx->bl, pr,
-                                 ctx->d_row_ij, ctx->n_rows, N, ctx->ld, dC[a], nk[a], dC[b], nk[b], dC[c], nk[c], dC[d], nk[d], dst, &s1, msg,
-                                 tiles ? &ctx->tv : nullptr);
-        secs += s1;
-        return r;
-    };
-    if (!packed) {
-        if ((rc = run(0, 1, 2, 3, *d_out))) return fail(rc, msg);
-    } else {
-        if (tf_malloc((void **)&dG[0], total * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "AO->MO transformation: out of device memory");
-        if ((rc = run(0, 1, 2, 3, dG[0]))) return fail(rc, msg);
-        if (!same_pairs) {
-            if (tf_malloc((void **)&dG[1], total * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "AO->MO transformation: out of device memory");
-            if ((rc = run(2, 3, 0, 1, dG[1]))) return fail(rc, msg);
-        }
-        const long long A = (long long)n1 * n2, B = (long long)n3 * n4;
-        hipLaunchKernelGGL(add_transposed_kernel, dim3((unsigned)((B + 31) / 32), (unsigned)((A + 31) / 32)), dim3(32, 8), 0, 0, dG[0],
-                           same_pairs ? dG[0] : dG[1], A, B, *d_out);
-        if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation: launch failed");
-    }
-    if (ctx->world > 1) {                                   // every rank transformed its own rows: the sum is the tensor
-        if (hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation failed on the device");
-        if (ctx->comm) {
-            if (comm_allreduce(ctx, *d_out, total, nullptr)) return fail(TF_ENODEVICE, ctx->err);
-        } else {
-            // the hook sums a buffer whose LAST element is a status word: a rank whose staging failed sends zeros and sets it
-            if (hipMemset(*d_out + total, 0, sizeof(double)) != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation: memset failed");
-            const int arc = ctx->allreduce(ctx->allreduce_user, *d_out, (long long)(total + 1), nullptr);
-            if (arc) return fail(TF_ENODEVICE, "AO->MO transformation: the all-reduce hook failed (code " + std::to_string(arc) + ")");
-            double status = 0.0;
-            if (hipMemcpy(&status, *d_out + total, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation: copy failed");
-            if (status != 0.0) return fail(TF_ENODEVICE, "AO->MO transformation: the exchange step failed on a rank: every rank stops");
-        }
-    }
-    if (hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "AO->MO transformation failed on the device");
-    cleanup();
-    if (seconds) *seconds = secs;
-    return TF_OK;
-}
-
-int tf_ao_to_mo(tf_ctx *ctx, int n1, const double *C1, int n2, const double *C2, int n3, const double *C3, int n4, const double *C4,
-                double *out)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_ao_to_mo: call tf_build_eri first");
-    if (n1 < 1 || n2 < 1 || n3 < 1 || n4 < 1 || !C1 || !C2 || !C3 || !C4 || !out) TF_FAIL(ctx, TF_EINVAL, "tf_ao_to_mo: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    double *d_out = nullptr;
-    int rc = mo_transform_device(ctx, C1, n1, C2, n2, C3, n3, C4, n4, &d_out, nullptr);
-    if (rc) return rc;
-    hipError_t e = hipMemcpy(out, d_out, (size_t)n1 * n2 * n3 * n4 * sizeof(double), hipMemcpyDeviceToHost);
-    (void)tf_free(d_out);
-    HIPCHK(ctx, e);
-    return TF_OK;
-}
-
-int tf_mp2_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double *e_os, double *e_ss, double *seconds)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!C || !eps || !e_os || !e_ss || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_rhf: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *d_g = nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    int rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, &d_g, nullptr);   // (ia|jb)
-    if (rc) return rc;
-    double *d_eps = nullptr, *d_part = nullptr;
-    const int nblk = 1024;
-    HIPCHK(ctx, tf_malloc((void **)&d_eps, (size_t)N * sizeof(double)));
-    HIPCHK(ctx, tf_malloc((void **)&d_part, (size_t)2 * nblk * sizeof(double)));
-    HIPCHK(ctx, hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(tfmp2::mp2_energy_kernel, dim3(nblk), dim3(256), 0, 0, d_g, d_eps, n_frozen, o, v, n_occ, d_part);
-    std::vector<double> part(2 * nblk);
-    hipError_t e = hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost);
-    (void)tf_free(d_g); (void)tf_free(d_eps); (void)tf_free(d_part);
-    HIPCHK(ctx, e);
-    double os = 0.0, ss = 0.0;
-    for (int b = 0; b < nblk; ++b) { os += part[2 * b]; ss += part[2 * b + 1]; }
-    *e_os = os; *e_ss = ss;
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return TF_OK;
-}
-
-// One UMP2 spin block: sum of tfmp2::ump2_energy_kernel's partials in block order (an empty block is 0 and launches nothing)
-static int ump2_block_energy(tf_ctx *ctx, const double *A, const double *B, int o1, int v1, int o2, int v2, const double *eo1, const double *ev1,
-                             const double *eo2, const double *ev2, int same_spin, double *d_part, double *sum)
-{
-    const int nblk = 1024;
-    *sum = 0.0;
-    if ((long long)o1 * v1 * o2 * v2 == 0) return TF_OK;
-    hipLaunchKernelGGL(tfmp2::ump2_energy_kernel, dim3(nblk), dim3(256), 0, 0, A, B, o1, v1, o2, v2, eo1, ev1, eo2, ev2, same_spin, d_part);
-    std::vector<double> part(nblk);
-    HIPCHK(ctx, hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost));
-    double s = 0.0;
-    for (int b = 0; b < nblk; ++b) s += part[b];
-    *sum = s;
-    return TF_OK;
-}
-
-int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
-               const double *eps_alpha, const double *eps_beta, double e_pairs[3], double *seconds)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!C_alpha || !C_beta || !eps_alpha || !eps_beta || !e_pairs || n_frozen_alpha < 0 || n_frozen_alpha > n_alpha || n_frozen_beta < 0 ||
-        n_frozen_beta > n_beta || n_alpha >= N || n_beta >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int oa = n_alpha - n_frozen_alpha, ob = n_beta - n_frozen_beta, va = N - n_alpha, vb = N - n_beta, n1 = oa + ob;
-    e_pairs[0] = e_pairs[1] = e_pairs[2] = 0.0;
-    if (n1 == 0) {                                           // no correlated electron: every block is empty
-        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return TF_OK;
-    }
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    if (ctx->world > 1 && !ctx->allreduce && !ctx->comm)
-        TF_FAIL(ctx, TF_EINVAL, "tf_mp2_uhf on a sharded tensor (world > 1) needs an RCCL communicator (tf_comm_init) or the all-reduce hook (tf_set_allreduce)");
-    // host: occupied / virtual windows of both spins, and the stacked bra [C_occ,a | C_occ,b]
-    std::vector<double> Coa((size_t)N * oa), Cva((size_t)N * va), Cob((size_t)N * ob), Cvb((size_t)N * vb), Cbra((size_t)N * n1);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < oa; ++i) Coa[(size_t)m * oa + i] = Cbra[(size_t)m * n1 + i] = C_alpha[(size_t)m * N + n_frozen_alpha + i];
-        for (int i = 0; i < ob; ++i) Cob[(size_t)m * ob + i] = Cbra[(size_t)m * n1 + oa + i] = C_beta[(size_t)m * N + n_frozen_beta + i];
-        for (int a = 0; a < va; ++a) Cva[(size_t)m * va + a] = C_alpha[(size_t)m * N + n_alpha + a];
-        for (int a = 0; a < vb; ++a) Cvb[(size_t)m * vb + a] = C_beta[(size_t)m * N + n_beta + a];
-    }
-    // device eps: occ a | vir a | occ b | vir b, and the energy partials
-    const int nblk = 1024;
-    double *d_eps = nullptr, *d_part = nullptr, *d_C = nullptr, *d_G = nullptr;
-    auto cleanup = [&]() { for (double *p : {d_eps, d_part, d_C, d_G}) if (p) (void)tf_free(p); };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    if (tf_malloc(&d_eps, (size_t)2 * N * sizeof(double)) != hipSuccess || tf_malloc(&d_part, (size_t)nblk * sizeof(double)) != hipSuccess)
-        return fail(TF_ENOMEM, "tf_mp2_uhf: out of device memory");
-    if (hipMemcpy(d_eps, eps_alpha + n_frozen_alpha, (size_t)(N - n_frozen_alpha) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_eps + N, eps_beta + n_frozen_beta, (size_t)(N - n_frozen_beta) * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
-    const double *eoa = d_eps, *eva = d_eps + oa, *eob = d_eps + N, *evb = d_eps + N + ob;
-    double E_ss[2] = {0.0, 0.0}, E_ab = 0.0;
-    // the spin-blocked route: packed layout, first quarter on the segments, every occupied space <= 32 and the stacked bra <= 48
-    const bool packed = ctx->layout >= 1, tiles = ctx->layout == 2;
-    const char *q1env = getenv("TF_MO_Q1");
-    const bool spin_blocked = packed && !tiles && !(q1env && q1env[0] == '0') && oa <= 32 && ob <= 32 && n1 <= 48 &&
-                              tfmp2::bra1_lds(N, n1) <= ((size_t)150 << 10);
-    if (spin_blocked) {
-        // L-transforms G_L(aa|aa) | G_L(bb|aa) | G_L(aa|bb) | G_L(bb|bb) | status word of the hook's exchange
-        const size_t Baa = (size_t)oa * va * oa * va, Bba = (size_t)ob * vb * oa * va, Bab = (size_t)oa * va * ob * vb, Bbb = (size_t)ob * vb * ob * vb;
-        const size_t total = Baa + Bba + Bab + Bbb;
-        if (tf_malloc(&d_G, (total + 1) * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp2_uhf: out of device memory");
-        double *Gaa = d_G, *Gba = Gaa + Baa, *Gab = Gba + Bba, *Gbb = Gab + Bab;
-        double *dCbra = nullptr, *dCoa = nullptr, *dCva = nullptr, *dCob = nullptr, *dCvb = nullptr;
-        const size_t nC = (size_t)N * (2 * n1 + va + vb);
-        bool ok = tf_malloc(&d_C, nC * sizeof(double)) == hipSuccess;
-        if (ok) {
-            dCbra = d_C; dCoa = dCbra + (size_t)N * n1; dCob = dCoa + (size_t)N * oa; dCva = dCob + (size_t)N * ob; dCvb = dCva + (size_t)N * va;
-            const std::vector<double> *hv[5] = {&Cbra, &Coa, &Cob, &Cva, &Cvb};
-            double *dv[5] = {dCbra, dCoa, dCob, dCva, dCvb};
-            for (int k = 0; k < 5 && ok; ++k) ok = hv[k]->empty() || hipMemcpy(dv[k], hv[k]->data(), hv[k]->size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-            if (!ok) msg = "tf_mp2_uhf: copy failed";
-        } else {
-            msg = "tf_mp2_uhf: out of device memory";
-        }
-        // the work space of the short-index-first transformation, kept by the context (grown when this call needs more)
-        const size_t need = tfmp2::ump2_pool_doubles(N, ctx->n_rows, oa, ob, va, vb) * sizeof(double);
-        if (ok && need > ctx->mo_pool_bytes) {
-            if (ctx->mo_pool) { (void)tf_free(ctx->mo_pool); ctx->mo_pool = nullptr; ctx->mo_pool_bytes = 0; }
-            if (tf_malloc(&ctx->mo_pool, need) == hipSuccess) ctx->mo_pool_bytes = need;
-            else { ctx->mo_pool = nullptr; (void)hipGetLastError(); ok = false; msg = "tf_mp2_uhf: out of device memory for the transformation work space"; }
-        }
-        int prc = ok ? TF_OK : TF_ENOMEM;
-        for (int s = 0; s < 2 && prc == TF_OK; ++s) {          // ket spin a: G_L(aa|aa), G_L(bb|aa); ket spin b: G_L(aa|bb), G_L(bb|bb)
-            if ((s ? ob : oa) == 0) continue;
-            prc = tfmp2::ump2_spin_pass(ctx->scf.blas, ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
-                                        dCbra, oa, ob, dCva, va, dCvb, vb, s ? dCob : dCoa, s ? ob : oa, s ? dCvb : dCva, s ? vb : va,
-                                        s ? Gab : Gaa, s ? Gbb : Gba, ctx->mo_pool, msg);
-        }
-        if (ctx->world > 1) {
-            // the L-transforms are linear in the rows a rank owns: sum them before the quadratic energy step.  A rank whose part failed
-            // sends zeros and a non-zero status word, so that every rank stops together.
-            if (hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: the transformation failed on the device");
-            if (prc != TF_OK && hipMemset(d_G, 0, total * sizeof(double)) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: memset failed");
-            const double st = prc != TF_OK ? 1.0 : 0.0;
-            if (hipMemcpy(d_G + total, &st, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
-            if (ctx->comm) {
-                if (comm_allreduce(ctx, d_G, total + 1, nullptr)) return fail(TF_ENODEVICE, ctx->err);
-            } else {
-                const int arc = ctx->allreduce(ctx->allreduce_user, d_G, (long long)(total + 1), nullptr);
-                if (arc) return fail(TF_ENODEVICE, "tf_mp2_uhf: the all-reduce hook failed (code " + std::to_string(arc) + ")");
-            }
-            double status = 0.0;
-            if (hipMemcpy(&status, d_G + total, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_uhf: copy failed");
-            if (prc != TF_OK) return fail(prc, msg);
-            if (status != 0.0) return fail(TF_ENODEVICE, "tf_mp2_uhf: the transformation failed on a rank: every rank stops");
-        }
-        if (prc != TF_OK) return fail(prc, msg);
-        if ((rc = ump2_block_energy(ctx, Gaa, Gaa, oa, va, oa, va, eoa, eva, eoa, eva, 1, d_part, &E_ss[0]))) { cleanup(); return rc; }
-        if ((rc = ump2_block_energy(ctx, Gbb, Gbb, ob, vb, ob, vb, eob, evb, eob, evb, 1, d_part, &E_ss[1]))) { cleanup(); return rc; }
-        if ((rc = ump2_block_energy(ctx, Gab, Gba, oa, va, ob, vb, eoa, eva, eob, evb, 0, d_part, &E_ab))) { cleanup(); return rc; }
-    } else {
-        // every other layout, or an occupied space above 32: the general transformation, one complete block (ia|jb) at a time
-        struct Blk { const std::vector<double> *Co1, *Cv1, *Co2, *Cv2; int o1, v1, o2, v2; const double *eo1, *ev1, *eo2, *ev2; int same; double *out; };
-        const Blk blks[3] = {{&Coa, &Cva, &Coa, &Cva, oa, va, oa, va, eoa, eva, eoa, eva, 1, &E_ss[0]},
-                             {&Cob, &Cvb, &Cob, &Cvb, ob, vb, ob, vb, eob, evb, eob, evb, 1, &E_ss[1]},
-                             {&Coa, &Cva, &Cob, &Cvb, oa, va, ob, vb, eoa, eva, eob, evb, 0, &E_ab}};
-        for (const Blk &k : blks) {
-            if ((long long)k.o1 * k.v1 * k.o2 * k.v2 == 0) continue;
-            double *d_g = nullptr;
-            if ((rc = mo_transform_device(ctx, k.Co1->data(), k.o1, k.Cv1->data(), k.v1, k.Co2->data(), k.o2, k.Cv2->data(), k.v2, &d_g, nullptr))) {
-                const std::string m = ctx->err;
-                return fail(rc, m);
-            }
-            rc = ump2_block_energy(ctx, d_g, nullptr, k.o1, k.v1, k.o2, k.v2, k.eo1, k.ev1, k.eo2, k.ev2, k.same, d_part, k.out);
-            (void)tf_free(d_g);
-            if (rc) { cleanup(); return rc; }
-        }
-    }
-    cleanup();
-    e_pairs[0] = 0.5 * E_ss[0];
-    e_pairs[1] = 0.5 * E_ss[1];
-    e_pairs[2] = E_ab;
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return TF_OK;
-}
-
-// One batch of the AO-direct ladder on the packed layout (null stream): Zh[p][mu][nu] = the stored-triangle contraction of the tensor
-// with the pair matrices Tm[p] (tfmp3::mp3_ladder_kernel), p < nb <= TFL_W, everything [N][N] in the internal AO order; Tt [N][N][TFL_W] is
-// the work space of the pairs-last image.  The one body behind tf_mp3_rhf and tf_mp3_ladder_probe.  false: a launch failed.
-static bool mp3_ladder_batch(tf_ctx *ctx, const double *Tm, int nb, double *Tt, double *Zh)
-{
-    const int N = ctx->N;
-    const long long tot = (long long)N * N * TFL_W;
-    int csize[4];
-    for (int q = 0; q < 4; ++q) csize[q] = ctx->hl.csize[q];
-    hipLaunchKernelGGL(tfmp3::mp3_pairs_last_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb, Tt);
-    tfmp3::LadderArgs LA{ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, tfmp3::ladder_blocks(csize)};
-    tfmp3::launch_ladder(LA, ctx->bl, N, 0);
-    return hipGetLastError() == hipSuccess;
-}
-
-// The MO blocks of tf_mp3_rhf and tf_ccd_rhf through mo_transform_device: (ia|jb) = g1[i][a][j][b], (ab|ij) = g2[a][b][i][j],
-// (ki|lj) = g3[k][i][l][j].  On failure ctx->err is set and the blocks made so far stay with the caller (who frees them).
-static int mp3_mo_blocks(tf_ctx *ctx, const char *who, const std::vector<double> &Co, const std::vector<double> &Cv, int o, int v, double **pg1,
-                         double **pg2, double **pg3)
-{
-    const int N = ctx->N;
-    const long long nn = (long long)N * N;
-    int rc;
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, pg1, nullptr))) return rc;
-    {
-        // (ab|ij) = g2[a][b][i][j], in slices of the first virtual index: on the packed and tiles layouts the transformation also forms
-        // the image with (ab) on the ket side, whose work space grows as N^2 v^2 (190 GB at N = 400); a slice of nc virtuals keeps it
-        // near 4 GB
-        if (tf_malloc(pg2, (size_t)v * v * o * o * sizeof(double)) != hipSuccess) { ctx->err = std::string(who) + ": out of device memory"; return TF_ENOMEM; }
-        double *g2 = *pg2;
-        const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
-        std::vector<double> Cs((size_t)N * nc);
-        for (int a0 = 0; a0 < v; a0 += nc) {
-            const int na = std::min(nc, v - a0);
-            for (int m = 0; m < N; ++m)
-                for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = Cv[(size_t)m * v + a0 + a];
-            double *d_s = nullptr;
-            if ((rc = mo_transform_device(ctx, Cs.data(), na, Cv.data(), v, Co.data(), o, Co.data(), o, &d_s, nullptr))) return rc;
-            const hipError_t ce = hipMemcpy(g2 + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
-            (void)tf_free(d_s);
-            if (ce != hipSuccess) { ctx->err = std::string(who) + ": copy failed"; return TF_ENODEVICE; }
-        }
-    }
-    return mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Co.data(), o, pg3, nullptr);
-}
-
-// Doubles of the ladder stage's batch work space: U [W][v][N] (later V [W][N][v]) | T [W][N][N] | Tt [N][N][W] (packed) or
-// J [chunk][N][N] (exchange route) | Zh [W][N][N]
-static size_t mp3_ladder_work_doubles(const tf_ctx *ctx, int v)
-{
-    const int N = ctx->N, W = TFL_W, chunk = ctx->layout == 2 ? 8 : 2;
-    const size_t nn = (size_t)N * N, nU = (size_t)W * v * N, nT = (size_t)W * nn;
-    return nU + nT + (ctx->layout == 1 ? nT : (size_t)chunk * nn) + nT;
-}
-
-// The particle-particle ladder stage of tf_mp3_rhf and tf_ccd_rhf: Y[ij][a][b] = 1/2 C_v^T Z C_v for the amplitudes too[ij][a][b], in
-// batches of TFL_W pairs (packed layout: Z's stored-triangle half through mp3_ladder_batch, the caller adds the transposed pair;
-// rows / tiles: the general-density exchange build).  Cvl = C_v in the AO order of T and Z (internal order on the packed layout),
-// batch = mp3_ladder_work_doubles of work space.  On failure ctx->err is set.
-// With Col (C_o in that AO order; tf_mp4_rhf's singles) every batch is back-transformed with the occupied coefficients as well:
-// OA[ij][k][a] = C_o^T Zh_ij C_v and, on the packed layout, OB[ij][a][k] = C_v^T Zh_ij C_o (the other stored-triangle half of
-// C_o^T Z_ji C_v); Vo = TFL_W N o doubles of work space.  These GEMMs are skinny and run without rocBLAS's atomics (split-K sums).
-// With Bol as well (tf_ccsd_rhf; Bol = C_v t1^T in that AO order, [N][o]) every pair matrix is dressed with c_i b_j^T + b_i c_j^T before the
-// contraction (tfccsd::ccsd_dress_pairs_kernel); n_batches, if given, counts the batches.
-static int mp3_ladder_stage(tf_ctx *ctx, const char *who, int o, int v, const double *too, const double *Cvl, double *batch, double *Y,
-                            const double *Col = nullptr, double *Vo = nullptr, double *OA = nullptr, double *OB = nullptr,
-                            const double *Bol = nullptr, long long *n_batches = nullptr)
-{
-    const int N = ctx->N;
-    const long long nn = (long long)N * N;
-    const bool packed = ctx->layout == 1;
-    rocblas_handle blas = ctx->scf.blas;
-    const int W = TFL_W, npair = o * o;
-    const size_t nU = (size_t)W * v * N, nT = (size_t)W * nn;
-    const int chunk = ctx->layout == 2 ? 8 : 2;
-    double *U = batch, *Tm = U + nU, *Tt = Tm + nT, *Jx = Tt, *Zh = Tt + (packed ? nT : (size_t)chunk * nn);
-    int rc;
-#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) { ctx->err = std::string(who) + ": rocBLAS failed: " #call; return TF_ELINALG; } } while (0)
-    for (int p0 = 0; p0 < npair; p0 += W) {
-        const int nb = std::min(W, npair - p0);
-        const double *tb = too + (size_t)p0 * v * v;
-        // U_p = t_p C_v^T (packed: Zh of T_p; exchange route: K of T_p^T, so t_p^T), T_p = C_v U_p
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, !packed, true, v, N, v, 1.0, tb, v, (long long)v * v, Cvl, v, 0, 0.0, U, N, (long long)v * N, nb));
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, N, v, 1.0, Cvl, v, 0, U, N, (long long)v * N, 0.0, Tm, N, nn, nb));
-        if (Bol) {
-            const long long tot = nn * nb;
-            hipLaunchKernelGGL(tfccsd::ccsd_dress_pairs_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb,
-                               p0, o, Col, Bol, packed ? 0 : 1);
-        }
-        if (n_batches) ++*n_batches;
-        if (packed) {
-            if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zh)) { ctx->err = std::string(who) + ": ladder kernel launch failed"; return TF_ENODEVICE; }
-        } else {
-            for (int d = 0; d < nb; d += chunk) {
-                const int nd = std::min(chunk, nb - d);
-                const double *pp[8]; double *jj[8], *kk[8];
-                int nonsym[8];
-                for (int q = 0; q < 8; ++q) {
-                    const int dq = d + std::min(q, nd - 1);
-                    pp[q] = Tm + (size_t)dq * nn; jj[q] = Jx + (size_t)std::min(q, nd - 1) * nn; kk[q] = Zh + (size_t)dq * nn; nonsym[q] = 1;
-                }
-                if ((rc = launch_jk(ctx, nd, pp, jj, kk, 0, nonsym))) return rc;
-            }
-        }
-        // V_p = Z_p C_v, Y_p = 1/2 C_v^T V_p
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, false, false, N, v, N, 1.0, Zh, N, nn, Cvl, v, 0, 0.0, U, v, (long long)N * v, nb));
-        MP3_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, N, 0.5, Cvl, v, 0, U, v, (long long)N * v, 0.0, Y + (size_t)p0 * v * v, v,
-                                        (long long)v * v, nb));
-        if (Col) {
-            rocblas_atomics_mode mode = rocblas_atomics_allowed;
-            const bool mode_set = rocblas_get_atomics_mode(blas, &mode) == rocblas_status_success &&
-                                  rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success;
-            rocblas_status st = tfmp3::gemm_rm_batched(blas, true, false, o, v, N, 1.0, Col, o, 0, U, v, (long long)N * v, 0.0,
-                                                       OA + (size_t)p0 * o * v, v, (long long)o * v, nb);
-            if (st == rocblas_status_success && packed) {
-                st = tfmp3::gemm_rm_batched(blas, false, false, N, o, N, 1.0, Zh, N, nn, Col, o, 0, 0.0, Vo, o, (long long)N * o, nb);
-                if (st == rocblas_status_success)
-                    st = tfmp3::gemm_rm_batched(blas, true, false, v, o, N, 1.0, Cvl, v, 0, Vo, o, (long long)N * o, 0.0, OB + (size_t)p0 * v * o, o,
-                                                (long long)v * o, nb);
-            }
-            if (mode_set) (void)rocblas_set_atomics_mode(blas, mode);
-            if (st != rocblas_status_success) { ctx->err = std::string(who) + ": rocBLAS failed in the occupied back-transformation"; return TF_ELINALG; }
-        }
-    }
-#undef MP3_BLAS
-    return TF_OK;
-}
-
-// Restricted MP3 (run_restricted_MP3, tuna_mp.py:1410-1470; tf_mp3.hip.h has the expressions).  Stages: the MO blocks (ia|jb),
-// (ij|ab), (ki|lj) through mo_transform_device; amplitudes and MP2 partials (mp3_amp_kernel); the particle-particle ladder in the AO
-// basis, batches of TFL_W pairs; the hole-hole and ring GEMMs; one energy reduction.
-int tf_mp3_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double *seconds)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!C || !eps || !e_mp2 || !e_mp3 || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: bad arguments (needs C, eps, outputs and 0 <= n_frozen < n_occ < N)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: a sharded tensor (world > 1) is not supported");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o;
-    if (ov > 0x7fffffffLL || (long long)v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_rhf: dimension overflow");
-    const bool packed = ctx->layout == 1;                     // the AO-direct ladder kernel; rows / tiles: the exchange build
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *work = nullptr, *d_eps = nullptr, *d_part = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *batch = nullptr;
-    auto cleanup = [&]() { for (double *p : {g1, g2, g3, work, d_eps, d_part, d_Cv, d_Cvi, batch}) if (p) (void)tf_free(p); };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- MO blocks: (ia|jb) = g1[i][a][j][b], (ab|ij) = g2[a][b][i][j], (ki|lj) = g3[k][i][l][j]
-    if ((rc = mp3_mo_blocks(ctx, "tf_mp3_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t1 = stamp();
-    // ---- work space: tov | too | tp | tsw | Moo | M1 | M2 | S13 | S2 | Xhh | Y
-    const size_t nwork = (size_t)10 * B2 + (size_t)o4;
-    double *tov, *too, *tp, *tsw, *Moo, *M1, *M2, *S13, *S2, *Xhh, *Y;
-    const int nblk = 1024;
-    if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || tf_malloc(&d_eps, (size_t)N * sizeof(double)) != hipSuccess ||
-        tf_malloc(&d_part, (size_t)3 * nblk * sizeof(double)) != hipSuccess || tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess ||
-        tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess)
-        return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory");
-    tov = work; too = tov + B2; tp = too + B2; tsw = tp + B2; M1 = tsw + B2; M2 = M1 + B2; S13 = M2 + B2; S2 = S13 + B2; Xhh = S2 + B2; Y = Xhh + B2;
-    Moo = Y + B2;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
-    // ---- amplitudes and the MP2 partials
-    hipLaunchKernelGGL(tfmp3::mp3_amp_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, tov, too, tp, tsw, d_part);
-    {
-        std::vector<double> part(2 * nblk);
-        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: copy failed");
-        double os = 0.0, ss = 0.0;
-        for (int b = 0; b < nblk; ++b) { os += part[2 * b]; ss += part[2 * b + 1]; }
-        e_mp2[0] = os; e_mp2[1] = ss;
-    }
-    const auto t2 = stamp();
-    // ---- particle-particle ladder: Y[ij][a][b] = 1/2 C_v^T Z C_v, in batches of TFL_W pairs
-    rocblas_handle blas = ctx->scf.blas;
-    if (tf_malloc(&batch, mp3_ladder_work_doubles(ctx, v) * sizeof(double)) != hipSuccess) return fail(TF_ENOMEM, "tf_mp3_rhf: out of device memory for the ladder work space");
-    const double *Cvl = d_Cv;                                 // C_v in the AO order of T and Z (internal order on the packed layout)
-    if (packed) {
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
-        Cvl = d_Cvi;
-    }
-    if ((rc = mp3_ladder_stage(ctx, "tf_mp3_rhf", o, v, too, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t3 = stamp();
-    // ---- hole-hole and ring terms
-#define MP3_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp3_rhf: rocBLAS failed: " #call); } while (0)
-    {
-        const long long tot = std::max(B2, o4);
-        hipLaunchKernelGGL(tfmp3::mp3_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3, o, v, Moo, M1, M2);
-    }
-    // Xhh[(ij)][(ab)] = 1/2 Moo[(ij)][(kl)] too[(kl)][(ab)]
-    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, o * o, v * v, o * o, 0.5, Moo, o * o, too, v * v, 0.0, Xhh, v * v));
-    // S13 = tov M1 - tsw g1;  S2 = tsw M2   (all [(ov)][(ov)])
-    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, 1.0, tov, (int)ov, M1, (int)ov, 0.0, S13, (int)ov));
-    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, -1.0, tsw, (int)ov, g1, (int)ov, 1.0, S13, (int)ov));
-    MP3_BLAS(tfmp3::gemm_rm(blas, false, false, (int)ov, (int)ov, (int)ov, 1.0, tsw, (int)ov, M2, (int)ov, 0.0, S2, (int)ov));
-#undef MP3_BLAS
-    hipLaunchKernelGGL(tfmp3::mp3_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, Y, packed ? 1 : 0, Xhh, S13, S2, o, v, d_part);
-    {
-        std::vector<double> part(3 * nblk);
-        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp3_rhf: the MP3 kernels failed on the device");
-        double e[3] = {0.0, 0.0, 0.0};
-        for (int b = 0; b < nblk; ++b)
-            for (int q = 0; q < 3; ++q) e[q] += part[3 * b + q];
-        for (int q = 0; q < 3; ++q) e_mp3[q] = e[q];
-    }
-    const auto t4 = stamp();
-    cleanup();
-    if (seconds) {
-        seconds[0] = std::chrono::duration<double>(t4 - t0).count();
-        seconds[1] = std::chrono::duration<double>(t1 - t0).count();
-        seconds[2] = std::chrono::duration<double>(t3 - t2).count();
-        seconds[3] = std::chrono::duration<double>((t2 - t1) + (t4 - t3)).count();
-    }
-    return TF_OK;
-}
-
-// Restricted MP4(SDQ) / MP4(DQ) (run_restricted_MP4, tuna_mp.py:1552-1685, without the triples; tf_mp4.hip.h has the expressions).
-// Stages: tf_mp3_rhf's own, in its order and with its kernels (so that e_mp2 and e_mp3 are bit for bit its values), the first ladder
-// pass also back-transforming with C_o for the singles; the singles from those o^3 v values and the block (ki|ld); t2 and a second pass
-// of the ladder, hole-hole and ring stages on it; the quadruples' GEMMs.
-int tf_mp4_rhf(tf_ctx *ctx, int level, int n_occ, int n_frozen, const double *C, const double *eps, double e_mp2[2], double e_mp3[3], double e_mp4[3],
-               double *seconds)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!C || !eps || !e_mp2 || !e_mp3 || !e_mp4 || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: bad arguments (needs C, eps, outputs and 0 <= n_frozen < n_occ < N)");
-    if (level != 0 && level != 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: level must be 0 (DQ) or 1 (SDQ)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: a sharded tensor (world > 1) is not supported");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o, o3v = (long long)o * o * ov;
-    if (ov > 0x7fffffffLL || (long long)v * v > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp4_rhf: dimension overflow");
-    const bool packed = ctx->layout == 1, singles = level == 1;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *g4 = nullptr, *work = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *d_Co = nullptr,
-           *d_Coi = nullptr, *batch = nullptr;
-    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
-    bool blas_mode_set = false;
-    auto cleanup = [&]() {
-        for (double *p : {g1, g2, g3, g4, work, d_small, d_Cv, d_Cvi, d_Co, d_Coi, batch}) if (p) (void)tf_free(p);
-        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
-    };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- MO blocks: tf_mp3_rhf's, and for the singles (ki|ld) = g4[k][i][l][d]
-    if ((rc = mp3_mo_blocks(ctx, "tf_mp4_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
-    if (singles && (rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t1 = stamp();
-    // ---- work space: tf_mp3_rhf's tov | too | tp | tsw | M1 | M2 | S13 | S2 | Xhh | Y, then t2's tov2 | too2 | tsw2, then Moo | Ioo (o^4);
-    //      small: partials [3 nblk] | sums [4] | eps [N] | F [o^2] | Fv [v^2] | t1 [ov] | singles' partials [ov] | OA [o^3 v] | OB [o^3 v] |
-    //      Vo [TFL_W N o]
-    const int nblk = 1024;
-    const size_t nwork = (size_t)13 * B2 + 2 * (size_t)o4;
-    const size_t nsmall = (size_t)3 * nblk + 4 + (size_t)N + (size_t)o * o + (size_t)v * v + 2 * (size_t)ov + 2 * (size_t)o3v + (size_t)TFL_W * N * o;
-    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
-    if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
-        tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess ||
-        tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Co, (size_t)N * o * sizeof(double)) != hipSuccess ||
-        tf_malloc(&d_Coi, (size_t)N * o * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        char text[160];
-        snprintf(text, sizeof text, "tf_mp4_rhf: out of device memory for %.2f GB of work space (13 arrays of o^2 v^2 values and the ladder's batch)",
-                 (double)(nwork + nsmall + nladder) * sizeof(double) / 1e9);
-        return fail(TF_ENOMEM, text);
-    }
-    double *tov = work, *too = tov + B2, *tp = too + B2, *tsw = tp + B2, *M1 = tsw + B2, *M2 = M1 + B2, *S13 = M2 + B2, *S2 = S13 + B2, *Xhh = S2 + B2,
-           *Y = Xhh + B2, *tov2 = Y + B2, *too2 = tov2 + B2, *tsw2 = too2 + B2, *Moo = tsw2 + B2, *Ioo = Moo + o4;
-    double *d_part = d_small, *d_sum = d_part + (size_t)3 * nblk, *d_eps = d_sum + 4, *Fjk = d_eps + N, *Fv = Fjk + (size_t)o * o, *d_t1 = Fv + (size_t)v * v,
-           *d_spart = d_t1 + ov, *OA = d_spart + ov, *OB = OA + o3v, *Vo = OB + o3v;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_mp4_rhf: copy failed");
-    // ---- amplitudes and the MP2 partials
-    hipLaunchKernelGGL(tfmp3::mp3_amp_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, tov, too, tp, tsw, d_part);
-    {
-        std::vector<double> part(2 * nblk);
-        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: copy failed");
-        double os = 0.0, ss = 0.0;
-        for (int b = 0; b < nblk; ++b) { os += part[2 * b]; ss += part[2 * b + 1]; }
-        e_mp2[0] = os; e_mp2[1] = ss;
-    }
-    const auto t2 = stamp();
-    // ---- first ladder pass, on t: Y and (singles) the occupied-virtual blocks OA, OB
-    rocblas_handle blas = ctx->scf.blas;
-    const double *Cvl = d_Cv, *Col = d_Co;                    // in the AO order of T and Z (internal order on the packed layout)
-    if (packed) {
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * o + 255) / 256)), dim3(256), 0, 0, d_Co, ctx->bl.origI, N, o, d_Coi);
-        Cvl = d_Cvi; Col = d_Coi;
-    }
-    if ((rc = mp3_ladder_stage(ctx, "tf_mp4_rhf", o, v, too, Cvl, batch, Y, singles ? Col : nullptr, Vo, OA, OB))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t3 = stamp();
-#define MP4_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_mp4_rhf: rocBLAS failed: " #call); } while (0)
-    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
-    // the hole-hole and ring GEMMs of X[.] on amplitudes in the three layouts (tf_mp3_rhf's, in its order), then its energy kernel
-    auto hh_ring_energy = [&](const double *a_ov, const double *a_oo, const double *a_sw, double e[3]) -> int {
-        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, Moo, oo, a_oo, vv, 0.0, Xhh, vv));
-        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, a_ov, iov, M1, iov, 0.0, S13, iov));
-        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, a_sw, iov, g1, iov, 1.0, S13, iov));
-        MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, a_sw, iov, M2, iov, 0.0, S2, iov));
-        hipLaunchKernelGGL(tfmp3::mp3_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, Y, packed ? 1 : 0, Xhh, S13, S2, o, v, d_part);
-        std::vector<double> part(3 * nblk);
-        if (hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the energy kernels failed on the device");
-        e[0] = e[1] = e[2] = 0.0;
-        for (int b = 0; b < nblk; ++b)
-            for (int q = 0; q < 3; ++q) e[q] += part[3 * b + q];
-        return TF_OK;
-    };
-    // ---- X[t]: E_MP3
-    {
-        const long long tot = std::max(B2, o4);
-        hipLaunchKernelGGL(tfmp3::mp3_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3, o, v, Moo, M1, M2);
-    }
-    if ((rc = hh_ring_energy(tov, too, tsw, e_mp3))) return rc;
-    // ---- singles
-    e_mp4[0] = 0.0;
-    if (singles) {
-        hipLaunchKernelGGL(tfmp4::mp4_singles_kernel, dim3((unsigned)ov), dim3(256), 0, 0, too, tp, g4, OA, OB, packed ? 1 : 0, d_eps, n_frozen, n_occ, o, v, d_t1,
-                           d_spart);
-        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_spart, (int)ov, 1, d_sum);
-        if (hipMemcpy(&e_mp4[0], d_sum, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the singles kernels failed on the device");
-    }
-    // ---- t2 = (X[t]_ijab + X[t]_jiba) / D, then X[t2]: E_D
-    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
-    hipLaunchKernelGGL(tfmp4::mp4_t2_kernel, grid_e, dim3(256), 0, 0, Y, packed ? 1 : 0, Xhh, S13, S2, d_eps, n_frozen, n_occ, o, v, tov2, too2, tsw2);
-    const auto t4 = stamp();
-    if ((rc = mp3_ladder_stage(ctx, "tf_mp4_rhf", o, v, too2, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t5 = stamp();
-    double eD[3];
-    if ((rc = hh_ring_energy(tov2, too2, tsw2, eD))) return rc;
-    e_mp4[1] = eD[0] + eD[1] + eD[2];
-    // ---- quadruples, in the buffers the doubles have left: Gx | Gw | Goo | Tmp | QA | QB | QC.  The skinny GEMMs (F, Fv, Ioo) would
-    //      otherwise take rocBLAS's split-K kernels, whose sums change from run to run
-    double *Gx = M1, *Gw = M2, *Goo = S13, *Tmp = S2, *QA = Xhh, *QB = Y, *QC = tov2;
-    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
-        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
-        blas_mode_set = true;
-    hipLaunchKernelGGL(tfmp4::mp4_integral_operands_kernel, grid_e, dim3(256), 0, 0, g1, o, v, Gx, Gw, Goo);
-    // QA = 1/2 (t Goo^T) t - F t - t_ij Fv^T
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, too, vv, Goo, vv, 0.0, Ioo, oo));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, Ioo, oo, too, vv, 0.0, QA, vv));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, tov, ovv, Gw, ovv, 0.0, Fjk, o));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fjk, o, too, ovv, 1.0, QA, ovv));
-    for (int k = 0; k < o; ++k)
-        MP4_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, 1.0, tov + (size_t)k * v * ov, iov, Gw + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fv, v));
-    MP4_BLAS(tfmp3::gemm_rm_batched(blas, false, true, v, v, v, -1.0, too, v, (long long)vv, Fv, v, 0, 1.0, QA, v, (long long)vv, oo));
-    // QB = Tn ((Tn - Tx) Gw)^T + 1/2 Tx (Tx G)^T
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tov, iov, Gw, iov, 0.0, Tmp, iov));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, tsw, iov, Gw, iov, 1.0, Tmp, iov));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 1.0, tov, iov, Tmp, iov, 0.0, QB, iov));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tsw, iov, g1, iov, 0.0, Tmp, iov));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 0.5, tsw, iov, Tmp, iov, 1.0, QB, iov));
-    // QC = 1/2 Tx (Tx Gx)^T
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, tsw, iov, Gx, iov, 0.0, Tmp, iov));
-    MP4_BLAS(tfmp3::gemm_rm(blas, false, true, iov, iov, iov, 0.5, tsw, iov, Tmp, iov, 0.0, QC, iov));
-#undef MP4_BLAS
-    hipLaunchKernelGGL(tfmp4::mp4_energy_kernel, dim3(nblk), dim3(256), 0, 0, tp, QA, QB, QC, o, v, d_part);
-    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 1, d_sum);
-    if (hipMemcpy(&e_mp4[2], d_sum, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: the quadruples kernels failed on the device");
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp4_rhf: a kernel launch failed");
-    const auto t6 = stamp();
-    cleanup();
-    if (seconds) {
-        seconds[0] = std::chrono::duration<double>(t6 - t0).count();
-        seconds[1] = std::chrono::duration<double>(t1 - t0).count();
-        seconds[2] = std::chrono::duration<double>((t3 - t2) + (t5 - t4)).count();
-        seconds[3] = seconds[0] - seconds[1] - seconds[2];
-    }
-    return TF_OK;
-}
-
-// Restricted LCCD / CCD (tuna_cc.py:830-864, :915-960, the loop of :3004-3161; tf_ccd.hip.h has the expressions and the operands).
-// Stages: the MO blocks of tf_mp3_rhf, once; per step the amplitude operands, the ladder stage of tf_mp3_rhf on the current amplitudes,
-// CCD's intermediates, the hole-hole and ring GEMMs, the fused update; then convergence, DIIS and damping.  Only dE, ||dt|| and the new
-// row of the DIIS matrix come back to the host per step.
-int tf_ccd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_cc_result *out)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
-    if (opts->max_iter < 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: max_iter must be at least 1");
-    if (opts->method != 0 && opts->method != 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: method must be 0 (LCCD) or 1 (CCD)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: a sharded tensor (world > 1) is not supported");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov, o4 = (long long)o * o * o * o;
-    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_ccd_rhf: dimension overflow");
-    const bool packed = ctx->layout == 1, ccd = opts->method == 1, diis = opts->use_diis != 0;
-    const int keep = std::max(1, std::min(opts->max_diis, 32));   // vectors of the history after the oldest has left (at most 32 here)
-    const int nslot = diis ? std::max(keep, 2) + 1 : 0;       // (steps 1 and 2 store without dropping: tuna_cc.py:482)
-    out->e_corr = out->e_mp2 = 0.0; out->n_iter = 0; out->converged = 0;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *work = nullptr, *hist = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr, *batch = nullptr;
-    int *d_slot = nullptr;
-    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
-    bool blas_mode_set = false;
-    auto cleanup = [&]() {
-        for (double *p : {g1, g2, g3, work, hist, d_small, d_Cv, d_Cvi, batch}) if (p) (void)tf_free(p);
-        if (d_slot) (void)tf_free(d_slot);
-        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
-    };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- MO blocks, as tf_mp3_rhf makes them
-    if ((rc = mp3_mo_blocks(ctx, "tf_ccd_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t1 = stamp();
-    // ---- work space, in arrays of o^2 v^2: t | t_new | dt | Tn | Tx | Tm | S1 | S2 | X | Y | H  (CCD: | A1 | A2 | Gx | Gw | Goo), then
-    //      Moo, W (o^4 each), F_ik, F_ca; the DIIS history: nslot amplitude vectors, then nslot error vectors
-    const int nblk = 1024;
-    const size_t narr = ccd ? 16 : 11;
-    const size_t nwork = narr * (size_t)B2 + 2 * (size_t)o4 + (size_t)o * o + (size_t)v * v;
-    const size_t nsmall = (size_t)nblk * std::max(2, nslot) + 2 * (size_t)std::max(2, nslot) + (size_t)N;
-    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
-    {
-        const double gb = (double)(nwork + 2 * (size_t)nslot * B2 + nladder) * sizeof(double) / 1e9;
-        char text[160];
-        snprintf(text, sizeof text, "tf_ccd_rhf: out of device memory for %.2f GB of work space (%zu arrays of o^2 v^2 values)", gb, narr + 2 * (size_t)nslot);
-        if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || (nslot && tf_malloc(&hist, 2 * (size_t)nslot * B2 * sizeof(double)) != hipSuccess) ||
-            tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_slot, (size_t)std::max(1, nslot) * sizeof(int)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TF_ENOMEM, text);
-        }
-    }
-    double *t = work, *t_new = t + B2, *dt = t_new + B2, *Tn = dt + B2, *Tx = Tn + B2, *Tm = Tx + B2, *S1 = Tm + B2, *S2 = S1 + B2, *X = S2 + B2,
-           *Y = X + B2, *H = Y + B2, *A1 = g1, *A2 = H, *Gx = nullptr, *Gw = nullptr, *Goo = nullptr, *tail = H + B2;
-    if (ccd) { A1 = tail; A2 = A1 + B2; Gx = A2 + B2; Gw = Gx + B2; Goo = Gw + B2; tail = Goo + B2; }
-    double *Moo = tail, *Woo = Moo + o4, *Fik = Woo + o4, *Fca = Fik + (size_t)o * o;
-    double *d_part = d_small, *d_sum = d_part + (size_t)nblk * std::max(2, nslot), *d_coef = d_sum + std::max(2, nslot), *d_eps = d_coef + std::max(2, nslot);
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-    const double *Cvl = d_Cv;                                 // C_v in the AO order of the ladder (internal order on the packed layout)
-    if (packed) {
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
-        Cvl = d_Cvi;
-    }
-    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
-    // ---- the integral operands, the guess amplitudes and their MP2 energy
-    {
-        const long long tot = std::max(B2, o4);
-        hipLaunchKernelGGL(tfccd::cc_integral_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3,
-                           o, v, H, Moo, Gx, Gw, Goo);
-    }
-    hipLaunchKernelGGL(tfccd::cc_guess_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, t, d_part);
-    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
-    {
-        double e2[2];
-        if (hipMemcpy(e2, d_sum, sizeof e2, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the guess kernels failed on the device");
-        out->e_mp2 = e2[0] + e2[1];
-    }
-    (void)tf_free(g2); g2 = nullptr;                          // (ab|ij) lives on in H
-    (void)tf_free(g3); g3 = nullptr;
-    rocblas_handle blas = ctx->scf.blas;
-    // the iteration's GEMMs run without atomics (the skinny ones -- F_ik, W_ijkl -- would otherwise take rocBLAS's split-K kernels, whose
-    // sums change from run to run); the AO->MO transformation above keeps them, as everywhere else
-    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
-        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
-        blas_mode_set = true;
-    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
-    std::vector<int> order;                                   // slots of the history, oldest first
-    std::vector<double> Bee((size_t)std::max(1, nslot) * std::max(1, nslot), 0.0);   // error dots by slot
-    double E = 0.0, ladder_seconds = 0.0;
-    int step = 0, code = TF_ENOTCONV;
-#define CCD_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_ccd_rhf: rocBLAS failed: " #call); } while (0)
-    for (step = 1; step <= opts->max_iter; ++step) {
-        const double E_old = E;
-        hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, t, o, v, Tn, Tx, Tm);
-        // ---- particle-particle ladder on the bare (ac|bd): Y[ij][a][b]
-        const auto l0 = stamp();
-        if ((rc = mp3_ladder_stage(ctx, "tf_ccd_rhf", o, v, t, Cvl, batch, Y))) { const std::string m = ctx->err; return fail(rc, m); }
-        const auto l1 = stamp();
-        ladder_seconds += std::chrono::duration<double>(l1 - l0).count();
-        const double *W = Moo;
-        if (ccd) {
-            // F_ik = Tn [i][(cld)] Gw [k][(cld)]^T;  F_ca = -sum_k Gw_k [c][(ld)] Tn_k [a][(ld)]^T
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, Tn, ovv, Gw, ovv, 0.0, Fik, o));
-            for (int k = 0; k < o; ++k)
-                CCD_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, -1.0, Gw + (size_t)k * v * ov, iov, Tn + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fca, v));
-            // W_ijkl = Moo + t [(ij)][(cd)] Goo [(kl)][(cd)]^T
-            if (hipMemcpyAsync(Woo, Moo, (size_t)o4 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
-                hipMemcpyAsync(A1, g1, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
-                hipMemcpyAsync(A2, H, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, t, vv, Goo, vv, 1.0, Woo, oo));
-            W = Woo;
-            // A1 = G + 1/2 Tn Gw - 1/2 Tx G;  A2 = H - 1/2 Tx Gx
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 0.5, Tn, iov, Gw, iov, 1.0, A1, iov));
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, g1, iov, 1.0, A1, iov));
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, Gx, iov, 1.0, A2, iov));
-        }
-        // X[(ij)][(ab)] = 1/2 W [(ij)][(kl)] t [(kl)][(ab)]  (CCD: + F_ca^T t_ij - F_ik t)
-        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, W, oo, t, vv, 0.0, X, vv));
-        if (ccd) {
-            CCD_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, v, 1.0, Fca, v, 0, t, v, (long long)vv, 1.0, X, v, (long long)vv, oo));
-            CCD_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fik, o, t, ovv, 1.0, X, ovv));
-        }
-        // S1 = A1 Tm - A2 Tn;  S2 = A2 Tx   (all [(ov)][(ov)])
-        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A1, iov, Tm, iov, 0.0, S1, iov));
-        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, A2, iov, Tn, iov, 1.0, S1, iov));
-        CCD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A2, iov, Tx, iov, 0.0, S2, iov));
-        // ---- the fused update: t_new, dt, E and ||dt||^2
-        hipLaunchKernelGGL(tfccd::cc_update_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, n_occ, o, v, t, Y, packed ? 1 : 0, X, S1, S2, t_new, dt,
-                           d_part);
-        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
-        double red[2];
-        if (hipMemcpy(red, d_sum, sizeof red, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the iteration kernels failed on the device");
-        E = red[0];
-        const double dE = E - E_old, dnorm = std::sqrt(red[1]);
-        out->e_corr = E; out->n_iter = step;
-        if (out->table) { double *row = out->table + 3 * (size_t)(step - 1); row[0] = step; row[1] = E; row[2] = dE; }
-        if (!std::isfinite(E) || !std::isfinite(dnorm) || E > 1000.0) { code = TF_ELINALG; break; }     // tuna_cc.py:3129
-        if (std::fabs(dE) < opts->conv_delta_E && dnorm < opts->conv_amplitudes) { code = TF_OK; out->converged = 1; break; }
-        if (step == opts->max_iter) break;
-        // ---- DIIS: store (t_new, dt); from step 3 on drop the oldest beyond max_diis and extrapolate
-        int n_ex = 0;
-        if (diis) {
-            int s = 0;
-            while (std::find(order.begin(), order.end(), s) != order.end()) ++s;
-            order.push_back(s);
-            if (hipMemcpyAsync(hist + (size_t)s * B2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
-                hipMemcpyAsync(hist + (size_t)(nslot + s) * B2, dt, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-            if (step > 2 && (int)order.size() > keep) order.erase(order.begin());
-            const int n = (int)order.size();
-            if (hipMemcpy(d_slot, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-            hipLaunchKernelGGL(tfccd::cc_diis_dots_kernel, dim3(nblk, (unsigned)n), dim3(256), 0, 0, hist + (size_t)nslot * B2, B2, d_slot, n, n - 1, B2, d_part);
-            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, n, d_sum);
-            std::vector<double> row(n);
-            if (hipMemcpy(row.data(), d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: the DIIS kernels failed on the device");
-            for (int m = 0; m < n; ++m) Bee[(size_t)order[m] * nslot + s] = Bee[(size_t)s * nslot + order[m]] = row[m];
-            if (step > 2) {
-                std::vector<double> B((size_t)n * n), coef(n);
-                for (int p = 0; p < n; ++p)
-                    for (int q = 0; q < n; ++q) B[(size_t)p * n + q] = Bee[(size_t)order[p] * nslot + order[q]];
-                if (tfccd::diis_solve(n, B.data(), coef.data())) {
-                    if (hipMemcpy(d_coef, coef.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-                    n_ex = n;
-                } else {
-                    order.clear();                            // "(Resetting DIIS)", tuna_cc.py:398-408
-                }
-            }
-        }
-        hipLaunchKernelGGL(tfccd::cc_mix_kernel, grid_e, dim3(256), 0, 0, t, t_new, hist, B2, d_slot, d_coef, n_ex, opts->damping, B2);
-    }
-#undef CCD_BLAS
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_ccd_rhf: a kernel launch failed");
-    if (out->t2 && hipMemcpy(out->t2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_ccd_rhf: copy failed");
-    const auto t4 = stamp();
-    cleanup();
-    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
-    out->seconds[1] = std::chrono::duration<double>(t1 - t0).count();
-    out->seconds[2] = ladder_seconds;
-    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
-    if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
-    if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
-    return TF_OK;
-}
-
-// out[a][b][i][j] = (C1_a C2_b|C3_i C4_j) into dst (v v o o doubles on the device), in slices of the first index as mp3_mo_blocks makes
-// (ab|ij): tf_ccsd_rhf's dressed W_ciak block.  On failure ctx->err is set.
-static int ccsd_vvoo_block(tf_ctx *ctx, const char *who, const std::vector<double> &C1, const std::vector<double> &C2, const std::vector<double> &C3,
-                           const std::vector<double> &C4, int o, int v, double *dst)
-{
-    const int N = ctx->N;
-    const long long nn = (long long)N * N;
-    const int nc = (int)std::max<long long>(1, std::min<long long>(v, (512LL << 20) / std::max<long long>(1, nn * v)));
-    std::vector<double> Cs((size_t)N * nc);
-    for (int a0 = 0; a0 < v; a0 += nc) {
-        const int na = std::min(nc, v - a0);
-        for (int m = 0; m < N; ++m)
-            for (int a = 0; a < na; ++a) Cs[(size_t)m * na + a] = C1[(size_t)m * v + a0 + a];
-        double *d_s = nullptr;
-        int rc = mo_transform_device(ctx, Cs.data(), na, C2.data(), v, C3.data(), o, C4.data(), o, &d_s, nullptr);
-        if (rc) return rc;
-        const hipError_t ce = hipMemcpy(dst + (size_t)a0 * v * o * o, d_s, (size_t)na * v * o * o * sizeof(double), hipMemcpyDeviceToDevice);
-        (void)tf_free(d_s);
-        if (ce != hipSuccess) { ctx->err = std::string(who) + ": copy failed"; return TF_ENODEVICE; }
-    }
-    return TF_OK;
-}
-
-// Restricted LCCSD / QCISD / CCSD (tuna_cc.py:1020-1063, :1503-1557, :1638-1718, the loop of :3004-3161; tf_ccsd.hip.h has the expressions).
-// tf_ccd_rhf's stages with t1 directly behind t2 in every amplitude buffer (o^2 v^2 + o v elements): per step the amplitude operands, ONE
-// ladder pass on the dressed pair matrices with the occupied back-transformation of tf_mp4_rhf, the intermediates (CCSD: two dressed
-// AO->MO transformations and one general-density J/K build), the GEMMs, the fused singles and doubles updates; then convergence, DIIS and
-// damping over both blocks.  Work space in arrays of o^2 v^2: t | t_new | dt (each o v longer) | Tn | Tx | Tm | S1 | S2 | X | Y | H
-// (QCISD, CCSD: | A1 | A2 | Gx | Gw | Goo) (CCSD: | th | Q) -- 11, 16, 18 -- then Moo, W (o^4), F_ik, F_ca, G2e, F_kc, OA, OB (o^3 v), the
-// stage's Vo, C_v t1^T and an N max(o, v) scratch; nothing with three or four virtual indices.
-int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, tf_ccsd_result *out)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
-    if (opts->max_iter < 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: max_iter must be at least 1");
-    if (opts->method != TF_CCSD_LCCSD && opts->method != TF_CCSD_QCISD && opts->method != TF_CCSD_CCSD)
-        TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: method must be 0 (LCCSD), 1 (QCISD) or 2 (CCSD)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: a sharded tensor (world > 1) is not supported");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov, BT = B2 + ov, o4 = (long long)o * o * o * o, o3v = (long long)o * o * ov, nn = (long long)N * N;
-    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL || o4 > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_ccsd_rhf: dimension overflow");
-    const int level = opts->method;
-    const bool packed = ctx->layout == 1, quad = level >= 1, full = level >= 2, diis = opts->use_diis != 0;
-    const int keep = std::max(1, std::min(opts->max_diis, 32));
-    const int nslot = diis ? std::max(keep, 2) + 1 : 0;
-    out->e_corr = out->e_mp2 = out->e_singles = out->e_connected = out->e_disconnected = out->t1_norm = 0.0;
-    out->n_iter = 0; out->converged = 0; out->ladder_batches = 0;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *g4 = nullptr, *work = nullptr, *hist = nullptr, *d_small = nullptr, *d_Cv = nullptr, *d_Cvi = nullptr,
-           *d_Co = nullptr, *d_Coi = nullptr, *batch = nullptr;
-    int *d_slot = nullptr;
-    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
-    bool blas_mode_set = false;
-    auto cleanup = [&]() {
-        for (double *p : {g1, g2, g3, g4, work, hist, d_small, d_Cv, d_Cvi, d_Co, d_Coi, batch}) if (p) (void)tf_free(p);
-        if (d_slot) (void)tf_free(d_slot);
-        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
-    };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- MO blocks: tf_mp3_rhf's, and (ik|ja) = g4[i][k][j][a]
-    if ((rc = mp3_mo_blocks(ctx, "tf_ccsd_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-    const auto t1s = stamp();
-    const int nblk = 1024;
-    const size_t narr = full ? 18 : (quad ? 16 : 11);
-    const int ntmp = std::max(o, v);
-    const size_t nwork = narr * (size_t)B2 + 3 * (size_t)ov + 2 * (size_t)o4 + (size_t)o * o + 2 * (size_t)v * v + (size_t)ov + 2 * (size_t)o3v +
-                         (size_t)TFL_W * N * o + (size_t)N * o + (size_t)N * ntmp;
-    const int nsum = std::max(4, nslot), npart = std::max(2, nslot);
-    const size_t nsmall = (size_t)nblk * npart + (size_t)nblk + (size_t)ov + (size_t)nsum + (size_t)npart + (size_t)N;
-    const size_t nladder = mp3_ladder_work_doubles(ctx, v);
-    {
-        const double gb = (double)(nwork + 2 * (size_t)nslot * BT + nladder) * sizeof(double) / 1e9;
-        char text[160];
-        snprintf(text, sizeof text, "tf_ccsd_rhf: out of device memory for %.2f GB of work space (%zu arrays of o^2 v^2 values)", gb, narr + 2 * (size_t)nslot);
-        if (tf_malloc(&work, nwork * sizeof(double)) != hipSuccess || (nslot && tf_malloc(&hist, 2 * (size_t)nslot * BT * sizeof(double)) != hipSuccess) ||
-            tf_malloc(&batch, nladder * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_Cv, (size_t)N * v * sizeof(double)) != hipSuccess || tf_malloc(&d_Cvi, (size_t)N * v * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_Co, (size_t)N * o * sizeof(double)) != hipSuccess || tf_malloc(&d_Coi, (size_t)N * o * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_slot, (size_t)std::max(1, nslot) * sizeof(int)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TF_ENOMEM, text);
-        }
-    }
-    double *t = work, *t_new = t + BT, *dt = t_new + BT, *Tn = dt + BT, *Tx = Tn + B2, *Tm = Tx + B2, *S1 = Tm + B2, *S2 = S1 + B2, *X = S2 + B2,
-           *Y = X + B2, *H = Y + B2, *A1 = g1, *A2 = H, *Gx = nullptr, *Gw = nullptr, *Goo = nullptr, *th = t, *Q = nullptr, *tail = H + B2;
-    if (quad) { A1 = tail; A2 = A1 + B2; Gx = A2 + B2; Gw = Gx + B2; Goo = Gw + B2; tail = Goo + B2; }
-    if (full) { th = tail; Q = th + B2; tail = Q + B2; }
-    double *Moo = tail, *Woo = Moo + o4, *Fik = Woo + o4, *Fca = Fik + (size_t)o * o, *G2e = Fca + (size_t)v * v, *Fkc = G2e + (size_t)v * v,
-           *OA = Fkc + ov, *OB = OA + o3v, *Vo = OB + o3v, *Bol = Vo + (size_t)TFL_W * N * o, *d_tmp = Bol + (size_t)N * o;
-    double *d_part = d_small, *d_part2 = d_part + (size_t)nblk * npart, *d_spart = d_part2 + nblk, *d_sum = d_spart + ov, *d_coef = d_sum + nsum,
-           *d_eps = d_coef + npart;
-    double *t1 = t + B2, *t1_new = t_new + B2, *dt1 = dt + B2;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(t1, 0, (size_t)ov * sizeof(double)) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-    const double *Cvl = d_Cv, *Col = d_Co;                    // in the AO order of the ladder (internal order on the packed layout)
-    if (packed) {
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * v + 255) / 256)), dim3(256), 0, 0, d_Cv, ctx->bl.origI, N, v, d_Cvi);
-        hipLaunchKernelGGL(tfmp2::permute_rows_kernel, dim3((unsigned)((N * o + 255) / 256)), dim3(256), 0, 0, d_Co, ctx->bl.origI, N, o, d_Coi);
-        Cvl = d_Cvi; Col = d_Coi;
-    }
-    const dim3 grid_e((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16));
-    const dim3 grid_t((unsigned)std::min<long long>((BT + 255) / 256, 1 << 16));
-    // ---- the integral operands, the guess amplitudes and their MP2 energy (tf_ccd_rhf's kernels: e_mp2 is bit for bit tf_mp2_rhf's)
-    {
-        const long long tot = std::max(B2, o4);
-        hipLaunchKernelGGL(tfccd::cc_integral_operands_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, g2, g3,
-                           o, v, H, Moo, Gx, Gw, Goo);
-    }
-    hipLaunchKernelGGL(tfccsd::ccsd_g2e_kernel, dim3((unsigned)((v * v + 255) / 256)), dim3(256), 0, 0, H, g1, o, v, G2e);
-    hipLaunchKernelGGL(tfccd::cc_guess_kernel, dim3(nblk), dim3(256), 0, 0, g1, d_eps, n_frozen, o, v, n_occ, t, d_part);
-    hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
-    {
-        double e2[2];
-        if (hipMemcpy(e2, d_sum, sizeof e2, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the guess kernels failed on the device");
-        out->e_mp2 = e2[0] + e2[1];
-    }
-    (void)tf_free(g2); g2 = nullptr;                          // (ab|ij) lives on in H
-    (void)tf_free(g3); g3 = nullptr;
-    rocblas_handle blas = ctx->scf.blas;
-    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
-        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
-        blas_mode_set = true;
-    const int iov = (int)ov, oo = o * o, vv = v * v, ovv = o * v * v;
-    std::vector<int> order;
-    std::vector<double> Bee((size_t)std::max(1, nslot) * std::max(1, nslot), 0.0);
-    std::vector<double> h_t1((size_t)ov), Lo, Xv, Bh, Ph;
-    if (full) { Lo.resize((size_t)N * o); Xv.resize((size_t)N * v); Bh.resize((size_t)N * o); Ph.resize((size_t)nn); }
-    double E = 0.0, ladder_seconds = 0.0;
-    long long batches = 0;
-    int step = 0, code = TF_ENOTCONV;
-#define CCSD_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_ccsd_rhf: rocBLAS failed: " #call); } while (0)
-    for (step = 1; step <= opts->max_iter; ++step) {
-        const double E_old = E;
-        hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, t, o, v, Tn, Tx, Tm);
-        if (full) hipLaunchKernelGGL(tfccsd::ccsd_tau_kernel, grid_e, dim3(256), 0, 0, t, t1, o, v, th);
-        // ---- the one ladder pass of the step, on the dressed pair matrices: Y, OA, OB
-        CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, N, o, v, 1.0, Cvl, v, t1, v, 0.0, Bol, o));
-        const auto l0 = stamp();
-        if ((rc = mp3_ladder_stage(ctx, "tf_ccsd_rhf", o, v, th, Cvl, batch, Y, Col, Vo, OA, OB, Bol, &batches))) { const std::string m = ctx->err; return fail(rc, m); }
-        const auto l1 = stamp();
-        ladder_seconds += std::chrono::duration<double>(l1 - l0).count();
-        const double *W = Moo;
-        if (quad) {
-            // F_ik, F_ca as tf_ccd_rhf's, on th (CCSD: its operand goes through S1, free until the ring GEMMs)
-            const double *Tnh = Tn;
-            if (full) {
-                hipLaunchKernelGGL(tfccd::cc_amplitude_operands_kernel, grid_e, dim3(256), 0, 0, th, o, v, S1, S2, X);
-                Tnh = S1;
-            }
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, ovv, 1.0, Tnh, ovv, Gw, ovv, 0.0, Fik, o));
-            for (int k = 0; k < o; ++k)
-                CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, v, v, iov, -1.0, Gw + (size_t)k * v * ov, iov, Tnh + (size_t)k * v * ov, iov, k ? 1.0 : 0.0, Fca, v));
-            hipLaunchKernelGGL(tfccsd::ccsd_fkc_kernel, dim3((unsigned)ov), dim3(256), 0, 0, Gw, t1, iov, Fkc);
-        }
-        // ---- the fused singles update, on F_ik and F_ca as they stand (CCSD dresses them to L_ik, L_ca for the doubles below)
-        hipLaunchKernelGGL(tfccsd::ccsd_singles_kernel, dim3((unsigned)ov), dim3(256), 0, 0, level, t, th, t1, g4, OA, OB, packed ? 1 : 0, G2e, Fik, Fca, Fkc, d_eps,
-                           n_frozen, n_occ, o, v, t1_new, dt1, d_spart);
-        if (quad) {
-            if (hipMemcpyAsync(Woo, Moo, (size_t)o4 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, true, oo, oo, vv, 1.0, th, vv, Goo, vv, 1.0, Woo, oo));
-            W = Woo;
-            if (!full) {
-                if (hipMemcpyAsync(A1, g1, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
-                    hipMemcpyAsync(A2, H, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                    return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-            } else {
-                hipLaunchKernelGGL(tfccsd::ccsd_woo_dress_kernel, dim3((unsigned)((o4 + 255) / 256)), dim3(256), 0, 0, g4, t1, o, v, Woo);
-                // the dressed coefficients L = C_o + C_v t1^T, X = C_v - C_o t1 and the density C_v t1^T C_o^T, on the host (N o v flops)
-                if (hipMemcpy(h_t1.data(), t1, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-                for (int m = 0; m < N; ++m) {
-                    for (int i = 0; i < o; ++i) {
-                        double b = 0.0;
-                        for (int a = 0; a < v; ++a) b += Cv[(size_t)m * v + a] * h_t1[(size_t)i * v + a];
-                        Bh[(size_t)m * o + i] = b;
-                        Lo[(size_t)m * o + i] = Co[(size_t)m * o + i] + b;
-                    }
-                    for (int a = 0; a < v; ++a) {
-                        double x = 0.0;
-                        for (int k = 0; k < o; ++k) x += Co[(size_t)m * o + k] * h_t1[(size_t)k * v + a];
-                        Xv[(size_t)m * v + a] = Cv[(size_t)m * v + a] - x;
-                    }
-                }
-                for (int m = 0; m < N; ++m)
-                    for (int n = 0; n < N; ++n) {
-                        double p = 0.0;
-                        for (int k = 0; k < o; ++k) p += Bh[(size_t)m * o + k] * Co[(size_t)n * o + k];
-                        Ph[(size_t)m * N + n] = p;
-                    }
-                // W_icak's t1 part (l_i x_a|kc) -> A1, W_ciak's (l_i k|x_a c) -> A2
-                double *d_a = nullptr;
-                if ((rc = mo_transform_device(ctx, Lo.data(), o, Xv.data(), v, Co.data(), o, Cv.data(), v, &d_a, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-                const hipError_t ce = hipMemcpy(A1, d_a, (size_t)B2 * sizeof(double), hipMemcpyDeviceToDevice);
-                (void)tf_free(d_a);
-                if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-                if ((rc = ccsd_vvoo_block(ctx, "tf_ccsd_rhf", Xv, Cv, Lo, Co, o, v, Q))) { const std::string m = ctx->err; return fail(rc, m); }
-                hipLaunchKernelGGL(tfccsd::ccsd_vvoo_operand_kernel, grid_e, dim3(256), 0, 0, Q, o, v, A2);
-                // M = 2 J - K of that density; L_ca = F_ca + C_v^T M C_v, L_ik = F_ik + C_o^T M C_o
-                if (hipMemcpy(ctx->d_P, Ph.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-                {
-                    const double *pp[8]; double *jj[8], *kk[8];
-                    int nonsym[8];
-                    for (int q = 0; q < 8; ++q) { pp[q] = ctx->d_P; jj[q] = ctx->d_J; kk[q] = ctx->d_K; nonsym[q] = 1; }
-                    if ((rc = launch_jk(ctx, 1, pp, jj, kk, 0, nonsym))) { const std::string m = ctx->err; return fail(rc, m); }
-                }
-                hipLaunchKernelGGL(tfccsd::ccsd_m_kernel, dim3((unsigned)std::min<long long>((nn + 255) / 256, 1 << 16)), dim3(256), 0, 0, ctx->d_J, ctx->d_K, nn);
-                CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, ctx->d_J, N, d_Cv, v, 0.0, d_tmp, v));
-                CCSD_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, N, 1.0, d_Cv, v, d_tmp, v, 1.0, Fca, v));
-                CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, N, o, N, 1.0, ctx->d_J, N, d_Co, o, 0.0, d_tmp, o));
-                CCSD_BLAS(tfmp3::gemm_rm(blas, true, false, o, o, N, 1.0, d_Co, o, d_tmp, o, 1.0, Fik, o));
-            }
-            // A1 += 1/2 Tn Gw - 1/2 Tx G;  A2 -= 1/2 Tx Gx
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 0.5, Tn, iov, Gw, iov, 1.0, A1, iov));
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, g1, iov, 1.0, A1, iov));
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -0.5, Tx, iov, Gx, iov, 1.0, A2, iov));
-        }
-        // X[(ij)][(ab)] = 1/2 W [(ij)][(kl)] th [(kl)][(ab)]  (QCISD, CCSD: + F_ca^T t_ij - F_ik t)
-        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, oo, vv, oo, 0.5, W, oo, th, vv, 0.0, X, vv));
-        if (quad) {
-            CCSD_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, v, v, 1.0, Fca, v, 0, t, v, (long long)vv, 1.0, X, v, (long long)vv, oo));
-            CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, o, ovv, o, -1.0, Fik, o, t, ovv, 1.0, X, ovv));
-        }
-        // S1 = A1 Tm - A2 Tn;  S2 = A2 Tx
-        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A1, iov, Tm, iov, 0.0, S1, iov));
-        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, -1.0, A2, iov, Tn, iov, 1.0, S1, iov));
-        CCSD_BLAS(tfmp3::gemm_rm(blas, false, false, iov, iov, iov, 1.0, A2, iov, Tx, iov, 0.0, S2, iov));
-        // ---- the fused doubles update, then the disconnected energy of the new singles
-        hipLaunchKernelGGL(tfccsd::ccsd_update_kernel, dim3(nblk), dim3(256), 0, 0, level, g1, d_eps, n_frozen, n_occ, o, v, t, Y, packed ? 1 : 0, X, S1, S2, g4, t1,
-                           OA, OB, t_new, dt, d_part);
-        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, 2, d_sum);
-        hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_spart, (int)ov, 1, d_sum + 2);
-        if (full) {
-            hipLaunchKernelGGL(tfccsd::ccsd_disconnected_kernel, dim3(nblk), dim3(256), 0, 0, g1, t1_new, o, v, d_part2);
-            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part2, nblk, 1, d_sum + 3);
-        }
-        double red[4] = {0.0, 0.0, 0.0, 0.0};
-        if (hipMemcpy(red, d_sum, (full ? 4 : 3) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the iteration kernels failed on the device");
-        out->e_connected = red[0];
-        out->e_disconnected = full ? red[3] : 0.0;
-        E = out->e_singles + out->e_connected + out->e_disconnected;
-        const double dE = E - E_old, dnorm2 = std::sqrt(red[1]), dnorm1 = std::sqrt(red[2]);
-        out->e_corr = E; out->n_iter = step;
-        if (out->table) { double *row = out->table + 3 * (size_t)(step - 1); row[0] = step; row[1] = E; row[2] = dE; }
-        if (!std::isfinite(E) || !std::isfinite(dnorm2) || !std::isfinite(dnorm1) || E > 1000.0) { code = TF_ELINALG; break; }
-        if (std::fabs(dE) < opts->conv_delta_E && dnorm2 < opts->conv_amplitudes && dnorm1 < opts->conv_amplitudes) { code = TF_OK; out->converged = 1; break; }
-        if (step == opts->max_iter) break;
-        // ---- DIIS and damping over (t2, t1): tf_ccd_rhf's, on o^2 v^2 + o v elements
-        int n_ex = 0;
-        if (diis) {
-            int s = 0;
-            while (std::find(order.begin(), order.end(), s) != order.end()) ++s;
-            order.push_back(s);
-            if (hipMemcpyAsync(hist + (size_t)s * BT, t_new, (size_t)BT * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess ||
-                hipMemcpyAsync(hist + (size_t)(nslot + s) * BT, dt, (size_t)BT * sizeof(double), hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-            if (step > 2 && (int)order.size() > keep) order.erase(order.begin());
-            const int n = (int)order.size();
-            if (hipMemcpy(d_slot, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-            hipLaunchKernelGGL(tfccd::cc_diis_dots_kernel, dim3(nblk, (unsigned)n), dim3(256), 0, 0, hist + (size_t)nslot * BT, BT, d_slot, n, n - 1, BT, d_part);
-            hipLaunchKernelGGL(tfccd::cc_sum_partials_kernel, dim3(1), dim3(64), 0, 0, d_part, nblk, n, d_sum);
-            std::vector<double> row(n);
-            if (hipMemcpy(row.data(), d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: the DIIS kernels failed on the device");
-            for (int m = 0; m < n; ++m) Bee[(size_t)order[m] * nslot + s] = Bee[(size_t)s * nslot + order[m]] = row[m];
-            if (step > 2) {
-                std::vector<double> B((size_t)n * n), coef(n);
-                for (int p = 0; p < n; ++p)
-                    for (int q = 0; q < n; ++q) B[(size_t)p * n + q] = Bee[(size_t)order[p] * nslot + order[q]];
-                if (tfccd::diis_solve(n, B.data(), coef.data())) {
-                    if (hipMemcpy(d_coef, coef.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-                    n_ex = n;
-                } else {
-                    order.clear();
-                }
-            }
-        }
-        hipLaunchKernelGGL(tfccd::cc_mix_kernel, grid_t, dim3(256), 0, 0, t, t_new, hist, BT, d_slot, d_coef, n_ex, opts->damping, BT);
-    }
-#undef CCSD_BLAS
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: a kernel launch failed");
-    if (hipMemcpy(h_t1.data(), t1_new, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        (out->t2 && hipMemcpy(out->t2, t_new, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-    {
-        double s = 0.0;
-        for (long long e = 0; e < ov; ++e) s += h_t1[(size_t)e] * h_t1[(size_t)e];
-        out->t1_norm = std::sqrt(s);
-        if (out->t1) std::memcpy(out->t1, h_t1.data(), (size_t)ov * sizeof(double));
-    }
-    out->ladder_batches = batches;
-    const auto t4 = stamp();
-    cleanup();
-    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
-    out->seconds[1] = std::chrono::duration<double>(t1s - t0).count();
-    out->seconds[2] = ladder_seconds;
-    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
-    if (code == TF_ELINALG) TF_FAIL(ctx, TF_ELINALG, "tf_ccsd_rhf: non-finite amplitudes or energy in step %d (try stronger damping)", (int)out->n_iter);
-    if (code == TF_ENOTCONV) TF_FAIL(ctx, TF_ENOTCONV, "tf_ccsd_rhf: the iterations did not converge in %d steps", (int)opts->max_iter);
-    return TF_OK;
-}
-
-// The perturbative triples of CCSD(T), QCISD(T) and full MP4 (tuna_cc.py:2688-2758, tuna_mp.py:403-428 and :1605-1637; tf_triples.hip.h has
-// the expressions and the fused kernel).  Stages: the blocks (ia|jb) and (ki|ld) as tf_ccsd_rhf makes them; (ia|bc) = [i][a][b][c], resident,
-// filled in slabs of occupied orbitals (TF_TRIPLES_SLAB bounds them) and slices of b (TF_TRIPLES_SLICE), both sized from the free memory: the transformation
-// holds N^2 values per element of its ket pair; then per unordered triple i >= j >= k (i = j = k skipped) twelve rocBLAS GEMMs write the
-// six X_pqr, one launch of triples_energy_kernel and one of triples_sum_partials_kernel leave two sums per triple on the device.  The host
-// reads them once after the loop and adds them in loop order with the number of distinct orderings of each triple.
-int tf_triples_rhf(tf_ctx *ctx, int kind, int n_occ, int n_frozen, const double *C, const double *eps, const double *t1, const double *t2,
-                   tf_triples_result *out)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: bad arguments (needs C, eps, out and 0 <= n_frozen < n_occ < N)");
-    if (kind != TF_TRIPLES_CCSD_T && kind != TF_TRIPLES_QCISD_T && kind != TF_TRIPLES_MP4)
-        TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: kind must be 0 (CCSD(T)), 1 (QCISD(T)) or 2 (MP4)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: a sharded tensor (world > 1) is not supported");
-    if (kind == TF_TRIPLES_MP4 && (t1 || t2)) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: MP4 makes its own amplitudes: t1 and t2 must be NULL");
-    if (kind != TF_TRIPLES_MP4 && (!t1 || !t2)) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: CCSD(T) and QCISD(T) need t1 and t2");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov;
-    if (ov > 0x7fffffffLL || (long long)o * v * v > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_triples_rhf: dimension overflow");
-    const size_t v2 = (size_t)v * v, v3 = v2 * v, o3 = (size_t)o * o * o;
-    const long long n_triples = (long long)o * (o + 1) * (o + 2) / 6 - o;
-    out->e_t = out->e_connected = out->e_disconnected = 0.0;
-    out->n_triples = n_triples;
-    for (int q = 0; q < 4; ++q) out->seconds[q] = 0.0;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g4 = nullptr, *gv = nullptr, *X = nullptr, *d_t2 = nullptr, *d_small = nullptr;
-    int *d_tiles = nullptr;
-    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
-    bool blas_mode_set = false;
-    auto cleanup = [&]() {
-        for (double *p : {g1, g4, gv, X, d_t2, d_small}) if (p) (void)tf_free(p);
-        if (d_tiles) (void)tf_free(d_tiles);
-        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
-    };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- the resident arrays: (ia|bc), the six X, t2; small: partials [2 n_blocks] | per-triple sums [2 n_triples] | eps [N] | t1 [ov]
-    const int nt = (v + tftriples::TT - 1) / tftriples::TT;
-    const long long n_blocks = (long long)nt * (nt + 1) * (nt + 2) / 6;
-    const size_t nsmall = 2 * (size_t)n_blocks + 2 * (size_t)std::max<long long>(1, n_triples) + (size_t)N + (size_t)ov;
-    {
-        char text[200];
-        snprintf(text, sizeof text, "tf_triples_rhf: out of device memory for %.2f GB of work space ((ia|bc): o v^3 values, six arrays of v^3 and t2)",
-                 (double)((size_t)o * v3 + 6 * v3 + (size_t)B2 + nsmall) * sizeof(double) / 1e9);
-        if (tf_malloc(&gv, (size_t)o * v3 * sizeof(double)) != hipSuccess || tf_malloc(&X, 6 * v3 * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_t2, (size_t)B2 * sizeof(double)) != hipSuccess || tf_malloc(&d_small, nsmall * sizeof(double)) != hipSuccess ||
-            tf_malloc(&d_tiles, (size_t)3 * n_blocks * sizeof(int)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TF_ENOMEM, text);
-        }
-    }
-    double *d_part = d_small, *d_e = d_part + 2 * (size_t)n_blocks, *d_eps = d_e + 2 * (size_t)std::max<long long>(1, n_triples), *d_t1 = d_eps + N;
-    // ---- MO blocks: (ia|jb) = g1[i][a][j][b], (ki|ld) = g4[k][i][l][d], (ia|bc) = gv[i][a][b][c]
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Cv.data(), v, Co.data(), o, Cv.data(), v, &g1, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-    if ((rc = mo_transform_device(ctx, Co.data(), o, Co.data(), o, Co.data(), o, Cv.data(), v, &g4, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-    {
-        // the transformation's scratch is about 1.5 N^2 values per element of the ket pair, for both images of a packed tensor: (slab, v) and
-        // (slice of b, v).  A quarter of the free memory, 32 GB at the most, bounds either.
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: hipMemGetInfo failed");
-        const size_t budget = std::min<size_t>((free_b + tfcache::cached()) / 4, (size_t)32 << 30);
-        const long long cap = std::max<long long>(1, (long long)(budget / ((size_t)12 * N * N * v)));
-        long long slab = std::min<long long>(o, cap);
-        if (const char *env = getenv("TF_TRIPLES_SLAB")) { const long long n = atoll(env); if (n >= 1) slab = std::min(slab, n); }
-        long long slice = std::min<long long>(v, cap);
-        if (const char *env = getenv("TF_TRIPLES_SLICE")) { const long long n = atoll(env); if (n >= 1) slice = std::min(slice, n); }
-        const int nb_max = (int)slice;
-        std::vector<double> Cos((size_t)N * slab), Cs((size_t)N * nb_max);
-        for (int i0 = 0; i0 < o; i0 += (int)slab) {
-            const int ns = (int)std::min<long long>(slab, o - i0);
-            for (int m = 0; m < N; ++m)
-                for (int i = 0; i < ns; ++i) Cos[(size_t)m * ns + i] = Co[(size_t)m * o + i0 + i];
-            for (int b0 = 0; b0 < v; b0 += nb_max) {
-                const int nb = std::min(nb_max, v - b0);
-                for (int m = 0; m < N; ++m)
-                    for (int b = 0; b < nb; ++b) Cs[(size_t)m * nb + b] = Cv[(size_t)m * v + b0 + b];
-                double *d_s = nullptr;
-                if ((rc = mo_transform_device(ctx, Cos.data(), ns, Cv.data(), v, Cs.data(), nb, Cv.data(), v, &d_s, nullptr))) { const std::string m = ctx->err; return fail(rc, m); }
-                // [is][a][b'][c] -> gv[i0 + is][a][b0 + b'][c]: ns v rows of nb v values, v^2 apart
-                const hipError_t ce = hipMemcpy2D(gv + (size_t)i0 * v3 + (size_t)b0 * v, v2 * sizeof(double), d_s, (size_t)nb * v * sizeof(double),
-                                                  (size_t)nb * v * sizeof(double), (size_t)ns * v, hipMemcpyDeviceToDevice);
-                (void)tf_free(d_s);
-                if (ce != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
-            }
-        }
-    }
-    const auto t1s = stamp();
-    // ---- amplitudes, orbital energies, the tile triples t0 <= t1 <= t2
-    {
-        std::vector<int> tiles((size_t)3 * n_blocks);
-        size_t n = 0;
-        for (int a = 0; a < nt; ++a)
-            for (int b = a; b < nt; ++b)
-                for (int c = b; c < nt; ++c) { tiles[n++] = a; tiles[n++] = b; tiles[n++] = c; }
-        if (hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
-    }
-    if (kind == TF_TRIPLES_MP4) {
-        hipLaunchKernelGGL(tftriples::triples_mp2_amplitudes_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, g1, d_eps,
-                           n_frozen, n_occ, o, v, d_t2);
-    } else if (hipMemcpy(d_t2, t2, (size_t)B2 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(d_t1, t1, (size_t)ov * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_triples_rhf: copy failed");
-    // ---- the loop over unordered triples.  Split-K GEMM kernels would change their sums from run to run
-    rocblas_handle blas = ctx->scf.blas;
-    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
-        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
-        blas_mode_set = true;
-    static const int P3[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};    // tftriples::perm3
-    const auto t2s = stamp();
-#define TRIPLES_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_triples_rhf: rocBLAS failed: " #call); } while (0)
-    {
-        tftriples::EnergyArgs A{};
-        for (int n = 0; n < 6; ++n) A.X[n] = X + (size_t)n * v3;
-        A.tiles = d_tiles; A.g1 = g1; A.t1 = d_t1; A.eps = d_eps;
-        A.vscale = kind == TF_TRIPLES_CCSD_T ? 1.0 : (kind == TF_TRIPLES_QCISD_T ? 2.0 : 0.0);
-        A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v; A.partial = d_part;
-        long long t = 0;
-        for (int i = 0; i < o; ++i)
-            for (int j = 0; j <= i; ++j)
-                for (int k = 0; k <= j; ++k) {
-                    if (i == k) continue;
-                    const int occ[3] = {i, j, k};
-                    for (int n = 0; n < 6; ++n) {
-                        const int p = occ[P3[n][0]], q = occ[P3[n][1]], r = occ[P3[n][2]];
-                        double *Xn = X + (size_t)n * v3;
-                        // X[(ab)][c] = (pa|b.) [v^2 x v] t2[r,q]^T;  X[a][(bc)] -= (pa|q.) [v x o] t2[.,r] [o x v^2]
-                        TRIPLES_BLAS(tfmp3::gemm_rm(blas, false, true, (int)v2, v, v, 1.0, gv + (size_t)p * v3, v, d_t2 + ((size_t)r * o + q) * v2, v, 0.0, Xn, v));
-                        TRIPLES_BLAS(tfmp3::gemm_rm(blas, true, false, v, (int)v2, o, -1.0, g4 + ((size_t)q * o * o + p) * v, (int)ov, d_t2 + (size_t)r * v2,
-                                                    (int)((size_t)o * v2), 1.0, Xn, (int)v2));
-                    }
-                    A.i = i; A.j = j; A.k = k;
-                    hipLaunchKernelGGL(tftriples::triples_energy_kernel, dim3((unsigned)n_blocks), dim3(tftriples::THREADS), 0, 0, A);
-                    hipLaunchKernelGGL(tftriples::triples_sum_partials_kernel, dim3(1), dim3(tftriples::THREADS), 0, 0, d_part, (int)n_blocks, d_e + 2 * t);
-                    ++t;
-                }
-    }
-#undef TRIPLES_BLAS
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_triples_rhf: a kernel launch failed");
-    std::vector<double> e2(2 * (size_t)std::max<long long>(1, n_triples), 0.0);
-    if (n_triples > 0 && hipMemcpy(e2.data(), d_e, 2 * (size_t)n_triples * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(TF_ENODEVICE, "tf_triples_rhf: the triples kernels failed on the device");
-    const auto t3s = stamp();
-    if (out->e_ijk) std::fill(out->e_ijk, out->e_ijk + o3, 0.0);
-    {
-        double ec = 0.0, ed = 0.0;
-        long long t = 0;
-        for (int i = 0; i < o; ++i)
-            for (int j = 0; j <= i; ++j)
-                for (int k = 0; k <= j; ++k) {
-                    if (i == k) continue;
-                    const double c = e2[2 * t] / 3.0, d = e2[2 * t + 1] / 3.0, w = (i == j || j == k) ? 3.0 : 6.0;
-                    ec += w * c; ed += w * d;
-                    if (out->e_ijk) {
-                        const int occ[3] = {i, j, k};
-                        for (int n = 0; n < 6; ++n)
-                            out->e_ijk[((size_t)occ[P3[n][0]] * o + occ[P3[n][1]]) * o + occ[P3[n][2]]] = c + d;
-                    }
-                    ++t;
-                }
-        out->e_connected = ec; out->e_disconnected = ed; out->e_t = ec + ed;
-    }
-    cleanup();
-    const auto t4 = std::chrono::steady_clock::now();
-    out->seconds[0] = std::chrono::duration<double>(t4 - t0).count();
-    out->seconds[1] = std::chrono::duration<double>(t1s - t0).count();
-    out->seconds[2] = std::chrono::duration<double>(t3s - t2s).count();
-    out->seconds[3] = out->seconds[0] - out->seconds[1] - out->seconds[2];
-    return TF_OK;
-}
-
-// Closed-shell CIS / TDHF (tuna_ci.py:719-841, :1161-1211, :1284-1366, :1466-1518; tf_cis.hip.h has the matrices and the reduction).
-// Stages: the MO blocks of tf_mp3_rhf; (ab|ij) transposed to [(ij)][(ab)] and every matrix of the call assembled in one pass, after which
-// the blocks are freed; then per multiplicity one dsyevd (CIS), or dpotrf of A - B once and per multiplicity two dtrmm, one dsyevd, one
-// dtrmm and -- for the kept states -- one dtrsm (TDHF); the transition moments of the singlets as GEMMs.  All dim x dim arrays of the
-// solves are symmetric or read column by column (state n = column n = dim contiguous values), so rocSOLVER's column-major view needs no
-// transposition.
-int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip, tf_cis_result *out)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: call tf_build_eri first");
-    const int N = ctx->N;
-    if (!opts || !C || !eps || !out || n_frozen < 0 || n_occ <= n_frozen || n_occ >= N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: bad arguments (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)");
-    if (!opts->singlets && !opts->triplets) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: neither singlets nor triplets asked for: there are no excited states to calculate");
-    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: n_keep must not be negative");
-    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: transition dipoles and oscillator strengths need the AO dipole matrices (dip)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: a sharded tensor (world > 1) is not supported");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const int o = n_occ - n_frozen, v = N - n_occ;
-    const long long ov = (long long)o * v, B2 = ov * ov;
-    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: dimension overflow");   // (grids of 32-wide tiles)
-    const int dim = (int)ov, nk = std::min(opts->n_keep, dim);
-    const bool tda = opts->tda != 0, sing = opts->singlets != 0, trip = opts->triplets != 0, moments = sing && dip && (out->tdm || out->osc);
-    out->dim = dim;
-    std::vector<double> Co((size_t)N * o), Cv((size_t)N * v);
-    for (int m = 0; m < N; ++m) {
-        for (int i = 0; i < o; ++i) Co[(size_t)m * o + i] = C[(size_t)m * N + n_frozen + i];
-        for (int a = 0; a < v; ++a) Cv[(size_t)m * v + a] = C[(size_t)m * N + n_occ + a];
-    }
-    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr, *Ht = nullptr, *Ms = nullptr, *Mt = nullptr, *Mm = nullptr, *T = nullptr, *kept = nullptr, *small = nullptr;
-    rocblas_int *d_info = nullptr;
-    rocblas_atomics_mode blas_mode = rocblas_atomics_allowed;
-    bool blas_mode_set = false;
-    auto cleanup = [&]() {
-        for (double *p : {g1, g2, g3, Ht, Ms, Mt, Mm, T, kept, small}) if (p) (void)tf_free(p);
-        if (d_info) (void)tf_free(d_info);
-        if (blas_mode_set) (void)rocblas_set_atomics_mode(ctx->scf.blas, blas_mode);
-    };
-    auto fail = [&](int code, const std::string &m) { ctx->err = m; cleanup(); return code; };
-    auto stamp = [&]() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); };
-    // ---- MO blocks, as tf_mp3_rhf makes them ((ki|lj) is not needed here)
-    if ((rc = mp3_mo_blocks(ctx, "tf_cis_rhf", Co, Cv, o, v, &g1, &g2, &g3))) { const std::string m = ctx->err; return fail(rc, m); }
-    (void)tf_free(g3); g3 = nullptr;
-    const auto t1 = stamp();
-    // ---- work space: the matrices (CIS: A per multiplicity; TDHF: A + B per multiplicity, A - B and one more dim^2 array for the
-    //      triangular products), the transposed (ij|ab) until the assembly is done, the kept vectors, and the small arrays:
-    //      w | w2 | e (dsyevd) | stat[2] | eps [N] | D_ia [3][dim] | mu [dim][3] | f [dim] | C_o | C_v | D C_v [N][v] | D [3][N][N]
-    const int n_mats = (sing ? 1 : 0) + (trip ? 1 : 0) + (tda ? 0 : 2);
-    const size_t nsmall = 3 * (size_t)dim + 2 + (size_t)N + 7 * (size_t)dim + (size_t)N * o + 2 * (size_t)N * v + 3 * (size_t)N * N;
-    const size_t nkept = (size_t)std::max(1, nk) * dim * (tda ? 0 : 3);
-    {
-        const double gb = (double)(((size_t)n_mats + 1) * (size_t)B2 + nkept + nsmall) * sizeof(double) / 1e9;
-        char text[200];
-        snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space (%d arrays of (o v)^2 = %lld^2 values)", gb, n_mats + 1, ov);
-        if (tf_malloc(&Ht, (size_t)B2 * sizeof(double)) != hipSuccess || (sing && tf_malloc(&Ms, (size_t)B2 * sizeof(double)) != hipSuccess) ||
-            (trip && tf_malloc(&Mt, (size_t)B2 * sizeof(double)) != hipSuccess) || (!tda && tf_malloc(&Mm, (size_t)B2 * sizeof(double)) != hipSuccess) ||
-            tf_malloc(&small, nsmall * sizeof(double)) != hipSuccess || tf_malloc((double **)&d_info, 4 * sizeof(rocblas_int)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TF_ENOMEM, text);
-        }
-    }
-    double *d_w = small, *d_w2 = d_w + dim, *d_e = d_w2 + dim, *d_stat = d_e + dim, *d_eps = d_stat + 2, *d_Dia = d_eps + N, *d_mu = d_Dia + 3 * (size_t)dim,
-           *d_f = d_mu + 3 * (size_t)dim, *d_Co = d_f + dim, *d_Cv = d_Co + (size_t)N * o, *d_T1 = d_Cv + (size_t)N * v, *d_dip = d_T1 + (size_t)N * v;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-    // ---- assembly
-    tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
-    {
-        tfcis::AssembleArgs A{};
-        A.g1 = g1; A.Ht = Ht; A.eps = d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v;
-        if (sing) { A.kind[A.n_out] = tda ? 0 : 2; A.out[A.n_out++] = Ms; }
-        if (trip) { A.kind[A.n_out] = tda ? 1 : 3; A.out[A.n_out++] = Mt; }
-        if (!tda) { A.kind[A.n_out] = 4; A.out[A.n_out++] = Mm; }
-        tfcis::launch_assemble(A, 0);
-    }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the assembly kernels failed on the device");
-    for (double **p : {&g1, &g2, &Ht}) { (void)tf_free(*p); *p = nullptr; }
-    {
-        const std::pair<double *, const double *> outs[3] = {{out->m_plus_singlet, Ms}, {out->m_plus_triplet, Mt}, {out->m_minus, Mm}};
-        for (const auto &pr : outs)
-            if (pr.first && pr.second && hipMemcpy(pr.first, pr.second, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-    }
-    const auto t2 = stamp();
-    // ---- solves
-    if (!tda) {
-        char text[200];
-        snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space for the TDHF reduction",
-                 (double)((size_t)B2 + nkept) * sizeof(double) / 1e9);
-        if (tf_malloc(&T, (size_t)B2 * sizeof(double)) != hipSuccess || tf_malloc(&kept, nkept * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TF_ENOMEM, text);
-        }
-    }
-    double *Q = kept, *Xk = kept ? kept + (size_t)std::max(1, nk) * dim : nullptr, *Yk = kept ? Xk + (size_t)std::max(1, nk) * dim : nullptr;
-    rocblas_handle blas = ctx->scf.blas;
-    // no atomics in the products: split-K sums would change from run to run
-    if (rocblas_get_atomics_mode(blas, &blas_mode) == rocblas_status_success &&
-        rocblas_set_atomics_mode(blas, rocblas_atomics_not_allowed) == rocblas_status_success)
-        blas_mode_set = true;
-#define CIS_BLAS(call) do { if ((call) != rocblas_status_success) return fail(TF_ELINALG, "tf_cis_rhf: rocBLAS / rocSOLVER failed: " #call); } while (0)
-    auto info = [&](int *h) { return hipMemcpy(h, d_info, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; };
-    const double one = 1.0;
-    if (moments) {
-        if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_Co, Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_Cv, Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-        for (int c = 0; c < 3; ++c) {                             // D^c_ia = C_o^T D^c C_v
-            CIS_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, d_dip + (size_t)c * N * N, N, d_Cv, v, 0.0, d_T1, v));
-            CIS_BLAS(tfmp3::gemm_rm(blas, true, false, o, v, N, 1.0, d_Co, o, d_T1, v, 0.0, d_Dia + (size_t)c * dim, v));
-        }
-    }
-    // mu_n[c] = sqrt(2) sum_ia D^c_ia V[ia][n] over the states (columns) of V, and the oscillator strengths, to the host
-    auto transition_moments = [&](const double *V) -> int {
-        if (tfmp3::gemm_rm(blas, false, true, dim, 3, dim, std::sqrt(2.0), V, dim, d_Dia, dim, 0.0, d_mu, 3) != rocblas_status_success) return TF_ELINALG;
-        hipLaunchKernelGGL(tfcis::oscillator_kernel, dim3((unsigned)((dim + 255) / 256)), dim3(256), 0, 0, d_mu, d_w, dim, d_f);
-        if ((out->tdm && hipMemcpy(out->tdm, d_mu, 3 * (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (out->osc && hipMemcpy(out->osc, d_f, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-            return TF_ENODEVICE;
-        return TF_OK;
-    };
-    if (!tda) {
-        // A - B = L L^T, once for both multiplicities
-        CIS_BLAS(rocsolver_dpotrf(blas, rocblas_fill_lower, dim, Mm, dim, d_info));
-        int h = 0;
-        if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the Cholesky factorisation failed on the device");
-        if (h != 0) {
-            char text[300];
-            snprintf(text, sizeof text, "tf_cis_rhf: A - B is not positive definite (dpotrf stopped at the leading minor of order %d of %d): the RHF "
-                     "reference is unstable, and TDHF has no real excitation energies for singlets or triplets; the states are not returned", h, dim);
-            return fail(TF_ELINALG, text);
-        }
-    }
-    for (int mult = 0; mult < 2; ++mult) {
-        double *M = mult == 0 ? Ms : Mt;
-        if (!M) continue;
-        const char *name = mult == 0 ? "singlet" : "triplet";
-        double *e_out = mult == 0 ? out->e_singlet : out->e_triplet, *x_out = mult == 0 ? out->x_singlet : out->x_triplet,
-               *y_out = mult == 0 ? out->y_singlet : out->y_triplet;
-        const double *V = M;                                      // the transition vectors X + Y, state by state
-        int h = 0;
-        if (tda) {
-            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w, d_e, d_info));
-            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
-            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the ") + name + " CIS matrix did not converge (rocsolver_dsyevd)");
-            if (nk > 0 && x_out && hipMemcpy(x_out, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-            if (nk > 0 && y_out) std::fill(y_out, y_out + (size_t)nk * dim, 0.0);
-        } else {
-            // M <- L^T (A + B) L; its eigenpairs (w^2, Z)
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
-                                   dim, T, dim));
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim,
-                                   T, dim, M, dim));
-            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w2, d_e, d_info));
-            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
-            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the reduced ") + name + " TDHF matrix did not converge (rocsolver_dsyevd)");
-            hipLaunchKernelGGL(tfcis::tdhf_roots_kernel, dim3(1), dim3(256), 0, 0, d_w2, dim, d_w, d_stat);
-            double stat[2];
-            if (hipMemcpy(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the root kernel failed on the device");
-            if (stat[0] != 0.0) {
-                char text[300];
-                snprintf(text, sizeof text, "tf_cis_rhf: %d %s root(s) of the TDHF problem have w^2 <= 0 (smallest w^2 = %.10g): the RHF reference is "
-                         "unstable towards a %s perturbation, and the states are not returned (CIS on the same orbitals still runs)", (int)stat[0], name, stat[1], name);
-                return fail(TF_ELINALG, text);
-            }
-            // X + Y = L Z / sqrt(w) for every state; X - Y = sqrt(w) L^-T Z for the kept ones
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
-                                   dim, T, dim));
-            if (nk > 0) {
-                if (hipMemcpy(Q, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-                CIS_BLAS(rocblas_dtrsm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, nk, &one, Mm, dim,
-                                       Q, dim));
-            }
-            hipLaunchKernelGGL(tfcis::tdhf_backsub_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, T, Q, d_w, dim, nk, Xk,
-                               Yk);
-            if (nk > 0 && ((x_out && hipMemcpy(x_out, Xk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-                           (y_out && hipMemcpy(y_out, Yk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)))
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-            V = T;
-        }
-        if (e_out && hipMemcpy(e_out, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-        if (mult == 0 && moments) {
-            const int mrc = transition_moments(V);
-            if (mrc) return fail(mrc, "tf_cis_rhf: the transition moments failed on the device");
-        }
-    }
-#undef CIS_BLAS
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: a kernel launch failed");
-    const auto t3 = stamp();
-    cleanup();
-    out->seconds[0] = std::chrono::duration<double>(t3 - t0).count();
-    out->seconds[1] = std::chrono::duration<double>(t1 - t0).count();
-    out->seconds[2] = std::chrono::duration<double>(t2 - t1).count();
-    out->seconds[3] = std::chrono::duration<double>(t3 - t2).count();
-    return TF_OK;
-}
-
-int tf_mp3_ladder_probe(tf_ctx *ctx, int n, const double *T, double *Zh)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: call tf_build_eri first");
-    if (n < 1 || !T || !Zh) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: bad arguments (needs n >= 1, T and Zh)");
-    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: a sharded tensor (world > 1) is not supported");
-    if (ctx->layout != 1) TF_FAIL(ctx, TF_EINVAL, "tf_mp3_ladder_probe: the ladder kernel runs on the packed layout only");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int N = ctx->N, W = TFL_W;
-    const size_t nn = (size_t)N * N, nT = (size_t)W * nn;
-    const int *oI = ctx->hl.origI.data();                     // internal -> caller's AO index
-    double *buf = nullptr;                                    // T [W][N][N] | Tt [N][N][W] | Zh [W][N][N]
-    if (tf_malloc(&buf, 3 * nT * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); TF_FAIL(ctx, TF_ENOMEM, "tf_mp3_ladder_probe: out of device memory"); }
-    auto fail = [&](int code, const char *m) { ctx->err = m; (void)tf_free(buf); return code; };
-    double *Tm = buf, *Tt = Tm + nT, *Zd = Tt + nT;
-    std::vector<double> h(nT);
-    for (int p0 = 0; p0 < n; p0 += W) {
-        const int nb = std::min(W, n - p0);
-        for (int p = 0; p < nb; ++p)
-            for (int x = 0; x < N; ++x) {
-                const double *src = T + (size_t)(p0 + p) * nn + (size_t)oI[x] * N;
-                double *dst = h.data() + (size_t)p * nn + (size_t)x * N;
-                for (int y = 0; y < N; ++y) dst[y] = src[oI[y]];
-            }
-        // every byte of the output 0xff first: an element the kernel does not write comes back as a NaN
-        if (hipMemcpy(Tm, h.data(), (size_t)nb * nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(Zd, 0xff, nT * sizeof(double)) != hipSuccess)
-            return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: copy failed");
-        if (!mp3_ladder_batch(ctx, Tm, nb, Tt, Zd)) return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: ladder kernel launch failed");
-        if (hipMemcpy(h.data(), Zd, (size_t)nb * nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(TF_ENODEVICE, "tf_mp3_ladder_probe: the ladder kernel failed on the device");
-        for (int p = 0; p < nb; ++p)
-            for (int x = 0; x < N; ++x) {
-                const double *src = h.data() + (size_t)p * nn + (size_t)x * N;
-                double *dst = Zh + (size_t)(p0 + p) * nn + (size_t)oI[x] * N;
-                for (int y = 0; y < N; ++y) dst[oI[y]] = src[y];
-            }
-    }
-    (void)tf_free(buf);
-    return TF_OK;
-}
+// ---- AO->MO transformation, MP2 ... CCSD(T), CIS / TDHF: the drivers of the correlated methods (consumers of the resident tensor) ----
+#include "tf_corr_host.hip.h"
 
 int tf_eigh_probe(tf_ctx *ctx, int n, int variant, int reps, double *seconds)
 {
