@@ -480,6 +480,38 @@ typedef struct {
 int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip,
                tf_cis_result *out);
 
+/* ---- CIS(D): replaces calculate_restricted_doubles_correction (tuna_ci.py:1874-1982), the perturbative doubles correction of
+ * Head-Gordon, Rico, Oumi and Lee to closed-shell CIS / TDHF states ---- */
+
+typedef struct {
+    double *e_d, *e_direct, *e_indirect;   /* [n_states], caller-allocated; e_d = e_direct + e_indirect */
+    double *min_denominator;               /* [n_states] may be NULL: min over ijab of |D_ijab + omega| */
+    double seconds[3];                     /* state-independent blocks; dressed transformations; kernels and GEMMs */
+} tf_cis_d_result;
+
+/* The (D) correction of n_states states of tf_cis_rhf's spectrum from canonical RHF orbitals C [N,N] and eps [N]; windows as tf_mp3_rhf:
+ * occupied [n_frozen, n_occ), virtual [n_occ, N).  Per state: b [o][v], normalised (CIS: the eigenvector; TDHF: X + Y), its excitation
+ * energy omega, and triplet = 0 (singlet) or 1.  With D_ijab = e_i + e_j - e_a - e_b, t = (ia|jb) / D and s = 1 / (D + omega):
+ *     M[iajb] = (i~ a|jb) - sum_k b_ka (ki|jb),   C~_o = C_v b^T,   u_S[ijab] = M[iajb] + M[jbia],   u_T[ijab] = M[iajb] - M[jbia]
+ *     e_direct = sum s u_S[ijab] (u_S[ijab] - 1/2 u_S[jiab])                              (singlet)
+ *              = 1/2 sum s (u_S[ijab]^2 - u_S[ijab] u_S[jiab] + u_T[ijab]^2)              (triplet)
+ *     e_indirect = sum_ia b_ia y_ia - sum_ija b_ia b_ja Goo_ij - sum_iab b_ia b_ib Gvv_ba,   L = 2 (jb|kc) - (jc|kb),
+ *     Goo_ij = sum_kbc L_jkbc t_ikbc,   Gvv_ba = sum_jkc L_jkbc t_jkac,   y = (2 t_ikac - t_ikca) (L b)  (singlet),   t_ikca ((jc|kb) b)  (triplet)
+ * No block with three virtual indices is formed: per state one AO->MO transformation with the dressed occupied orbitals ((i~ a|jb), as
+ * tf_ao_to_mo makes it, on every tensor layout), one GEMM on (ki|jb), one fused pass over M (16 x 16 tiles of (a, b) per pair (i, j),
+ * the two transposed elements gathered through LDS) and two to four matrix-vector products.  States are processed one after the other
+ * by the same calls, the per-block partial sums are added in block order and nothing is reduced with atomics: a state's three numbers
+ * are the same bits alone, in any batch and in two calls.
+ * Work space: 5 arrays of o^2 v^2 values ((ia|jb), t, 2 t - t', L, M) plus 2 inside a transformation on the packed and tiles layouts,
+ * and (ki|jb) of o^3 v.
+ * Measured on one MI355X: 114 states of seven systems within 4.2e-16 Eh of the reference program's E_D on every layout; N = 400, o = 18,
+ * warm: 0.04 - 0.14 s for the state-independent blocks (two machines), then 0.022 s (transformation) + 0.002 s (kernels and GEMMs) per state.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL C, eps, b, omega, triplet, out, e_d, e_direct or e_indirect, with
+ * n_states < 1, a flag outside {0, 1}, unless 0 <= n_frozen < n_occ < N, or world > 1.  TF_ENOMEM, with the size in the message. */
+int tf_cis_d_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, int n_states,
+                 const double *b /* [n_states][o][v] */, const double *omega /* [n_states] */,
+                 const int32_t *triplet /* [n_states], 0 or 1 */, tf_cis_d_result *out);
+
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */
 int tf_diagonalise(tf_ctx *ctx, int n, const double *F, const double *X, double *eps, double *C);

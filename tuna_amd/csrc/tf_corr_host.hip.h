@@ -1,7 +1,7 @@
 // tf_corr_host.hip.h -- the host drivers of the correlated methods: the AO->MO transformation, RMP2 / UMP2, MP3, MP4, LCCD / CCD,
-// LCCSD / QCISD / CCSD, the perturbative triples, CIS / TDHF and the ladder probe.  Included by tf_device.hip (one translation unit:
+// LCCSD / QCISD / CCSD, the perturbative triples, CIS / TDHF, CIS(D) and the ladder probe.  Included by tf_device.hip (one translation unit:
 // struct tf_ctx, tf_malloc, launch_jk, TF_FAIL and HIPCHK are defined there, above the include); the kernels are in tf_mp2.hip.h ...
-// tf_cis.hip.h.  First the pieces the drivers share, then the drivers.  DESIGN.md section 4.5a has the table of who uses what and the
+// tf_cisd.hip.h.  First the pieces the drivers share, then the drivers.  DESIGN.md section 4.5a has the table of who uses what and the
 // invariants: every driver keeps its order of launches, rocBLAS calls and copies on the null stream, and the order of its host sums.
 #pragma once
 #include "tf_cc_diis.h"
@@ -1553,6 +1553,134 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
     out->seconds[1] = corr_secs(t1 - S.t0);
     out->seconds[2] = corr_secs(t2 - t1);
     out->seconds[3] = corr_secs(t3 - t2);
+    return TF_OK;
+}
+
+// CIS(D) of closed-shell CIS / TDHF states (calculate_restricted_doubles_correction, tuna_ci.py:1874-1982; tf_cisd.hip.h has the
+// expressions and the kernels).  Stages: (ia|jb) and (ik|jb) through mo_transform_device, t, tt and L in one pass, Goo and Gvv by one GEMM
+// each; then state by state the dressed block (i~ a|jb) through mo_transform_device with Ct_o = C_v b^T made on the device, the (ik|jb)
+// GEMMs that turn it into M, the fused direct kernel, and the matrix-vector products of the indirect part.  Every state goes through
+// the same calls with the same shapes whatever else the call holds, so its numbers do not depend on its neighbours; states do not share
+// a transformation or a GEMM (rocBLAS promises the same bits for the same call, not for one column of a wider one).
+// Work space: 5 arrays of o^2 v^2 (g, t, tt, L, M) and on the packed and tiles layouts 2 more inside a transformation.
+int tf_cis_d_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, int n_states, const double *b, const double *omega,
+                 const int32_t *triplet, tf_cis_d_result *out)
+{
+    static const char *who = "tf_cis_d_rhf";
+    const bool pointers = C && eps && b && omega && triplet && out && out->e_d && out->e_direct && out->e_indirect;
+    int rc = corr_args(ctx, who, pointers, " (needs C, eps, b, omega, triplet, out with e_d, e_direct and e_indirect, and 0 <= n_frozen < n_occ < N)",
+                       n_occ, n_frozen);
+    if (rc) return rc;
+    if (n_states < 1) TF_FAIL(ctx, TF_EINVAL, "tf_cis_d_rhf: n_states must be at least 1, got %d", n_states);
+    for (int s = 0; s < n_states; ++s)
+        if (triplet[s] != 0 && triplet[s] != 1) TF_FAIL(ctx, TF_EINVAL, "tf_cis_d_rhf: triplet[%d] = %d is neither 0 (singlet) nor 1 (triplet)", s, (int)triplet[s]);
+    CorrSetup S;
+    if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
+    const int N = S.N, o = S.o, v = S.v;
+    const long long ov = S.ov, B2 = S.B2, nblk = tfcisd::tile_blocks(o, v);
+    if (ov > 0x7fffffffLL / std::max(o, v) || nblk > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_cis_d_rhf: dimension overflow");
+    const int dim = (int)ov;
+    DeviceBlocks mem;
+    auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
+    auto oom = [&](const char *what, size_t doubles) {
+        char text[240];
+        snprintf(text, sizeof text, "tf_cis_d_rhf: out of device memory for %.2f GB of %s (5 arrays of (o v)^2 = %lld^2 values in all)",
+                 (double)doubles * sizeof(double) / 1e9, what, ov);
+        return fail(TF_ENOMEM, text);
+    };
+    // ---- state-independent blocks: g = (ia|jb), h[i][k][j][b] = (ik|jb) = (ki|jb)
+    double *g = nullptr, *h = nullptr;
+    if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g, nullptr)))
+        return rc == TF_ENOMEM ? oom("the transformation to (ia|jb)", 3 * (size_t)B2) : rc;
+    if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Co.data(), o, S.Co.data(), o, S.Cv.data(), v, mem, &h, nullptr)))
+        return rc == TF_ENOMEM ? oom("the transformation to (ki|jb)", 3 * (size_t)o * o * dim) : rc;
+    // t | tt | L, and the small arrays: eps [N] | C_v [N][v] | Ct_o [N][o] | b [o][v] | x [dim] | y [dim] | Goo [o][o] | Gvv [v][v]
+    const size_t nsmall = (size_t)N + (size_t)N * v + (size_t)N * o + 3 * (size_t)dim + (size_t)o * o + (size_t)v * v;
+    double *ops = mem.alloc(3 * (size_t)B2);
+    if (!ops) return oom("operands", 3 * (size_t)B2);
+    double *small = mem.alloc(nsmall), *d_part = mem.alloc(2 * (size_t)nblk);
+    if (!small || !d_part) return oom("partial sums", nsmall + 2 * (size_t)nblk);
+    double *t = ops, *tt = t + B2, *L = tt + B2;
+    double *d_eps = small, *d_Cv = d_eps + N, *d_Ct = d_Cv + (size_t)N * v, *d_b = d_Ct + (size_t)N * o, *d_x = d_b + dim, *d_y = d_x + dim, *d_Goo = d_y + dim,
+           *d_Gvv = d_Goo + (size_t)o * o, *d_pmin = d_part + nblk;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Cv, S.Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_cis_d_rhf: copy failed");
+    rocblas_handle blas = ctx->scf.blas;
+    BlasAtomicsOff no_atomics(blas);                          // no split-K sums: the same call gives the same bits
+    tfcisd::launch_operands(g, d_eps, n_frozen, n_occ, o, v, t, tt, L, 0);
+    // Goo[i][j] = sum_(bkc) t[i][(bkc)] L[j][(bkc)];  Gvv[b][a] = sum_(kcj) L[(kcj)][b] t[(kcj)][a]  (t and L are symmetric in their pairs)
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, v * dim, 1.0, t, v * dim, L, v * dim, 0.0, d_Goo, o));
+    CORR_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, o * dim, 1.0, L, v, t, v, 0.0, d_Gvv, v));
+    std::vector<double> Goo((size_t)o * o), Gvv((size_t)v * v), y((size_t)dim), pmin((size_t)nblk);
+    if (hipMemcpy(Goo.data(), d_Goo, Goo.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(Gvv.data(), d_Gvv, Gvv.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_cis_d_rhf: the operand kernel or the GEMMs of the intermediates failed on the device");
+    const auto t1 = corr_stamp();
+    std::chrono::steady_clock::duration d_transform{}, d_rest{};
+    // y = alpha A x + beta y for a row-major A [dim][dim]
+    auto matvec = [&](double alpha, const double *A, const double *x, double beta, double *yv) {
+        return rocblas_dgemv(blas, rocblas_operation_transpose, dim, dim, &alpha, A, dim, x, 1, &beta, yv, 1);
+    };
+    std::vector<double> Ct((size_t)N * o);
+    for (int s = 0; s < n_states; ++s) {
+        const double *bs = b + (size_t)s * dim;
+        const auto ta = corr_stamp();
+        // ---- Ct_o = C_v b^T [N][o], and the dressed block (i~ a|j b)
+        if (hipMemcpy(d_b, bs, (size_t)dim * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_d_rhf: copy failed");
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, true, N, o, v, 1.0, d_Cv, v, d_b, v, 0.0, d_Ct, o));
+        if (hipMemcpy(Ct.data(), d_Ct, Ct.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_d_rhf: copy failed");
+        DeviceBlocks state;                                   // M: gone before the next state's transformation
+        double *M = nullptr;
+        if ((rc = mo_transform_device(ctx, Ct.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, state, &M, nullptr)))
+            return rc == TF_ENOMEM ? oom("the dressed transformation", 3 * (size_t)B2) : rc;
+        const auto tb = corr_stamp();
+        // ---- M[i][a][(jb)] -= sum_k b[k][a] h[i][k][(jb)]
+        CORR_BLAS(tfmp3::gemm_rm_batched(blas, true, false, v, dim, o, -1.0, d_b, v, 0, h, dim, (long long)o * dim, 1.0, M, dim, (long long)v * dim, o));
+        tfcisd::launch_direct(M, d_eps, n_frozen, n_occ, o, v, omega[s], triplet[s], d_part, d_pmin, 0);
+        double e_direct = 0.0;
+        if (sum_partials_host(d_part, (int)nblk, 1, &e_direct) != hipSuccess ||
+            hipMemcpy(pmin.data(), d_pmin, (size_t)nblk * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_cis_d_rhf: the direct kernel failed on the device");
+        double dmin = INFINITY;
+        for (long long k = 0; k < nblk; ++k) dmin = std::min(dmin, pmin[(size_t)k]);
+        // ---- x = L b, y = tt x (singlet);  x = (2 g - L) b, y = (2 t - tt) x (triplet)
+        if (triplet[s]) {
+            CORR_BLAS(matvec(2.0, g, d_b, 0.0, d_x));
+            CORR_BLAS(matvec(-1.0, L, d_b, 1.0, d_x));
+            CORR_BLAS(matvec(2.0, t, d_x, 0.0, d_y));
+            CORR_BLAS(matvec(-1.0, tt, d_x, 1.0, d_y));
+        } else {
+            CORR_BLAS(matvec(1.0, L, d_b, 0.0, d_x));
+            CORR_BLAS(matvec(1.0, tt, d_x, 0.0, d_y));
+        }
+        if (hipMemcpy(y.data(), d_y, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess)
+            return fail(TF_ENODEVICE, "tf_cis_d_rhf: the products of the indirect part failed on the device");
+        double e_y = 0.0, e_oo = 0.0, e_vv = 0.0;
+        for (int k = 0; k < dim; ++k) e_y += bs[k] * y[(size_t)k];
+        for (int i = 0; i < o; ++i)
+            for (int j = 0; j < o; ++j) {
+                double bb = 0.0;
+                for (int a = 0; a < v; ++a) bb += bs[(size_t)i * v + a] * bs[(size_t)j * v + a];
+                e_oo += bb * Goo[(size_t)i * o + j];
+            }
+        for (int c = 0; c < v; ++c)
+            for (int a = 0; a < v; ++a) {
+                double bb = 0.0;
+                for (int i = 0; i < o; ++i) bb += bs[(size_t)i * v + a] * bs[(size_t)i * v + c];
+                e_vv += bb * Gvv[(size_t)c * v + a];
+            }
+        out->e_direct[s] = e_direct;
+        out->e_indirect[s] = (e_y - e_oo) - e_vv;
+        out->e_d[s] = out->e_direct[s] + out->e_indirect[s];
+        if (out->min_denominator) out->min_denominator[s] = dmin;
+        const auto tc = corr_stamp();
+        d_transform += tb - ta;
+        d_rest += tc - tb;
+    }
+    out->seconds[0] = corr_secs(t1 - S.t0);
+    out->seconds[1] = corr_secs(d_transform);
+    out->seconds[2] = corr_secs(d_rest);
     return TF_OK;
 }
 

@@ -11,7 +11,7 @@ CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3
 MP4[SDQ] / MP4[DQ]; full MP4 with triples through Calculation.mp4 = "SDTQ", not on the input line), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
 iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, or TD on an HF line
-(TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x).  Everything numerical runs on the GPU through the C ABI.  The initial
+(TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x; (D) or [D] adds CIS(D) to the ROOT state).  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
 """
 from __future__ import annotations
@@ -79,6 +79,7 @@ class Calculation:
     root: int = 1                                      # ROOT / STATE, calc:167
     n_states: int = 10                                 # NSTATES, calc:169
     excited_state_contribution_threshold: float = 1.0  # EXTHRESH (per cent), calc:168
+    do_perturbative_doubles: bool = False              # (D) / [D], calc:121: CIS(D) of the ROOT state after the spectrum (tuna_ci.py:2293-2295)
 
 
 @dataclass
@@ -209,6 +210,8 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.n_states = int(value())
         elif p == "EXTHRESH":
             calc.excited_state_contribution_threshold = float(value())
+        elif p in ("(D)", "[D]"):
+            calc.do_perturbative_doubles = True
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -597,7 +600,8 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
     (tuna_ci.py:2150-2290; kernel:1175-1190, :1289-1301) with its log lines (tuna_ci.py:1222-1273, :1324-1362, :1736-1863).  All states of
     the requested multiplicities are merged and sorted; out.energy = E_SCF + the excitation energy of ROOT; out.excited holds the
     merged energies, labels, |mu|, oscillator strengths, the root's X and Y and E_transition.  The root's difference density (P_diff of
-    determine_restricted_excited_state_energy_and_density) and properties on it are not formed in this build.  A TDHF run on an
+    determine_restricted_excited_state_energy_and_density) and properties on it are not formed in this build.  With
+    calc.do_perturbative_doubles the root gets its CIS(D) correction after the spectrum (run_perturbative_doubles).  A TDHF run on an
     unstable reference raises the library's TunaError (TF_ELINALG) where the reference warns and drops states."""
     n_occ, N = molecule.n_doubly_occ, molecule.n_basis
     v = N - n_occ
@@ -673,9 +677,44 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
                    "E_transition": E_transition, "root": calc.root, "method": calc.excited_state, "seconds": r["seconds"],
                    "E_singlet": r["E_singlet"], "E_triplet": r["E_triplet"], "tdm_singlet": r["tdm"]}
     out.energy = out.energy + E_transition                                                # tuna_ci.py:1642
+    if calc.do_perturbative_doubles:                                                      # tuna_ci.py:2293-2295
+        E_transition = run_perturbative_doubles(calc, molecule, out, engine, silent, log)
     if not silent:                                                                        # kernel:1295-1299
         log(f"\n Excitation energy is the energy difference to excited state {calc.root}.")
         log(f"\n Excitation energy from {f'{calc.excited_state}:':<11} {E_transition:15.10f}")
+
+
+def run_perturbative_doubles(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """CIS(D) of the ROOT state after run_excited_states (all-electron), tf_cis_d_rhf: run_perturbative_doubles and the section of
+    calculate_restricted_doubles_correction (tuna_ci.py:2090-2139, :1899-1980) at the priorities the log shows (the eV line is priority 3).
+    b = X + Y of the root, omega its excitation energy, the multiplicity from its label; out.energy and E_transition move by E_D, and
+    out.excited gains E_D, E_direct and E_indirect.  The MPC / double-hybrid scaling (:1966) is not built: there are no DFT excited
+    states here.  Returns the corrected excitation energy."""
+    ex = out.excited
+    state = calc.root - 1
+    omega = ex["E_transition"]
+    t0 = time.perf_counter()
+    r = engine.cis_d_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, b=(ex["X"] + ex["Y"])[None], omega=[omega],
+                         triplet=[int(str(ex["state_types"][state]) == "triplet")])
+    out.timings["Perturbative doubles"] = time.perf_counter() - t0
+    E_D = float(r["E_D"][0])
+    if not silent:
+        log("\n" + SPACER)                                                                # tuna_ci.py:1899-1903
+        log("          Perturbative Doubles Correction")
+        log(SPACER)
+        log(f"  Applying doubles correction to state {state + 1} only.")
+        log("\n  Building doubles amplitudes...             [Done]")                       # :1905, :1915
+        log("\n  Calculating direct contribution...         [Done]")                       # :1917, :1937
+        log("  Calculating indirect contribution...       [Done]")                         # :1939, :1958
+        # :1960 ends its line with end = "" and the restricted function never prints its [Done]: the next line follows on the same one
+        log("\n  Calculating doubles correction...         " + f"\n  Original excitation energy:       {omega:15.10f}")      # :1970
+        log(f"  Correction energy from (D):       {E_D:15.10f}")
+        log(f"\n  Corrected excitation energy:      {(E_D + omega):15.10f}")
+        log(SPACER)
+    ex.update(E_D=E_D, E_direct=float(r["E_direct"][0]), E_indirect=float(r["E_indirect"][0]), E_transition=omega + E_D,
+              min_denominator=float(r["min_denominator"][0]), seconds_doubles=r["seconds"])
+    out.energy = out.energy + E_D                                                         # tuna_ci.py:2135
+    return omega + E_D
 
 
 def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=print):
@@ -703,7 +742,7 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: MP4 runs on a closed-shell restricted reference.")
     if method in ("CIS(D)", "CIS[D]", "UCIS(D)", "UCIS[D]"):
         raise TunaError(f"{method} is not available in this build: the perturbative doubles correction to CIS is not implemented.  CIS gives the "
-                        "uncorrected states.")
+                        "uncorrected states.  The keyword (D) on a CIS, TDHF, RPA or HF ... : TD line adds the doubles correction to the ROOT state.")
     if method in ("UCIS", "UTDHF", "URPA"):
         raise TunaError(f"Unrestricted {method[1:]} is not available in this build: {method[1:]} runs on a closed-shell restricted reference.")
     excited = method if method in ("CIS", "TDHF", "RPA") else None
@@ -728,6 +767,9 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
             raise TunaError("There are no excited states to calculate!")                  # tuna_ci.py:2171
         calc.excited_state = excited
         calc.tamm_dancoff_approximation = calc.tamm_dancoff_approximation or excited == "CIS"      # tuna_ci.py:1314
+    elif calc.do_perturbative_doubles:
+        raise TunaError(f"The (D) keyword needs an excited-state method: the perturbative doubles correction applies to a CIS, TDHF, RPA or "
+                        f"HF ... : TD state, not to {method}.")
     if cc and calc.multiplicity != 1:
         raise TunaError(f"{method} is available for a closed-shell restricted reference only in this build (ML 1).")
     if cc and (calc.dipole or calc.polarisability or calc.hyperpolarisability):

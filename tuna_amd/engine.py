@@ -439,6 +439,40 @@ class Engine:
                 out[name] = a
         return out
 
+    def cis_d_rhf(self, C, eps, n_occ, n_frozen=0, *, b, omega, triplet) -> dict:
+        """CIS(D), the perturbative doubles correction to closed-shell CIS / TDHF states (tunafock.h: tf_cis_d_rhf; tuna_ci.py:1874-1982).
+        b [n_states, o, v] (or [o, v] for one state) are the normalised state vectors (CIS: X; TDHF: X + Y), omega their excitation
+        energies and triplet their flags (0 = singlet, 1 = triplet).  Returns {"E_D", "E_direct", "E_indirect", "min_denominator"
+        [n_states] (E_D = E_direct + E_indirect; min over ijab of |e_i + e_j - e_a - e_b + omega|), "seconds" = [state-independent
+        blocks, dressed transformations, kernels and GEMMs]}.  Raises TunaError on a shape mismatch before any device call."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"cis_d_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        n_occ, n_frozen = int(n_occ), int(n_frozen)
+        if not 0 <= n_frozen < n_occ < self.N:
+            raise TunaError(f"cis_d_rhf: the windows must satisfy 0 <= n_frozen < n_occ < N, got n_frozen = {n_frozen}, n_occ = {n_occ}, N = {self.N}")
+        o, v = n_occ - n_frozen, self.N - n_occ
+        b = f64(b)
+        if b.ndim == 2:
+            b = b[None]
+        omega = np.atleast_1d(f64(omega))
+        flags = np.atleast_1d(np.asarray(triplet))
+        if b.ndim != 3 or b.shape[1:] != (o, v) or b.shape[0] < 1:
+            raise TunaError(f"cis_d_rhf: b must be [n_states, {o}, {v}] with n_states >= 1, got {list(b.shape)}")
+        n = b.shape[0]
+        if omega.shape != (n,) or flags.shape != (n,):
+            raise TunaError(f"cis_d_rhf: omega and triplet must have one entry per state ({n}), got {list(omega.shape)} and {list(flags.shape)}")
+        if not all(int(f) == f and int(f) in (0, 1) for f in flags.tolist()):
+            raise TunaError(f"cis_d_rhf: every triplet flag must be 0 (singlet) or 1 (triplet), got {flags.tolist()}")
+        import ctypes
+        from ._lib import CisDResult, i32
+        b, flags = f64(b), i32(flags)
+        res = CisDResult()
+        arrays = {k: np.zeros(n) for k in ("E_D", "E_direct", "E_indirect", "min_denominator")}
+        res.e_d, res.e_direct, res.e_indirect, res.min_denominator = (ptr(arrays[k]) for k in ("E_D", "E_direct", "E_indirect", "min_denominator"))
+        self._check(self._L.tf_cis_d_rhf(self._ctx, n_occ, n_frozen, ptr(C), ptr(eps), n, ptr(b), ptr(omega), ptr(flags), ctypes.byref(res)))
+        return dict(arrays, seconds=list(res.seconds))
+
     def mp3_ladder_probe(self, T) -> np.ndarray:
         """Zh[p] = the stored-triangle ladder contraction of the packed tensor with T[p] ([N,N] or [n,N,N], any matrices), by the kernel
         and the batching of mp3_rhf (tunafock.h: tf_mp3_ladder_probe); Z[T] = Zh[T] + Zh[T^T]^T."""
