@@ -125,6 +125,41 @@ def test_unrestricted_cycle_matches_reference(engine, uhf_golden, tag, damping):
     np.testing.assert_allclose(out.table[:n, 6], ref[:n, 6], atol=1e-6)
 
 
+@pytest.mark.parametrize("symbol,na,nb,max_diis,damping", [("H", 1, 0, 6, True), ("H", 1, 0, 6, False), ("LI", 2, 1, 2, False), ("LI", 2, 1, 3, True)])
+def test_unrestricted_cycle_without_beta_electrons_and_with_a_trimmed_history(engine, symbol, na, nb, max_diis, damping):
+    """tf_scf_uhf on H and Li / 6-31G (n = 2, 9) where the other unrestricted tests do not go: n_beta = 0 (the beta density is the zero
+    matrix, no beta solve) and a DIIS history of 2 or 3 entries over more iterations than that (an entry leaves in every iteration,
+    its slot is reused).  Against oracle/scf_oracle.run_uhf on the library's own J and K, with the tolerances of
+    test_unrestricted_cycle_matches_reference.  (The Li quartet, n_beta = 0 over ten iterations, is not a case here: its DIIS iterates
+    are rounding-driven -- the cycle and the oracle differ by 1.1e-6 Eh in iteration 7 and agree to 4e-14 at convergence -- so it is
+    compared between builds instead, tools/gpu_scf_cycle_ab.py.)"""
+    atoms = mol.make_atoms([symbol], None)
+    shells = mol.build_shells(atoms, "6-31G")
+    engine.set_basis(mol.expand_cartesian_aos(shells)).build_eri(True)
+    xyz, chg, org = atom_arrays(atoms)
+    S, T, V, _, _ = engine.one_electron(xyz, chg, org, spherical=True)
+    X, _, _ = so.orthogonaliser(S)
+    Pa0, Pb0, E0 = so.core_guess_uhf(T, V, X, na, nb)
+    o = so.run_uhf(S, T, V, None, X, Pa0, Pb0, E0, na, nb, 0.0, [engine.N], conv="extreme", max_diis=max_diis, damping=damping, jk=engine.fock_jk)
+    r = engine.scf_uhf(S, T, V, Pa0, Pb0, E0, na, nb, 0.0, X=X, conv="extreme", max_diis=max_diis, damping="dynamic" if damping else "none",
+                       n_atom_ao=[engine.N])
+    n = min(r["n_iter"], o["n_iter"])
+    print(f"\n[{symbol} {na}/{nb}, DIIS {max_diis}, damping {damping}] iterations {r['n_iter']} / {o['n_iter']}, dE {abs(r['energy'] - o['energy']):.1e}, "
+          f"table dE {np.abs(r['table'][:n, 1] - o['table'][:n, 1]).max():.1e}, "
+          f"d(eps) {max(np.abs(r['epsilons_spin'][0] - o['epsilons_alpha']).max(), np.abs(r['epsilons_spin'][1] - o['epsilons_beta']).max()):.1e}")
+    assert r["converged"] and abs(r["energy"] - o["energy"]) < 1e-9
+    np.testing.assert_allclose(r["epsilons_spin"][0], o["epsilons_alpha"], atol=1e-7)
+    np.testing.assert_allclose(r["epsilons_spin"][1], o["epsilons_beta"], atol=1e-7)
+    if nb:
+        assert r["n_iter"] > max_diis + 2                            # the history was trimmed more than once
+    else:
+        assert np.array_equal(r["P_spin"][1], np.zeros_like(S))
+    assert abs(np.trace(r["P_spin"][0] @ S) - na) < 1e-9 and abs(np.trace(r["P_spin"][1] @ S) - nb) < 1e-9
+    assert abs(r["n_iter"] - o["n_iter"]) <= 1
+    np.testing.assert_allclose(r["table"][:n, 1], o["table"][:n, 1], atol=2e-8)
+    np.testing.assert_allclose(r["table"][:n, 6], o["table"][:n, 6], atol=1e-6)
+
+
 def test_native_and_host_orchestrated_unrestricted_cycles_agree(engine, monkeypatch):
     """tf_scf_uhf (whole cycle in the library) against the host-orchestrated loop (the path a sharded tensor takes): same
     trajectory, same orbitals."""

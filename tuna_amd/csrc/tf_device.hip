@@ -3469,6 +3469,35 @@ struct ShardedCycleGuard {
         if (on && ctx->scf.blas) (void)rocblas_set_atomics_mode(ctx->scf.blas, rocblas_atomics_allowed);
     }
 };
+
+// The J/K hook of the native cycles: J and K of the iteration's nd densities (1: restricted, 2: both spins in one fused pass),
+// summed over the ranks of a sharded tensor
+static int cycle_jk(tf_ctx *ctx, int nd, const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st)
+{
+    const double *p[2] = {dPa, dPb};
+    double *j[2] = {dJa, dJb}, *k[2] = {dKa, dKb};
+    ctx->jk_try_class_diagonal = true;                              // (a cycle's densities are class-diagonal unless a field along x / y mixes the classes)
+    int rcj = launch_jk(ctx, nd, p, j, k, st);
+    ctx->jk_try_class_diagonal = false;
+    return rcj ? rcj : allreduce_jk(ctx, nd, j, k, st);
+}
+
+// What tf_scf_uhf and tf_scf_uks do alike once each has checked its arguments; xc empty for Hartree-Fock (its failures go to msg)
+static int scf_unrestricted(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V, const double *Fext,
+                            const double *X, const double *P0_alpha, const double *P0_beta, double E0, int n_alpha, int n_beta, double V_NN,
+                            tf_scf_uhf_result *out, std::string &msg, const tfscf::XC2Fn &xc)
+{
+    auto jk2 = [&](const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st) {
+        return cycle_jk(ctx, 2, dPa, dPb, dJa, dJb, dKa, dKb, st);
+    };
+    tfscf::UhfOut uo;
+    for (int sp = 0; sp < 2; ++sp) { uo.P[sp] = out->P_spin[sp]; uo.C[sp] = out->C_spin[sp]; uo.eps[sp] = out->eps_spin[sp]; uo.F[sp] = out->F_spin[sp]; }
+    ShardedCycleGuard guard(ctx);
+    offer_symmetry(ctx, ctx->scf, ctx->N);
+    int rc = tfscf::run_uhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, jk2, out->common, uo, msg, xc);
+    if (rc && !msg.empty()) ctx->err = msg;
+    return rc;
+}
 }
 
 int tf_scf_rhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V, const double *Fext,
@@ -3479,14 +3508,7 @@ int tf_scf_rhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     if (!opts || !S || !T || !V || !P0 || !out || n_occ < 1 || n_occ > ctx->N) TF_FAIL(ctx, TF_EINVAL, "tf_scf_rhf: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string msg;
-    auto jk = [&](const double *dP, double *dJ, double *dK, hipStream_t st) {
-        const double *p[2] = {dP, dP};
-        double *j[2] = {dJ, dJ}, *k[2] = {dK, dK};
-        ctx->jk_try_class_diagonal = true;                          // (a cycle's densities are class-diagonal unless a field along x / y mixes the classes)
-        int rcj = launch_jk(ctx, 1, p, j, k, st);
-        ctx->jk_try_class_diagonal = false;
-        return rcj ? rcj : allreduce_jk(ctx, 1, j, k, st);
-    };
+    auto jk = [&](const double *dP, double *dJ, double *dK, hipStream_t st) { return cycle_jk(ctx, 1, dP, dP, dJ, dJ, dK, dK, st); };
     tfscf::XCFn xc;
     if (ctx->grid.G > 0) {
         if (ctx->grid.N != ctx->N) TF_FAIL(ctx, TF_EINVAL, "tf_scf_rhf: the DFT grid was set up for a different AO dimension");
@@ -3494,7 +3516,7 @@ int tf_scf_rhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     }
     ShardedCycleGuard guard(ctx);
     offer_symmetry(ctx, ctx->scf, ctx->N);
-    int rc = tfscf::run_rhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0, E0, n_occ, V_NN, jk, ctx->world, *out, msg, xc);
+    int rc = tfscf::run_rhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0, E0, n_occ, V_NN, jk, *out, msg, xc);
     if (rc && !msg.empty()) ctx->err = msg;
     return rc;
 }
@@ -3597,7 +3619,7 @@ int tf_scf_rhf_batch(tf_ctx *ctx, int n_cycles, const tf_scf_opts *opts, const d
             tfscf::t_stream = st;
             auto jk = [&](const double *dP, double *dJ, double *dK, hipStream_t s2) { return ls.fock(dP, dJ, dK, s2); };
             offer_symmetry(ctx, *ctx->scf_batch[(size_t)c], ctx->N);
-            rcs[(size_t)c] = tfscf::run_rhf(*ctx->scf_batch[(size_t)c], ctx->N, *opts, S, T, V, Fext ? Fext[c] : nullptr, X, P0[c], E0[c], n_occ, V_NN, jk, 1,
+            rcs[(size_t)c] = tfscf::run_rhf(*ctx->scf_batch[(size_t)c], ctx->N, *opts, S, T, V, Fext ? Fext[c] : nullptr, X, P0[c], E0[c], n_occ, V_NN, jk,
                                              out[c], msgs[(size_t)c], tfscf::XCFn());
             (void)hipStreamSynchronize(st);
             ls.finish(st);
@@ -3628,24 +3650,8 @@ int tf_scf_uhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
         TF_FAIL(ctx, TF_EINVAL, "tf_scf_uhf: unrestricted Kohn-Sham is not implemented by the Hartree-Fock entry point (call tf_scf_uks, or tf_dft_clear)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string msg;
-    auto jk2 = [&](const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st) {
-        const double *p[2] = {dPa, dPb};
-        double *j[2] = {dJa, dJb}, *k[2] = {dKa, dKb};
-        ctx->jk_try_class_diagonal = true;
-        int rcj = launch_jk(ctx, 2, p, j, k, st);
-        ctx->jk_try_class_diagonal = false;
-        return rcj ? rcj : allreduce_jk(ctx, 2, j, k, st);
-    };
-    tfscf::UhfOut uo;
-    for (int sp = 0; sp < 2; ++sp) { uo.P[sp] = out->P_spin[sp]; uo.C[sp] = out->C_spin[sp]; uo.eps[sp] = out->eps_spin[sp]; uo.F[sp] = out->F_spin[sp]; }
-    ShardedCycleGuard guard(ctx);
-    offer_symmetry(ctx, ctx->scf, ctx->N);
-    int rc = tfscf::run_uhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, jk2, ctx->world,
-                            out->common, uo, msg);
-    if (rc && !msg.empty()) ctx->err = msg;
-    return rc;
+    return scf_unrestricted(ctx, opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, out, msg, tfscf::XC2Fn());
 }
-
 
 int tf_scf_uks(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const double *T, const double *V, const double *Fext,
                const double *X, const double *P0_alpha, const double *P0_beta, double E0, int n_alpha, int n_beta, double V_NN,
@@ -3660,25 +3666,10 @@ int tf_scf_uks(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: unrestricted Kohn-Sham runs on an unsharded tensor (world = 1) in this build");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string msg;
-    auto jk2 = [&](const double *dPa, const double *dPb, double *dJa, double *dJb, double *dKa, double *dKb, hipStream_t st) {
-        const double *p[2] = {dPa, dPb};
-        double *j[2] = {dJa, dJb}, *k[2] = {dKa, dKb};
-        ctx->jk_try_class_diagonal = true;
-        int rcj = launch_jk(ctx, 2, p, j, k, st);
-        ctx->jk_try_class_diagonal = false;
-        return rcj ? rcj : allreduce_jk(ctx, 2, j, k, st);
-    };
     tfscf::XC2Fn xc = [&](const double *dPa, const double *dPb, double *dVa, double *dVb, double *o5) {
         return tfdft::vxc_unrestricted(ctx->scf.blas, ctx->grid, dPa, dPb, dVa, dVb, o5, msg);
     };
-    tfscf::UhfOut uo;
-    for (int sp = 0; sp < 2; ++sp) { uo.P[sp] = out->P_spin[sp]; uo.C[sp] = out->C_spin[sp]; uo.eps[sp] = out->eps_spin[sp]; uo.F[sp] = out->F_spin[sp]; }
-    ShardedCycleGuard guard(ctx);
-    offer_symmetry(ctx, ctx->scf, ctx->N);
-    int rc = tfscf::run_uhf(ctx->scf, ctx->N, *opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, jk2, ctx->world,
-                            out->common, uo, msg, xc);
-    if (rc && !msg.empty()) ctx->err = msg;
-    return rc;
+    return scf_unrestricted(ctx, opts, S, T, V, Fext, X, P0_alpha, P0_beta, E0, n_alpha, n_beta, V_NN, out, msg, xc);
 }
 
 }  // extern "C"

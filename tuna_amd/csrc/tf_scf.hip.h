@@ -10,8 +10,10 @@
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <string>
@@ -20,9 +22,7 @@
 #include "../../include/tunafock.h"
 #include "tf_jacobi.hip.h"
 #include "tf_refine.hip.h"
-#include <algorithm>
-#include <cstdio>
-#include <vector>
+#include "tf_scf_host.h"   // the host arithmetic of an iteration: small_solve, DiisHistory, damping_factor_tail, scf_converged
 
 namespace tfscf {
 
@@ -988,33 +988,6 @@ inline int ref_store(Workspace &w, int n, const double *V, std::string &msg, int
     return TF_OK;
 }
 
-inline bool small_solve(int m, std::vector<double> A, std::vector<double> b, std::vector<double> &x)
-{
-    for (int c = 0; c < m; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < m; ++r)
-            if (std::fabs(A[r * m + c]) > std::fabs(A[piv * m + c])) piv = r;
-        if (A[piv * m + c] == 0.0 || !std::isfinite(A[piv * m + c])) return false;
-        if (piv != c) {
-            for (int k = 0; k < m; ++k) std::swap(A[c * m + k], A[piv * m + k]);
-            std::swap(b[c], b[piv]);
-        }
-        for (int r = c + 1; r < m; ++r) {
-            const double f = A[r * m + c] / A[c * m + c];
-            if (f == 0.0) continue;
-            for (int k = c; k < m; ++k) A[r * m + k] -= f * A[c * m + k];
-            b[r] -= f * b[c];
-        }
-    }
-    x.assign(m, 0.0);
-    for (int r = m - 1; r >= 0; --r) {
-        double s = b[r];
-        for (int k = r + 1; k < m; ++k) s -= A[r * m + k] * x[k];
-        x[r] = s / A[r * m + r];
-    }
-    return true;
-}
-
 // X = S^-1/2, S^-1, smallest eigenvalue (kernel:756-816).  The reference forms V sqrt(s) V^T and inverts it with
 // LAPACK; here the inverse is applied in the eigenbasis, X = V s^-1/2 V^T, which is the same matrix.
 inline int orthogonaliser_device(Workspace &w, int n, const double *dS, double *dX, double *dSinv, double *smallest, double *scratch,
@@ -1151,13 +1124,260 @@ using JKFn = std::function<int(const double *, double *, double *, hipStream_t)>
 // Kohn-Sham hook: V_XC (device [N,N]) and {n_elec, E_X, E_C} for the device density (tf_dft.hip.h); empty for Hartree-Fock
 using XCFn = std::function<int(const double *, double *, double *)>;
 
+// ---- the stages run_rhf and run_uhf share ---------------------------------------------------------------------
+// Each stage queues, on TFS_ST and in this order, the device work its text queued when it stood in both cycles.
+
+// device-time spans without synchronising inside the cycle: events from a pool, read after the last iteration
+struct SpanTimer {
+    Workspace &w;
+    size_t used = 0;
+    std::vector<std::pair<size_t, int>> spans;                    // (first event index, 0 = Fock build, 1 = eigensolver)
+    int begin(int kind)
+    {
+        while (w.tev.size() < used + 2) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return -1;
+            w.tev.push_back(e);
+        }
+        spans.emplace_back(used, kind);
+        (void)hipEventRecord(w.tev[used], TFS_ST);
+        used += 2;
+        return (int)used - 1;
+    }
+    void end(int idx) { if (idx >= 0) (void)hipEventRecord(w.tev[idx], TFS_ST); }
+    void read(tf_scf_result &out) const                           // after a synchronisation
+    {
+        for (const auto &sp : spans) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, w.tev[sp.first], w.tev[sp.first + 1]) == hipSuccess) (sp.second == 0 ? out.fock_seconds : out.eig_seconds) += ms * 1e-3;
+        }
+    }
+};
+
+// What the two cycles hold alike: the sizes, the matrices every stage works on (each cycle's own mat(k)), the span timer
+struct CycleBase {
+    Workspace &w;
+    int n; size_t nn; int g;                                      // g: blocks of 256 threads over nn elements
+    double *dS, *dH, *dX, *dT, *dV, *dFx, *t1, *t2, *dW, *dC, *scr, *vals, *ework;
+    SpanTimer spans;
+};
+
+// One matrix of every history entry: logical entry k at base + slot * stride (DiisHistory, tf_scf_host.h)
+struct HistMats {
+    const DiisHistory &H;
+    double *base;
+    size_t stride;
+    double *operator()(int k) const { return base + (size_t)H.slot_of(k) * stride; }
+};
+
+// Prologue, in three steps around the upload of the cycle's own guess densities: S, T, V and the field term; H = T + V (+ field);
+// X from the host or from S
+inline int upload_integrals(CycleBase &c, const double *S, const double *T, const double *V, const double *Fext, std::string &msg)
+{
+    TFS_HIP(tfs_memcpy(c.dS, S, c.nn * sizeof(double), hipMemcpyHostToDevice));
+    TFS_HIP(tfs_memcpy(c.dT, T, c.nn * sizeof(double), hipMemcpyHostToDevice));
+    TFS_HIP(tfs_memcpy(c.dV, V, c.nn * sizeof(double), hipMemcpyHostToDevice));
+    if (Fext) TFS_HIP(tfs_memcpy(c.dFx, Fext, c.nn * sizeof(double), hipMemcpyHostToDevice));
+    else TFS_HIP(hipMemsetAsync(c.dFx, 0, c.nn * sizeof(double), TFS_ST));
+    return TF_OK;
+}
+inline void core_hamiltonian(CycleBase &c)
+{
+    hipLaunchKernelGGL(k_axpby, dim3(c.g), dim3(256), 0, TFS_ST, 1.0, c.dT, 1.0, c.dV, c.dH, (int)c.nn);      // H = T + V (+ field)
+    hipLaunchKernelGGL(k_axpby, dim3(c.g), dim3(256), 0, TFS_ST, 1.0, c.dH, 1.0, c.dFx, c.dH, (int)c.nn);
+}
+inline int take_orthogonaliser(CycleBase &c, const double *X, double *scratch, std::string &msg)
+{
+    double sm = 0;
+    if (!X) return orthogonaliser_device(c.w, c.n, c.dS, c.dX, nullptr, &sm, scratch, msg);
+    TFS_HIP(tfs_memcpy(c.dX, X, c.nn * sizeof(double), hipMemcpyHostToDevice));
+    return TF_OK;
+}
+
+// dW = sym(X^T F X)
+inline int fock_to_orthogonal(CycleBase &c, const double *Fao, std::string &msg)
+{
+    TFS_BLAS(gemm_rm(c.w.blas, true, false, c.n, 1.0, c.dX, Fao, 0.0, c.t1));     // X^T F
+    TFS_BLAS(gemm_rm(c.w.blas, false, false, c.n, 1.0, c.t1, c.dX, 0.0, c.t2));   // (X^T F) X
+    hipLaunchKernelGGL(k_symmetrise, dim3(c.g), dim3(256), 0, TFS_ST, c.t2, c.dW, c.n);
+    return TF_OK;
+}
+
+// F = sym(H + J - hfx/2 K (+ V_XC))   (scf:497-531, 542-589)
+inline void assemble_fock(CycleBase &c, const double *dJ, const double *dK, double hfx, const double *dVxc, double *dF)
+{
+    hipLaunchKernelGGL(k_fock, dim3(c.g), dim3(256), 0, TFS_ST, c.dH, dJ, dK, hfx, c.t1, (int)c.nn);
+    if (dVxc) hipLaunchKernelGGL(k_axpby, dim3(c.g), dim3(256), 0, TFS_ST, 1.0, c.t1, 1.0, dVxc, c.t1, (int)c.nn);        // + V_XC, scf:525
+    hipLaunchKernelGGL(k_symmetrise, dim3(c.g), dim3(256), 0, TFS_ST, c.t1, dF, c.n);
+}
+
+// DIIS error e = X^T (F P S - S P F) X into histE, F into histF   (scf:906-920)
+inline int diis_error(CycleBase &c, const double *dF, const double *dP, double *histE, double *histF, std::string &msg)
+{
+    rocblas_handle h = c.w.blas;
+    const int n = c.n;
+    TFS_BLAS(gemm_rm(h, false, false, n, 1.0, dF, dP, 0.0, c.t1));          // F P
+    TFS_BLAS(gemm_rm(h, false, false, n, 1.0, c.t1, c.dS, 0.0, c.t2));      // F P S
+    TFS_BLAS(gemm_rm(h, false, false, n, 1.0, c.dS, dP, 0.0, c.t1));        // S P
+    TFS_BLAS(gemm_rm(h, false, false, n, -1.0, c.t1, dF, 1.0, c.t2));       // F P S - S P F
+    TFS_BLAS(gemm_rm(h, true, false, n, 1.0, c.dX, c.t2, 0.0, c.t1));       // X^T e
+    TFS_BLAS(gemm_rm(h, false, false, n, 1.0, c.t1, c.dX, 0.0, histE));     // (X^T e) X
+    TFS_HIP(hipMemcpyAsync(histF, dF, c.nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
+    return TF_OK;
+}
+
+// <e_k, e_newest> for every entry of the history into out[k], eight scalar products per launch
+inline void history_dots(CycleBase &c, const HistMats &histE, double *out)
+{
+    const int n_hist = histE.H.n_hist;
+    for (int k0 = 0; k0 < n_hist; k0 += 8) {
+        Ptr8 a;
+        const int mk = std::min(8, n_hist - k0);
+        for (int k = 0; k < 8; ++k) { a.p[k] = histE(0); a.c[k] = 0.0; }
+        for (int k = 0; k < mk; ++k) a.p[k] = histE(k0 + k);
+        launch_multi_dot(c.w, histE(n_hist - 1), a, mk, (int)c.nn, out + k0);
+    }
+}
+
+// <P, T>, <P, V>, <P, field>, <P, J>, <P, K> into out[0..4]: read back at the end of the iteration, together with the density changes
+inline void energy_dots(CycleBase &c, const double *dPn, const double *dJ, const double *dK, double *out)
+{
+    Ptr8 a;
+    for (int k = 0; k < 8; ++k) { a.p[k] = c.dT; a.c[k] = 0.0; }
+    a.p[0] = c.dT; a.p[1] = c.dV; a.p[2] = c.dFx; a.p[3] = dJ; a.p[4] = dK;
+    launch_multi_dot(c.w, dPn, a, 5, (int)c.nn, out);
+}
+
+// scr = sum_k x_k F_k   (scf:1025)
+inline void extrapolate_fock(CycleBase &c, const HistMats &histF, const std::vector<double> &x)
+{
+    const int n_hist = histF.H.n_hist;
+    for (int k0 = 0; k0 < n_hist; k0 += 8) {
+        Ptr8 a;
+        const int mk = std::min(8, n_hist - k0);
+        for (int k = 0; k < 8; ++k) { a.p[k] = histF(0); a.c[k] = 0.0; }
+        for (int k = 0; k < mk; ++k) { a.p[k] = histF(k0 + k); a.c[k] = x[k0 + k]; }
+        hipLaunchKernelGGL(k_lincomb, dim3(c.g), dim3(256), 0, TFS_ST, a, mk, c.scr, (int)c.nn, k0 > 0 ? 1 : 0);
+    }
+}
+
+// diagonalise F (AO) -> eps, C ; P = occ C_occ C_occ^T symmetrised      (scf:222-250, 183-211; occ = 2, or 1 per spin: scf:1227-1228)
+// After the first solve of a cycle the density comes from refined eigenvectors: GEMM-based for n > 64 (where the eigensolver
+// would be rocsolver_dsyevd), one LDS-resident launch for n <= 64 (where it would be the Jacobi kernel).  `current`: vals and dC
+// hold the eigenpairs of Fao (a full solve).  TF_REFINE_CHECK (debugging) compares every refined density with a real eigensolve.
+inline int density_from_fock(CycleBase &c, int n_occ, double occ, const double *Fao, double *Pout, bool &current, std::string &msg)
+{
+    Workspace &w = c.w;
+    const int n = c.n, g = c.g;
+    double *t1 = c.t1, *t2 = c.t2, *dW = c.dW, *dC = c.dC;
+    static const bool no_refine = getenv("TF_EIGH") != nullptr;
+    static const bool no_fused = getenv("TF_REFINE_UNFUSED") != nullptr;
+    const bool refining = !no_refine && n >= 2 && n_occ > 0 && n_occ < n;
+    const double zero = 0.0;
+    current = false;
+    if (refining && !no_fused && n <= TFR_NMAX && w.ref_n == n && !getenv("TF_REFINE_CHECK")) {
+        const int te = c.spans.begin(1);
+        std::string rmsg;
+        const int rr = ref_density_lds(w, n, n_occ, Fao, c.dX, Pout, occ, rmsg);
+        c.spans.end(te);
+        if (rr == TF_OK) return TF_OK;
+        if (rr != TF_ELINALG) { msg = rmsg; return rr; }
+    }
+    int r = fock_to_orthogonal(c, Fao, msg);
+    if (r) return r;
+    const int te = c.spans.begin(1);
+    if (refining && w.ref_n == n) {
+        double *Xocc = nullptr;
+        std::string rmsg;
+        const int rr = (n <= TFR_NMAX) ? ref_refine_lds(w, n, n_occ, dW, &Xocc, rmsg)
+                     : (w.blk_ref_n == n)  ? ref_refine_blocks(w, n, dW, &Xocc, rmsg) : ref_refine(w, n, n_occ, dW, &Xocc, rmsg);
+        if (rr == TF_OK) {
+            TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, Xocc, c.dX, 0.0, t1));    // rows: occupied orbitals in the AO basis (others 0)
+            TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_none, rocblas_operation_transpose, n, n, n, &occ, t1, n, t1, n, &zero, t2, n));
+            hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, Pout, n);
+            c.spans.end(te);
+            if (getenv("TF_REFINE_CHECK")) {                 // debugging aid: the same density from a real eigensolve
+                std::vector<double> hp(c.nn), hq(c.nn);
+                TFS_HIP(tfs_memcpy(hp.data(), Pout, c.nn * sizeof(double), hipMemcpyDeviceToHost));
+                int r2 = eigh(w, n, dW, c.vals, c.ework, msg);
+                if (r2) return r2;
+                TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, c.dX, dW, 0.0, dC));
+                TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_transpose, rocblas_operation_none, n, n, n_occ, &occ, dC, n, dC, n, &zero, t1, n));
+                hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, t2, n);
+                TFS_HIP(tfs_memcpy(hq.data(), t2, c.nn * sizeof(double), hipMemcpyDeviceToHost));
+                double dmax = 0.0;
+                for (size_t q = 0; q < c.nn; ++q) dmax = std::max(dmax, std::fabs(hp[q] - hq[q]));
+                fprintf(stderr, "[tf refine] max |P_refined - P_eigh| = %.3e\n", dmax);
+            }
+            return TF_OK;
+        }
+        if (rr != TF_ELINALG) { msg = rmsg; return rr; }
+    }
+    r = eigh(w, n, dW, c.vals, c.ework, msg);
+    if (r) return r;
+    if (refining) { r = ref_store(w, n, dW, msg, n_occ); if (r) return r; }
+    c.spans.end(te);
+    TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, c.dX, dW, 0.0, dC));      // C = X V   (dW rows = eigenvectors)
+    // col-major view of dC is C^T: P = sum_{k<nocc} C[:,k] C[:,k]^T = M[:nocc,:]^T M[:nocc,:]
+    TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_transpose, rocblas_operation_none, n, n, n_occ, &occ, dC, n, dC, n, &zero, t1, n));
+    hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, Pout, n);
+    current = true;
+    return TF_OK;
+}
+
+// orbitals and orbital energies of a cycle's last Fock matrix, when its last density did not come from a full solve of it
+// (what the reference's last diagonalisation leaves, scf:1133, 1224-1225)
+inline int final_orbitals(CycleBase &c, const double *dF, double *eps, double *C, std::string &msg)
+{
+    int rc = fock_to_orthogonal(c, dF, msg);
+    if (rc) return rc;
+    const int te = c.spans.begin(1);
+    rc = eigh(c.w, c.n, c.dW, c.vals, c.ework, msg);
+    if (rc) return rc;
+    TFS_BLAS(gemm_rm(c.w.blas, false, true, c.n, 1.0, c.dX, c.dW, 0.0, c.dC));
+    c.spans.end(te);
+    if (eps) TFS_HIP(tfs_memcpy(eps, c.vals, c.n * sizeof(double), hipMemcpyDeviceToHost));
+    if (C) TFS_HIP(tfs_memcpy(C, c.dC, c.nn * sizeof(double), hipMemcpyDeviceToHost));
+    return TF_OK;
+}
+
+// The table row of an iteration, its convergence test (scf:261-333), and the agreement of the ranks on both
+inline int report_iteration(Workspace &w, const tf_scf_opts &o, tf_scf_result &out, int step, int n_hist, double E_total, double dE,
+                            double rmsDP, double maxDP, double commutator, double damp, std::string &msg)
+{
+    out.n_iter = step;
+    if (out.table) {
+        double *row = out.table + (size_t)(step - 1) * 7;
+        row[0] = step; row[1] = E_total; row[2] = dE; row[3] = rmsDP; row[4] = maxDP; row[5] = commutator; row[6] = damp;
+    }
+    const bool conv_now = scf_converged(o, dE, maxDP, rmsDP, commutator);
+    if (w.agree) {                                               // collective control flow on a sharded tensor
+        const double vals[3] = {conv_now ? 1.0 : 0.0, (double)n_hist, (double)step};
+        int rc = w.agree(vals, 3, msg);
+        if (rc) return rc;
+    }
+    out.converged = conv_now;
+    return TF_OK;
+}
+
+// Epilogue, after the last synchronisation and the copies of the cycle's own matrices
+inline int finish_cycle(const CycleBase &c, const tf_scf_opts &o, tf_scf_result &out, double E_total, const double comps[7],
+                        std::chrono::steady_clock::time_point t_wall, std::string &msg)
+{
+    c.spans.read(out);
+    out.energy = E_total;
+    std::memcpy(out.components, comps, 7 * sizeof(double));
+    out.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wall).count();
+    if (!out.converged) { msg = "Self-consistent field not converged in " + std::to_string(o.max_iter) + " iterations! Increase maximum iterations or give up."; return TF_ENOTCONV; }
+    return TF_OK;
+}
+
+// world > 1: the J/K hook completes the partial sums of this rank's tensor rows with the communicator (tf_comm_init) or the registered
+// all-reduce (tf_set_allreduce); every rank then runs the O(N^3) steps redundantly on identical data
 inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, const double *T, const double *V, const double *Fext,
-                   const double *X, const double *P0, double E0, int n_occ, double V_NN, const JKFn &jk, int world,
+                   const double *X, const double *P0, double E0, int n_occ, double V_NN, const JKFn &jk,
                    tf_scf_result &out, std::string &msg, const XCFn &xc = XCFn())
 {
-    // world > 1: the J/K hook completes the partial sums of this rank's tensor rows with the communicator (tf_comm_init) or the registered all-reduce (tf_set_allreduce);
-    // every rank then runs the O(N^3) steps redundantly on identical data
-    (void)world;
     if (o.max_diis > TF_MAX_DIIS) { msg = "tf_scf_rhf: at most 64 DIIS matrices are held by the native cycle"; return TF_EINVAL; }
     const int max_diis = std::max(1, (int)o.max_diis);
     const int n_mats = 22 + 2 * max_diis;
@@ -1174,113 +1394,20 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     double *dC = mat(16), *dW = mat(17), *dPn = mat(18), *scr = mat(19), *dVxc = mat(20), *dCsave = mat(21);
     double *hist = mat(22);
     double *vals = base + (size_t)n_mats * nn, *ework = vals + n, *vals_save = ework + n;
-    // logical history entry k lives in physical slot slot[k]: trimming the oldest entry renumbers, nothing is copied
-    std::vector<int> slot(max_diis);
-    for (int k = 0; k < max_diis; ++k) slot[k] = k;
-    auto histF = [&](int k) { return hist + (size_t)(2 * slot[k]) * nn; };
-    auto histE = [&](int k) { return hist + (size_t)(2 * slot[k] + 1) * nn; };
+    CycleBase c{w, n, nn, g, dS, dH, dX, dT, dV, dFx, t1, t2, dW, dC, scr, vals, ework, SpanTimer{w}};
+    DiisHistory H(max_diis);
+    const HistMats histF{H, hist, 2 * nn}, histE{H, hist + nn, 2 * nn};
 
-    TFS_HIP(tfs_memcpy(dS, S, nn * sizeof(double), hipMemcpyHostToDevice));
-    TFS_HIP(tfs_memcpy(dT, T, nn * sizeof(double), hipMemcpyHostToDevice));
-    TFS_HIP(tfs_memcpy(dV, V, nn * sizeof(double), hipMemcpyHostToDevice));
-    if (Fext) TFS_HIP(tfs_memcpy(dFx, Fext, nn * sizeof(double), hipMemcpyHostToDevice));
-    else TFS_HIP(hipMemsetAsync(dFx, 0, nn * sizeof(double), TFS_ST));
+    rc = upload_integrals(c, S, T, V, Fext, msg);
+    if (rc) return rc;
     TFS_HIP(tfs_memcpy(dP, P0, nn * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dT, 1.0, dV, dH, (int)nn);      // H = T + V (+ field)
-    hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dH, 1.0, dFx, dH, (int)nn);
-    if (X) TFS_HIP(tfs_memcpy(dX, X, nn * sizeof(double), hipMemcpyHostToDevice));
-    else {
-        double sm = 0;
-        rc = orthogonaliser_device(w, n, dS, dX, nullptr, &sm, scr - 0 /*uses scr..*/, msg);
-        if (rc) return rc;
-    }
-    TFS_HIP(hipMemsetAsync(dPold, 0, nn * sizeof(double), TFS_ST));
-    TFS_HIP(hipMemsetAsync(dPbd, 0, nn * sizeof(double), TFS_ST));
-    TFS_HIP(hipMemsetAsync(dPvold, 0, nn * sizeof(double), TFS_ST));
-    TFS_HIP(hipMemsetAsync(dPoldbd, 0, nn * sizeof(double), TFS_ST));
-
+    core_hamiltonian(c);
+    rc = take_orthogonaliser(c, X, scr, msg);
+    if (rc) return rc;
+    for (double *zeroed : {dPold, dPbd, dPvold, dPoldbd}) TFS_HIP(hipMemsetAsync(zeroed, 0, nn * sizeof(double), TFS_ST));
     TFS_BLAS(rocblas_set_pointer_mode(w.blas, rocblas_pointer_mode_host));
-    // device-time spans without synchronising inside the cycle: events from a pool, read after the last iteration
-    size_t tev_used = 0;
-    std::vector<std::pair<size_t, int>> spans;                    // (first event index, 0 = Fock build, 1 = eigensolver)
-    auto span_begin = [&](int kind) -> int {
-        while (w.tev.size() < tev_used + 2) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return -1;
-            w.tev.push_back(e);
-        }
-        spans.emplace_back(tev_used, kind);
-        (void)hipEventRecord(w.tev[tev_used], TFS_ST);
-        tev_used += 2;
-        return (int)tev_used - 1;
-    };
-    auto span_end = [&](int idx) { if (idx >= 0) (void)hipEventRecord(w.tev[idx], TFS_ST); };
-
-    // diagonalise F (AO) -> eps, C ; P = 2 C_occ C_occ^T symmetrised      (scf:222-250, 183-211)
-    // After the first solve of a cycle the density comes from refined eigenvectors: GEMM-based for n > 64 (where the eigensolver
-    // would be rocsolver_dsyevd), one LDS-resident launch for n <= 64 (where it would be the Jacobi kernel).
-    static const bool no_refine = getenv("TF_EIGH") != nullptr;
-    const bool refining = !no_refine && n >= 2 && n_occ > 0 && n_occ < n;
     bool orbitals_current = false, orbitals_final = false;
     w.ref_n = 0; w.blk_ref_n = 0;
-    static const bool no_fused = getenv("TF_REFINE_UNFUSED") != nullptr;
-    auto diag_density = [&](const double *Fao, double *Pout) -> int {
-        if (refining && !no_fused && n <= TFR_NMAX && w.ref_n == n && !getenv("TF_REFINE_CHECK")) {
-            const int te = span_begin(1);
-            std::string rmsg;
-            const int rr = ref_density_lds(w, n, n_occ, Fao, dX, Pout, 2.0, rmsg);
-            span_end(te);
-            if (rr == TF_OK) { orbitals_current = false; return TF_OK; }
-            if (rr != TF_ELINALG) { msg = rmsg; return rr; }
-        }
-        TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, Fao, 0.0, t1));     // X^T F
-        TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, t2));     // (X^T F) X
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, dW, n);
-        const int te = span_begin(1);
-        orbitals_current = false;
-        if (refining && w.ref_n == n) {
-            double *Xocc = nullptr;
-            std::string rmsg;
-            const int rr = (n <= TFR_NMAX) ? ref_refine_lds(w, n, n_occ, dW, &Xocc, rmsg)
-                         : (w.blk_ref_n == n)  ? ref_refine_blocks(w, n, dW, &Xocc, rmsg) : ref_refine(w, n, n_occ, dW, &Xocc, rmsg);
-            if (rr == TF_OK) {
-                const double two = 2.0, zero = 0.0;
-                TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, Xocc, dX, 0.0, t1));    // rows: occupied orbitals in the AO basis (others 0)
-                TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_none, rocblas_operation_transpose, n, n, n, &two, t1, n, t1, n, &zero, t2, n));
-                hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, Pout, n);
-                span_end(te);
-                if (getenv("TF_REFINE_CHECK")) {                 // debugging aid: the same density from a real eigensolve
-                    std::vector<double> hp(nn), hq(nn);
-                    TFS_HIP(tfs_memcpy(hp.data(), Pout, nn * sizeof(double), hipMemcpyDeviceToHost));
-                    int r2 = eigh(w, n, dW, vals, ework, msg);
-                    if (r2) return r2;
-                    TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, dX, dW, 0.0, dC));
-                    TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_transpose, rocblas_operation_none, n, n, n_occ, &two, dC, n, dC, n, &zero, t1, n));
-                    hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, t2, n);
-                    TFS_HIP(tfs_memcpy(hq.data(), t2, nn * sizeof(double), hipMemcpyDeviceToHost));
-                    double dmax = 0.0;
-                    for (size_t q = 0; q < nn; ++q) dmax = std::max(dmax, std::fabs(hp[q] - hq[q]));
-                    fprintf(stderr, "[tf refine] max |P_refined - P_eigh| = %.3e\n", dmax);
-                }
-                return TF_OK;
-            }
-            if (rr != TF_ELINALG) { msg = rmsg; return rr; }
-        }
-        int r = eigh(w, n, dW, vals, ework, msg);
-        if (r) return r;
-        if (refining) { r = ref_store(w, n, dW, msg, n_occ); if (r) return r; }
-        span_end(te);
-        TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, dX, dW, 0.0, dC));      // C = X V   (dW rows = eigenvectors)
-        const double two = 2.0, zero = 0.0;
-        // col-major view of dC is C^T: P = sum_{k<nocc} C[:,k] C[:,k]^T = M[:nocc,:]^T M[:nocc,:]
-        TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_transpose, rocblas_operation_none, n, n, n_occ, &two, dC, n, dC, n, &zero, t1, n));
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, Pout, n);
-        orbitals_current = true;
-        return TF_OK;
-    };
-
-    std::vector<double> B((size_t)max_diis * max_diis, 0.0);
-    int n_hist = 0;
     w.warm_ok = true;                 // successive Fock matrices are close: warm-start the Jacobi solver from the last eigenvectors
     w.jac_prev_n = 0; w.sym_prev_n = 0;   // (no warm start across cycles: a cycle's result must not depend on what the context solved before)
     struct WarmGuard { Workspace &w; ~WarmGuard() { w.warm_ok = false; w.jac_prev_n = 0; w.sym_prev_n = 0; w.eig_fail = nullptr; } } warm_guard{w};
@@ -1305,64 +1432,34 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             rc = xc(dP, dVxc, xc3);
             if (rc) { msg = "exchange-correlation evaluation failed"; return rc; }
         }
-        const int tf = span_begin(0);
+        const int tf = c.spans.begin(0);
         rc = jk(dP, dJ, dK, TFS_ST);
         if (rc) { msg.clear(); return rc; }                          // (the hook has left its message in the context)
-        span_end(tf);
-        // push into the history: trim to max_diis first (scf:943-946), so that the slot of the new entry is known
-        if (n_hist == max_diis) {
-            std::rotate(slot.begin(), slot.begin() + 1, slot.end());     // the oldest entry's slot becomes the newest
-            for (int r = 0; r + 1 < n_hist; ++r)
-                for (int c = 0; c + 1 < n_hist; ++c) B[r * max_diis + c] = B[(r + 1) * max_diis + c + 1];
-            --n_hist;
-        }
+        c.spans.end(tf);
+        H.make_room();                                               // before the push, so that the slot of the new entry is known
         static const bool no_fused_fock = getenv("TF_FOCK_UNFUSED") != nullptr;
         hipError_t ferr = hipSuccess;
         if (!no_fused_fock && n <= TFR_NMAX &&
-            tfref::launch_fock_diis(n, dH, dJ, dK, o.hfx, xc ? dVxc : nullptr, dP, dS, dX, dF, histF(n_hist), histE(n_hist), TFS_ST, &ferr)) {
+            tfref::launch_fock_diis(n, dH, dJ, dK, o.hfx, xc ? dVxc : nullptr, dP, dS, dX, dF, histF(H.n_hist), histE(H.n_hist), TFS_ST, &ferr)) {
             // n <= 64: Fock matrix, DIIS error and the history entry in one launch (tf_refine.hip.h)
         } else {
             if (ferr != hipSuccess) { msg = std::string("Fock / DIIS kernel launch failed: ") + hipGetErrorString(ferr); return TF_ENODEVICE; }
-            hipLaunchKernelGGL(k_fock, dim3(g), dim3(256), 0, TFS_ST, dH, dJ, dK, o.hfx, t1, (int)nn);
-            if (xc) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, t1, 1.0, dVxc, t1, (int)nn);        // + V_XC, scf:525
-            hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, dF, n);
-            // DIIS error e = X^T (F P S - S P F) X   (scf:906-920)
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, dF, dP, 0.0, t1));        // F P
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dS, 0.0, t2));        // F P S
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, dS, dP, 0.0, t1));        // S P
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, -1.0, t1, dF, 1.0, t2));       // F P S - S P F
-            TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, t2, 0.0, t1));         // X^T e
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, histE(n_hist)));   // (X^T e) X
-            TFS_HIP(hipMemcpyAsync(histF(n_hist), dF, nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
+            assemble_fock(c, dJ, dK, o.hfx, xc ? dVxc : nullptr, dF);
+            rc = diis_error(c, dF, dP, histE(H.n_hist), histF(H.n_hist), msg);
+            if (rc) return rc;
         }
-        ++n_hist;
-        double ee = 0.0;
-        {
-            double hd[TF_MAX_DIIS];
-            for (int k0 = 0; k0 < n_hist; k0 += 8) {               // eight scalar products per launch
-                Ptr8 a;
-                const int mk = std::min(8, n_hist - k0);
-                for (int k = 0; k < 8; ++k) { a.p[k] = histE(0); a.c[k] = 0.0; }
-                for (int k = 0; k < mk; ++k) a.p[k] = histE(k0 + k);
-                launch_multi_dot(w, histE(n_hist - 1), a, mk, (int)nn, w.d_scal + 128 + k0);
-            }
-            TFS_HIP(tfs_memcpy(hd, w.d_scal + 128, n_hist * sizeof(double), hipMemcpyDeviceToHost));
-            for (int k = 0; k < n_hist; ++k) {
-                // the reference stores the error twice (alpha and beta copies, scf:934), hence the factor 2
-                B[(n_hist - 1) * max_diis + k] = B[k * max_diis + (n_hist - 1)] = 2.0 * hd[k];
-                if (k == n_hist - 1) ee = hd[k];
-            }
-        }
-        commutator = std::sqrt(ee / (double)nn);                                       // scf:918
+        ++H.n_hist;
+        double hd[TF_MAX_DIIS], row[TF_MAX_DIIS];
+        history_dots(c, histE, w.d_scal + 128);
+        TFS_HIP(tfs_memcpy(hd, w.d_scal + 128, H.n_hist * sizeof(double), hipMemcpyDeviceToHost));
+        // the reference stores the error twice (alpha and beta copies, scf:934), hence the factor 2
+        for (int k = 0; k < H.n_hist; ++k) row[k] = 2.0 * hd[k];
+        H.enter_dots(row);
+        commutator = std::sqrt(hd[H.n_hist - 1] / (double)nn);                         // scf:918
         // diagonalise, new density, energy with the NEW P and the OLD J,K   (scf:1133-1141)
-        rc = diag_density(dF, dPn);
+        rc = density_from_fock(c, n_occ, 2.0, dF, dPn, orbitals_current, msg);
         if (rc) return rc;
-        {   // the five energy terms are read back at the end of the iteration, together with the density changes
-            Ptr8 a;
-            for (int k = 0; k < 8; ++k) { a.p[k] = dT; a.c[k] = 0.0; }
-            a.p[0] = dT; a.p[1] = dV; a.p[2] = dFx; a.p[3] = dJ; a.p[4] = dK;
-            launch_multi_dot(w, dPn, a, 5, (int)nn, w.d_scal + 18);
-        }
+        energy_dots(c, dPn, dJ, dK, w.d_scal + 18);
         orbitals_final = orbitals_current;                            // of THIS iteration's Fock matrix (the DIIS solve below reuses dC)
         if (orbitals_final && (out.eps || out.C)) {                  // kept on the device; copied out after the cycle
             TFS_HIP(hipMemcpyAsync(vals_save, vals, n * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
@@ -1370,27 +1467,11 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         }
         // DIIS extrapolation (scf:991-1059)
         double *Pcur = dPn;
-        if (step > 2 && o.use_diis && commutator < 0.3) {
-            const int m = n_hist + 1;
-            std::vector<double> A((size_t)m * m, 0.0), rhs(m, 0.0), x;
-            for (int r = 0; r < n_hist; ++r) {
-                for (int c = 0; c < n_hist; ++c) A[r * m + c] = B[r * max_diis + c];
-                A[r * m + n_hist] = -1.0; A[n_hist * m + r] = -1.0;
-            }
-            rhs[n_hist] = -1.0;
-            if (small_solve(m, A, rhs, x)) {
-                for (int k0 = 0; k0 < n_hist; k0 += 8) {
-                    Ptr8 a;
-                    const int mk = std::min(8, n_hist - k0);
-                    for (int k = 0; k < 8; ++k) { a.p[k] = histF(0); a.c[k] = 0.0; }
-                    for (int k = 0; k < mk; ++k) { a.p[k] = histF(k0 + k); a.c[k] = x[k0 + k]; }
-                    hipLaunchKernelGGL(k_lincomb, dim3(g), dim3(256), 0, TFS_ST, a, mk, scr, (int)nn, k0 > 0 ? 1 : 0);
-                }
-                rc = diag_density(scr, dPn);     // overwrites dC/vals: results were copied out above
-                if (rc) return rc;
-            } else {
-                n_hist = 0;                        // "Resetting DIIS", scf:1042-1048
-            }
+        std::vector<double> x;
+        if (step > 2 && o.use_diis && commutator < 0.3 && H.solve(x)) {
+            extrapolate_fock(c, histF, x);
+            rc = density_from_fock(c, n_occ, 2.0, scr, dPn, orbitals_current, msg);     // overwrites dC/vals: results were copied out above
+            if (rc) return rc;
         }
         // P_before_damping = P ; damping (scf:763-868)
         TFS_HIP(hipMemcpyAsync(dPbd, Pcur, nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
@@ -1399,21 +1480,12 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
         else if (o.damping == 1 && commutator > 0.01 && step > 1) {
             double pop[4][2];
             const double *dens[4] = {dPbd, dPold, dPoldbd, dPvold};   // A_n_out, A_n1_in, A_n1_out, A_n2_in
-            for (int q = 0; q < 4; ++q) {
-                hipLaunchKernelGGL(k_mulliken, dim3(1), dim3(256), 0, TFS_ST, dens[q], dS, n, nA, w.d_scal + 2 * q);
-            }
+            for (int q = 0; q < 4; ++q) hipLaunchKernelGGL(k_mulliken, dim3(1), dim3(256), 0, TFS_ST, dens[q], dS, n, nA, w.d_scal + 2 * q);
             TFS_HIP(tfs_memcpy(&pop[0][0], w.d_scal, 8 * sizeof(double), hipMemcpyDeviceToHost));
             if (o.n_atoms < 2) { for (int q = 0; q < 4; ++q) pop[q][1] = 0.0; }
-            double den[2], alpha[2] = {0.0, 0.0};
-            for (int a = 0; a < 2; ++a) den[a] = pop[0][a] - pop[2][a] - pop[1][a] + pop[3][a];
-            if (den[0] != 0.0 && den[1] != 0.0)
-                for (int a = 0; a < 2; ++a) alpha[a] = (pop[0][a] - pop[2][a]) / den[a];
-            if (o.n_atoms >= 2) {
-                const double r0 = o.n_atom_ao[0], r1 = o.n_atom_ao[1];
-                damp = (alpha[0] * r0 + alpha[1] * r1) / (r0 + r1);
-            } else damp = alpha[0] * o.n_atom_ao[0];
-            damp = std::max(damp, 0.0);
-            damp = (damp < std::min(o.max_damping, 1.0)) ? damp : o.max_damping;
+            double num[2], den[2];
+            for (int a = 0; a < 2; ++a) { num[a] = pop[0][a] - pop[2][a]; den[a] = pop[0][a] - pop[2][a] - pop[1][a] + pop[3][a]; }
+            damp = damping_factor_tail(o, num, den);
         }
         hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, damp, dPold, 1.0 - damp, dPbd, dP, (int)nn);
         // changes and convergence (scf:261-333)
@@ -1427,23 +1499,9 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             comps[5] = eF; comps[6] = 0.0;
             E = comps[0] + comps[1] + comps[2] + comps[3] + comps[4] + comps[5] + comps[6];
         }
-        const double dE = E - E_old, maxDP = res[0], rmsDP = std::sqrt(res[1] / (double)nn);
-        out.n_iter = step;
-        if (out.table) {
-            double *row = out.table + (size_t)(step - 1) * 7;
-            row[0] = step; row[1] = E + V_NN; row[2] = dE; row[3] = rmsDP; row[4] = maxDP; row[5] = commutator; row[6] = damp;
-        }
-        const bool conv_now = std::fabs(dE) < o.conv_delta_E && std::fabs(maxDP) < o.conv_max_DP && std::fabs(rmsDP) < o.conv_rms_DP &&
-                              std::fabs(commutator) < o.conv_commutator;
-        if (w.agree) {                                               // collective control flow on a sharded tensor
-            const double vals[3] = {conv_now ? 1.0 : 0.0, (double)n_hist, (double)step};
-            rc = w.agree(vals, 3, msg);
-            if (rc) return rc;
-        }
-        if (conv_now) {
-            out.converged = 1;
-            break;
-        }
+        rc = report_iteration(w, o, out, step, H.n_hist, E + V_NN, E - E_old, std::sqrt(res[1] / (double)nn), res[0], commutator, damp, msg);
+        if (rc) return rc;
+        if (out.converged) break;
     }
     if (orbitals_final) {
         if (out.eps) TFS_HIP(tfs_memcpy(out.eps, vals_save, n * sizeof(double), hipMemcpyDeviceToHost));
@@ -1451,31 +1509,14 @@ inline int run_rhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     }
     w.eig_fail = nullptr;
     if (!orbitals_final && (out.eps || out.C) && out.n_iter > 0) {
-        // orbitals and orbital energies of the last Fock matrix (what the reference's last diagonalisation leaves, scf:1133)
-        TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, dF, 0.0, t1));
-        TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, t2));
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, dW, n);
-        const int te = span_begin(1);
-        rc = eigh(w, n, dW, vals, ework, msg);
+        rc = final_orbitals(c, dF, out.eps, out.C, msg);
         if (rc) return rc;
-        TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, dX, dW, 0.0, dC));
-        span_end(te);
-        if (out.eps) TFS_HIP(tfs_memcpy(out.eps, vals, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (out.C) TFS_HIP(tfs_memcpy(out.C, dC, nn * sizeof(double), hipMemcpyDeviceToHost));
     }
     w.ref_n = 0; w.blk_ref_n = 0;
     TFS_HIP(tfs_sync());
-    for (const auto &sp : spans) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, w.tev[sp.first], w.tev[sp.first + 1]) == hipSuccess) (sp.second == 0 ? out.fock_seconds : out.eig_seconds) += ms * 1e-3;
-    }
-    out.energy = E + V_NN;
-    std::memcpy(out.components, comps, sizeof(comps));
     if (out.P) TFS_HIP(tfs_memcpy(out.P, dP, nn * sizeof(double), hipMemcpyDeviceToHost));
     if (out.F) TFS_HIP(tfs_memcpy(out.F, dF, nn * sizeof(double), hipMemcpyDeviceToHost));
-    out.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wall).count();
-    if (!out.converged) { msg = "Self-consistent field not converged in " + std::to_string(o.max_iter) + " iterations! Increase maximum iterations or give up."; return TF_ENOTCONV; }
-    return TF_OK;
+    return finish_cycle(c, o, out, E + V_NN, comps, t_wall, msg);
 }
 
 // ---- unrestricted cycle: run_unrestricted_SCF_cycle (scf:1165-1281) inside the outer loop (scf:1292-1435) ---------------------
@@ -1495,9 +1536,8 @@ using XC2Fn = std::function<int(const double *, const double *, double *, double
 
 inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, const double *T, const double *V, const double *Fext,
                    const double *X, const double *Pa0, const double *Pb0, double E0, int n_alpha, int n_beta, double V_NN, const JK2Fn &jk2,
-                   int world, tf_scf_result &out, const UhfOut &uo, std::string &msg, const XC2Fn &xc = XC2Fn())
+                   tf_scf_result &out, const UhfOut &uo, std::string &msg, const XC2Fn &xc = XC2Fn())
 {
-    (void)world;                                                    // (sharded tensors: see run_rhf)
     if (o.max_diis > TF_MAX_DIIS) { msg = "tf_scf_uhf: at most 64 DIIS matrices are held by the native cycle"; return TF_EINVAL; }
     const int max_diis = std::max(1, (int)o.max_diis);
     const int n_fixed = xc ? 32 : 30;                               // (Kohn-Sham: V_XC^alpha, V_XC^beta in mat(30), mat(31))
@@ -1518,45 +1558,21 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     double *dVxc[2] = {xc ? mat(30) : nullptr, xc ? mat(31) : nullptr};
     double *hist = mat(n_fixed);
     double *vals = base + (size_t)n_mats * nn, *ework = vals + n, *vals_save[2] = {ework + n, ework + 2 * (size_t)n};
-    std::vector<int> slot(max_diis);                             // logical history entry -> physical slot (see run_rhf)
-    for (int k = 0; k < max_diis; ++k) slot[k] = k;
-    auto histF = [&](int k, int s) { return hist + (size_t)(4 * slot[k] + s) * nn; };
-    auto histE = [&](int k, int s) { return hist + (size_t)(4 * slot[k] + 2 + s) * nn; };
+    CycleBase c{w, n, nn, g, dS, dH, dX, dT, dV, dFx, t1, t2, dW, dC, scr, vals, ework, SpanTimer{w}};
+    DiisHistory H(max_diis);                                     // one history for both spins: four matrices per entry
+    const HistMats histF[2] = {{H, hist, 4 * nn}, {H, hist + nn, 4 * nn}}, histE[2] = {{H, hist + 2 * nn, 4 * nn}, {H, hist + 3 * nn, 4 * nn}};
     const int n_occ[2] = {n_alpha, n_beta};
 
-    TFS_HIP(tfs_memcpy(dS, S, nn * sizeof(double), hipMemcpyHostToDevice));
-    TFS_HIP(tfs_memcpy(dT, T, nn * sizeof(double), hipMemcpyHostToDevice));
-    TFS_HIP(tfs_memcpy(dV, V, nn * sizeof(double), hipMemcpyHostToDevice));
-    if (Fext) TFS_HIP(tfs_memcpy(dFx, Fext, nn * sizeof(double), hipMemcpyHostToDevice));
-    else TFS_HIP(hipMemsetAsync(dFx, 0, nn * sizeof(double), TFS_ST));
+    rc = upload_integrals(c, S, T, V, Fext, msg);
+    if (rc) return rc;
     TFS_HIP(tfs_memcpy(dP[0], Pa0, nn * sizeof(double), hipMemcpyHostToDevice));
     TFS_HIP(tfs_memcpy(dP[1], Pb0, nn * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dT, 1.0, dV, dH, (int)nn);
-    hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dH, 1.0, dFx, dH, (int)nn);
+    core_hamiltonian(c);
     hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dP[0], 1.0, dP[1], dPt, (int)nn);
-    if (X) TFS_HIP(tfs_memcpy(dX, X, nn * sizeof(double), hipMemcpyHostToDevice));
-    else {
-        double sm = 0;
-        rc = orthogonaliser_device(w, n, dS, dX, nullptr, &sm, mat(28), msg);
-        if (rc) return rc;
-    }
+    rc = take_orthogonaliser(c, X, mat(28), msg);
+    if (rc) return rc;
     TFS_BLAS(rocblas_set_pointer_mode(w.blas, rocblas_pointer_mode_host));
-    size_t tev_used = 0;
-    std::vector<std::pair<size_t, int>> spans;
-    auto span_begin = [&](int kind) -> int {
-        while (w.tev.size() < tev_used + 2) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return -1;
-            w.tev.push_back(e);
-        }
-        spans.emplace_back(tev_used, kind);
-        (void)hipEventRecord(w.tev[tev_used], TFS_ST);
-        tev_used += 2;
-        return (int)tev_used - 1;
-    };
-    auto span_end = [&](int idx) { if (idx >= 0) (void)hipEventRecord(w.tev[idx], TFS_ST); };
 
-    static const bool no_refine = getenv("TF_EIGH") != nullptr;
     // the refinement state of the beta spin lives in the alternate slot and is swapped in around its solves
     struct SpinSlot {
         Workspace &w; bool on;
@@ -1574,51 +1590,11 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
     // diagonalise F_s (AO) -> P_s = C_occ C_occ^T symmetrised (one electron per orbital, scf:1227-1228)
     auto diag_density = [&](int sp, const double *Fao, double *Pout) -> int {
         orbitals_current[sp] = false;
-        const int no = n_occ[sp];
-        if (no <= 0) { TFS_HIP(hipMemsetAsync(Pout, 0, nn * sizeof(double), TFS_ST)); return TF_OK; }
+        if (n_occ[sp] <= 0) { TFS_HIP(hipMemsetAsync(Pout, 0, nn * sizeof(double), TFS_ST)); return TF_OK; }
         SpinSlot slot(w, sp == 1);
-        const bool refining = !no_refine && n >= 2 && no < n;
-        static const bool no_fused = getenv("TF_REFINE_UNFUSED") != nullptr;
-        if (refining && !no_fused && n <= TFR_NMAX && w.ref_n == n) {
-            const int te0 = span_begin(1);
-            std::string rmsg;
-            const int rr = ref_density_lds(w, n, no, Fao, dX, Pout, 1.0, rmsg);
-            span_end(te0);
-            if (rr == TF_OK) return TF_OK;
-            if (rr != TF_ELINALG) { msg = rmsg; return rr; }
-        }
-        TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, Fao, 0.0, t1));
-        TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, t2));
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, dW, n);
-        const int te = span_begin(1);
-        const double one = 1.0, zero = 0.0;
-        if (refining && w.ref_n == n) {
-            double *Xocc = nullptr;
-            std::string rmsg;
-            const int rr = (n <= TFR_NMAX) ? ref_refine_lds(w, n, no, dW, &Xocc, rmsg)
-                         : (w.blk_ref_n == n)  ? ref_refine_blocks(w, n, dW, &Xocc, rmsg) : ref_refine(w, n, no, dW, &Xocc, rmsg);
-            if (rr == TF_OK) {
-                TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, Xocc, dX, 0.0, t1));
-                TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_none, rocblas_operation_transpose, n, n, n, &one, t1, n, t1, n, &zero, t2, n));
-                hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, Pout, n);
-                span_end(te);
-                return TF_OK;
-            }
-            if (rr != TF_ELINALG) { msg = rmsg; return rr; }
-        }
-        int r = eigh(w, n, dW, vals, ework, msg);
-        if (r) return r;
-        if (refining) { r = ref_store(w, n, dW, msg, no); if (r) return r; }
-        span_end(te);
-        TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, dX, dW, 0.0, dC));
-        TFS_BLAS(rocblas_dgemm(w.blas, rocblas_operation_transpose, rocblas_operation_none, n, n, no, &one, dC, n, dC, n, &zero, t1, n));
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, Pout, n);
-        orbitals_current[sp] = true;
-        return TF_OK;
+        return density_from_fock(c, n_occ[sp], 1.0, Fao, Pout, orbitals_current[sp], msg);
     };
 
-    std::vector<double> B((size_t)max_diis * max_diis, 0.0);
-    int n_hist = 0;
     double E = E0, E_old = E0, commutator = 1.0;
     double comps[7] = {0, 0, 0, 0, 0, 0, 0};
     out.fock_seconds = 0; out.eig_seconds = 0; out.n_iter = 0; out.converged = 0;
@@ -1635,46 +1611,24 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             if (rc) { msg = "exchange-correlation evaluation failed"; return rc; }
         }
         // Fock matrices (scf:542-589): F_s = H + J_alpha + J_beta - HFX K_s (+ V_XC^s), symmetrised
-        const int tf = span_begin(0);
+        const int tf = c.spans.begin(0);
         rc = jk2(dP[0], dP[1], dJ[0], dJ[1], dK[0], dK[1], TFS_ST);
         if (rc) { msg.clear(); return rc; }
-        span_end(tf);
+        c.spans.end(tf);
         hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, dJ[0], 1.0, dJ[1], dJt, (int)nn);
-        if (n_hist == max_diis) {                                   // trim the history to max_diis entries (scf:1216-1219)
-            std::rotate(slot.begin(), slot.begin() + 1, slot.end());
-            for (int r = 0; r + 1 < n_hist; ++r)
-                for (int c = 0; c + 1 < n_hist; ++c) B[r * max_diis + c] = B[(r + 1) * max_diis + c + 1];
-            --n_hist;
-        }
+        H.make_room();                                              // trim the history to max_diis entries (scf:1216-1219)
         for (int sp = 0; sp < 2; ++sp) {
-            hipLaunchKernelGGL(k_fock, dim3(g), dim3(256), 0, TFS_ST, dH, dJt, dK[sp], 2.0 * o.hfx, t1, (int)nn);   // k_fock: H + J - hfx/2 K
-            if (xc) hipLaunchKernelGGL(k_axpby, dim3(g), dim3(256), 0, TFS_ST, 1.0, t1, 1.0, dVxc[sp], t1, (int)nn);
-            hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t1, dF[sp], n);
-            // e_s = X^T (F_s P_s S - S P_s F_s) X   (scf:906-920)
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, dF[sp], dP[sp], 0.0, t1));
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dS, 0.0, t2));
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, dS, dP[sp], 0.0, t1));
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, -1.0, t1, dF[sp], 1.0, t2));
-            TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, t2, 0.0, t1));
-            TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, histE(n_hist, sp)));
-            TFS_HIP(hipMemcpyAsync(histF(n_hist, sp), dF[sp], nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
+            assemble_fock(c, dJt, dK[sp], 2.0 * o.hfx, dVxc[sp], dF[sp]);                   // k_fock: H + J - hfx/2 K
+            rc = diis_error(c, dF[sp], dP[sp], histE[sp](H.n_hist), histF[sp](H.n_hist), msg);   // e_s = X^T (F_s P_s S - S P_s F_s) X
+            if (rc) return rc;
         }
-        ++n_hist;
-        double ee[2] = {0.0, 0.0};
-        {
-            double hd[2 * TF_MAX_DIIS];
-            for (int sp = 0; sp < 2; ++sp)
-                for (int k0 = 0; k0 < n_hist; k0 += 8) {            // eight scalar products per launch
-                    Ptr8 a;
-                    const int mk = std::min(8, n_hist - k0);
-                    for (int k = 0; k < 8; ++k) { a.p[k] = histE(0, sp); a.c[k] = 0.0; }
-                    for (int k = 0; k < mk; ++k) a.p[k] = histE(k0 + k, sp);
-                    launch_multi_dot(w, histE(n_hist - 1, sp), a, mk, (int)nn, w.d_scal + 128 + TF_MAX_DIIS * sp + k0);
-                }
-            TFS_HIP(tfs_memcpy(hd, w.d_scal + 128, 2 * TF_MAX_DIIS * sizeof(double), hipMemcpyDeviceToHost));
-            for (int k = 0; k < n_hist; ++k) B[(n_hist - 1) * max_diis + k] = B[k * max_diis + (n_hist - 1)] = hd[k] + hd[TF_MAX_DIIS + k];
-            ee[0] = hd[n_hist - 1]; ee[1] = hd[TF_MAX_DIIS + n_hist - 1];
-        }
+        ++H.n_hist;
+        double hd[2 * TF_MAX_DIIS], row[TF_MAX_DIIS];
+        for (int sp = 0; sp < 2; ++sp) history_dots(c, histE[sp], w.d_scal + 128 + TF_MAX_DIIS * sp);
+        TFS_HIP(tfs_memcpy(hd, w.d_scal + 128, 2 * TF_MAX_DIIS * sizeof(double), hipMemcpyDeviceToHost));
+        for (int k = 0; k < H.n_hist; ++k) row[k] = hd[k] + hd[TF_MAX_DIIS + k];
+        H.enter_dots(row);
+        const double ee[2] = {hd[H.n_hist - 1], hd[TF_MAX_DIIS + H.n_hist - 1]};
         const double comm_s[2] = {std::sqrt(ee[0] / (double)nn), std::sqrt(ee[1] / (double)nn)};
         commutator = std::max(comm_s[0], comm_s[1]);                  // scf:1211
         // new densities from F_alpha, F_beta; energy with the NEW densities and the OLD J, K (scf:1224-1232)
@@ -1687,35 +1641,15 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
                 TFS_HIP(hipMemcpyAsync(dCsave[sp], dC, nn * sizeof(double), hipMemcpyDeviceToDevice, TFS_ST));
             }
         }
-        for (int sp = 0; sp < 2; ++sp) {     // the energy terms are read back at the end of the iteration, together with the density changes
-            Ptr8 a;
-            for (int k = 0; k < 8; ++k) { a.p[k] = dT; a.c[k] = 0.0; }
-            a.p[0] = dT; a.p[1] = dV; a.p[2] = dFx; a.p[3] = dJt; a.p[4] = dK[sp];
-            launch_multi_dot(w, dPn[sp], a, 5, (int)nn, w.d_scal + 18 + 6 * sp);
-        }
+        for (int sp = 0; sp < 2; ++sp) energy_dots(c, dPn[sp], dJt, dK[sp], w.d_scal + 18 + 6 * sp);
         // DIIS (scf:1236-1256): one set of coefficients for both spins
-        if (step > 2 && o.use_diis && commutator < 0.3) {
-            const int m = n_hist + 1;
-            std::vector<double> A((size_t)m * m, 0.0), rhs(m, 0.0), x;
-            for (int r = 0; r < n_hist; ++r) {
-                for (int c = 0; c < n_hist; ++c) A[r * m + c] = B[r * max_diis + c];
-                A[r * m + n_hist] = -1.0; A[n_hist * m + r] = -1.0;
+        std::vector<double> x;
+        if (step > 2 && o.use_diis && commutator < 0.3 && H.solve(x)) {
+            for (int sp = 0; sp < 2; ++sp) {
+                extrapolate_fock(c, histF[sp], x);
+                rc = diag_density(sp, scr, dPn[sp]);
+                if (rc) return rc;
             }
-            rhs[n_hist] = -1.0;
-            if (small_solve(m, A, rhs, x)) {
-                for (int sp = 0; sp < 2; ++sp) {
-                    for (int k0 = 0; k0 < n_hist; k0 += 8) {
-                        Ptr8 a;
-                        const int mk = std::min(8, n_hist - k0);
-                        for (int k = 0; k < 8; ++k) { a.p[k] = histF(0, sp); a.c[k] = 0.0; }
-                        for (int k = 0; k < mk; ++k) { a.p[k] = histF(k0 + k, sp); a.c[k] = x[k0 + k]; }
-                        hipLaunchKernelGGL(k_lincomb, dim3(g), dim3(256), 0, TFS_ST, a, mk, scr, (int)nn, k0 > 0 ? 1 : 0);
-                    }
-                    rc = diag_density(sp, scr, dPn[sp]);
-                    if (rc) return rc;
-                }
-            } else
-                n_hist = 0;
         }
         // damping, each spin with its own commutator (scf:1259-1260; calculate_damping_factor scf:763-868 with zero
         // "P_very_old" / "P_old_before_damping")
@@ -1730,17 +1664,8 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             for (int sp = 0; sp < 2; ++sp) {
                 if (!(comm_s[sp] > 0.01)) continue;
                 const double *out_p = pop[2 * sp], *in_p = pop[2 * sp + 1];
-                double den[2], alpha[2] = {0.0, 0.0};
-                for (int a = 0; a < 2; ++a) den[a] = out_p[a] - in_p[a];
-                if (den[0] != 0.0 && den[1] != 0.0)
-                    for (int a = 0; a < 2; ++a) alpha[a] = out_p[a] / den[a];
-                double f;
-                if (o.n_atoms >= 2) {
-                    const double r0 = o.n_atom_ao[0], r1 = o.n_atom_ao[1];
-                    f = (alpha[0] * r0 + alpha[1] * r1) / (r0 + r1);
-                } else f = alpha[0] * o.n_atom_ao[0];
-                f = std::max(f, 0.0);
-                damp[sp] = (f < std::min(o.max_damping, 1.0)) ? f : o.max_damping;
+                const double den[2] = {out_p[0] - in_p[0], out_p[1] - in_p[1]};
+                damp[sp] = damping_factor_tail(o, out_p, den);
             }
         }
         for (int sp = 0; sp < 2; ++sp)
@@ -1759,26 +1684,13 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             if (xc) { comps[3] += xc5[2] + xc5[3]; comps[4] = xc5[4]; }                       // scf:467-472
             E = comps[0] + comps[1] + comps[2] + comps[3] + comps[4] + comps[5] + comps[6];
         }
-        const double dE = E - E_old, maxDP = res[0], rmsDP = std::sqrt(res[1] / (double)nn);
-        out.n_iter = step;
-        if (out.table) {
-            double *row = out.table + (size_t)(step - 1) * 7;
-            row[0] = step; row[1] = E + V_NN; row[2] = dE; row[3] = rmsDP; row[4] = maxDP; row[5] = commutator; row[6] = std::max(damp[0], damp[1]);
-        }
-        const bool conv_now = std::fabs(dE) < o.conv_delta_E && std::fabs(maxDP) < o.conv_max_DP && std::fabs(rmsDP) < o.conv_rms_DP &&
-                              std::fabs(commutator) < o.conv_commutator;
-        if (w.agree) {                                               // collective control flow on a sharded tensor
-            const double vals[3] = {conv_now ? 1.0 : 0.0, (double)n_hist, (double)step};
-            rc = w.agree(vals, 3, msg);
-            if (rc) return rc;
-        }
-        if (conv_now) {
-            out.converged = 1;
-            break;
-        }
+        rc = report_iteration(w, o, out, step, H.n_hist, E + V_NN, E - E_old, std::sqrt(res[1] / (double)nn), res[0], commutator,
+                              std::max(damp[0], damp[1]), msg);
+        if (rc) return rc;
+        if (out.converged) break;
     }
     w.eig_fail = nullptr;
-    // orbitals and orbital energies of the last Fock matrices (what the reference's last diagonalisations leave, scf:1224-1225)
+    // orbitals and orbital energies of the last Fock matrices
     for (int sp = 0; sp < 2 && out.n_iter > 0; ++sp) {
         if (!uo.eps[sp] && !uo.C[sp]) continue;
         if (orbitals_final[sp]) {
@@ -1786,33 +1698,17 @@ inline int run_uhf(Workspace &w, int n, const tf_scf_opts &o, const double *S, c
             if (uo.C[sp]) TFS_HIP(tfs_memcpy(uo.C[sp], dCsave[sp], nn * sizeof(double), hipMemcpyDeviceToHost));
             continue;
         }
-        TFS_BLAS(gemm_rm(w.blas, true, false, n, 1.0, dX, dF[sp], 0.0, t1));
-        TFS_BLAS(gemm_rm(w.blas, false, false, n, 1.0, t1, dX, 0.0, t2));
-        hipLaunchKernelGGL(k_symmetrise, dim3(g), dim3(256), 0, TFS_ST, t2, dW, n);
-        const int te = span_begin(1);
-        rc = eigh(w, n, dW, vals, ework, msg);
+        rc = final_orbitals(c, dF[sp], uo.eps[sp], uo.C[sp], msg);
         if (rc) return rc;
-        TFS_BLAS(gemm_rm(w.blas, false, true, n, 1.0, dX, dW, 0.0, dC));
-        span_end(te);
-        if (uo.eps[sp]) TFS_HIP(tfs_memcpy(uo.eps[sp], vals, n * sizeof(double), hipMemcpyDeviceToHost));
-        if (uo.C[sp]) TFS_HIP(tfs_memcpy(uo.C[sp], dC, nn * sizeof(double), hipMemcpyDeviceToHost));
     }
     w.ref_n = 0; w.ref_alt_n = 0; w.ref_vcls_n = 0; w.ref_alt_vcls_n = 0; w.blk_ref_n = 0; w.blk_alt_ref_n = 0;
     TFS_HIP(tfs_sync());
-    for (const auto &sp : spans) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, w.tev[sp.first], w.tev[sp.first + 1]) == hipSuccess) (sp.second == 0 ? out.fock_seconds : out.eig_seconds) += ms * 1e-3;
-    }
-    out.energy = E + V_NN;
-    std::memcpy(out.components, comps, sizeof(comps));
     for (int sp = 0; sp < 2; ++sp) {
         if (uo.P[sp]) TFS_HIP(tfs_memcpy(uo.P[sp], dP[sp], nn * sizeof(double), hipMemcpyDeviceToHost));
         if (uo.F[sp]) TFS_HIP(tfs_memcpy(uo.F[sp], dF[sp], nn * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (out.P) TFS_HIP(tfs_memcpy(out.P, dPt, nn * sizeof(double), hipMemcpyDeviceToHost));
-    out.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wall).count();
-    if (!out.converged) { msg = "Self-consistent field not converged in " + std::to_string(o.max_iter) + " iterations! Increase maximum iterations or give up."; return TF_ENOTCONV; }
-    return TF_OK;
+    return finish_cycle(c, o, out, E + V_NN, comps, t_wall, msg);
 }
 
 }  // namespace tfscf
