@@ -512,6 +512,50 @@ int tf_cis_d_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const do
                  const double *b /* [n_states][o][v] */, const double *omega /* [n_states] */,
                  const int32_t *triplet /* [n_states], 0 or 1 */, tf_cis_d_result *out);
 
+/* ---- MP2 densities: replaces the density part of run_restricted_MP2 (tuna_mp.py:908-966), calculate_restricted_relaxed_MP2_density_matrix
+ * (:177-279) and calculate_natural_orbitals (:514-565) ---- */
+
+typedef struct {
+    int32_t relaxed;                       /* 0: unrelaxed; 1: Z-vector relaxed (needs n_frozen = 0) */
+    double c_os, c_ss;                     /* weights of the opposite- and same-spin parts: 1, 1 for MP2; OSS, SSS for SCS-MP2 */
+} tf_mp2_density_opts;
+
+typedef struct {
+    double e_os, e_ss;                     /* the unscaled MP2 components, as tf_mp2_rhf returns them */
+    double *P_mo;                          /* [N][N] may be NULL: the density in the MO basis, with the 2 of every occupied orbital */
+    double *P_ao;                          /* [N][N] may be NULL: C P_mo C^T */
+    double *L, *z;                         /* [n_occ][v] may be NULL, written by a relaxed call: the Lagrangian and the Z-vector */
+    double seconds[5];                     /* wall; MO blocks; ladder; Z-vector (assembly, dpotrf, dpotrs); rest */
+} tf_mp2_density_result;
+
+/* The MP2 one-particle density of canonical RHF orbitals C [N,N], eps [N]; windows as tf_mp3_rhf: occupied [n_frozen, n_occ), virtual
+ * [n_occ, N).  With D = e_i + e_j - e_a - e_b, tOS = -2 (ia|jb) / D, tSS = [(ia|jb) - (ib|ja)] / D:
+ *     P_ij = -1/2 c_os sum_kab tOS_kiab tOS_kjab - c_ss sum_kab tSS_kiab tSS_kjab      (occupied window)
+ *     P_ab = +1/2 c_os sum_ijc tOS_ijbc tOS_ijac + c_ss sum_ijc tSS_ijbc tSS_ijac      (virtual window)
+ * plus 2 on the diagonal of every occupied orbital.  A relaxed call (n_frozen = 0) adds z_ia / 2 to both occupied-virtual blocks, where
+ * (A + B) z = -L with the singlet A + B of tf_cis_rhf, w = c_os 2 (ia|jb) / D + c_ss 2 [(ia|jb) - (ib|ja)] / D and
+ *     L_ia = 2 sum_jbc w_ijbc (ab|jc) - 2 sum_jkb w_jkab (ji|kb) + [C_o^T (4 J[P_src] - 2 K[P_src]) C_v]_ia,   P_src = C P^(2) C^T.
+ * No block with three virtual indices is formed: the first term is one pass of the AO-direct ladder of tf_mp3_rhf on w, back-transformed
+ * with the occupied coefficients as tf_mp4_rhf's singles are; the second is a GEMM over (ji|kb); the third one J/K build.  The system is
+ * solved by rocSOLVER dpotrf / dpotrs.  A + B that is not positive definite -- a singlet-unstable RHF solution -- is TF_ELINALG, the
+ * message names the leading minor, nothing of that call is valid and the context stays usable.  Every reduction has one owner and a
+ * fixed order, rocBLAS runs without atomics: two calls return the same bits.  All three tensor layouts.
+ * Work space: relaxed at most 6 arrays of o^2 v^2 values at a time -- (ia|jb), (ab|ij), tOS, tSS and w in two layouts; after the
+ * unrelaxed stage the ladder's Y, then the transposed (ij|ab) and the (o v)^2 of A + B stand where the amplitudes stood -- plus the
+ * ladder's batch; unrelaxed 3 arrays.
+ * Measured on one MI355X against the reference program's densities of six systems (MP2 and SCS-MP2, both kinds, every layout): P within
+ * 3.3e-15 (MO basis) and 6.5e-14 (AO basis), z within 6.6e-15; N = 400, o = 18, warm: relaxed 1.31 s (MO blocks 0.67 s, ladder 0.57 s,
+ * Z-vector 0.03 s), unrelaxed 0.037 s.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL opts, C, eps or out, unless 0 <= n_frozen < n_occ < N, on a relaxed
+ * call with n_frozen > 0 or without any output array, or world > 1.  TF_ENOMEM, with the size in the message. */
+int tf_mp2_density_rhf(tf_ctx *ctx, const tf_mp2_density_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps,
+                       tf_mp2_density_result *out);
+
+/* Natural orbitals of a density P [n,n] (AO basis) with the Fock orthogonaliser X [n,n]: eigenpairs of X^-1 P X^-T by the context's
+ * eigensolver on the device (X^-1 by dgetrf / dgetri), occ [n] in descending order, orbitals [n,n] = X vectors, column k with occ[k].
+ * Needs no tensor.  TF_EINVAL on a NULL pointer or n < 1, TF_ELINALG on a singular X or an eigensolver failure. */
+int tf_natural_orbitals(tf_ctx *ctx, int n, const double *P, const double *X, double *occ, double *orbitals);
+
 /* eps[N], C[N,N] = eigenpairs of the Fock matrix in the orthogonalised basis, C = X C' (diagonalise_Fock_matrix,
  * scf:222-250): rocBLAS dgemm + rocSOLVER dsyevd; host buffers. */
 int tf_diagonalise(tf_ctx *ctx, int n, const double *F, const double *X, double *eps, double *C);

@@ -76,11 +76,20 @@ class CisDResult(C.Structure):                            # tf_cis_d_result
                 ("seconds", C.c_double * 3)]
 
 
+class Mp2DensityOpts(C.Structure):                        # tf_mp2_density_opts
+    _fields_ = [("relaxed", C.c_int32), ("c_os", C.c_double), ("c_ss", C.c_double)]
+
+
+class Mp2DensityResult(C.Structure):                      # tf_mp2_density_result
+    _fields_ = [("e_os", C.c_double), ("e_ss", C.c_double), ("P_mo", C.c_void_p), ("P_ao", C.c_void_p), ("L", C.c_void_p), ("z", C.c_void_p),
+                ("seconds", C.c_double * 5)]
+
+
 EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normalize", "tf_set_basis", "tf_get_norms",
            "tf_dims", "tf_get_sph_matrix", "tf_one_electron", "tf_cross_overlap", "tf_build_eri", "tf_eri_storage",
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
            "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_eri_build_stats", "tf_shard_plan", "tf_jk_profile",
-           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_ccsd_rhf", "tf_triples_rhf", "tf_cis_rhf", "tf_cis_d_rhf", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
+           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_ccsd_rhf", "tf_triples_rhf", "tf_cis_rhf", "tf_cis_d_rhf", "tf_mp2_density_rhf", "tf_natural_orbitals", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
            "tf_dft_clear", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
 
@@ -156,6 +165,8 @@ def lib():
     L.tf_triples_rhf.restype = ci; L.tf_triples_rhf.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, C.POINTER(TriplesResult)]
     L.tf_cis_rhf.restype = ci; L.tf_cis_rhf.argtypes = [vp, C.POINTER(CisOpts), ci, ci, vp, vp, vp, C.POINTER(CisResult)]
     L.tf_cis_d_rhf.restype = ci; L.tf_cis_d_rhf.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, C.POINTER(CisDResult)]
+    L.tf_mp2_density_rhf.restype = ci; L.tf_mp2_density_rhf.argtypes = [vp, C.POINTER(Mp2DensityOpts), ci, ci, vp, vp, C.POINTER(Mp2DensityResult)]
+    L.tf_natural_orbitals.restype = ci; L.tf_natural_orbitals.argtypes = [vp, ci, vp, vp, vp, vp]
     L.tf_dft_setup.restype = ci; L.tf_dft_setup.argtypes = [vp, C.c_int64, vp, vp, ci, ci, cd, cd, cd]
     L.tf_dft_vxc.restype = ci; L.tf_dft_vxc.argtypes = [vp, vp, vp, dp, dp, dp]
     L.tf_dft_vxc_unrestricted.restype = ci; L.tf_dft_vxc_unrestricted.argtypes = [vp, vp, vp, vp, vp, dp, dp, dp]

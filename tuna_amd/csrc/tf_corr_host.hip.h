@@ -1684,6 +1684,194 @@ int tf_cis_d_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const do
     return TF_OK;
 }
 
+// The restricted MP2 one-particle density, unrelaxed or Z-vector relaxed (run_restricted_MP2, tuna_mp.py:908-966;
+// calculate_restricted_relaxed_MP2_density_matrix, :177-279; tf_mp2dens.hip.h has the expressions).  Stages: the MO blocks (ia|jb) and,
+// relaxed, (ab|ij) and (ji|kb) through mo_transform_device; the amplitudes and the MP2 partials (mp2dens_amp_kernel); the unrelaxed blocks
+// as four GEMMs; relaxed: one pass of mp3_ladder_stage on w with the occupied back-transformation (tf_mp4_rhf's singles), o GEMMs over
+// (ji|kb), one J/K build of C P^(2) C^T, the Lagrangian (mp2dens_lagrangian_kernel), A + B by tf_cis_rhf's assembly pass, dpotrf and
+// dpotrs.  Work space of a relaxed call: at most 6 arrays of o^2 v^2 values at a time ((ia|jb), (ab|ij), tOS, tSS, w in two layouts; tOS
+// and tSS are freed before the ladder's Y comes, w before the transposed (ij|ab) and the (o v)^2 of A + B); an unrelaxed call has 3.
+int tf_mp2_density_rhf(tf_ctx *ctx, const tf_mp2_density_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps,
+                       tf_mp2_density_result *out)
+{
+    static const char *who = "tf_mp2_density_rhf";
+    int rc = corr_args(ctx, who, opts && C && eps && out, " (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)", n_occ, n_frozen);
+    if (rc) return rc;
+    const bool relaxed = opts->relaxed != 0;
+    if (relaxed && n_frozen != 0)
+        TF_FAIL(ctx, TF_EINVAL, "tf_mp2_density_rhf: the relaxed density needs n_frozen = 0, got %d: the frozen-core Z-vector equations (A over all "
+                "occupied orbitals, B over the active ones) are not built; the unrelaxed density takes a frozen core", n_frozen);
+    if (relaxed && !out->P_mo && !out->P_ao && !out->L && !out->z) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_density_rhf: a relaxed call needs one of P_mo, P_ao, L, z");
+    CorrSetup S;
+    if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
+    const int N = S.N, o = S.o, v = S.v;
+    const long long ov = S.ov, B2 = S.B2, o3v = (long long)o * o * ov;
+    if (ov > 2000000LL || (long long)v * v > 2000000LL || ov * (long long)std::max(o, v) > 0x7fffffffLL) TF_FAIL(ctx, TF_EINVAL, "tf_mp2_density_rhf: dimension overflow");
+    const int dim = (int)ov, iov = dim;
+    const size_t nn = (size_t)N * N;
+    DeviceBlocks mem;
+    auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
+    // ---- MO blocks: (ia|jb) = g1[i][a][j][b]; relaxed: (ab|ij) = g2[a][b][i][j] and (ji|kb) = g4[j][i][k][b]
+    double *g1 = nullptr, *g2 = nullptr, *g4 = nullptr;
+    if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g1, nullptr))) return rc;
+    if (relaxed) {
+        if (!(g2 = mem.alloc((size_t)B2))) return fail(TF_ENOMEM, "tf_mp2_density_rhf: out of device memory");
+        if ((rc = mo_vvoo_block(ctx, who, S.Cv, S.Cv, S.Co, S.Co, o, v, g2))) return rc;
+        if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Co.data(), o, S.Co.data(), o, S.Cv.data(), v, mem, &g4, nullptr))) return rc;
+    }
+    const auto t1 = corr_stamp();
+    // ---- work space.  amps: tOS | tSS; ww: w[i][a][j][b] | w[i][j][a][b]; small: partials [2 nblk] | Poo [o^2] | Pvv [v^2] | C [N^2] |
+    //      P2 (MO) [N^2] | P_mo [N^2] | T [N^2] | P_ao [N^2], and relaxed J | K | P_src [N^2 each] | T1 [N v] | L2 | Lf | L | z [o v each] |
+    //      OA | OB [o^3 v each] | Vo [TFL_W N o]
+    const int nblk = CORR_NBLK;
+    const size_t nsmall = (size_t)2 * nblk + (size_t)o * o + (size_t)v * v + 5 * nn +
+                          (relaxed ? 3 * nn + (size_t)N * v + 4 * (size_t)ov + 2 * (size_t)o3v + (size_t)TFL_W * N * o : 0);
+    const size_t nladder = relaxed ? mp3_ladder_work_doubles(ctx, v) : 0;
+    char oom[220];
+    snprintf(oom, sizeof oom, "tf_mp2_density_rhf: out of device memory for %.2f GB of work space (%s)",
+             (double)((relaxed ? 6 : 3) * (size_t)B2 + nsmall + nladder) * sizeof(double) / 1e9,
+             relaxed ? "6 arrays of o^2 v^2 values at a time, (o v)^2 for A + B among them, and the ladder's batch" : "3 arrays of o^2 v^2 values");
+    double *amps = mem.alloc(2 * (size_t)B2), *ww = relaxed ? mem.alloc(2 * (size_t)B2) : nullptr, *small = mem.alloc(nsmall);
+    if (!amps || (relaxed && !ww) || !small) return fail(TF_ENOMEM, oom);
+    double *tos = amps, *tss = amps + B2, *wov = ww, *woo = ww ? ww + B2 : nullptr;
+    double *d_part = small, *Poo = d_part + (size_t)2 * nblk, *Pvv = Poo + (size_t)o * o, *dC = Pvv + (size_t)v * v, *P2 = dC + nn, *Pmo = P2 + nn, *Tn = Pmo + nn,
+           *Pao = Tn + nn, *dJ = Pao + nn, *dK = dJ + nn, *Psrc = dK + nn, *T1 = Psrc + nn, *L2 = T1 + (size_t)N * v, *Lf = L2 + ov, *dL = Lf + ov, *dz = dL + ov,
+           *OA = dz + ov, *OB = OA + o3v, *Vo = OB + o3v;
+    if ((rc = corr_upload(ctx, who, S, mem, eps, nullptr, relaxed, oom))) return rc;
+    if (hipMemcpy(dC, C, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: copy failed");
+    rocblas_handle blas = ctx->scf.blas;
+    BlasAtomicsOff no_atomics(blas);                          // no split-K sums: the same call gives the same bits
+    // ---- amplitudes and the MP2 partials
+    hipLaunchKernelGGL(tfmp2dens::mp2dens_amp_kernel, dim3(nblk), dim3(256), 0, 0, g1, S.d_eps, n_frozen, o, v, n_occ, opts->c_os, opts->c_ss, tos, tss, wov, woo,
+                       d_part);
+    double e2[2];
+    if (sum_partials_host(d_part, nblk, 2, e2) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the amplitude kernel failed on the device");
+    out->e_os = e2[0]; out->e_ss = e2[1];
+    // ---- unrelaxed: Poo = -1/2 c_os TOS TOS^T - c_ss TSS TSS^T with T [o][(v o v)]; Pvv = 1/2 c_os MOS^T MOS + c_ss MSS^T MSS with M [(o v o)][v]
+    const int vov = v * iov, ovo = o * iov;
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, vov, -0.5 * opts->c_os, tos, vov, tos, vov, 0.0, Poo, o));
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, o, o, vov, -opts->c_ss, tss, vov, tss, vov, 1.0, Poo, o));
+    CORR_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, ovo, 0.5 * opts->c_os, tos, v, tos, v, 0.0, Pvv, v));
+    CORR_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, ovo, opts->c_ss, tss, v, tss, v, 1.0, Pvv, v));
+    const dim3 grid_nn((unsigned)((nn + 255) / 256));
+    hipLaunchKernelGGL(tfmp2dens::mp2dens_assemble_kernel, grid_nn, dim3(256), 0, 0, Poo, Pvv, (const double *)nullptr, 0, N, n_frozen, n_occ, P2);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the unrelaxed stage failed on the device");
+    mem.release(amps);
+    auto t2 = corr_stamp(), t3 = t2, t4 = t2, t5 = t2;
+    if (relaxed) {
+        // ---- Lagrangian, first term: one ladder pass on w with the occupied back-transformation (OA, OB)
+        double *Y = mem.alloc((size_t)B2), *batch = Y ? mem.alloc(nladder) : nullptr;
+        if (!batch) return fail(TF_ENOMEM, oom);
+        corr_permute(ctx, S);
+        if ((rc = mp3_ladder_stage(ctx, who, o, v, woo, S.Cvl, batch, Y, S.Col, Vo, OA, OB))) return rc;
+        t3 = corr_stamp();
+        mem.release(batch); mem.release(Y);
+        // ---- second term: L2[i][a] = sum_j sum_(kb) (ji|kb) w[j][a][(kb)]
+        for (int j = 0; j < o; ++j)
+            CORR_BLAS(tfmp3::gemm_rm(blas, false, true, o, v, iov, 1.0, g4 + (size_t)j * o * ov, iov, wov + (size_t)j * v * ov, iov, j ? 1.0 : 0.0, L2, v));
+        // ---- Fock response: P_src = sym(C P2 C^T), Lf = C_o^T (4 J - 2 K) C_v
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, N, N, 1.0, dC, N, P2, N, 0.0, Tn, N));
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, true, N, N, N, 1.0, Tn, N, dC, N, 0.0, Pao, N));
+        hipLaunchKernelGGL(tfscf::k_symmetrise, grid_nn, dim3(256), 0, 0, Pao, Psrc, N);
+        {
+            const double *pp[8]; double *jj[8], *kk[8];
+            for (int q = 0; q < 8; ++q) { pp[q] = Psrc; jj[q] = dJ; kk[q] = dK; }
+            if ((rc = launch_jk(ctx, 1, pp, jj, kk, 0))) return rc;
+        }
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 4.0, dJ, N, S.d_Cv, v, 0.0, T1, v));
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, -2.0, dK, N, S.d_Cv, v, 1.0, T1, v));
+        CORR_BLAS(tfmp3::gemm_rm(blas, true, false, o, v, N, 1.0, S.d_Co, o, T1, v, 0.0, Lf, v));
+        hipLaunchKernelGGL(tfmp2dens::mp2dens_lagrangian_kernel, dim3((unsigned)((ov + 255) / 256)), dim3(256), 0, 0, OA, OB, S.packed ? 1 : 0, L2, Lf, o, v, dL, dz);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the Lagrangian stage failed on the device");
+        mem.release(ww);
+        t4 = corr_stamp();
+        // ---- Z-vector: (A + B) z = -L
+        double *Ht = mem.alloc((size_t)B2), *M = Ht ? mem.alloc((size_t)B2) : nullptr;
+        rocblas_int *d_info = M ? mem.alloc_int(4) : nullptr;
+        if (!d_info) return fail(TF_ENOMEM, oom);
+        tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+        {
+            tfcis::AssembleArgs A{};
+            A.g1 = g1; A.Ht = Ht; A.eps = S.d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v;
+            A.kind[0] = 2; A.out[0] = M; A.n_out = 1;
+            tfcis::launch_assemble(A, 0);
+        }
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the assembly kernels failed on the device");
+        mem.release(Ht);
+        CORR_BLAS_WHAT("rocSOLVER", rocsolver_dpotrf(blas, rocblas_fill_lower, dim, M, dim, d_info));
+        int h = 0;
+        if (hipMemcpy(&h, d_info, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the Cholesky factorisation failed on the device");
+        if (h != 0) {
+            char text[320];
+            snprintf(text, sizeof text, "tf_mp2_density_rhf: A + B is not positive definite (dpotrf stopped at the leading minor of order %d of %d): the RHF "
+                     "solution is singlet-unstable, the Z-vector equations have no meaningful solution and no relaxed density is returned", h, dim);
+            return fail(TF_ELINALG, text);
+        }
+        CORR_BLAS_WHAT("rocSOLVER", rocsolver_dpotrs(blas, rocblas_fill_lower, dim, 1, M, dim, dz, dim));
+        t5 = corr_stamp();
+    }
+    // ---- P_mo with the reference determinant's 2 on the occupied diagonal, P_ao = C P_mo C^T
+    hipLaunchKernelGGL(tfmp2dens::mp2dens_assemble_kernel, grid_nn, dim3(256), 0, 0, Poo, Pvv, relaxed ? (const double *)dz : (const double *)nullptr, 1, N, n_frozen,
+                       n_occ, Pmo);
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, N, N, 1.0, dC, N, Pmo, N, 0.0, Tn, N));
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, N, N, N, 1.0, Tn, N, dC, N, 0.0, Pao, N));
+    if ((out->P_mo && hipMemcpy(out->P_mo, Pmo, nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (out->P_ao && hipMemcpy(out->P_ao, Pao, nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (relaxed && out->L && hipMemcpy(out->L, dL, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (relaxed && out->z && hipMemcpy(out->z, dz, (size_t)ov * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) || hipGetLastError() != hipSuccess)
+        return fail(TF_ENODEVICE, "tf_mp2_density_rhf: the density kernels or the copies failed on the device");
+    const auto t6 = corr_stamp();
+    out->seconds[0] = corr_secs(t6 - S.t0);
+    out->seconds[1] = corr_secs(t1 - S.t0);
+    out->seconds[2] = corr_secs(t3 - t2);
+    out->seconds[3] = corr_secs(t5 - t4);
+    out->seconds[4] = out->seconds[0] - out->seconds[1] - out->seconds[2] - out->seconds[3];
+    return TF_OK;
+}
+
+// Natural orbitals of a density matrix P [n][n] in a basis with orthogonaliser X (calculate_natural_orbitals, tuna_mp.py:514-565): the
+// eigenpairs of X^-1 P X^-T by the context's eigensolver (X^-1 by dgetrf / dgetri), occupations descending, orbitals = X vectors.
+int tf_natural_orbitals(tf_ctx *ctx, int n, const double *P, const double *X, double *occ, double *orbitals)
+{
+    static const char *who = "tf_natural_orbitals";
+    if (!ctx) return TF_EINVAL;
+    if (n < 1 || !P || !X || !occ || !orbitals) TF_FAIL(ctx, TF_EINVAL, "tf_natural_orbitals: bad arguments (needs n >= 1, P, X, occ and orbitals)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    int rc = tfscf::ensure(ctx->scf, n, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    offer_symmetry(ctx, ctx->scf, n);
+    const size_t nn = (size_t)n * n;
+    DeviceBlocks mem;
+    double *buf = mem.alloc(6 * nn + 5 * (size_t)n);           // X | X^-1 | P | T | W | orbitals, then vals | work [3 n] | occ
+    rocblas_int *ipiv = buf ? mem.alloc_int((size_t)n + 4) : nullptr;
+    if (!ipiv) TF_FAIL(ctx, TF_ENOMEM, "tf_natural_orbitals: out of device memory");
+    rocblas_int *d_info = ipiv + n;
+    double *dX = buf, *dXi = dX + nn, *dP = dXi + nn, *T = dP + nn, *W = T + nn, *dO = W + nn, *vals = dO + nn, *work = vals + n, *d_occ = work + 3 * (size_t)n;
+    if (hipMemcpy(dX, X, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dXi, X, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dP, P, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, "tf_natural_orbitals: copy failed");
+    rocblas_handle blas = ctx->scf.blas;
+    BlasAtomicsOff no_atomics(blas);
+    // the inverse of a row-major matrix is the row-major reading of the inverse of its column-major reading
+    CORR_BLAS_WHAT("rocSOLVER", rocsolver_dgetrf(blas, n, n, dXi, n, ipiv, d_info));
+    int h = 0;
+    if (hipMemcpy(&h, d_info, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return corr_fail(ctx, TF_ENODEVICE, "tf_natural_orbitals: the factorisation failed on the device");
+    if (h != 0) TF_FAIL(ctx, TF_ELINALG, "tf_natural_orbitals: X is singular (dgetrf found a zero pivot at %d of %d)", h, n);
+    CORR_BLAS_WHAT("rocSOLVER", rocsolver_dgetri(blas, n, dXi, n, ipiv, d_info));
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, false, n, n, n, 1.0, dXi, n, dP, n, 0.0, T, n));
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, n, n, n, 1.0, T, n, dXi, n, 0.0, dO, n));
+    hipLaunchKernelGGL(tfscf::k_symmetrise, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, 0, dO, W, n);
+    if ((rc = tfscf::eigh(ctx->scf, n, W, vals, work, msg))) { ctx->err = msg; return rc; }
+    // the solver's vectors are the rows of W: X W^T has them as columns, in ascending order
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, true, n, n, n, 1.0, dX, n, W, n, 0.0, T, n));
+    hipLaunchKernelGGL(tfmp2dens::natorb_reverse_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, 0, vals, T, n, d_occ, dO);
+    if (hipMemcpy(occ, d_occ, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(orbitals, dO, nn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, "tf_natural_orbitals: the kernels or the copies failed on the device");
+    return TF_OK;
+}
+
 int tf_mp3_ladder_probe(tf_ctx *ctx, int n, const double *T, double *Zh)
 {
     if (!ctx) return TF_EINVAL;

@@ -40,6 +40,7 @@
 #include "tf_cis.hip.h"
 #include "tf_cisd.hip.h"
 #include "tf_mp4.hip.h"
+#include "tf_mp2dens.hip.h"
 #include "tf_triples.hip.h"
 #include "tf_dft.hip.h"
 

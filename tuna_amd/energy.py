@@ -80,6 +80,9 @@ class Calculation:
     n_states: int = 10                                 # NSTATES, calc:169
     excited_state_contribution_threshold: float = 1.0  # EXTHRESH (per cent), calc:168
     do_perturbative_doubles: bool = False              # (D) / [D], calc:121: CIS(D) of the ROOT state after the spectrum (tuna_ci.py:2293-2295)
+    relaxed_density: bool = False                      # RELAXED: the Z-vector relaxed MP2 density (tuna_mp.py:908, :939-945)
+    unrelaxed_density: bool = False                    # UNRELAXED: the unrelaxed MP2 density, the reference's default
+    natural_orbitals: bool = False                     # NATORBS: natural orbitals of the MP2 density (tuna_mp.py:971-973)
 
 
 @dataclass
@@ -212,6 +215,12 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.excited_state_contribution_threshold = float(value())
         elif p in ("(D)", "[D]"):
             calc.do_perturbative_doubles = True
+        elif p == "RELAXED":
+            calc.relaxed_density = True
+        elif p == "UNRELAXED":
+            calc.unrelaxed_density = True
+        elif p == "NATORBS":
+            calc.natural_orbitals = True
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -369,6 +378,8 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                     log(f"\n  Same spin contribution:             {E_SS:13.10f}")       # mp:904-906
                 log(f"  Opposite spin contribution:         {E_OS:13.10f}")
                 log(f"\n  MP2 correlation energy:             {r['E_MP2']:13.10f}")
+            if mp2_density_requested(calc):
+                run_mp2_density(calc, molecule, integrals, X, out, engine, silent, log)
             if calc.mp3:
                 E_MP3 = r3["E_MP3"]
                 if not silent:
@@ -397,6 +408,8 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             run_excited_states(calc, molecule, integrals, out, engine, silent, log)
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
+            if getattr(out, "mp2_density_type", None):
+                log(f"\n Using the MP2 {out.mp2_density_type} density for property calculations.")     # tuna_props.py:826
         if calc.dipole or calc.polarisability or calc.hyperpolarisability:
             # finite-field properties (energy:941-957): the cycles of a property run in lockstep on the resident tensor
             from . import properties as props
@@ -417,6 +430,44 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
     finally:
         if own:
             engine.close()
+
+
+def mp2_density_requested(calc: Calculation) -> bool:
+    return calc.relaxed_density or calc.unrelaxed_density or calc.natural_orbitals
+
+
+def run_mp2_density(calc: Calculation, molecule, integrals, X, out, engine: Engine, silent=True, log=print):
+    """The MP2 one-particle density after a restricted MP2 / SCS-MP2 energy (all-electron), tf_mp2_density_rhf and tf_natural_orbitals:
+    the density part of run_restricted_MP2 (tuna_mp.py:908-973) -- unrelaxed unless RELAXED asks for the Z-vector relaxed one, the
+    SCS weights on both spin parts -- then calculate_natural_orbitals (:514-565; its block is printed with NATORBS, as there) and the
+    analytical dipole moment about the centre of mass (tuna_props.py:96-121).  out.P, out.P_alpha and out.P_beta become the MP2 density."""
+    from . import guess as guess_mod
+    relaxed = calc.relaxed_density
+    density_type = "relaxed" if relaxed else "unrelaxed"
+    c_os, c_ss = (calc.opposite_spin_scaling, calc.same_spin_scaling) if calc.spin_component_scaling else (1.0, 1.0)
+    t0 = time.perf_counter()
+    d = engine.mp2_density_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, 0, relaxed=relaxed, c_os=c_os, c_ss=c_ss)
+    occ, orbitals = engine.natural_orbitals(d["P_ao"], X)
+    out.timings["MP2 density"] = time.perf_counter() - t0
+    if not silent:
+        pad = "   " if relaxed else " "
+        log(f"\n  Constructing MP2 {density_type} density...{pad}     [Done]")                        # mp:910-914, :967
+        if calc.natural_orbitals:                                                                  # mp:551-562
+            log("")
+            log("  Natural orbital occupancies: \n")
+            for k, n in enumerate(occ):
+                log(f"    {(k + 1):2.0f}. {n:12.8f}")
+            log(f"\n  Sum of natural orbital occupancies: {np.sum(occ):.6f}")
+            log(f"  Trace of density matrix: {np.sum(occ):.6f}")
+    out.P, out.P_alpha, out.P_beta = d["P_ao"], d["P_ao"] / 2, d["P_ao"] / 2
+    out.mp2 = dict(out.mp2, P_mo=d["P_mo"], L=d["L"], z=d["z"], density_seconds=d["seconds"])
+    out.mp2_density_type = density_type
+    out.natural_orbital_occupancies, out.natural_orbitals = occ, orbitals
+    atoms = molecule.atoms
+    com = guess_mod.centre_of_mass(atoms) if len(atoms) == 2 else 0.0
+    nuclear = float(sum((a.origin[2] - com) * float(a.charge) for a in atoms))
+    electronic = -float(np.einsum("ij,ij->", d["P_ao"], integrals.D[2], optimize=True))
+    out.properties = dict(getattr(out, "properties", None) or {}, dipole_moment=(nuclear + electronic, nuclear, electronic))
 
 
 def run_restricted_mp4(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
@@ -753,6 +804,25 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         raise TunaError(f"Electronic structure method \"{method}\" is not supported.")
     calc = interpret_keywords(params, Calculation(ctype, method if method in dft_mod.FUNCTIONALS else ("MP2" if "MP" in method else "HF"), basis))
     calc.coupled_cluster = cc
+    if mp2_density_requested(calc):
+        asked = " / ".join(k for k, on in (("RELAXED", calc.relaxed_density), ("UNRELAXED", calc.unrelaxed_density), ("NATORBS", calc.natural_orbitals)) if on)
+        if unrestricted_mp2 or (calc.method == "MP2" and calc.multiplicity != 1):
+            raise TunaError(f"{asked}: the unrestricted MP2 density is not built: the MP2 density and its natural orbitals are available on a "
+                            "closed-shell restricted MP2 or SCS-MP2 line only.")
+        if mp3 or mp4:
+            raise TunaError(f"{asked}: the MP2 density on an {method} line is not built: the MP2 density and its natural orbitals are available on "
+                            "a closed-shell restricted MP2 or SCS-MP2 line only.")
+        if cc:
+            raise TunaError(f"{asked}: the linearised coupled-cluster density is not built: the MP2 density and its natural orbitals are available on "
+                            "a closed-shell restricted MP2 or SCS-MP2 line only.")
+        if excited or calc.time_dependent:
+            raise TunaError(f"{asked}: excited-state densities are not built: the MP2 density and its natural orbitals are available on a "
+                            "closed-shell restricted MP2 or SCS-MP2 line only.")
+        if calc.method != "MP2":
+            raise TunaError(f"{asked}: densities and natural orbitals of a {method} line are not built: the MP2 density and its natural orbitals are "
+                            "available on a closed-shell restricted MP2 or SCS-MP2 line only.")
+        if calc.relaxed_density and calc.unrelaxed_density:
+            raise TunaError("RELAXED and UNRELAXED ask for two different MP2 densities: give one of them.")
     if calc.time_dependent and not excited:                  # TD on an HF line: time-dependent Hartree-Fock (kernel:1175)
         if method not in ("HF", "RHF"):
             raise TunaError(f"The TD keyword is available on an HF or RHF line only in this build: excited states of {method} (time-dependent DFT, "

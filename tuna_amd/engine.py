@@ -473,6 +473,43 @@ class Engine:
         self._check(self._L.tf_cis_d_rhf(self._ctx, n_occ, n_frozen, ptr(C), ptr(eps), n, ptr(b), ptr(omega), ptr(flags), ctypes.byref(res)))
         return dict(arrays, seconds=list(res.seconds))
 
+    def mp2_density_rhf(self, C, eps, n_occ, n_frozen=0, relaxed=False, c_os=1.0, c_ss=1.0) -> dict:
+        """The MP2 one-particle density of canonical RHF orbitals, unrelaxed or Z-vector relaxed (tunafock.h: tf_mp2_density_rhf;
+        tuna_mp.py:177-279, :908-966).  c_os, c_ss weigh the opposite- and same-spin parts (1, 1: MP2; OSS, SSS: SCS-MP2).  Returns
+        {"E_OS", "E_SS", "E_MP2" (unscaled), "P_mo", "P_ao" [N, N] (with the 2 of every occupied orbital), "L", "z" [n_occ, v] (None
+        unless relaxed), "seconds" = [wall, MO blocks, ladder, Z-vector, rest]}.  Raises TunaError on a shape or window mismatch before
+        any device call."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"mp2_density_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        n_occ, n_frozen = int(n_occ), int(n_frozen)
+        if not 0 <= n_frozen < n_occ < self.N:
+            raise TunaError(f"mp2_density_rhf: the windows must satisfy 0 <= n_frozen < n_occ < N, got n_frozen = {n_frozen}, n_occ = {n_occ}, N = {self.N}")
+        if relaxed and n_frozen != 0:
+            raise TunaError(f"mp2_density_rhf: the relaxed density needs n_frozen = 0, got {n_frozen}: the frozen-core Z-vector equations are not built")
+        import ctypes
+        from ._lib import Mp2DensityOpts, Mp2DensityResult
+        opts = Mp2DensityOpts(1 if relaxed else 0, float(c_os), float(c_ss))
+        res = Mp2DensityResult()
+        P_mo, P_ao = np.zeros((self.N, self.N)), np.zeros((self.N, self.N))
+        L = np.zeros((n_occ, self.N - n_occ)) if relaxed else None
+        z = np.zeros_like(L) if relaxed else None
+        res.P_mo, res.P_ao, res.L, res.z = ptr(P_mo), ptr(P_ao), ptr(L), ptr(z)
+        self._check(self._L.tf_mp2_density_rhf(self._ctx, ctypes.byref(opts), n_occ, n_frozen, ptr(C), ptr(eps), ctypes.byref(res)))
+        return {"E_OS": res.e_os, "E_SS": res.e_ss, "E_MP2": res.e_os + res.e_ss, "P_mo": P_mo, "P_ao": P_ao, "L": L, "z": z,
+                "seconds": list(res.seconds)}
+
+    def natural_orbitals(self, P, X):
+        """(occupations, orbitals) of a density matrix P in the AO basis with the Fock orthogonaliser X (tunafock.h: tf_natural_orbitals;
+        tuna_mp.py:514-565): eigenpairs of X^-1 P X^-T on the device, occupations descending, orbitals = X vectors (column k)."""
+        P, X = f64(P), f64(X)
+        n = P.shape[0] if P.ndim == 2 else -1
+        if n < 1 or P.shape != (n, n) or X.shape != (n, n):
+            raise TunaError(f"natural_orbitals: P and X must be square matrices of one size, got {list(P.shape)} and {list(X.shape)}")
+        occ, orb = np.zeros(n), np.zeros((n, n))
+        self._check(self._L.tf_natural_orbitals(self._ctx, n, ptr(P), ptr(X), ptr(occ), ptr(orb)))
+        return occ, orb
+
     def mp3_ladder_probe(self, T) -> np.ndarray:
         """Zh[p] = the stored-triangle ladder contraction of the packed tensor with T[p] ([N,N] or [n,N,N], any matrices), by the kernel
         and the batching of mp3_rhf (tunafock.h: tf_mp3_ladder_probe); Z[T] = Zh[T] + Zh[T^T]^T."""
