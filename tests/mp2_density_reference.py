@@ -8,6 +8,12 @@ Occupied window i, j, k = [n_frozen, n_occ), virtual a, b, c = [n_occ, N), D = e
     L_ia = 2 sum_jbc w_ijbc (ab|jc) - 2 sum_jkb w_jkab (ji|kb) + 4 J[P2]_ia - 2 K[P2]_ia     (J, K of the MO-basis density P2 = P_ij + P_ab)
     (A + B)_ia,jb = delta (e_a - e_i) + 4 (ia|jb) - (ij|ab) - (ib|ja),   (A + B) z = -L,   P_ia = P_ai = z_ia / 2
 and 2 on the diagonal of every occupied orbital.
+
+Next to every value stands the sum of the magnitudes of the terms it was formed from (the same expression with |.| on every factor):
+S_oo, S_vv, S_L, S_M (of A + B: |delta (e_a - e_i)| + 4 |(ia|jb)| + |(ij|ab)| + |(ib|ja)|), S_E_OS, S_E_SS, and lambda_min, norm2 of
+the symmetrised A + B.  A float64 evaluation of such a sum of n terms is off by about sqrt(n) 2^-53 S, whatever cancels in it, so the
+GPU tests bound |device - checker| by a multiple of S element by element (tests/test_gpu_mp2_density_shapes.py).
+mp2_density_from_blocks states the same density from the four MO blocks (ia|jb), (ij|ab), (ji|kb), (ia|bc) alone.
 """
 import numpy as np
 
@@ -24,7 +30,8 @@ def mo_integrals(E, C):
 
 
 def mp2_density(E, C, eps, n_occ, n_frozen=0, relaxed=False, c_os=1.0, c_ss=1.0, g=None):
-    """{"E_OS", "E_SS", "P_mo", "P_ao", "L", "z", "cond"}; g = mo_integrals(E, C) if the caller has it already."""
+    """{"E_OS", "E_SS", "P_mo", "P_ao", "L", "z", "cond"}, "P2" (P_mo without the 2 and without z) and the sums of magnitudes();
+    g = mo_integrals(E, C) if the caller has it already."""
     N = len(eps)
     g = mo_integrals(E, C) if g is None else g
     o, v = slice(n_frozen, n_occ), slice(n_occ, N)
@@ -60,6 +67,107 @@ def mp2_density(E, C, eps, n_occ, n_frozen=0, relaxed=False, c_os=1.0, c_ss=1.0,
         out.update(L=L, z=z, cond=float(np.linalg.cond(M)))
     out["P_mo"] = P
     out["P_ao"] = C @ P @ C.T
+    out["P2"] = P2
+    blocks = (G, g[o, o, v, v], g[o, o, o, v], g[o, v, v, v]) if relaxed else (G, None, None, None)
+    out.update(magnitudes(eo, ev, *blocks, P2[o, o], P2[v, v], relaxed, c_os, c_ss))
+    return out
+
+
+def magnitudes(eo, ev, ovov, oovv, ooov, ovvv, P2oo, P2vv, relaxed, c_os, c_ss, dtype=np.float64):
+    """The sums of magnitudes of the module docstring, every expression of mp2_density again with |.| on each factor:
+    {"S_oo" [o, o], "S_vv" [v, v], "S_E_OS", "S_E_SS", "S_L" [o, v], "S_M" [o v, o v], "T_L" [o, v], "lambda_min", "norm2"}, the last
+    five None unless relaxed.  T_L is the first-order sensitivity of L to its integrals, sum |dL_ia / dg|: integrals that are all off
+    by delta move L_ia by at most delta T_L[i, a].  Blocks: ovov[i, a, j, b] = (ia|jb), oovv[i, j, a, b] = (ij|ab),
+    ooov[j, i, k, b] = (ji|kb), ovvv[i, a, b, c] = (ia|bc); P2oo, P2vv the blocks of P^(2)."""
+    no, nv = len(eo), len(ev)
+    eo, ev = np.asarray(eo, dtype), np.asarray(ev, dtype)
+    c_os, c_ss = dtype(c_os), dtype(c_ss)
+    G = np.abs(np.asarray(ovov, dtype))
+    Gx = G.transpose(0, 3, 2, 1)
+    D = np.abs(eo[:, None, None, None] + eo[None, None, :, None] - ev[None, :, None, None] - ev[None, None, None, :])
+    tos, tss = 2.0 * G / D, (G + Gx) / D
+    S_oo, S_vv = np.zeros((no, no), dtype), np.zeros((nv, nv), dtype)
+    for c, t, f in ((abs(c_os), tos, 0.5), (abs(c_ss), tss, 1.0)):
+        S_oo += f * c * np.einsum("kaib,kajb->ij", t, t, optimize=True)
+        S_vv += f * c * np.einsum("ibjc,iajc->ab", t, t, optimize=True)
+    out = {"S_oo": S_oo, "S_vv": S_vv, "S_E_OS": float(np.sum(G * G / D)), "S_E_SS": float(np.sum(G * (G + Gx) / D)),
+           "S_L": None, "S_M": None, "T_L": None, "lambda_min": None, "norm2": None}
+    if relaxed:
+        oovv, ooov, ovvv = (np.asarray(x, dtype) for x in (oovv, ooov, ovvv))
+        w = abs(c_os) * 2.0 * G / D + abs(c_ss) * 2.0 * (G + Gx) / D
+        Aoo, Avv, a_ooov, a_ovvv = np.abs(np.asarray(P2oo, dtype)), np.abs(np.asarray(P2vv, dtype)), np.abs(ooov), np.abs(ovvv)
+        S_L = 2.0 * np.einsum("ibjc,jcab->ia", w, a_ovvv, optimize=True) + 2.0 * np.einsum("jakb,jikb->ia", w, a_ooov, optimize=True)
+        S_L += 4.0 * (np.einsum("jkia,jk->ia", a_ooov, Aoo, optimize=True) + np.einsum("iabc,bc->ia", a_ovvv, Avv, optimize=True))
+        S_L += 2.0 * (np.einsum("ijka,jk->ia", a_ooov, Aoo, optimize=True) + np.einsum("ibac,bc->ia", a_ovvv, Avv, optimize=True))
+        S_M = (4.0 * G + np.abs(oovv).transpose(0, 2, 1, 3) + Gx).reshape(no * nv, no * nv).copy()
+        S_M[np.diag_indices(no * nv)] += np.abs(ev[None, :] - eo[:, None]).ravel()
+        M = _a_plus_b(eo, ev, np.asarray(ovov, dtype), oovv).astype(np.float64)
+        lam = np.linalg.eigvalsh(M)
+        out.update(S_L=S_L, S_M=S_M, lambda_min=float(lam[0]), norm2=float(max(abs(lam[0]), abs(lam[-1]))))
+        # T_L = sum |dL_ia / dg| over every MO integral L is formed from, by the product rule on the same expression: each factor in
+        # turn replaced by the magnitude of its derivative (an integral: 1; t: 2 / |D|; w: (2 |c_os| + 4 |c_ss|) / |D|)
+        dt, dw = 2.0 / D, (2.0 * abs(c_os) + 4.0 * abs(c_ss)) / D
+        dPoo, dPvv = np.zeros((no, no), dtype), np.zeros((nv, nv), dtype)
+        for c, t, f in ((abs(c_os), tos, 0.5), (abs(c_ss), tss, 1.0)):
+            dPoo += f * c * (np.einsum("kaib,kajb->ij", dt, t, optimize=True) + np.einsum("kaib,kajb->ij", t, dt, optimize=True))
+            dPvv += f * c * (np.einsum("ibjc,iajc->ab", dt, t, optimize=True) + np.einsum("ibjc,iajc->ab", t, dt, optimize=True))
+        T_L = 2.0 * (np.sum(w, axis=(1, 2, 3))[:, None] + np.einsum("ibjc,jcab->ia", dw, a_ovvv, optimize=True))
+        T_L += 2.0 * (np.sum(w, axis=(0, 2, 3))[None, :] + np.einsum("jakb,jikb->ia", dw, a_ooov, optimize=True))
+        T_L += 6.0 * (np.sum(Aoo) + np.sum(Avv))
+        T_L += 4.0 * (np.einsum("jkia,jk->ia", a_ooov, dPoo, optimize=True) + np.einsum("iabc,bc->ia", a_ovvv, dPvv, optimize=True))
+        T_L += 2.0 * (np.einsum("ijka,jk->ia", a_ooov, dPoo, optimize=True) + np.einsum("ibac,bc->ia", a_ovvv, dPvv, optimize=True))
+        out["T_L"] = T_L
+    return out
+
+
+def _a_plus_b(eo, ev, ovov, oovv):
+    """The symmetrised singlet A + B [o v, o v] as mp2_density forms it"""
+    no, nv = len(eo), len(ev)
+    M = 4.0 * ovov - oovv.transpose(0, 2, 1, 3) - ovov.transpose(0, 3, 2, 1)
+    M = M.reshape(no * nv, no * nv).copy()
+    M[np.diag_indices(no * nv)] += (ev[None, :] - eo[:, None]).ravel()
+    return 0.5 * (M + M.T)
+
+
+def mp2_density_from_blocks(eo, ev, ovov, oovv, ooov, ovvv, relaxed=False, c_os=1.0, c_ss=1.0, dtype=np.float64):
+    """The outputs of mp2_density from the MO blocks of the window alone (oovv, ooov, ovvv may be None unless relaxed), no N^4 array
+    formed: in the occupied-virtual block J[P2]_ia = sum_jk (ia|jk) P_jk + sum_bc (ia|bc) P_bc and K[P2]_ia = sum_jk (ij|ka) P_jk +
+    sum_bc (ib|ac) P_bc.  "P_mo" is [o + v, o + v], the window and the virtuals (with the 2 on the occupied diagonal), "P2" the same
+    without the 2; "P_ao" is None, there being no orbitals.  dtype = np.longdouble evaluates every contraction in extended precision
+    on the same inputs (the solve stays in float64)."""
+    no, nv = len(eo), len(ev)
+    eo, ev = np.asarray(eo, dtype), np.asarray(ev, dtype)
+    c_os, c_ss = dtype(c_os), dtype(c_ss)
+    G = np.asarray(ovov, dtype)
+    Gx = G.transpose(0, 3, 2, 1)
+    D = eo[:, None, None, None] + eo[None, None, :, None] - ev[None, :, None, None] - ev[None, None, None, :]
+    tos, tss = -2.0 * G / D, (G - Gx) / D
+    Poo, Pvv = np.zeros((no, no), dtype), np.zeros((nv, nv), dtype)
+    for c, t, f in ((c_os, tos, 0.5), (c_ss, tss, 1.0)):
+        Poo += -f * c * np.einsum("kaib,kajb->ij", t, t, optimize=True)
+        Pvv += f * c * np.einsum("ibjc,iajc->ab", t, t, optimize=True)
+    out = {"E_OS": np.sum(G * G / D), "E_SS": np.sum(G * (G - Gx) / D), "L": None, "z": None, "cond": None, "D_max": float(D.max())}
+    if dtype is np.float64:
+        out.update(E_OS=float(out["E_OS"]), E_SS=float(out["E_SS"]))
+    P2 = np.zeros((no + nv, no + nv), dtype)
+    P2[:no, :no], P2[no:, no:] = Poo, Pvv
+    P = P2.copy()
+    P[:no, :no] += 2.0 * np.eye(no)
+    if relaxed:
+        oovv, ooov, ovvv = (np.asarray(x, dtype) for x in (oovv, ooov, ovvv))
+        w = c_os * 2.0 * G / D + c_ss * 2.0 * (G - Gx) / D
+        L = 2.0 * np.einsum("ibjc,jcab->ia", w, ovvv, optimize=True)
+        L -= 2.0 * np.einsum("jakb,jikb->ia", w, ooov, optimize=True)
+        J = np.einsum("jkia,jk->ia", ooov, Poo, optimize=True) + np.einsum("iabc,bc->ia", ovvv, Pvv, optimize=True)
+        K = np.einsum("ijka,jk->ia", ooov, Poo, optimize=True) + np.einsum("ibac,bc->ia", ovvv, Pvv, optimize=True)
+        L += 4.0 * J - 2.0 * K
+        M = _a_plus_b(eo, ev, G, oovv).astype(np.float64)
+        z = np.linalg.solve(M, -L.astype(np.float64).ravel()).reshape(no, nv)
+        P[:no, no:] += 0.5 * z
+        P[no:, :no] += 0.5 * z.T
+        out.update(L=L, z=z, cond=float(np.linalg.cond(M)))
+    out.update(P_mo=P, P2=P2, P_ao=None)
+    out.update(magnitudes(eo, ev, ovov, oovv, ooov, ovvv, Poo, Pvv, relaxed, c_os, c_ss, dtype))
     return out
 
 
