@@ -480,6 +480,82 @@ typedef struct {
 int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip,
                tf_cis_result *out);
 
+/* ---- unrestricted CIS / TDHF: replaces calculate_unrestricted_single_reference_excited_states (tuna_ci.py:1377-1455) and
+ * calculate_unrestricted_transition_dipoles (:1529-1571) ---- */
+
+typedef struct {
+    int32_t tda;                /* 1 = CIS (the matrix A alone), 0 = TDHF / RPA */
+    int32_t n_keep;             /* state vectors returned: the lowest n_keep (0 = none; clamped to dim) */
+} tf_ucis_opts;
+
+typedef struct {
+    int32_t dim;                /* d_alpha + d_beta: the number of states (set by the call) */
+    int32_t dim_alpha;          /* d_alpha = o_alpha v_alpha: where the beta block of the compound index starts (set by the call) */
+    double *e;                  /* [dim] ascending, caller-allocated, may be NULL */
+    double *x;                  /* [n_keep][dim] caller-allocated, may be NULL: X of the lowest states, alpha block then beta block */
+    double *y;                  /* [n_keep][dim] likewise: Y (zeros for CIS) */
+    double *tdm;                /* [dim][3] may be NULL: transition dipoles, x y z; needs dip */
+    double *osc;                /* [dim] may be NULL: oscillator strengths; needs dip */
+    double *m_plus;             /* [dim][dim] may be NULL: the assembled matrix, A + B (TDHF) or A (CIS) -- tests */
+    double *m_minus;            /* [dim][dim] may be NULL: A - B (TDHF only; untouched for CIS) */
+    double seconds[4];          /* wall time, MO blocks, assembly, solves and transition moments */
+} tf_ucis_result;
+
+/* Spin-conserving CIS / TDHF excitation energies, state vectors and transition moments of a UHF determinant: canonical orbitals
+ * C_alpha, C_beta [N,N] and eps_alpha, eps_beta [N].  Per spin s the occupied window is [n_frozen_s, n_s) and the virtual window
+ * [n_s, N); d_s = o_s v_s, dim = d_alpha + d_beta.  Compound index: the alpha block first, (ia) = i v_alpha + a, then the beta block,
+ * d_alpha + j v_beta + b (the reference's spin-conserving subset of its energy-sorted spin orbitals up to a permutation, which leaves
+ * the energies, |mu| and f as they are).  With chemists' integrals and HFX = 1,
+ *     A[(ia s),(jb t)] = d_st d_ij d_ab (e_a - e_i) + (ia s|jb t) - d_st (ij|ab),     B[(ia s),(jb t)] = (ia s|jb t) - d_st (ib|ja),
+ * each assembled matrix symmetrised as 1/2 (M + M^T) to the last bit; A - B is block-diagonal in spin, its alpha-beta rectangles are
+ * exact zeros.  The five MO blocks -- (ia|jb) for aa, bb and ab, (ab|ij) for aa and bb -- come from the general transformation on every
+ * tensor layout; one kernel pass writes all matrices of the call, then the blocks are freed.  An empty spin block (o_s = 0 or v_s = 0,
+ * the H atom's beta spin) launches nothing.
+ * CIS: one dsyevd of A; negative eigenvalues are returned as they are.
+ * TDHF: as tf_cis_rhf: A - B = L L^T (dpotrf), [L^T (A + B) L] Z = w^2 Z (dsyevd), X + Y = L Z / sqrt(w), X - Y = sqrt(w) L^-T Z, so that
+ *     X.X - Y.Y = 1 over both spins.  If dpotrf fails or any w^2 <= 0 the UHF reference is unstable: TF_ELINALG, the message names the
+ *     leading minor or the smallest w^2, no state of that call is valid; the context stays usable.
+ * Transition moments (dip = the three AO dipole matrices [3][N][N], host): mu_n[c] = sum_s sum_ia (C_os^T D^c C_vs)_ia (X + Y)^n_ias,
+ *     without the sqrt(2) of the restricted singlets; f_n = (2/3) w_n |mu_n|^2.
+ * Nothing is reduced with atomics: two calls give the same bits.
+ * Work space: the matrices of the call (CIS 1, TDHF 2 arrays of dim^2) plus, during the TDHF solves, one more array of dim^2; until the
+ * assembly is done the five blocks (d_a^2 + d_b^2 + d_a d_b values and the two (ij|ab) of o_s^2 v_s^2, each briefly in two orders), and
+ * rocSOLVER's own.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL opts, C_alpha, C_beta, eps_alpha, eps_beta or out, unless
+ * 0 <= n_frozen_s <= n_s <= N for both spins, with dim = 0, n_keep < 0, tdm or osc without dip, or world > 1.  TF_ENOMEM, with the
+ * size in the message. */
+int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta,
+               const double *C_alpha, const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *dip,
+               tf_ucis_result *out);
+
+/* ---- SCF stability analysis: replaces determine_self_consistent_field_stability (tuna_ci.py:852-1106), the STAB keyword ---- */
+
+typedef struct {
+    int32_t dim;                /* order of every matrix: o v (RHF), d_alpha + d_beta (UHF) (set by the call) */
+    int32_t dim_alpha;          /* UHF: d_alpha; RHF: dim */
+    int32_t n_matrices;         /* RHF 3: A + B singlet, A + B triplet, A - B (matrices 0, 1, 2); UHF 2: A + B, A - B (matrices 0, 1) */
+    int32_t source[2];          /* the number of the matrix lowest[k] is an eigenvalue of */
+    double lowest[2];           /* RHF: the lowest eigenvalue of the singlet and of the triplet Hessian; UHF: lowest[0] = lowest[1] */
+    double *spectra;            /* [n_matrices][dim] may be NULL: every matrix's eigenvalues, ascending */
+    double *kappa;              /* [2][dim] may be NULL: the normalised eigenvector u of lowest[k] in its matrix, the orbital rotation
+                                 * kappa_ia of that mode (the Hessian's vector is (u, u) / sqrt(2) for A + B, (u, -u) / sqrt(2) for A - B) */
+    double seconds[4];          /* wall time, MO blocks, assembly, solves */
+} tf_stability_result;
+
+/* The lowest eigenvalues of the orbital Hessian [[A, B], [B, A]] of an RHF or UHF determinant, whose spectrum is eig(A + B) u eig(A - B):
+ * the matrix of order 2 dim is never formed.  Only the assembly pass of tf_cis_rhf (its matrices A + B singlet, A + B triplet, A - B) or
+ * tf_cis_uhf (A + B, A - B) runs, then one dsyevd per matrix -- eigenvalues only unless kappa is asked for.
+ *     RHF: lowest[0] = min(l_min(A + B singlet), l_min(A - B))   (restricted, "singlet" rotations)
+ *          lowest[1] = min(l_min(A + B triplet), l_min(A - B))   (unrestricted, "triplet" rotations)
+ *     UHF: lowest[0] = lowest[1] = min(l_min(A + B), l_min(A - B)) of the spin-blocked matrices (spin-conserving rotations)
+ * Windows, index order, layouts and work space as tf_cis_rhf / tf_cis_uhf in their TDHF form, without the extra array of the solves.  An
+ * unstable reference is a result, not an error.  Two calls give the same bits.
+ * TF_EINVAL (the context stays usable) without a tensor, on a NULL C, eps or out, windows out of range (RHF: 0 <= n_frozen < n_occ < N;
+ * UHF: as tf_cis_uhf, dim = 0 included), or world > 1.  TF_ENOMEM, with the size in the message. */
+int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, tf_stability_result *out);
+int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+                     const double *C_beta, const double *eps_alpha, const double *eps_beta, tf_stability_result *out);
+
 /* ---- CIS(D): replaces calculate_restricted_doubles_correction (tuna_ci.py:1874-1982), the perturbative doubles correction of
  * Head-Gordon, Rico, Oumi and Lee to closed-shell CIS / TDHF states ---- */
 

@@ -71,6 +71,20 @@ class CisResult(C.Structure):                             # tf_cis_result
                 ("m_plus_triplet", C.c_void_p), ("m_minus", C.c_void_p), ("seconds", C.c_double * 4)]
 
 
+class UcisOpts(C.Structure):                              # tf_ucis_opts
+    _fields_ = [("tda", C.c_int32), ("n_keep", C.c_int32)]
+
+
+class UcisResult(C.Structure):                            # tf_ucis_result
+    _fields_ = [("dim", C.c_int32), ("dim_alpha", C.c_int32), ("e", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("tdm", C.c_void_p),
+                ("osc", C.c_void_p), ("m_plus", C.c_void_p), ("m_minus", C.c_void_p), ("seconds", C.c_double * 4)]
+
+
+class StabilityResult(C.Structure):                       # tf_stability_result
+    _fields_ = [("dim", C.c_int32), ("dim_alpha", C.c_int32), ("n_matrices", C.c_int32), ("source", C.c_int32 * 2), ("lowest", C.c_double * 2),
+                ("spectra", C.c_void_p), ("kappa", C.c_void_p), ("seconds", C.c_double * 4)]
+
+
 class CisDResult(C.Structure):                            # tf_cis_d_result
     _fields_ = [("e_d", C.c_void_p), ("e_direct", C.c_void_p), ("e_indirect", C.c_void_p), ("min_denominator", C.c_void_p),
                 ("seconds", C.c_double * 3)]
@@ -89,7 +103,7 @@ EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normali
            "tf_dims", "tf_get_sph_matrix", "tf_one_electron", "tf_cross_overlap", "tf_build_eri", "tf_eri_storage",
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
            "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_eri_build_stats", "tf_shard_plan", "tf_jk_profile",
-           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_ccsd_rhf", "tf_triples_rhf", "tf_cis_rhf", "tf_cis_d_rhf", "tf_mp2_density_rhf", "tf_natural_orbitals", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
+           "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_ccsd_rhf", "tf_triples_rhf", "tf_cis_rhf", "tf_cis_uhf", "tf_stability_rhf", "tf_stability_uhf", "tf_cis_d_rhf", "tf_mp2_density_rhf", "tf_natural_orbitals", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
            "tf_dft_clear", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
 
@@ -164,6 +178,9 @@ def lib():
     L.tf_ccsd_rhf.restype = ci; L.tf_ccsd_rhf.argtypes = [vp, C.POINTER(CcOpts), ci, ci, vp, vp, C.POINTER(CcsdResult)]
     L.tf_triples_rhf.restype = ci; L.tf_triples_rhf.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, C.POINTER(TriplesResult)]
     L.tf_cis_rhf.restype = ci; L.tf_cis_rhf.argtypes = [vp, C.POINTER(CisOpts), ci, ci, vp, vp, vp, C.POINTER(CisResult)]
+    L.tf_cis_uhf.restype = ci; L.tf_cis_uhf.argtypes = [vp, C.POINTER(UcisOpts), ci, ci, ci, ci, vp, vp, vp, vp, vp, C.POINTER(UcisResult)]
+    L.tf_stability_rhf.restype = ci; L.tf_stability_rhf.argtypes = [vp, ci, ci, vp, vp, C.POINTER(StabilityResult)]
+    L.tf_stability_uhf.restype = ci; L.tf_stability_uhf.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(StabilityResult)]
     L.tf_cis_d_rhf.restype = ci; L.tf_cis_d_rhf.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, C.POINTER(CisDResult)]
     L.tf_mp2_density_rhf.restype = ci; L.tf_mp2_density_rhf.argtypes = [vp, C.POINTER(Mp2DensityOpts), ci, ci, vp, vp, C.POINTER(Mp2DensityResult)]
     L.tf_natural_orbitals.restype = ci; L.tf_natural_orbitals.argtypes = [vp, ci, vp, vp, vp, vp]

@@ -1377,6 +1377,133 @@ int tf_triples_rhf(tf_ctx *ctx, int kind, int n_occ, int n_frozen, const double 
     return TF_OK;
 }
 
+// ---- CIS / TDHF and the stability analysis: the solve stages tf_cis_rhf and tf_cis_uhf share -------------------------------------
+
+#define CIS_BLAS(call) CORR_BLAS_WHAT("rocBLAS / rocSOLVER", call)
+
+// What a solve stage works with: the driver's names for its messages, the handle, the order of the matrices, the small device arrays
+// w | w2 | e (dsyevd) | stat[2], and -- TDHF -- the dim^2 array T of the triangular products and the kept vectors Q | Xk | Yk
+struct __attribute__((visibility("hidden"))) CisSolve {
+    tf_ctx *ctx = nullptr;
+    const char *who = "", *ref = "";                          // "tf_cis_rhf", "RHF"
+    rocblas_handle blas = nullptr;
+    int dim = 0, nk = 0;
+    rocblas_int *d_info = nullptr;
+    double *d_w = nullptr, *d_w2 = nullptr, *d_e = nullptr, *d_stat = nullptr, *T = nullptr, *Q = nullptr, *Xk = nullptr, *Yk = nullptr;
+    bool info(int *h) const { return hipMemcpy(h, d_info, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; }
+    int fail(int code, const std::string &m) const { return corr_fail(ctx, code, std::string(who) + m); }
+};
+
+// D^c_ia = C_o^T D^c C_v for c = x, y, z into Dia[c][offset + i v + a] (rows of length dim); T1 is [N][v] of work space
+static int cis_dipole_block(const CisSolve &s, int N, int o, int v, const double *d_dip, const double *d_Co, const double *d_Cv, double *d_T1, double *d_Dia,
+                            size_t offset)
+{
+    tf_ctx *ctx = s.ctx; const char *who = s.who;
+    for (int c = 0; c < 3; ++c) {
+        CIS_BLAS(tfmp3::gemm_rm(s.blas, false, false, N, v, N, 1.0, d_dip + (size_t)c * N * N, N, d_Cv, v, 0.0, d_T1, v));
+        CIS_BLAS(tfmp3::gemm_rm(s.blas, true, false, o, v, N, 1.0, d_Co, o, d_T1, v, 0.0, d_Dia + (size_t)c * s.dim + offset, v));
+    }
+    return TF_OK;
+}
+
+// mu_n[c] = scale sum_ia D^c_ia V[ia][n] over the states (columns) of V, and the oscillator strengths, to the host
+static int cis_transition_moments(const CisSolve &s, const double *V, double scale, const double *d_Dia, double *d_mu, double *d_f, double *tdm, double *osc)
+{
+    const int dim = s.dim;
+    if (tfmp3::gemm_rm(s.blas, false, true, dim, 3, dim, scale, V, dim, d_Dia, dim, 0.0, d_mu, 3) != rocblas_status_success) return TF_ELINALG;
+    hipLaunchKernelGGL(tfcis::oscillator_kernel, dim3((unsigned)((dim + 255) / 256)), dim3(256), 0, 0, d_mu, s.d_w, dim, d_f);
+    if ((tdm && hipMemcpy(tdm, d_mu, 3 * (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (osc && hipMemcpy(osc, d_f, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+        return TF_ENODEVICE;
+    return TF_OK;
+}
+
+// A - B = L L^T in place (lower).  Not positive definite: the reference is unstable, TF_ELINALG; whom = " for singlets or triplets" or ""
+static int cis_tdhf_factor(const CisSolve &s, double *Mm, const char *whom)
+{
+    tf_ctx *ctx = s.ctx; const char *who = s.who;
+    CIS_BLAS(rocsolver_dpotrf(s.blas, rocblas_fill_lower, s.dim, Mm, s.dim, s.d_info));
+    int h = 0;
+    if (!s.info(&h)) return s.fail(TF_ENODEVICE, ": the Cholesky factorisation failed on the device");
+    if (h != 0) {
+        char text[300];
+        snprintf(text, sizeof text, ": A - B is not positive definite (dpotrf stopped at the leading minor of order %d of %d): the %s "
+                 "reference is unstable, and TDHF has no real excitation energies%s; the states are not returned", h, s.dim, s.ref, whom);
+        return s.fail(TF_ELINALG, text);
+    }
+    return TF_OK;
+}
+
+// CIS: the eigenpairs of M in place (energies in d_w, state n = column n); the lowest nk vectors to x_out, zeros to y_out
+static int cis_tda_solve(const CisSolve &s, double *M, const char *name, double *x_out, double *y_out)
+{
+    tf_ctx *ctx = s.ctx; const char *who = s.who;
+    const int dim = s.dim, nk = s.nk;
+    int h = 0;
+    CIS_BLAS(rocsolver_dsyevd(s.blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, s.d_w, s.d_e, s.d_info));
+    if (!s.info(&h)) return s.fail(TF_ENODEVICE, ": the eigensolver failed on the device");
+    if (h != 0) return s.fail(TF_ELINALG, std::string(": the eigenvalues of the ") + name + " CIS matrix did not converge (rocsolver_dsyevd)");
+    if (nk > 0 && x_out && hipMemcpy(x_out, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return s.fail(TF_ENODEVICE, ": copy failed");
+    if (nk > 0 && y_out) std::fill(y_out, y_out + (size_t)nk * dim, 0.0);
+    return TF_OK;
+}
+
+// TDHF with Mm = L of cis_tdhf_factor and M = A + B: M <- L^T (A + B) L, its eigenpairs (w^2, Z); energies in d_w; X + Y = L Z / sqrt(w)
+// for every state in T (state n = column n), X and Y of the lowest nk to x_out, y_out.  Any w^2 <= 0: TF_ELINALG.
+static int cis_tdhf_solve(const CisSolve &s, const double *Mm, double *M, const char *name, double *x_out, double *y_out)
+{
+    tf_ctx *ctx = s.ctx; const char *who = s.who;
+    const int dim = s.dim, nk = s.nk;
+    const long long B2 = (long long)dim * dim;
+    const double one = 1.0;
+    double *T = s.T, *Q = s.Q;
+    int h = 0;
+    CIS_BLAS(rocblas_dtrmm(s.blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
+                           dim, T, dim));
+    CIS_BLAS(rocblas_dtrmm(s.blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim,
+                           T, dim, M, dim));
+    CIS_BLAS(rocsolver_dsyevd(s.blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, s.d_w2, s.d_e, s.d_info));
+    if (!s.info(&h)) return s.fail(TF_ENODEVICE, ": the eigensolver failed on the device");
+    if (h != 0) return s.fail(TF_ELINALG, std::string(": the eigenvalues of the reduced ") + name + " TDHF matrix did not converge (rocsolver_dsyevd)");
+    hipLaunchKernelGGL(tfcis::tdhf_roots_kernel, dim3(1), dim3(256), 0, 0, s.d_w2, dim, s.d_w, s.d_stat);
+    double stat[2];
+    if (hipMemcpy(stat, s.d_stat, sizeof stat, hipMemcpyDeviceToHost) != hipSuccess) return s.fail(TF_ENODEVICE, ": the root kernel failed on the device");
+    if (stat[0] != 0.0) {
+        char text[300];
+        snprintf(text, sizeof text, ": %d %s root(s) of the TDHF problem have w^2 <= 0 (smallest w^2 = %.10g): the %s reference is "
+                 "unstable towards a %s perturbation, and the states are not returned (CIS on the same orbitals still runs)", (int)stat[0], name, stat[1], s.ref,
+                 name);
+        return s.fail(TF_ELINALG, text);
+    }
+    // X + Y = L Z / sqrt(w) for every state; X - Y = sqrt(w) L^-T Z for the kept ones
+    CIS_BLAS(rocblas_dtrmm(s.blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
+                           dim, T, dim));
+    if (nk > 0) {
+        if (hipMemcpy(Q, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) return s.fail(TF_ENODEVICE, ": copy failed");
+        CIS_BLAS(rocblas_dtrsm(s.blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, nk, &one, Mm, dim,
+                               Q, dim));
+    }
+    hipLaunchKernelGGL(tfcis::tdhf_backsub_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, T, Q, s.d_w, dim, nk, s.Xk,
+                       s.Yk);
+    if (nk > 0 && ((x_out && hipMemcpy(x_out, s.Xk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+                   (y_out && hipMemcpy(y_out, s.Yk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)))
+        return s.fail(TF_ENODEVICE, ": copy failed");
+    return TF_OK;
+}
+
+// The dim^2 array of the triangular products and the kept vectors of a TDHF solve (owner's); false: out of memory, *bytes = the size
+static bool cis_tdhf_workspace(CisSolve &s, DeviceBlocks &mem, size_t *bytes)
+{
+    const size_t B2 = (size_t)s.dim * s.dim, rows = (size_t)std::max(1, s.nk) * s.dim;
+    *bytes = (B2 + 3 * rows) * sizeof(double);
+    s.T = mem.alloc(B2);
+    s.Q = s.T ? mem.alloc(3 * rows) : nullptr;
+    if (!s.Q) return false;
+    s.Xk = s.Q + rows; s.Yk = s.Xk + rows;
+    return true;
+}
+
 // Closed-shell CIS / TDHF (tuna_ci.py:719-841, :1161-1211, :1284-1366, :1466-1518; tf_cis.hip.h has the matrices and the reduction).
 // Stages: the MO blocks of tf_mp3_rhf; (ab|ij) transposed to [(ij)][(ab)] and every matrix of the call assembled in one pass, after which
 // the blocks are freed; then per multiplicity one dsyevd (CIS), or dpotrf of A - B once and per multiplicity two dtrmm, one dsyevd, one
@@ -1443,110 +1570,41 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
                 return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
     }
     const auto t2 = corr_stamp();
-    // ---- solves
-    double *T = nullptr, *kept = nullptr;
+    // ---- solves (the stages shared with tf_cis_uhf)
+    CisSolve sv;
+    sv.ctx = ctx; sv.who = who; sv.ref = "RHF"; sv.blas = ctx->scf.blas; sv.dim = dim; sv.nk = nk; sv.d_info = d_info;
+    sv.d_w = d_w; sv.d_w2 = d_w2; sv.d_e = d_e; sv.d_stat = d_stat;
     if (!tda) {
-        T = mem.alloc((size_t)B2);
-        kept = T ? mem.alloc(nkept) : nullptr;
-        if (!kept) {
+        size_t bytes = 0;
+        if (!cis_tdhf_workspace(sv, mem, &bytes)) {
             char text[200];
-            snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space for the TDHF reduction",
-                     (double)((size_t)B2 + nkept) * sizeof(double) / 1e9);
+            snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space for the TDHF reduction", (double)bytes / 1e9);
             return fail(TF_ENOMEM, text);
         }
     }
-    double *Q = kept, *Xk = kept ? kept + (size_t)std::max(1, nk) * dim : nullptr, *Yk = kept ? Xk + (size_t)std::max(1, nk) * dim : nullptr;
-    rocblas_handle blas = ctx->scf.blas;
-    BlasAtomicsOff no_atomics(blas);                          // no atomics in the products: split-K sums would change from run to run
-#define CIS_BLAS(call) CORR_BLAS_WHAT("rocBLAS / rocSOLVER", call)
-    auto info = [&](int *h) { return hipMemcpy(h, d_info, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; };
-    const double one = 1.0;
+    BlasAtomicsOff no_atomics(sv.blas);                       // no atomics in the products: split-K sums would change from run to run
     if (moments) {
         if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_Co, S.Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_Cv, S.Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
             return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-        for (int c = 0; c < 3; ++c) {                             // D^c_ia = C_o^T D^c C_v
-            CIS_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, d_dip + (size_t)c * N * N, N, d_Cv, v, 0.0, d_T1, v));
-            CIS_BLAS(tfmp3::gemm_rm(blas, true, false, o, v, N, 1.0, d_Co, o, d_T1, v, 0.0, d_Dia + (size_t)c * dim, v));
-        }
+        if ((rc = cis_dipole_block(sv, N, o, v, d_dip, d_Co, d_Cv, d_T1, d_Dia, 0))) return rc;     // D^c_ia = C_o^T D^c C_v
     }
-    // mu_n[c] = sqrt(2) sum_ia D^c_ia V[ia][n] over the states (columns) of V, and the oscillator strengths, to the host
-    auto transition_moments = [&](const double *V) -> int {
-        if (tfmp3::gemm_rm(blas, false, true, dim, 3, dim, std::sqrt(2.0), V, dim, d_Dia, dim, 0.0, d_mu, 3) != rocblas_status_success) return TF_ELINALG;
-        hipLaunchKernelGGL(tfcis::oscillator_kernel, dim3((unsigned)((dim + 255) / 256)), dim3(256), 0, 0, d_mu, d_w, dim, d_f);
-        if ((out->tdm && hipMemcpy(out->tdm, d_mu, 3 * (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (out->osc && hipMemcpy(out->osc, d_f, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-            return TF_ENODEVICE;
-        return TF_OK;
-    };
-    if (!tda) {
-        // A - B = L L^T, once for both multiplicities
-        CIS_BLAS(rocsolver_dpotrf(blas, rocblas_fill_lower, dim, Mm, dim, d_info));
-        int h = 0;
-        if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the Cholesky factorisation failed on the device");
-        if (h != 0) {
-            char text[300];
-            snprintf(text, sizeof text, "tf_cis_rhf: A - B is not positive definite (dpotrf stopped at the leading minor of order %d of %d): the RHF "
-                     "reference is unstable, and TDHF has no real excitation energies for singlets or triplets; the states are not returned", h, dim);
-            return fail(TF_ELINALG, text);
-        }
-    }
+    if (!tda && (rc = cis_tdhf_factor(sv, Mm, " for singlets or triplets"))) return rc;             // A - B = L L^T, once for both multiplicities
     for (int mult = 0; mult < 2; ++mult) {
         double *M = mult == 0 ? Ms : Mt;
         if (!M) continue;
         const char *name = mult == 0 ? "singlet" : "triplet";
         double *e_out = mult == 0 ? out->e_singlet : out->e_triplet, *x_out = mult == 0 ? out->x_singlet : out->x_triplet,
                *y_out = mult == 0 ? out->y_singlet : out->y_triplet;
-        const double *V = M;                                      // the transition vectors X + Y, state by state
-        int h = 0;
-        if (tda) {
-            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w, d_e, d_info));
-            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
-            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the ") + name + " CIS matrix did not converge (rocsolver_dsyevd)");
-            if (nk > 0 && x_out && hipMemcpy(x_out, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-            if (nk > 0 && y_out) std::fill(y_out, y_out + (size_t)nk * dim, 0.0);
-        } else {
-            // M <- L^T (A + B) L; its eigenpairs (w^2, Z)
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
-                                   dim, T, dim));
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim,
-                                   T, dim, M, dim));
-            CIS_BLAS(rocsolver_dsyevd(blas, rocblas_evect_original, rocblas_fill_upper, dim, M, dim, d_w2, d_e, d_info));
-            if (!info(&h)) return fail(TF_ENODEVICE, "tf_cis_rhf: the eigensolver failed on the device");
-            if (h != 0) return fail(TF_ELINALG, std::string("tf_cis_rhf: the eigenvalues of the reduced ") + name + " TDHF matrix did not converge (rocsolver_dsyevd)");
-            hipLaunchKernelGGL(tfcis::tdhf_roots_kernel, dim3(1), dim3(256), 0, 0, d_w2, dim, d_w, d_stat);
-            double stat[2];
-            if (hipMemcpy(stat, d_stat, sizeof stat, hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the root kernel failed on the device");
-            if (stat[0] != 0.0) {
-                char text[300];
-                snprintf(text, sizeof text, "tf_cis_rhf: %d %s root(s) of the TDHF problem have w^2 <= 0 (smallest w^2 = %.10g): the RHF reference is "
-                         "unstable towards a %s perturbation, and the states are not returned (CIS on the same orbitals still runs)", (int)stat[0], name, stat[1], name);
-                return fail(TF_ELINALG, text);
-            }
-            // X + Y = L Z / sqrt(w) for every state; X - Y = sqrt(w) L^-T Z for the kept ones
-            CIS_BLAS(rocblas_dtrmm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, dim, dim, &one, Mm, dim, M,
-                                   dim, T, dim));
-            if (nk > 0) {
-                if (hipMemcpy(Q, M, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-                CIS_BLAS(rocblas_dtrsm(blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, dim, nk, &one, Mm, dim,
-                                       Q, dim));
-            }
-            hipLaunchKernelGGL(tfcis::tdhf_backsub_kernel, dim3((unsigned)std::min<long long>((B2 + 255) / 256, 1 << 16)), dim3(256), 0, 0, T, Q, d_w, dim, nk, Xk,
-                               Yk);
-            if (nk > 0 && ((x_out && hipMemcpy(x_out, Xk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-                           (y_out && hipMemcpy(y_out, Yk, (size_t)nk * dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)))
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-            V = T;
-        }
+        if ((rc = tda ? cis_tda_solve(sv, M, name, x_out, y_out) : cis_tdhf_solve(sv, Mm, M, name, x_out, y_out))) return rc;
+        const double *V = tda ? M : sv.T;                         // the transition vectors X + Y, state by state
         if (e_out && hipMemcpy(e_out, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
-        if (mult == 0 && moments) {
-            const int mrc = transition_moments(V);
+        if (mult == 0 && moments) {                               // mu_n[c] = sqrt(2) sum_ia D^c_ia V[ia][n]
+            const int mrc = cis_transition_moments(sv, V, std::sqrt(2.0), d_Dia, d_mu, d_f, out->tdm, out->osc);
             if (mrc) return fail(mrc, "tf_cis_rhf: the transition moments failed on the device");
         }
     }
-#undef CIS_BLAS
     if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: a kernel launch failed");
     const auto t3 = corr_stamp();
     out->seconds[0] = corr_secs(t3 - S.t0);
@@ -1555,6 +1613,311 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
     out->seconds[3] = corr_secs(t3 - t2);
     return TF_OK;
 }
+
+// ---- unrestricted CIS / TDHF and the stability analysis ----------------------------------------------------------------------------
+
+// The prologue of a driver on UHF orbitals: the checks, one rank only, the device, the start of the clock, the SCF work space and the
+// windows of either spin.  An empty spin block (o_s = 0 or v_s = 0) is allowed; dim = 0 is not.
+struct __attribute__((visibility("hidden"))) UcisSetup {
+    CorrSetup s[2];                                           // alpha, beta
+    int N = 0, dim = 0;
+    long long d[2] = {0, 0};                                  // o_s v_s
+    std::chrono::steady_clock::time_point t0;
+};
+
+static int ucis_begin(tf_ctx *ctx, const char *who, bool pointers_ok, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+                      const double *C_beta, UcisSetup &U)
+{
+    if (!ctx) return TF_EINVAL;
+    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "%s: call tf_build_eri first", who);
+    const int N = ctx->N;
+    if (!pointers_ok || n_frozen_alpha < 0 || n_frozen_alpha > n_alpha || n_alpha > N || n_frozen_beta < 0 || n_frozen_beta > n_beta || n_beta > N)
+        TF_FAIL(ctx, TF_EINVAL, "%s: bad arguments (needs every pointer but dip, and 0 <= n_frozen <= n <= N for both spins)", who);
+    const long long da = (long long)(n_alpha - n_frozen_alpha) * (N - n_alpha), db = (long long)(n_beta - n_frozen_beta) * (N - n_beta);
+    if (da + db == 0) TF_FAIL(ctx, TF_EINVAL, "%s: no spin-conserving excitation (o v = 0 for both spins): there is nothing to calculate", who);
+    if (da + db > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);                      // (grids of 32-wide tiles)
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "%s: a sharded tensor (world > 1) is not supported", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    U.t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    const int rc = tfscf::ensure(ctx->scf, N, 6, msg);
+    if (rc) { ctx->err = msg; return rc; }
+    U.N = N; U.d[0] = da; U.d[1] = db; U.dim = (int)(da + db);
+    U.s[0].windows(N, n_alpha, n_frozen_alpha, C_alpha);
+    U.s[1].windows(N, n_beta, n_frozen_beta, C_beta);
+    return TF_OK;
+}
+
+// The five MO blocks of tfucis::uassemble_kernel through the general transformation, on every layout (mem's): per spin with d_s > 0
+// (ia|jb) and (ab|ij), the latter transposed to [i][j][a][b]; (ia alpha|jb beta) when both spins have excitations
+static int ucis_mo_blocks(tf_ctx *ctx, const char *who, const UcisSetup &U, DeviceBlocks &mem, tfucis::AssembleArgs &A)
+{
+    int rc;
+    for (int s = 0; s < 2; ++s) {
+        if (U.d[s] == 0) continue;
+        const CorrSetup &S = U.s[s];
+        const int o = S.o, v = S.v;
+        double *g = nullptr;
+        if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g, nullptr))) return rc;
+        double *g2 = mem.alloc((size_t)v * v * o * o), *Ht = g2 ? mem.alloc((size_t)v * v * o * o) : nullptr;
+        if (!Ht) {
+            char text[200];
+            snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space ((ab|ij) of one spin in two orders)", who,
+                     2.0 * (double)v * v * o * o * sizeof(double) / 1e9);
+            return corr_fail(ctx, TF_ENOMEM, text);
+        }
+        if ((rc = mo_vvoo_block(ctx, who, S.Cv, S.Cv, S.Co, S.Co, o, v, g2))) return rc;
+        tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+            return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the transposition of (ab|ij) failed on the device");
+        mem.release(g2);
+        A.s[s].g = g; A.s[s].Ht = Ht;
+    }
+    if (U.d[0] > 0 && U.d[1] > 0) {
+        double *g = nullptr;
+        if ((rc = mo_transform_device(ctx, U.s[0].Co.data(), U.s[0].o, U.s[0].Cv.data(), U.s[0].v, U.s[1].Co.data(), U.s[1].o, U.s[1].Cv.data(), U.s[1].v, mem,
+                                      &g, nullptr)))
+            return rc;
+        A.g_ab = g;
+    }
+    return TF_OK;
+}
+
+// One assembly pass: the matrices A.out of kinds A.kind from the blocks of ucis_mo_blocks, which are freed afterwards; d_eps = 2 N doubles
+static int ucis_assemble(tf_ctx *ctx, const char *who, const UcisSetup &U, DeviceBlocks &mem, tfucis::AssembleArgs &A, const double *eps_alpha,
+                         const double *eps_beta, double *d_eps)
+{
+    const int N = U.N;
+    if (hipMemcpy(d_eps, eps_alpha, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_eps + N, eps_beta, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    for (int s = 0; s < 2; ++s) {
+        A.s[s].eps = d_eps + (size_t)s * N;
+        A.s[s].n_frozen = U.s[s].n_frozen; A.s[s].n_occ = U.s[s].n_occ;
+        A.s[s].o = U.d[s] ? U.s[s].o : 0; A.s[s].v = U.d[s] ? U.s[s].v : 0;     // an empty block: d_s = 0 in the kernel whichever of o, v is 0
+    }
+    tfucis::launch_uassemble(A, 0);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the assembly kernel failed on the device");
+    for (int s = 0; s < 2; ++s) { mem.release((void *)A.s[s].g); mem.release((void *)A.s[s].Ht); }
+    mem.release((void *)A.g_ab);
+    return TF_OK;
+}
+
+// Unrestricted CIS / TDHF (tuna_ci.py:755-757, :823-825, :1377-1455, :1529-1571; tf_ucis.hip.h has the matrices).  Stages: the five MO
+// blocks; every matrix of the call assembled in one pass, after which the blocks are freed; then the solve stages of tf_cis_rhf on the
+// spin-blocked matrices (CIS: one dsyevd; TDHF: dpotrf of A - B, two dtrmm, dsyevd, dtrmm, and dtrsm for the kept states); the
+// transition moments with D_ia of both spins side by side in the compound index, without the sqrt(2) of the restricted singlets.
+int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+               const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *dip, tf_ucis_result *out)
+{
+    static const char *who = "tf_cis_uhf";
+    UcisSetup U;
+    int rc = ucis_begin(ctx, who, opts && C_alpha && C_beta && eps_alpha && eps_beta && out, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, U);
+    if (rc) return rc;
+    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "tf_cis_uhf: n_keep must not be negative");
+    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "tf_cis_uhf: transition dipoles and oscillator strengths need the AO dipole matrices (dip)");
+    const int N = U.N, dim = U.dim, nk = std::min(opts->n_keep, dim);
+    const size_t B2 = (size_t)dim * dim;
+    const bool tda = opts->tda != 0, moments = dip && (out->tdm || out->osc);
+    out->dim = dim; out->dim_alpha = (int)U.d[0];
+    DeviceBlocks mem;
+    auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
+    tfucis::AssembleArgs A{};
+    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A))) return rc;
+    const auto t1 = corr_stamp();
+    // ---- work space: the matrices (CIS: A; TDHF: A + B and A - B) and the small arrays
+    //      w | w2 | e (dsyevd) | stat[2] | eps [2][N] | D_ia [3][dim] | mu [dim][3] | f [dim] | C_o | C_v | D C_v [N][v] (the larger spin) | D [3][N][N]
+    const int omax = std::max(U.s[0].o, U.s[1].o), vmax = std::max(U.s[0].v, U.s[1].v);
+    const size_t nsmall = 3 * (size_t)dim + 2 + 2 * (size_t)N + 7 * (size_t)dim + (size_t)N * omax + 2 * (size_t)N * vmax + 3 * (size_t)N * N;
+    double *Mp = mem.alloc(B2), *Mm = tda ? nullptr : mem.alloc(B2), *small = mem.alloc(nsmall);
+    rocblas_int *d_info = mem.alloc_int(4);
+    if (!Mp || (!tda && !Mm) || !small || !d_info) {
+        char text[200];
+        snprintf(text, sizeof text, "tf_cis_uhf: out of device memory for %.2f GB of work space (%d arrays of (d_alpha + d_beta)^2 = %d^2 values)",
+                 (double)((tda ? 1 : 2) * B2 + nsmall) * sizeof(double) / 1e9, tda ? 1 : 2, dim);
+        return fail(TF_ENOMEM, text);
+    }
+    double *d_w = small, *d_w2 = d_w + dim, *d_e = d_w2 + dim, *d_stat = d_e + dim, *d_eps = d_stat + 2, *d_Dia = d_eps + 2 * (size_t)N,
+           *d_mu = d_Dia + 3 * (size_t)dim, *d_f = d_mu + 3 * (size_t)dim, *d_Co = d_f + dim, *d_Cv = d_Co + (size_t)N * omax, *d_T1 = d_Cv + (size_t)N * vmax,
+           *d_dip = d_T1 + (size_t)N * vmax;
+    // ---- assembly
+    A.kind[0] = tda ? 0 : 1; A.out[0] = Mp; A.n_out = 1;
+    if (!tda) { A.kind[1] = 2; A.out[1] = Mm; A.n_out = 2; }
+    if ((rc = ucis_assemble(ctx, who, U, mem, A, eps_alpha, eps_beta, d_eps))) return rc;
+    if ((out->m_plus && hipMemcpy(out->m_plus, Mp, B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (out->m_minus && Mm && hipMemcpy(out->m_minus, Mm, B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+    const auto t2 = corr_stamp();
+    // ---- solves
+    CisSolve sv;
+    sv.ctx = ctx; sv.who = who; sv.ref = "UHF"; sv.blas = ctx->scf.blas; sv.dim = dim; sv.nk = nk; sv.d_info = d_info;
+    sv.d_w = d_w; sv.d_w2 = d_w2; sv.d_e = d_e; sv.d_stat = d_stat;
+    if (!tda) {
+        size_t bytes = 0;
+        if (!cis_tdhf_workspace(sv, mem, &bytes)) {
+            char text[200];
+            snprintf(text, sizeof text, "tf_cis_uhf: out of device memory for %.2f GB of work space for the TDHF reduction", (double)bytes / 1e9);
+            return fail(TF_ENOMEM, text);
+        }
+    }
+    BlasAtomicsOff no_atomics(sv.blas);                       // no atomics in the products: split-K sums would change from run to run
+    if (moments) {
+        if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+        for (int s = 0; s < 2; ++s) {
+            if (U.d[s] == 0) continue;
+            const CorrSetup &S = U.s[s];
+            if (hipMemcpy(d_Co, S.Co.data(), (size_t)N * S.o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_Cv, S.Cv.data(), (size_t)N * S.v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+                return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+            if ((rc = cis_dipole_block(sv, N, S.o, S.v, d_dip, d_Co, d_Cv, d_T1, d_Dia, s ? (size_t)U.d[0] : 0))) return rc;
+        }
+    }
+    if (tda) {
+        if ((rc = cis_tda_solve(sv, Mp, "unrestricted", out->x, out->y))) return rc;
+    } else {
+        if ((rc = cis_tdhf_factor(sv, Mm, ""))) return rc;
+        if ((rc = cis_tdhf_solve(sv, Mm, Mp, "spin-conserving", out->x, out->y))) return rc;
+    }
+    if (out->e && hipMemcpy(out->e, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+    if (moments) {                                            // mu_n[c] = sum over both spins of D^c_ia V[ia][n]: no sqrt(2)
+        const int mrc = cis_transition_moments(sv, tda ? Mp : sv.T, 1.0, d_Dia, d_mu, d_f, out->tdm, out->osc);
+        if (mrc) return fail(mrc, "tf_cis_uhf: the transition moments failed on the device");
+    }
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: a kernel launch failed");
+    const auto t3 = corr_stamp();
+    out->seconds[0] = corr_secs(t3 - U.t0);
+    out->seconds[1] = corr_secs(t1 - U.t0);
+    out->seconds[2] = corr_secs(t2 - t1);
+    out->seconds[3] = corr_secs(t3 - t2);
+    return TF_OK;
+}
+
+// The solves of the stability analysis: the eigenvalues of each of the n matrices M[k] (order dim) to spec[k][dim] on the host, and --
+// vectors -- the eigenvector of each matrix's lowest eigenvalue to vec0[k][dim]
+static int stability_solves(tf_ctx *ctx, const char *who, int dim, int n, double *const *M, double *d_w, double *d_e, rocblas_int *d_info, bool vectors,
+                            std::vector<double> &spec, std::vector<double> &vec0)
+{
+    rocblas_handle blas = ctx->scf.blas;
+    BlasAtomicsOff no_atomics(blas);
+    spec.assign((size_t)n * dim, 0.0);
+    vec0.assign(vectors ? (size_t)n * dim : 0, 0.0);
+    for (int k = 0; k < n; ++k) {
+        CIS_BLAS(rocsolver_dsyevd(blas, vectors ? rocblas_evect_original : rocblas_evect_none, rocblas_fill_upper, dim, M[k], dim, d_w, d_e, d_info));
+        int h = 0;
+        if (hipMemcpy(&h, d_info, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the eigensolver failed on the device");
+        if (h != 0) return corr_fail(ctx, TF_ELINALG, std::string(who) + ": the eigenvalues of an orbital-rotation matrix did not converge (rocsolver_dsyevd)");
+        if (hipMemcpy(spec.data() + (size_t)k * dim, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+            (vectors && hipMemcpy(vec0.data() + (size_t)k * dim, M[k], (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+            return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    }
+    return TF_OK;
+}
+
+// lowest[k] = min(l_min(plus[k]), l_min(minus)) with its source and mode; ties go to A + B
+static void stability_verdict(int dim, const std::vector<double> &spec, const std::vector<double> &vec0, const int plus[2], int minus, tf_stability_result *out)
+{
+    for (int k = 0; k < 2; ++k) {
+        const double lp = spec[(size_t)plus[k] * dim], lm = spec[(size_t)minus * dim];
+        const int src = lm < lp ? minus : plus[k];
+        out->lowest[k] = spec[(size_t)src * dim];
+        out->source[k] = src;
+        if (out->kappa) std::copy(vec0.begin() + (size_t)src * dim, vec0.begin() + (size_t)(src + 1) * dim, out->kappa + (size_t)k * dim);
+    }
+    if (out->spectra) std::copy(spec.begin(), spec.end(), out->spectra);
+}
+
+// RHF stability (tuna_ci.py:926-985): tf_cis_rhf's MO blocks and assembly pass with kinds 2, 3, 4, then three dsyevd
+int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, tf_stability_result *out)
+{
+    static const char *who = "tf_stability_rhf";
+    int rc = corr_args(ctx, who, C && eps && out, " (needs C, eps, out and 0 <= n_frozen < n_occ < N)", n_occ, n_frozen);
+    if (rc) return rc;
+    CorrSetup S;
+    if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
+    const int N = S.N, o = S.o, v = S.v;
+    const long long ov = S.ov, B2 = S.B2;
+    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "tf_stability_rhf: dimension overflow");
+    const int dim = (int)ov;
+    out->dim = dim; out->dim_alpha = dim; out->n_matrices = 3;
+    DeviceBlocks mem;
+    auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
+    double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr;
+    if ((rc = mp3_mo_blocks(ctx, who, S, mem, &g1, &g2, &g3))) return rc;
+    mem.release(g3);
+    const auto t1 = corr_stamp();
+    double *Ht = mem.alloc((size_t)B2), *M[3] = {mem.alloc((size_t)B2), mem.alloc((size_t)B2), mem.alloc((size_t)B2)}, *small = mem.alloc(2 * (size_t)dim + N);
+    rocblas_int *d_info = mem.alloc_int(4);
+    if (!Ht || !M[0] || !M[1] || !M[2] || !small || !d_info) {
+        char text[200];
+        snprintf(text, sizeof text, "tf_stability_rhf: out of device memory for %.2f GB of work space (4 arrays of (o v)^2 = %lld^2 values)",
+                 (double)(4 * (size_t)B2 + 2 * (size_t)dim + N) * sizeof(double) / 1e9, ov);
+        return fail(TF_ENOMEM, text);
+    }
+    double *d_w = small, *d_e = d_w + dim, *d_eps = d_e + dim;
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_stability_rhf: copy failed");
+    tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+    {
+        tfcis::AssembleArgs A{};
+        A.g1 = g1; A.Ht = Ht; A.eps = d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v; A.n_out = 3;
+        for (int k = 0; k < 3; ++k) { A.kind[k] = 2 + k; A.out[k] = M[k]; }
+        tfcis::launch_assemble(A, 0);
+    }
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_stability_rhf: the assembly kernels failed on the device");
+    mem.release(g1); mem.release(g2); mem.release(Ht);
+    const auto t2 = corr_stamp();
+    std::vector<double> spec, vec0;
+    if ((rc = stability_solves(ctx, who, dim, 3, M, d_w, d_e, d_info, out->kappa != nullptr, spec, vec0))) return rc;
+    const int plus[2] = {0, 1};
+    stability_verdict(dim, spec, vec0, plus, 2, out);
+    const auto t3 = corr_stamp();
+    out->seconds[0] = corr_secs(t3 - S.t0);
+    out->seconds[1] = corr_secs(t1 - S.t0);
+    out->seconds[2] = corr_secs(t2 - t1);
+    out->seconds[3] = corr_secs(t3 - t2);
+    return TF_OK;
+}
+
+// UHF stability (tuna_ci.py:994-1038; the spin-conserving Hessian of build_orbital_hessian): tf_cis_uhf's blocks and assembly pass with
+// A + B and A - B, then two dsyevd
+int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+                     const double *eps_alpha, const double *eps_beta, tf_stability_result *out)
+{
+    static const char *who = "tf_stability_uhf";
+    UcisSetup U;
+    int rc = ucis_begin(ctx, who, C_alpha && C_beta && eps_alpha && eps_beta && out, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, U);
+    if (rc) return rc;
+    const int N = U.N, dim = U.dim;
+    const size_t B2 = (size_t)dim * dim;
+    out->dim = dim; out->dim_alpha = (int)U.d[0]; out->n_matrices = 2;
+    DeviceBlocks mem;
+    tfucis::AssembleArgs A{};
+    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A))) return rc;
+    const auto t1 = corr_stamp();
+    double *M[2] = {mem.alloc(B2), mem.alloc(B2)}, *small = mem.alloc(2 * (size_t)dim + 2 * (size_t)N);
+    rocblas_int *d_info = mem.alloc_int(4);
+    if (!M[0] || !M[1] || !small || !d_info) {
+        char text[200];
+        snprintf(text, sizeof text, "tf_stability_uhf: out of device memory for %.2f GB of work space (2 arrays of (d_alpha + d_beta)^2 = %d^2 values)",
+                 (double)(2 * B2 + 2 * (size_t)dim + 2 * (size_t)N) * sizeof(double) / 1e9, dim);
+        return corr_fail(ctx, TF_ENOMEM, text);
+    }
+    double *d_w = small, *d_e = d_w + dim, *d_eps = d_e + dim;
+    A.n_out = 2; A.kind[0] = 1; A.out[0] = M[0]; A.kind[1] = 2; A.out[1] = M[1];
+    if ((rc = ucis_assemble(ctx, who, U, mem, A, eps_alpha, eps_beta, d_eps))) return rc;
+    const auto t2 = corr_stamp();
+    std::vector<double> spec, vec0;
+    if ((rc = stability_solves(ctx, who, dim, 2, M, d_w, d_e, d_info, out->kappa != nullptr, spec, vec0))) return rc;
+    const int plus[2] = {0, 0};
+    stability_verdict(dim, spec, vec0, plus, 1, out);
+    const auto t3 = corr_stamp();
+    out->seconds[0] = corr_secs(t3 - U.t0);
+    out->seconds[1] = corr_secs(t1 - U.t0);
+    out->seconds[2] = corr_secs(t2 - t1);
+    out->seconds[3] = corr_secs(t3 - t2);
+    return TF_OK;
+}
+#undef CIS_BLAS
 
 // CIS(D) of closed-shell CIS / TDHF states (calculate_restricted_doubles_correction, tuna_ci.py:1874-1982; tf_cisd.hip.h has the
 // expressions and the kernels).  Stages: (ia|jb) and (ik|jb) through mo_transform_device, t, tt and L in one pass, Goo and Gvv by one GEMM

@@ -38,6 +38,7 @@
 #include "tf_ccd.hip.h"
 #include "tf_ccsd.hip.h"
 #include "tf_cis.hip.h"
+#include "tf_ucis.hip.h"
 #include "tf_cisd.hip.h"
 #include "tf_mp4.hip.h"
 #include "tf_mp2dens.hip.h"

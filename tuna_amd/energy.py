@@ -11,7 +11,9 @@ CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3
 MP4[SDQ] / MP4[DQ]; full MP4 with triples through Calculation.mp4 = "SDTQ", not on the input line), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
 iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, or TD on an HF line
-(TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x; (D) or [D] adds CIS(D) to the ROOT state).  Everything numerical runs on the GPU through the C ABI.  The initial
+(TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x; (D) or [D] adds CIS(D) to the ROOT state), and STAB, the stability analysis of a Hartree-Fock SCF (RHF or UHF) in front
+of any post-SCF stage.  Through calculate_energy, a Calculation with reference "UHF" and excited_state set runs the spin-conserving CIS /
+TDHF of the open shell.  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
 """
 from __future__ import annotations
@@ -83,6 +85,9 @@ class Calculation:
     relaxed_density: bool = False                      # RELAXED: the Z-vector relaxed MP2 density (tuna_mp.py:908, :939-945)
     unrelaxed_density: bool = False                    # UNRELAXED: the unrelaxed MP2 density, the reference's default
     natural_orbitals: bool = False                     # NATORBS: natural orbitals of the MP2 density (tuna_mp.py:971-973)
+    stability_analysis: bool = False                   # STAB, calc:118: the lowest orbital-Hessian eigenvalues after the SCF (kernel:1146)
+    freeze_core: bool = False                          # read by the unrestricted excited states and STAB only (tuna_ci.py:545, :650): the
+                                                       # core orbitals of FROZEN_CORE_ORBITALS stay out of the occupied window of either spin
 
 
 @dataclass
@@ -221,6 +226,8 @@ def interpret_keywords(params, calc: Calculation) -> Calculation:
             calc.unrelaxed_density = True
         elif p == "NATORBS":
             calc.natural_orbitals = True
+        elif p == "STAB":
+            calc.stability_analysis = True
         elif p in ("EX", "EY", "EZ"):
             f = list(calc.electric_field)
             f["XYZ".index(p[1])] = float(value())
@@ -340,6 +347,8 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
             else:
                 label = "\n Unrestricted Hartree-Fock energy: " if calc.reference == "UHF" else "\n Restricted Hartree-Fock energy:   "
                 log(label + f"{out.energy:16.10f}")                                      # kernel:846-850
+        if calc.stability_analysis:                          # after the SCF's energy components, before any post-SCF stage (kernel:1144-1148)
+            run_stability_analysis(calc, molecule, out, engine, silent, log)
         if calc.method == "MP2" and calc.mp4:
             run_restricted_mp4(calc, molecule, out, engine, silent, log)
         elif calc.method == "MP2":
@@ -430,6 +439,74 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
     finally:
         if own:
             engine.close()
+
+
+def frozen_core_orbitals(molecule, calc: Calculation) -> int:
+    """The frozen orbitals of either spin: 0 unless calc.freeze_core, else the sum over the atoms of 0 (H - Be), 1 (B - Mg), 5 (Al - Ar),
+    the counts the reference's atomic data holds (tuna_molecule.py:332)."""
+    if not calc.freeze_core:
+        return 0
+    n = sum(0 if a.charge <= 4 else (1 if a.charge <= 12 else 5) for a in molecule.atoms)
+    if 2 * n > molecule.n_electrons:
+        raise TunaError("Not enough spatial orbitals to freeze!")                         # tuna_ci.py:547, :652
+    return n
+
+
+def run_stability_analysis(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """STAB: determine_self_consistent_field_stability (tuna_ci.py:1049-1106) for a Hartree-Fock SCF, tf_stability_rhf / tf_stability_uhf:
+    the lowest eigenvalues of the orbital Hessian [[A, B], [B, A]] from eig(A + B) and eig(A - B) -- singlet and triplet for RHF,
+    spin-conserving for UHF -- with the reference's block (:946-983, :1014-1036, :1092-1106) and its threshold of -1e-5.  out.stability
+    holds the eigenvalues, which matrix each came from, the verdicts and the seconds.  An unstable solution is reported, not raised."""
+    if calc.functional is not None:
+        raise TunaError("STAB: the stability analysis of a Kohn-Sham solution needs the exchange-correlation kernel, which is not built: "
+                        "STAB is available on Hartree-Fock references (HF, UHF, and the correlated methods on them).")
+    N = molecule.n_basis
+    threshold = ORB_HESS_EIG_THRESH
+    nf = frozen_core_orbitals(molecule, calc)
+    t0 = time.perf_counter()
+    if calc.reference == "UHF":
+        if (molecule.n_alpha - nf) * (N - molecule.n_alpha) + (molecule.n_beta - nf) * (N - molecule.n_beta) <= 0:
+            raise TunaError("Stability analysis requested on system with no orbital rotations!")
+        r = engine.stability_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, molecule.n_alpha,
+                                 molecule.n_beta, nf, nf)
+        lowest = r["lowest"]
+        st = {"reference": "UHF", "lowest": lowest, "source": r["source"], "unstable_unrestricted": lowest <= threshold, "stable": lowest > threshold}
+    else:
+        if N - molecule.n_doubly_occ <= 0:
+            raise TunaError("Stability analysis requested on system with no orbital rotations!")
+        r = engine.stability_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, nf)
+        ls, lt = r["lowest_singlet"], r["lowest_triplet"]
+        st = {"reference": "RHF", "lowest_singlet": ls, "lowest_triplet": lt, "source_singlet": r["source_singlet"], "source_triplet": r["source_triplet"],
+              "unstable_restricted": ls <= threshold, "unstable_unrestricted": lt <= threshold, "stable": ls > threshold and lt > threshold}
+    out.timings["Stability analysis"] = time.perf_counter() - t0
+    st.update(threshold=threshold, dim=r["dim"], n_frozen=nf, seconds=r["seconds"])
+    out.stability = st
+    if silent:
+        return
+    log("\n" + SPACER)
+    log("                  Stability Analysis")
+    log(SPACER)
+    if calc.reference == "UHF":
+        log("  Building unrestricted orbital Hessian...   [Done]")
+        log("\n  Diagonalising orbital Hessian...           [Done]")
+        log(f"\n  Lowest Hessian eigenvalue:             {st['lowest']:10.5f}")
+        if st["unstable_unrestricted"]:
+            log("\n  The SCF is unstable wrt. unrestricted rotations.")
+        else:
+            log("\n  The self-consistent field solution is stable!")
+    else:
+        log("  Building singlet orbital Hessian...        [Done]")
+        log("  Building triplet orbital Hessian...        [Done]")
+        log("\n  Diagonalising orbital Hessians...          [Done]")
+        log(f"\n  Lowest singlet eigenvalue:             {st['lowest_singlet']:10.5f}")
+        log(f"  Lowest triplet eigenvalue:             {st['lowest_triplet']:10.5f}")
+        if st["unstable_restricted"]:
+            log("\n  The SCF is unstable wrt. restricted rotations.")
+        if st["unstable_unrestricted"]:
+            log("\n  The SCF is unstable wrt. unrestricted rotations.")
+        if st["stable"]:
+            log("\n  The self-consistent field solution is stable!")
+    log(SPACER)
 
 
 def mp2_density_requested(calc: Calculation) -> bool:
@@ -625,6 +702,7 @@ def run_perturbative_triples(calc: Calculation, molecule, out, engine: Engine, s
     out.energy += E_T
 
 
+ORB_HESS_EIG_THRESH = -1e-5                                                                      # tuna_util.py:103
 _HARTREE_IN_JOULES = (mol._hbar ** 2) / (mol._me * mol.BOHR_IN_METRES ** 2)                       # tuna_util.py:53
 PER_CM_IN_HARTREE = _HARTREE_IN_JOULES / (299792458 * mol._h * 10 ** 2)                          # tuna_util.py:60
 EV_IN_HARTREE = _HARTREE_IN_JOULES / mol._e                                                      # tuna_util.py:63
@@ -654,6 +732,8 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
     determine_restricted_excited_state_energy_and_density) and properties on it are not formed in this build.  With
     calc.do_perturbative_doubles the root gets its CIS(D) correction after the spectrum (run_perturbative_doubles).  A TDHF run on an
     unstable reference raises the library's TunaError (TF_ELINALG) where the reference warns and drops states."""
+    if calc.reference == "UHF":
+        return run_unrestricted_excited_states(calc, molecule, integrals, out, engine, silent, log)
     n_occ, N = molecule.n_doubly_occ, molecule.n_basis
     v = N - n_occ
     if calc.calculate_no_singlets and calc.calculate_no_triplets:
@@ -730,6 +810,104 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
     out.energy = out.energy + E_transition                                                # tuna_ci.py:1642
     if calc.do_perturbative_doubles:                                                      # tuna_ci.py:2293-2295
         E_transition = run_perturbative_doubles(calc, molecule, out, engine, silent, log)
+    if not silent:                                                                        # kernel:1295-1299
+        log(f"\n Excitation energy is the energy difference to excited state {calc.root}.")
+        log(f"\n Excitation energy from {f'{calc.excited_state}:':<11} {E_transition:15.10f}")
+
+
+def spin_orbital_labels(eps_alpha, eps_beta):
+    """(label of alpha orbital k, label of beta orbital k): the reference numbers the orbitals of a spin as they come in the combined
+    energy order (tuna_ci.py:586-603), and within one spin that is the spin's own order: the k-th alpha orbital is "<k + 1>a"."""
+    return [f"{k + 1}a" for k in range(len(eps_alpha))], [f"{k + 1}b" for k in range(len(eps_beta))]
+
+
+def run_unrestricted_excited_states(calc: Calculation, molecule, integrals, out, engine: Engine, silent=True, log=print):
+    """Spin-conserving CIS / TDHF of a UHF determinant on the device-resident tensor, tf_cis_uhf: the "UHF" branch of
+    run_excited_state_calculation (tuna_ci.py:2215-2290) with its log lines (:1222-1257, :1416-1451, :1736-1863; no multiplicity line, no
+    singlet / triplet tags, spin-orbital labels such as "3a -> 5a").  Reached through calculate_energy with reference == "UHF" and
+    calc.excited_state set -- the input-line names UCIS / UTDHF / URPA stay refused by run().  Honours tamm_dancoff_approximation,
+    n_states, root, excited_state_contribution_threshold and freeze_core.  out.energy = E_SCF + the excitation energy of ROOT;
+    out.excited holds the energies, |mu|, oscillator strengths, the root's X and Y split by spin and E_transition.  The root's density and
+    difference density are not formed, and (D) on an unrestricted state is refused.  A TDHF run on an unstable reference raises the
+    library's TunaError (TF_ELINALG)."""
+    if calc.do_perturbative_doubles:
+        raise TunaError("The (D) keyword is available for a closed-shell restricted reference only in this build: the unrestricted perturbative "
+                        "doubles correction is not built.")
+    N, na, nb = molecule.n_basis, molecule.n_alpha, molecule.n_beta
+    nf = frozen_core_orbitals(molecule, calc)
+    oa, ob, va, vb = na - nf, nb - nf, N - na, N - nb
+    da, db = max(0, oa) * va, max(0, ob) * vb
+    if da + db <= 0:
+        raise TunaError("Excited state calculation requested on system with no virtual orbitals!")   # kernel:1181
+    tda = calc.tamm_dancoff_approximation or calc.excited_state == "CIS"                  # tuna_ci.py:1401
+    if not silent:
+        log("\n Beginning excited state calculation...")                                  # kernel:1177
+        log("\n" + SPACER)                                                                # tuna_ci.py:1236-1257
+        log("          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
+        log(SPACER)
+        log(("  Using" if tda else "  Not using") + " the Tamm-Dancoff approximation...\n")
+    t0 = time.perf_counter()
+    n_keep = max(calc.n_states, calc.root, 0)
+    r = engine.cis_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, na, nb, nf, nf,
+                       method="CIS" if tda else "TDHF", n_keep=n_keep, dip=integrals.D)
+    out.timings["Excited state calculation"] = time.perf_counter() - t0
+    energies = np.asarray(r["E"], dtype=float)
+    mu, f = np.linalg.norm(np.asarray(r["tdm"], dtype=float).reshape(len(energies), -1), axis=1), np.asarray(r["osc"], dtype=float)
+    if not silent:
+        log("  Building excited state Hamiltonian...      [Done]")                        # tuna_ci.py:1416-1451
+        log("  Diagonalising Hamiltonian...               [Done]")
+        log("\n  Calculating oscillator strengths...        [Done]")                      # tuna_ci.py:2243-2259
+    state = calc.root - 1
+    if not 0 <= state < len(energies):
+        raise TunaError(f"Specified root ({state + 1}) does not exist!")                  # tuna_ci.py:1696
+    if not silent:
+        log("  Constructing density matrix...             [Done]")                        # tuna_ci.py:2269-2281 (the energy only, here)
+    labels_a, labels_b = spin_orbital_labels(out.epsilons_alpha, out.epsilons_beta)
+
+    def split_by_spin(vec):
+        return vec[:da].reshape(max(0, oa), va), vec[da:].reshape(max(0, ob), vb)
+    if not silent:
+        log("\n  Printing excited state information...")                                  # tuna_ci.py:1817-1861
+        log(f"  Only printing contributions larger than {calc.excited_state_contribution_threshold:.1f} %.")
+        for n in range(min(len(energies), calc.n_states)):
+            log(f"\n  ~~~~~ State {n + 1} ~~~~~  ")
+            log(f"\n  Excitation energy: {energies[n]:16.10f}\n")
+            contributions = 100 * (r["X"][n] ** 2 - r["Y"][n] ** 2)
+            for index in np.argsort(contributions)[::-1]:
+                if contributions[index] <= calc.excited_state_contribution_threshold:
+                    break
+                if index < da:
+                    i, a = divmod(int(index), va)
+                    occ_label, virt_label = labels_a[nf + i], labels_a[na + a]
+                else:
+                    i, a = divmod(int(index) - da, vb)
+                    occ_label, virt_label = labels_b[nf + i], labels_b[nb + a]
+                log(f"    {occ_label:>4}  ->  {virt_label:<4}  {contributions[index]:7.2f} %")
+        # print_excited_state_absorption_spectrum, tuna_ci.py:1754-1785, with the gaps of an unrestricted reference
+        from . import guess as guess_mod
+        com = guess_mod.centre_of_mass(molecule.atoms) if len(molecule.atoms) == 2 else 0.0
+        with np.errstate(divide="ignore"):
+            wavelengths_nm = 1e7 / (energies * PER_CM_IN_HARTREE)
+        log("\n" + SPACER)
+        log(f"\n Transition dipole moment origin is the centre of mass, {com * mol.BOHR_RADIUS_IN_ANGSTROM:.4f} angstroms from the first atom.")
+        log("\n" + BIG_SPACER)
+        log("                                     Excited State Absorption Spectrum")
+        log(BIG_SPACER)
+        log("   State         Energy          Energy (eV)     Wavelength (nm)    Osc. Strength     Transition Dipole")
+        log(BIG_SPACER)
+        for n in range(min(len(energies), calc.n_states)):
+            log(f"    {(n + 1):2}    {energies[n]:16.10f}  {EV_IN_HARTREE * energies[n]:14.5f}   {wavelengths_nm[n]:16.5f}       "
+                f"{f[n]:10.5f}          {mu[n]:10.5f}")
+        log(BIG_SPACER)
+    if state < n_keep:
+        (X_alpha, X_beta), (Y_alpha, Y_beta) = split_by_spin(r["X"][state]), split_by_spin(r["Y"][state])
+    else:
+        X_alpha = X_beta = Y_alpha = Y_beta = None
+    E_transition = float(energies[state])
+    out.excited = {"energies": energies, "state_types": np.array([""] * len(energies)), "transition_dipoles": mu, "oscillator_strengths": f,
+                   "X_alpha": X_alpha, "X_beta": X_beta, "Y_alpha": Y_alpha, "Y_beta": Y_beta, "E_transition": E_transition, "root": calc.root,
+                   "method": calc.excited_state, "seconds": r["seconds"], "dim": r["dim"], "dim_alpha": r["dim_alpha"], "n_frozen": nf, "tdm": r["tdm"]}
+    out.energy = out.energy + E_transition                                                # tuna_ci.py:1719
     if not silent:                                                                        # kernel:1295-1299
         log(f"\n Excitation energy is the energy difference to excited state {calc.root}.")
         log(f"\n Excitation energy from {f'{calc.excited_state}:':<11} {E_transition:15.10f}")
@@ -872,4 +1050,7 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         calc.reference = "UHF"
     if method in dft_mod.FUNCTIONALS:
         calc.functional = method
+        if calc.stability_analysis:
+            raise TunaError(f"STAB on a {method} line: the stability analysis of a Kohn-Sham solution needs the exchange-correlation kernel, "
+                            "which is not built.  STAB is available on Hartree-Fock references.")
     return calculate_energy(symbols, R, calc, engine, silent, log)

@@ -439,6 +439,96 @@ class Engine:
                 out[name] = a
         return out
 
+    def _uhf_orbitals(self, who, C_alpha, C_beta, eps_alpha, eps_beta):
+        Ca, Cb, ea, eb = f64(C_alpha), f64(C_beta), f64(eps_alpha), f64(eps_beta)
+        if Ca.shape != (self.N, self.N) or Cb.shape != (self.N, self.N) or ea.shape != (self.N,) or eb.shape != (self.N,):
+            raise TunaError(f"{who}: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}] for both spins")
+        return Ca, Cb, ea, eb
+
+    def cis_uhf(self, C_alpha, C_beta, eps_alpha, eps_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0, method="CIS", n_keep=0, dip=None,
+                return_matrices=False) -> dict:
+        """Spin-conserving CIS or TDHF (RPA) excited states of a UHF determinant on the resident tensor (tunafock.h: tf_cis_uhf;
+        tuna_ci.py:1377-1455, :1529-1571): {"dim", "dim_alpha" (the compound index holds the alpha block (ia) = i v_alpha + a first, then
+        the beta block), "E" [dim] ascending, "X", "Y" [n_keep, dim] of the lowest n_keep states (Y = 0 for CIS; None with n_keep = 0),
+        "tdm" [dim, 3] and "osc" [dim] with dip = the AO dipole matrices [3, N, N] (None otherwise), "seconds" = [wall, MO blocks,
+        assembly, solves]; with return_matrices "M_plus" (A + B, or A for CIS) and "M_minus" (A - B, TDHF) [dim, dim]}.  Raises TunaError
+        with the library's code and message; TF_ELINALG (-5) when TDHF meets an unstable reference."""
+        Ca, Cb, ea, eb = self._uhf_orbitals("cis_uhf", C_alpha, C_beta, eps_alpha, eps_beta)
+        if method not in ("CIS", "TDHF", "RPA"):
+            raise TunaError(f"cis_uhf: method must be \"CIS\", \"TDHF\" or \"RPA\", got {method!r}")
+        if dip is not None:
+            dip = f64(dip)
+            if dip.shape != (3, self.N, self.N):
+                raise TunaError(f"cis_uhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        import ctypes
+        from ._lib import UcisOpts, UcisResult
+        tda = method == "CIS"
+        dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
+        nk = max(0, min(int(n_keep), dim))
+        opts = UcisOpts(int(tda), int(n_keep))
+        res = UcisResult()
+        arrays = {}
+
+        def take(name, shape, wanted=True):
+            arrays[name] = np.zeros(shape) if wanted else None
+            return ptr(arrays[name])
+        res.e = take("E", dim)
+        res.x, res.y = take("X", (nk, dim), nk > 0), take("Y", (nk, dim), nk > 0)
+        res.tdm, res.osc = take("tdm", (dim, 3), dip is not None), take("osc", dim, dip is not None)
+        res.m_plus, res.m_minus = take("M_plus", (dim, dim), return_matrices), take("M_minus", (dim, dim), return_matrices and not tda)
+        self._check(self._L.tf_cis_uhf(self._ctx, ctypes.byref(opts), int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca), ptr(Cb),
+                                       ptr(ea), ptr(eb), ptr(dip), ctypes.byref(res)))
+        out = {"dim": int(res.dim), "dim_alpha": int(res.dim_alpha), "seconds": list(res.seconds)}
+        for name, a in arrays.items():
+            if return_matrices or not name.startswith("M_"):
+                out[name] = a
+        return out
+
+    def _stability(self, call, dim, n_matrices, return_spectra, return_mode):
+        import ctypes
+        from ._lib import StabilityResult
+        res = StabilityResult()
+        spectra = np.zeros((n_matrices, dim)) if return_spectra else None
+        kappa = np.zeros((2, dim)) if return_mode else None
+        res.spectra, res.kappa = ptr(spectra), ptr(kappa)
+        self._check(call(ctypes.byref(res)))
+        return res, spectra, kappa
+
+    STABILITY_MATRICES_RHF = ("plus_singlet", "plus_triplet", "minus")
+    STABILITY_MATRICES_UHF = ("plus", "minus")
+
+    def stability_rhf(self, C, eps, n_occ, n_frozen=0, return_spectra=False, return_mode=False) -> dict:
+        """The lowest eigenvalues of the RHF orbital Hessian [[A, B], [B, A]], singlet (restricted rotations) and triplet (unrestricted
+        rotations), from eig(A + B) and eig(A - B) (tunafock.h: tf_stability_rhf; tuna_ci.py:926-985): {"dim", "lowest_singlet",
+        "lowest_triplet", "source_singlet", "source_triplet" (a name of STABILITY_MATRICES_RHF), "spectra" {name: [dim] ascending} and
+        "mode_singlet", "mode_triplet" [o, v] (the normalised orbital rotation of the lowest mode) when asked for, "seconds" = [wall, MO
+        blocks, assembly, solves]}.  An unstable reference is a result: nothing is raised."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"stability_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
+        names = self.STABILITY_MATRICES_RHF
+        res, spectra, kappa = self._stability(lambda r: self._L.tf_stability_rhf(self._ctx, int(n_occ), int(n_frozen), ptr(C), ptr(eps), r), o * v, 3,
+                                              return_spectra, return_mode)
+        return {"dim": int(res.dim), "lowest_singlet": res.lowest[0], "lowest_triplet": res.lowest[1], "source_singlet": names[res.source[0]],
+                "source_triplet": names[res.source[1]], "spectra": dict(zip(names, spectra)) if return_spectra else None,
+                "mode_singlet": kappa[0].reshape(o, v) if return_mode else None, "mode_triplet": kappa[1].reshape(o, v) if return_mode else None,
+                "seconds": list(res.seconds)}
+
+    def stability_uhf(self, C_alpha, C_beta, eps_alpha, eps_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0, return_spectra=False,
+                      return_mode=False) -> dict:
+        """The lowest eigenvalue of the spin-conserving UHF orbital Hessian from the spin-blocked A + B and A - B (tunafock.h:
+        tf_stability_uhf; tuna_ci.py:994-1038): {"dim", "dim_alpha", "lowest", "source" (a name of STABILITY_MATRICES_UHF), "spectra"
+        {name: [dim] ascending} and "mode" [dim] (alpha block, then beta block) when asked for, "seconds"}.  Nothing is raised for an
+        unstable reference."""
+        Ca, Cb, ea, eb = self._uhf_orbitals("stability_uhf", C_alpha, C_beta, eps_alpha, eps_beta)
+        dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
+        names = self.STABILITY_MATRICES_UHF
+        res, spectra, kappa = self._stability(lambda r: self._L.tf_stability_uhf(self._ctx, int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta),
+                                                                                  ptr(Ca), ptr(Cb), ptr(ea), ptr(eb), r), dim, 2, return_spectra, return_mode)
+        return {"dim": int(res.dim), "dim_alpha": int(res.dim_alpha), "lowest": res.lowest[0], "source": names[res.source[0]],
+                "spectra": dict(zip(names, spectra)) if return_spectra else None, "mode": kappa[0] if return_mode else None, "seconds": list(res.seconds)}
+
     def cis_d_rhf(self, C, eps, n_occ, n_frozen=0, *, b, omega, triplet) -> dict:
         """CIS(D), the perturbative doubles correction to closed-shell CIS / TDHF states (tunafock.h: tf_cis_d_rhf; tuna_ci.py:1874-1982).
         b [n_states, o, v] (or [o, v] for one state) are the normalised state vectors (CIS: X; TDHF: X + Y), omega their excitation
