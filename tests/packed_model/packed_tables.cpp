@@ -3,6 +3,7 @@
 // nothing in the product links it.
 #include <cstring>
 #include "../../tuna_amd/csrc/tf_packed_host.h"
+#include "../../tuna_amd/csrc/tf_jk_plan.h"
 
 struct Handle {
     tfp::HostLayout H;
@@ -63,6 +64,23 @@ long long ptm_const(const char *name)
     if (n == "sizeof_JKSuper") return sizeof(JKSuper);
     if (n == "sizeof_JKTask") return sizeof(JKTask);
     return -1;
+}
+
+// the buffer plan of the packed Fock build (tf_jk_plan.h).  in[12]: N, n_rows, NW, MP, RS, NPtot, n_groups[2], ypart_len[2], nseg[2];
+// out[45]: Jrow, ypart, DI, DJ, Jt, cd[4], then per pass type (ND = 1, 2) the 18 members of JkPassPlan in the order of packed_tables.py
+long long ptm_jk_plan(const long long *in, long long *out)
+{
+    JkPlanIn I;
+    I.N = (int)in[0]; I.n_rows = in[1]; I.NW = (int)in[2]; I.MP = (int)in[3]; I.RS = (int)in[4]; I.NPtot = in[5];
+    for (int t = 0; t < 2; ++t) { I.n_groups[t] = (int)in[6 + t]; I.ypart_len[t] = in[8 + t]; I.nseg[t] = (int)in[10 + t]; }
+    const JkPlan P = jk_plan(I);
+    long long *o = out;
+    for (size_t v : {P.Jrow, P.ypart, P.DI, P.DJ, P.Jt, P.cd[0], P.cd[1], P.cd[2], P.cd[3]}) *o++ = (long long)v;
+    for (const JkPassPlan &q : P.pass)
+        for (size_t v : {q.DI0, q.DJ0, q.y0[0], q.y0[1], q.DIr, q.DJr, q.sP, q.sPp, q.sy, q.sJd, q.sDIc, q.sDIr, q.sDJc, q.sDJr, q.sJt, q.planeJd,
+                         q.planeI, q.planeJ})
+            *o++ = (long long)v;
+    return o - out;
 }
 
 // copies table `name` to out (if not null) and returns its number of elements; -1: no such table

@@ -31,7 +31,7 @@ def lib():
         so = os.path.join(HERE, "packed_model", "_build", "libpackedtables.so")
         csrc = os.path.join(HERE, "..", "tuna_amd", "csrc")
         src = [os.path.join(HERE, "packed_model", "packed_tables.cpp")] + [os.path.join(csrc, h) for h in
-                                                                           ("tf_packed.h", "tf_packed_host.h", "tf_tiles.h", "tf_tiles_host.h", "tf_internal.h")]
+                                                                           ("tf_packed.h", "tf_packed_host.h", "tf_tiles.h", "tf_tiles_host.h", "tf_internal.h", "tf_jk_plan.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
             subprocess.check_call(["sh", os.path.join(HERE, "packed_model", "build.sh")])
         L = C.CDLL(so)
@@ -44,6 +44,8 @@ def lib():
         L.ptm_const.argtypes = [C.c_char_p]
         L.ptm_get.restype = C.c_longlong
         L.ptm_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+        L.ptm_jk_plan.restype = C.c_longlong
+        L.ptm_jk_plan.argtypes = [C.c_void_p, C.c_void_p]
         for name, dt in (("sizeof_JKGroup", GROUP), ("sizeof_JKSuper", SUPER), ("sizeof_JKTask", TASK)):
             assert L.ptm_const(name.encode()) == dt.itemsize, name
         _LIB = L
@@ -96,3 +98,18 @@ def group_table(T):
     """[n_groups][5] = (i, j0, nr, r0, c) of every group: what tf_debug_groups reports"""
     g = T.groups
     return np.stack([g["i"], g["j0"], g["nr"], g["r0"], g["c"]], axis=1).astype(np.int32) if len(g) else np.zeros((0, 5), np.int32)
+
+
+PLAN_SIZES = ("Jrow", "ypart", "DI", "DJ", "Jt", "cd_Jrow", "cd_ypart", "cd_DI", "cd_DJ")
+PLAN_PASS = ("DI0", "DJ0", "y0", "y0_cd", "DIr", "DJr", "sP", "sPp", "sy", "sJd", "sDIc", "sDIr", "sDJc", "sDJr", "sJt", "planeJd", "planeI", "planeJ")
+
+
+def jk_plan(N, n_rows, NW, MP, RS, NPtot, n_groups, ypart_len, nseg):
+    """the buffer plan of the packed Fock build (tuna_amd/csrc/tf_jk_plan.h) in doubles: {size name: doubles, "pass": {ND: {member: value}}};
+    n_groups, ypart_len, nseg: per table set (set 0: one density per pass, set 1: two)"""
+    arg = np.array([N, n_rows, NW, MP, RS, NPtot, *n_groups, *ypart_len, *nseg], dtype=np.int64)
+    out = np.full(len(PLAN_SIZES) + 2 * len(PLAN_PASS), -1, dtype=np.int64)
+    assert lib().ptm_jk_plan(arg.ctypes.data, out.ctypes.data) == len(out)
+    plan = {k: int(v) for k, v in zip(PLAN_SIZES, out)}
+    plan["pass"] = {nd: {k: int(v) for k, v in zip(PLAN_PASS, out[len(PLAN_SIZES) + (nd - 1) * len(PLAN_PASS):])} for nd in (1, 2)}
+    return plan

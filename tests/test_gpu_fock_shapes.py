@@ -208,6 +208,52 @@ def test_cut_walks(engine, monkeypatch, tag, parts):
         _reset(engine)
 
 
+PARENT_DROP_BYTES = 0      # free device memory after the third build minus after the sixth, measured on the commit before tf_jk_host.hip.h
+
+
+def _free_device_memory():
+    """hipMemGetInfo of the HIP runtime the library uses: the one mapped into this process -- the system's, or, where an earlier test
+    imported torch first, the wheel's copy, which the library's dependency then resolved to.  With both mapped (torch imported after the
+    library) the library's is the one outside the wheel."""
+    import ctypes as C
+    with open("/proc/self/maps") as f:
+        paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line}, key=lambda p: "/torch/" in p)
+    assert paths, "no HIP runtime is mapped into this process"
+    path = paths[0]
+    free, total = C.c_size_t(), C.c_size_t()
+    assert C.CDLL(path).hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+def test_ownership_across_rebuilds(engine):
+    """One context built packed -> tiles -> rows -> packed -> tiles -> rows on c0_65 (every block of the Fock state comes from one owner
+    that free_eri clears; the cache recycles freed blocks at once, so a block freed twice would serve two later allocations).  After
+    each build: fock_jk on the seeded symmetric pair and on the non-symmetric density; the second round's J and K equal the first
+    round's bit for bit, per layout.  Free device memory after the sixth build is not lower than after the third by more than the
+    commit before this test showed for the same sequence: PARENT_DROP_BYTES = 0 (measured on that commit's library with this test alone
+    in the process and behind the c0_65 cases of this file: free memory 307 958 382 592 B and 307 895 468 032 B, each time the same
+    after build 3 and after build 6)."""
+    rounds, free = [], []
+    try:
+        for rnd in range(2):
+            out = {}
+            for layout in LAYOUTS:
+                L = _build(engine, "c0_65", True, layout)
+                pool = _pool(L.N)
+                out[layout] = engine.fock_jk(pool[[0, 1]]) + engine.fock_jk(pool[NONSYM])
+                assert all(np.isfinite(x).all() and np.abs(x).max() > 0 for x in out[layout]), (rnd, layout)
+            rounds.append(out)
+            free.append(_free_device_memory())
+    finally:
+        _reset(engine)
+    print(f"\n[fock-shapes] rebuilds on c0_65: free device memory after build 3 {free[0]} B, after build 6 {free[1]} B, drop {free[0] - free[1]} B "
+          f"(the parent's: {PARENT_DROP_BYTES} B)")
+    for layout in LAYOUTS:
+        for what, a, b in zip(("J sym pair", "K sym pair", "J nonsym", "K nonsym"), rounds[0][layout], rounds[1][layout]):
+            assert np.array_equal(a, b), f"layout {layout}: {what} of the second round differs from the first"
+    assert free[0] - free[1] <= PARENT_DROP_BYTES, (free, PARENT_DROP_BYTES)
+
+
 def child_device_entry(layout):
     """What the child of test_device_entry_on_a_side_stream runs (torch initialises the device first, as in test_gpu_sharded.py: the
     wheel brings its own HIP runtime, which finds no device once the library's has the card)."""

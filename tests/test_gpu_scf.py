@@ -312,7 +312,7 @@ def test_symmetry_blocked_eigensolve_and_its_refusal():
 
 @pytest.mark.parametrize("kind", ["rhf", "uhf", "mixed"])
 def test_class_diagonal_task_list_gives_the_same_bits(kind):
-    """tf_device.hip: launch_jk_packed -- the native cycles send class-diagonal densities (no element between AOs of different x/y parity)
+    """tf_jk_host.hip.h: launch_jk_packed -- the native cycles send class-diagonal densities (no element between AOs of different x/y parity)
     over a shorter task list; the skipped products are exact zeros, so the whole cycle (scf:1072-1154 / 1165-1281) must come out bit for
     bit as with the full list (TF_JK_CLASS_DIAGONAL=0), and the counters must show that the shorter list was really taken."""
     import json

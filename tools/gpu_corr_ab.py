@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU: A/B of the correlated-method drivers (tf_ao_to_mo, tf_mp2_rhf ... tf_cis_rhf, tf_mp3_ladder_probe) between two builds of the
-library, each call in a fresh child process that loads its library through TUNAFOCK_LIB, the processes alternating.  Unlike
+library, each call in a fresh child process that loads its library through TUNAFOCK_LIB, the processes alternating.  Like
 gpu_jk_ab.py it stops at the first child that exits non-zero or is killed by its time limit and starts nothing after it.
 
   --bits LIB_A LIB_B   N2/cc-pVTZ (N = 60) with the golden orbitals of tests/golden/mp3_systems.npz on the packed, rows and tiles layouts:

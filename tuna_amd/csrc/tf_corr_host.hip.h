@@ -10,30 +10,7 @@
 
 static const int CORR_NBLK = 1024;     // blocks of the energy and update kernels: their partials are summed in block order
 
-// Owner of the device allocations of one call: whatever it still holds is freed, in the order it was handed out, when the owner goes
-// out of scope -- on every return path.
-struct __attribute__((visibility("hidden"))) DeviceBlocks {
-    std::vector<void *> held;
-    DeviceBlocks() = default;
-    DeviceBlocks(const DeviceBlocks &) = delete;
-    DeviceBlocks &operator=(const DeviceBlocks &) = delete;
-    ~DeviceBlocks() { clear(); }
-    void *alloc_bytes(size_t bytes)                           // nullptr: out of device memory
-    {
-        void *p = nullptr;
-        if (tf_malloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        held.push_back(p);
-        return p;
-    }
-    double *alloc(size_t n) { return (double *)alloc_bytes(n * sizeof(double)); }
-    int *alloc_int(size_t n) { return (int *)alloc_bytes(n * sizeof(int)); }   // (rocblas_int is int)
-    void release(void *p)                                     // early free of one block (a null or foreign pointer is left alone)
-    {
-        const auto it = std::find(held.begin(), held.end(), p);
-        if (p && it != held.end()) { (void)tf_free(p); held.erase(it); }
-    }
-    void clear() { for (void *p : held) (void)tf_free(p); held.clear(); }
-};
+// (DeviceBlocks, the owner of the device allocations of one call -- freed on every return path -- is defined in tf_device.hip)
 
 // "set ctx->err, return the code"; m may be ctx->err itself (a callee's message passed on)
 static int corr_fail(tf_ctx *ctx, int code, const std::string &m)
@@ -78,14 +55,9 @@ static hipError_t sum_partials_host(const double *d_part, int nblk, int k, doubl
 // slots past nd repeating the last density
 static int launch_jk_general(tf_ctx *ctx, int nd, const double *P, double *J, double *K)
 {
-    const size_t nn = (size_t)ctx->N * ctx->N;
-    const double *pp[8]; double *jj[8], *kk[8];
-    int nonsym[8];
-    for (int q = 0; q < 8; ++q) {
-        const size_t d = (size_t)std::min(q, nd - 1);
-        pp[q] = P + d * nn; jj[q] = J + d * nn; kk[q] = K + d * nn; nonsym[q] = 1;
-    }
-    return launch_jk(ctx, nd, pp, jj, kk, 0, nonsym);
+    const JkSlots s(nd, (size_t)ctx->N * ctx->N, P, J, K);
+    const int nonsym[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    return launch_jk(ctx, nd, s.p, s.j, s.k, 0, nonsym);
 }
 
 static std::chrono::steady_clock::time_point corr_stamp() { (void)hipDeviceSynchronize(); return std::chrono::steady_clock::now(); }
@@ -1176,12 +1148,12 @@ int tf_ccsd_rhf(tf_ctx *ctx, const tf_cc_opts *opts, int n_occ, int n_frozen, co
                 if ((rc = mo_vvoo_block(ctx, who, Xv, Cv, Lo, Co, o, v, Q))) return rc;
                 hipLaunchKernelGGL(tfccsd::ccsd_vvoo_operand_kernel, grid_e, dim3(256), 0, 0, Q, o, v, A2);
                 // M = 2 J - K of that density; L_ca = F_ca + C_v^T M C_v, L_ik = F_ik + C_o^T M C_o
-                if (hipMemcpy(ctx->d_P, Ph.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
-                if ((rc = launch_jk_general(ctx, 1, ctx->d_P, ctx->d_J, ctx->d_K))) return rc;
-                hipLaunchKernelGGL(tfccsd::ccsd_m_kernel, dim3((unsigned)std::min<long long>((nn + 255) / 256, 1 << 16)), dim3(256), 0, 0, ctx->d_J, ctx->d_K, nn);
-                CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, ctx->d_J, N, d_Cv, v, 0.0, d_tmp, v));
+                if (hipMemcpy(ctx->jk.all.P, Ph.data(), (size_t)nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_ccsd_rhf: copy failed");
+                if ((rc = launch_jk_general(ctx, 1, ctx->jk.all.P, ctx->jk.all.J, ctx->jk.all.K))) return rc;
+                hipLaunchKernelGGL(tfccsd::ccsd_m_kernel, dim3((unsigned)std::min<long long>((nn + 255) / 256, 1 << 16)), dim3(256), 0, 0, ctx->jk.all.J, ctx->jk.all.K, nn);
+                CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, v, N, 1.0, ctx->jk.all.J, N, d_Cv, v, 0.0, d_tmp, v));
                 CORR_BLAS(tfmp3::gemm_rm(blas, true, false, v, v, N, 1.0, d_Cv, v, d_tmp, v, 1.0, Fca, v));
-                CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, o, N, 1.0, ctx->d_J, N, d_Co, o, 0.0, d_tmp, o));
+                CORR_BLAS(tfmp3::gemm_rm(blas, false, false, N, o, N, 1.0, ctx->jk.all.J, N, d_Co, o, 0.0, d_tmp, o));
                 CORR_BLAS(tfmp3::gemm_rm(blas, true, false, o, o, N, 1.0, d_Co, o, d_tmp, o, 1.0, Fik, o));
             }
             if ((rc = cc_a1_a2(ctx, who, K))) return rc;

@@ -26,6 +26,7 @@
 #include "tf_jkpacked.hip.h"
 #include "tf_packed_host.h"
 #include "tf_tiles_host.h"
+#include "tf_jk_plan.h"
 #include "tf_jktile.hip.h"
 #include "tf_eri.hip.h"
 #include "tf_eri_team.hip.h"
@@ -137,6 +138,37 @@ static inline hipError_t tf_malloc(void **p, size_t bytes) { return tfcache::cma
 template <class T> static inline hipError_t tf_malloc(T **p, size_t bytes) { return tfcache::cmalloc((void **)p, bytes); }
 static inline hipError_t tf_free(void *p) { return tfcache::cfree(p); }
 
+// Owner of device allocations with one lifetime -- one call of a post-SCF driver (tf_corr_host.hip.h), one tensor build (tf_ctx::build_mem):
+// whatever it still holds is freed, in the order it was handed out, by clear() and when the owner goes out of scope.  A block is freed
+// through its owner only, so no pointer can reach the cache twice.
+struct __attribute__((visibility("hidden"))) DeviceBlocks {
+    std::vector<void *> held;
+    DeviceBlocks() = default;
+    DeviceBlocks(const DeviceBlocks &) = delete;
+    DeviceBlocks &operator=(const DeviceBlocks &) = delete;
+    ~DeviceBlocks() { clear(); }
+    hipError_t take(void **p, size_t bytes)                   // tf_malloc into *p; the block is held from then on
+    {
+        const hipError_t e = tf_malloc(p, bytes);
+        if (e == hipSuccess) held.push_back(*p);
+        return e;
+    }
+    void *alloc_bytes(size_t bytes)                           // nullptr: out of device memory
+    {
+        void *p = nullptr;
+        if (take(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return p;
+    }
+    double *alloc(size_t n) { return (double *)alloc_bytes(n * sizeof(double)); }
+    int *alloc_int(size_t n) { return (int *)alloc_bytes(n * sizeof(int)); }   // (rocblas_int is int)
+    void release(void *p)                                     // early free of one block (a null or foreign pointer is left alone)
+    {
+        const auto it = std::find(held.begin(), held.end(), p);
+        if (p && it != held.end()) { (void)tf_free(p); held.erase(it); }
+    }
+    void clear() { for (void *p : held) (void)tf_free(p); held.clear(); }
+};
+
 using namespace tfk;
 
 static std::string g_create_error;
@@ -172,21 +204,15 @@ struct tf_ctx {
     std::vector<int> h_ct_ix, h_ct_ord;  // host mirrors of DBasis::ct_ix / ct_ord / ct_sc (the team kernels' transform tables are built from them)
     std::vector<double> h_ct_sc;
     std::vector<std::vector<int>> class_pairs;   // pairs of each class, ascending
-    // J/K scratch
-    double *d_Jrow = nullptr, *d_Kp = nullptr, *d_Ppad = nullptr, *d_J = nullptr, *d_K = nullptr, *d_P = nullptr;
     // packed (8-fold unique) layout: tf_jkpacked.hip.h
     int layout_req = -1;                // -1 auto, 0 rows (i >= j) x [k][l], 1 packed
     int layout = 0;
     long long n_elems = 0;              // stored doubles
     long long *d_rowoff = nullptr;
-    int *d_jptr = nullptr;                       // rows by second index x (internal): d_jrows[d_jptr[x] .. d_jptr[x + 1])
-    int2 *d_jrows = nullptr;                     // (local row, ORIGINAL first index of the row)
-    int *d_xorder = nullptr;                     // output rows of the exchange reduction, most partial vectors first
     int *d_rowsec = nullptr;            // [n_rows][6]: start of section a inside local row r; position in its storage unit, rows of the unit
     // parity-blocked layout tables (tf_layout.hip.h), host mirror (tf_packed_host.h) and device view
     tfp::HostLayout hl;
     BLayout bl{};
-    std::vector<void *> layout_allocs;
     // work tables of jk_packed_kernel: set 0 for one density per pass (groups of 8 rows), set 1 for two (groups of 4 rows)
     struct JKTables {
         JKGroup *d_groups = nullptr;
@@ -201,15 +227,7 @@ struct tf_ctx {
         int n_tasks_cd = 0, bucket_cd[4] = {0, 0, 0, 0};
         long long ypart_len = 0;
         JKJtPlan jp{};
-    } jkt[2];
-    double *d_Psym = nullptr, *d_Pp = nullptr, *d_ypart = nullptr, *d_DI = nullptr, *d_DJ = nullptr, *d_Jt = nullptr, *d_D = nullptr;
-    // second set of partial-sum buffers for passes over the class-diagonal task list (the entries its skipped tasks would write stay
-    // zero, which the reductions rely on); allocated at the first such pass.  cd_bytes: sizes of d_Jrow, d_ypart, d_DI, d_DJ
-    double *cd_Jrow = nullptr, *cd_ypart = nullptr, *cd_DI = nullptr, *cd_DJ = nullptr;
-    size_t cd_bytes[4] = {0, 0, 0, 0};
-    unsigned long long *d_cdflag = nullptr;       // device word: largest |P| between AOs of different classes (bit pattern), per build
-    bool jk_try_class_diagonal = false;           // set by the SCF cycles around their Fock builds (their densities usually are)
-    long long jk_cd_passes = 0, jk_cd_declined = 0;
+    };
     // tiles layout (tf_tiles.h, tf_jktile.hip.h): host tables, their device copies and the partial-sum buffers of the Fock kernel
     tft::Tables tiles;
     tft::TaskList tsub1;                 // the one-density task list when its strips are shorter than the stored ones (TF_TILE_KSUB)
@@ -224,16 +242,42 @@ struct tf_ctx {
         long long dj_len = 0, jd_len = 0, jt_len = 0;
         double *DJ = nullptr, *Jt = nullptr, *Jd = nullptr, *DIk = nullptr, *DIl = nullptr;
         int nd_cap = 0;                  // densities the buffers are sized for
-    } tl1, tlw;                          // one density per pass (strips of ksub1 rows); 4 / 8 densities per pass (strips of 16 rows: built at first use)
+    };
     tft::TaskList tsubw;
-    tft::ClassInfo tclass;               // what the list builder needs again for tlw
+    tft::ClassInfo tclass;               // what the list builder needs again for the wide list
     std::vector<std::pair<int, int>> trows;
-    int *d_jlist_ptr = nullptr, *d_jlist = nullptr, *d_tvtab = nullptr;
-    double *t_X = nullptr, *t_Pm = nullptr;   // [8][N][N] internal densities, [8] pair matrices
-    double *t_out = nullptr;             // [6: Dj, Di, ED, EDT, JD, EJ][densities of the pass][N][N]; two such sets (the two passes of a general density)
-    double *t_JtTot = nullptr;
-    std::vector<void *> tile_allocs;
-    size_t tile_lds_set = 48 * 1024;     // dynamic LDS limit requested for the tiles layout's edge / reduce kernels
+    // The Fock state of a tensor build, grouped by layout (tf_jk_host.hip.h).  Every device block behind these pointers -- and behind the
+    // tiles layout's view `tv` -- comes from build_mem and has the lifetime of the build: free_eri clears the owner and assigns a fresh
+    // JkState, nothing is freed by name.
+    struct JkAll {                       // every layout
+        double *P = nullptr, *J = nullptr, *K = nullptr;   // the densities of one call of tf_fock_jk and their results
+        double *Ppad = nullptr, *Jrow = nullptr;           // rows: padded densities; rows, packed: per-row Coulomb partials (zeroed once)
+    };
+    struct JkRows { double *Kp = nullptr; };
+    struct JkPacked {
+        JKTables t[2];
+        int *jptr = nullptr;             // rows by second index x (internal): jrows[jptr[x] .. jptr[x + 1])
+        int2 *jrows = nullptr;           // (local row, ORIGINAL first index of the row)
+        int *xorder = nullptr;           // output rows of the exchange reduction, most partial vectors first
+        JkPlan plan;                     // sizes, offsets and strides of the buffers below (tf_jk_plan.h)
+        double *Psym = nullptr, *Pp = nullptr, *ypart = nullptr, *DI = nullptr, *DJ = nullptr, *Jt = nullptr, *D = nullptr;
+        // second set of partial-sum buffers (JK_CD_JROW .. JK_CD_DJ) for passes over the class-diagonal task list (the entries its skipped
+        // tasks would write stay zero, which the reductions rely on); allocated and zeroed at the first such pass
+        double *cd[4] = {nullptr, nullptr, nullptr, nullptr};
+        unsigned long long *cdflag = nullptr;   // device word: largest |P| between AOs of different classes (bit pattern)
+    };
+    struct JkTiles {
+        TileList tl1, tlw;               // one density per pass (strips of ksub1 rows); 4 / 8 densities per pass (strips of 16 rows: built at first use)
+        int *jlist_ptr = nullptr, *jlist = nullptr, *tvtab = nullptr;
+        double *X = nullptr, *Pm = nullptr;   // [8][N][N] internal densities, [8] pair matrices
+        double *out = nullptr;           // [6: Dj, Di, ED, EDT, JD, EJ][densities of the pass][N][N]; two such sets (the two passes of a general density)
+        double *JtTot = nullptr;
+    };
+    struct JkState { JkAll all; JkRows rows; JkPacked packed; JkTiles tiles; } jk;
+    DeviceBlocks build_mem;
+    // (context lifetime: counters of tf_jk_path_stats; dynamic LDS limit requested for the tiles layout's edge / reduce kernels)
+    long long jk_cd_passes = 0, jk_cd_declined = 0;
+    size_t tile_lds_set = 48 * 1024;
     // instrumentation
     bool prof_jk = false;
     std::vector<hipEvent_t> prof_ev;     // pairs (before, after) around the row kernel, on the launch stream
@@ -305,6 +349,14 @@ static int upload(tf_ctx *ctx, const std::vector<T> &h, T **d, bool track = true
     if (!h.empty()) HIPCHK(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return TF_OK;
 }
+// ... into a block that `owner` holds
+template <class T>
+static int upload(tf_ctx *ctx, const std::vector<T> &h, T **d, DeviceBlocks &owner)
+{
+    HIPCHK(ctx, owner.take((void **)d, std::max<size_t>(h.size(), 1) * sizeof(T)));
+    if (!h.empty()) HIPCHK(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return TF_OK;
+}
 
 // ---- RCCL, loaded on demand (include/tunafock.h: tf_comm_*) ------------------------------------------------------------------------
 namespace tfrccl {
@@ -352,7 +404,7 @@ static int comm_allreduce(tf_ctx *ctx, double *buf, size_t count, hipStream_t st
 }
 
 extern "C++" {
-static int tile_list_upload(tf_ctx *ctx, const tft::TaskList &TL, bool own_shapes, tf_ctx::TileList &D);
+static int tile_list_upload(tf_ctx *ctx, const tft::TaskList &TL, bool own_shapes, tf_ctx::TileList &D);   // (tf_jk_host.hip.h; the tensor build uploads the first list)
 }
 
 // The blocks freed by free_eri / free_basis are recycled at once (tfcache): nothing queued earlier may still use them, hence the
@@ -376,35 +428,11 @@ struct DrainedFree {
 static void free_eri(tf_ctx *ctx)
 {
     DrainedFree drained(ctx, "free_eri");
-    for (void *p : {(void *)ctx->d_class_rows, (void *)ctx->d_row_pos, (void *)ctx->d_row_ij, (void *)ctx->d_rowmap, (void *)ctx->d_Jrow, (void *)ctx->d_Kp,
-                    (void *)ctx->d_Ppad, (void *)ctx->d_J, (void *)ctx->d_K, (void *)ctx->d_P, (void *)ctx->d_rowoff, (void *)ctx->d_Psym,
-                    (void *)ctx->d_Pp, (void *)ctx->d_ypart, (void *)ctx->d_DI, (void *)ctx->d_DJ, (void *)ctx->d_Jt, (void *)ctx->d_D})
-        if (p) (void)tf_free(p);
-    for (void *p : {(void *)ctx->cd_Jrow, (void *)ctx->cd_ypart, (void *)ctx->cd_DI, (void *)ctx->cd_DJ, (void *)ctx->d_cdflag})
-        if (p) (void)tf_free(p);
-    ctx->cd_Jrow = ctx->cd_ypart = ctx->cd_DI = ctx->cd_DJ = nullptr; ctx->d_cdflag = nullptr;
-    for (auto &t : ctx->jkt) {
-        for (void *p : {(void *)t.d_groups, (void *)t.d_tasks, (void *)t.d_supers, (void *)t.d_gfirst, (void *)t.d_tasks_cd})
-            if (p) (void)tf_free(p);
-        t = tf_ctx::JKTables();
-    }
-    for (void *p : {(void *)ctx->d_jptr, (void *)ctx->d_jrows, (void *)ctx->d_xorder})
-        if (p) (void)tf_free(p);
-    ctx->d_jptr = nullptr; ctx->d_jrows = nullptr; ctx->d_xorder = nullptr;
-    for (void *p : ctx->layout_allocs) (void)tf_free(p);
-    ctx->layout_allocs.clear();
-    for (void *p : ctx->tile_allocs) (void)tf_free(p);
-    ctx->tile_allocs.clear();
-    ctx->tl1 = tf_ctx::TileList(); ctx->tlw = tf_ctx::TileList();
+    ctx->build_mem.clear();
+    ctx->jk = tf_ctx::JkState();
     ctx->tv = TView{};
-    ctx->d_jlist_ptr = ctx->d_jlist = ctx->d_tvtab = nullptr;
-    ctx->t_X = ctx->t_Pm = ctx->t_out = ctx->t_JtTot = nullptr;
-    if (ctx->d_rowsec) { (void)tf_free(ctx->d_rowsec); ctx->d_rowsec = nullptr; }
     ctx->bl = BLayout{};
-    ctx->d_class_rows = nullptr; ctx->d_row_pos = nullptr; ctx->d_row_ij = nullptr; ctx->d_rowmap = nullptr; ctx->d_Jrow = nullptr; ctx->d_Kp = nullptr;
-    ctx->d_Ppad = nullptr; ctx->d_J = nullptr; ctx->d_K = nullptr; ctx->d_P = nullptr;
-    ctx->d_rowoff = nullptr; ctx->d_Psym = nullptr; ctx->d_Pp = nullptr;
-    ctx->d_ypart = nullptr; ctx->d_DI = nullptr; ctx->d_DJ = nullptr; ctx->d_Jt = nullptr; ctx->d_D = nullptr;
+    ctx->d_class_rows = ctx->d_row_pos = ctx->d_rowmap = ctx->d_rowsec = nullptr; ctx->d_row_ij = nullptr; ctx->d_rowoff = nullptr;
     ctx->n_elems = 0;
     ctx->have_eri = false;
 }
@@ -442,30 +470,15 @@ static int build_blocked_layout(tf_ctx *ctx, const std::vector<int> &cls)
         for (int a = 0; a < 4; ++a) itab[BL_FULLSEC + 4 * c + a] = H.fullsec[c][a];
     }
     for (int b = 0; b < 5; ++b) itab[BL_WFIRST + b] = H.wfirst[b];
-    auto up_i = [&](const std::vector<int> &h, const int **d) -> int {
-        int *p = nullptr;
-        int rc = upload(ctx, h, &p, false);
-        if (rc) return rc;
-        ctx->layout_allocs.push_back(p);
-        *d = p;
-        return TF_OK;
-    };
+    auto up_i = [&](const std::vector<int> &h, const int **d) { return upload(ctx, h, const_cast<int **>(d), ctx->build_mem); };
     int rc;
-    {
-        long long *dl = nullptr;
-        if ((rc = upload(ctx, ltab, &dl, false))) return rc;
-        ctx->layout_allocs.push_back(dl);
-        L.ltab = dl;
-    }
+    if ((rc = upload(ctx, ltab, const_cast<long long **>(&L.ltab), ctx->build_mem))) return rc;
     if ((rc = up_i(itab, &L.itab)) || (rc = up_i(H.ao, &L.ao)) || (rc = up_i(H.origI, &L.origI)) || (rc = up_i(H.clsI, &L.clsI)) || (rc = up_i(H.cntA, &L.cntA)) ||
         (rc = up_i(H.kap0, &L.kap0)) || (rc = up_i(H.kapF, &L.kapF)) || (rc = up_i(H.rpoff, &L.rpoff)) || (rc = up_i(H.chunk_c0, &L.chunk_c0)) ||
         (rc = up_i(H.chunk_width, &L.chunk_width)) || (rc = up_i(H.chunk_cls, &L.chunk_cls)) || (rc = up_i(H.chunk_of, &L.chunk_of)) ||
         (rc = up_i(H.gk, &L.gk)))
         return rc;
-    KInfo *dk = nullptr;
-    if ((rc = upload(ctx, H.kinfo, &dk, false))) return rc;
-    ctx->layout_allocs.push_back(dk);
-    L.kinfo = dk;
+    if ((rc = upload(ctx, H.kinfo, const_cast<KInfo **>(&L.kinfo), ctx->build_mem))) return rc;
     ctx->bl = L;
     return TF_OK;
 }
@@ -831,9 +844,10 @@ static int upload_jk_tables(tf_ctx *ctx, const tfp::RowTables &rows, int RB, tf_
         DBG("J/K tasks: %zu (class-diagonal list: %zu), wave steps %lld (%lld)", W.tasks.size(), W.tasks_cd.size(), st_all, st_cd);
     }
     int rc2;
-    if ((rc2 = upload(ctx, W.groups, &T.d_groups, false)) || (rc2 = upload(ctx, W.gfirst, &T.d_gfirst, false)) ||
-        (rc2 = upload(ctx, W.tasks, &T.d_tasks, false)) || (rc2 = upload(ctx, W.supers, &T.d_supers, false)) ||
-        (rc2 = upload(ctx, W.tasks_cd, &T.d_tasks_cd, false)))
+    DeviceBlocks &mem = ctx->build_mem;
+    if ((rc2 = upload(ctx, W.groups, &T.d_groups, mem)) || (rc2 = upload(ctx, W.gfirst, &T.d_gfirst, mem)) ||
+        (rc2 = upload(ctx, W.tasks, &T.d_tasks, mem)) || (rc2 = upload(ctx, W.supers, &T.d_supers, mem)) ||
+        (rc2 = upload(ctx, W.tasks_cd, &T.d_tasks_cd, mem)))
         return rc2;
     T.n_groups = (int)W.groups.size(); T.n_tasks = (int)W.tasks.size(); T.n_supers = (int)W.supers.size();
     T.n_tasks_cd = (int)W.tasks_cd.size();
@@ -846,7 +860,7 @@ static int upload_jk_tables(tf_ctx *ctx, const tfp::RowTables &rows, int RB, tf_
 
 // the device reads (i, j) pairs as int2
 static_assert(sizeof(TFInt2) == sizeof(int2) && offsetof(TFInt2, y) == offsetof(int2, y), "TFInt2 must have the layout of int2");
-static int upload_int2(tf_ctx *ctx, const std::vector<TFInt2> &h, int2 **d) { return upload(ctx, h, reinterpret_cast<TFInt2 **>(d), false); }
+static int upload_int2(tf_ctx *ctx, const std::vector<TFInt2> &h, int2 **d) { return upload(ctx, h, reinterpret_cast<TFInt2 **>(d), ctx->build_mem); }
 
 static double seconds_between(hipEvent_t a, hipEvent_t b)
 {
@@ -1103,19 +1117,16 @@ int EriBuild::plan_storage()
         for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) tab[TVT_PID + 4 * a + b] = std::max(0, TT.pid[a][b]);
         for (int p2 = 0; p2 < TT.npair; ++p2) { tab[TVT_PA + p2] = TT.pa[p2]; tab[TVT_PB + p2] = TT.pb[p2]; tab[TVT_PMOFF + p2] = TT.pm_off[p2]; tab[TVT_PMPITCH + p2] = TT.pm_pitch[p2]; }
         for (int q = 0; q < 4; ++q) { tab[TVT_CSTART + q] = H.cstart[q]; tab[TVT_CSIZE + q] = H.csize[q]; }
-        auto up_t = [&](const auto &h, auto **d) -> int {
-            int rc2 = upload(ctx, h, d, false);
-            if (!rc2) ctx->tile_allocs.push_back(*d);
-            return rc2;
-        };
+        DeviceBlocks &mem = ctx->build_mem;
+        tf_ctx::JkTiles &Z = ctx->jk.tiles;
         TTask *d_regions = nullptr; TPairI *d_pp = nullptr; TRunI *d_rr = nullptr;
-        if ((rc = up_t(TT.primary.tasks_by_region, &d_regions)) || (rc = up_t(TT.primary.pairs, &d_pp)) || (rc = up_t(TT.primary.runs, &d_rr)) ||
-            (rc = up_t(tab, &ctx->d_tvtab)))
+        if ((rc = upload(ctx, TT.primary.tasks_by_region, &d_regions, mem)) || (rc = upload(ctx, TT.primary.pairs, &d_pp, mem)) ||
+            (rc = upload(ctx, TT.primary.runs, &d_rr, mem)) || (rc = upload(ctx, tab, &Z.tvtab, mem)))
             return rc;
         TView V{};
-        V.regions = d_regions; V.prim_pairs = d_pp; V.prim_runs = d_rr; V.edge_base = TT.edge_base; V.N = N; V.pm_len = TT.pm_len; V.tab = ctx->d_tvtab;
+        V.regions = d_regions; V.prim_pairs = d_pp; V.prim_runs = d_rr; V.edge_base = TT.edge_base; V.N = N; V.pm_len = TT.pm_len; V.tab = Z.tvtab;
         ctx->tv = V;
-        ctx->tl1.d_pairs = d_pp; ctx->tl1.d_runs = d_rr;
+        Z.tl1.d_pairs = d_pp; Z.tl1.d_runs = d_rr;
     }
     ctx->n_rows = (long long)row_ij.size();
     row_len = (long long)N * ld;
@@ -1138,9 +1149,9 @@ int EriBuild::plan_storage()
             ctx->eri_cap = need;
         }
     }
-    if ((rc = upload_int2(ctx, row_ij, &ctx->d_row_ij)) || (rc = upload(ctx, rows.rowmap, &ctx->d_rowmap, false))) return rc;
+    if ((rc = upload_int2(ctx, row_ij, &ctx->d_row_ij)) || (rc = upload(ctx, rows.rowmap, &ctx->d_rowmap, ctx->build_mem))) return rc;
     if (packed) {
-        if (!tiles && ((rc = upload(ctx, rows.rowoff, &ctx->d_rowoff, false)) || (rc = upload(ctx, rows.rowsec, &ctx->d_rowsec, false)))) return rc;
+        if (!tiles && ((rc = upload(ctx, rows.rowoff, &ctx->d_rowoff, ctx->build_mem)) || (rc = upload(ctx, rows.rowsec, &ctx->d_rowsec, ctx->build_mem)))) return rc;
         ctx->db.bl = ctx->bl;
         ctx->db.RLS = H.RLS;
     }
@@ -1157,23 +1168,22 @@ int EriBuild::upload_consumer_tables()
     tfp::ConsumerTables CT;
     tfp::build_class_rows(H, rows, CT);
     std::copy(CT.class_row_off, CT.class_row_off + 5, ctx->class_row_off);
-    if ((rc2 = upload(ctx, CT.class_rows, &ctx->d_class_rows, false)) || (rc2 = upload(ctx, CT.row_pos, &ctx->d_row_pos, false))) return rc2;
+    DeviceBlocks &mem = ctx->build_mem;
+    if ((rc2 = upload(ctx, CT.class_rows, &ctx->d_class_rows, mem)) || (rc2 = upload(ctx, CT.row_pos, &ctx->d_row_pos, mem))) return rc2;
     if (tiles) {
         const tft::Tables &TT = ctx->tiles;
         const tft::TaskList &TL = ctx->ksub1 == TT_KS ? TT.primary : ctx->tsub1;
-        auto up_t = [&](const auto &h, auto **d) -> int {
-            int rc3 = upload(ctx, h, d, false);
-            if (!rc3) ctx->tile_allocs.push_back(*d);
-            return rc3;
-        };
-        if ((rc2 = tile_list_upload(ctx, TL, ctx->ksub1 != TT_KS, ctx->tl1)) || (rc2 = up_t(TT.jlist_ptr, &ctx->d_jlist_ptr)) || (rc2 = up_t(TT.jlist, &ctx->d_jlist)))
+        tf_ctx::JkTiles &Z = ctx->jk.tiles;
+        if ((rc2 = tile_list_upload(ctx, TL, ctx->ksub1 != TT_KS, Z.tl1)) || (rc2 = upload(ctx, TT.jlist_ptr, &Z.jlist_ptr, mem)) ||
+            (rc2 = upload(ctx, TT.jlist, &Z.jlist, mem)))
             return rc2;
         return TF_OK;
     }
-    if ((rc2 = upload_jk_tables(ctx, rows, JKShape<1>::RB, ctx->jkt[0])) || (rc2 = upload_jk_tables(ctx, rows, JKShape<2>::RB, ctx->jkt[1]))) return rc2;
+    tf_ctx::JkPacked &K = ctx->jk.packed;
+    if ((rc2 = upload_jk_tables(ctx, rows, JKShape<1>::RB, K.t[0])) || (rc2 = upload_jk_tables(ctx, rows, JKShape<2>::RB, K.t[1]))) return rc2;
     tfp::build_reduction_lists(H, rows, CT);
-    if ((rc2 = upload(ctx, CT.jptr, &ctx->d_jptr, false)) || (rc2 = upload_int2(ctx, CT.jrows, &ctx->d_jrows))) return rc2;
-    if ((rc2 = upload(ctx, CT.xorder, &ctx->d_xorder, false))) return rc2;
+    if ((rc2 = upload(ctx, CT.jptr, &K.jptr, mem)) || (rc2 = upload_int2(ctx, CT.jrows, &K.jrows))) return rc2;
+    if ((rc2 = upload(ctx, CT.xorder, &K.xorder, mem))) return rc2;
     return TF_OK;
 }
 
@@ -2395,65 +2405,6 @@ int EriBuild::finish()
     return TF_OK;
 }
 
-// ---- J/K scratch
-int EriBuild::alloc_jk_scratch()
-{
-    int rc;
-    const size_t nn = (size_t)N * N;
-    // (sized for two densities per pass)
-    const int NWjk = packed ? std::max(1, H.NW) * H.MP : 1;         // column chunks of jk_packed_kernel x parts of a walk
-    ctx->cd_bytes[0] = 2 * (size_t)std::max(1, NWjk) * std::max<size_t>(1, (size_t)ctx->n_rows) * sizeof(double);
-    HIPCHK(ctx, tf_malloc((void **)&ctx->d_Jrow, 2 * (size_t)std::max(1, NWjk) * std::max<size_t>(1, (size_t)ctx->n_rows) * sizeof(double)));
-    HIPCHK(ctx, hipMemset(ctx->d_Jrow, 0, 2 * (size_t)std::max(1, NWjk) * std::max<size_t>(1, (size_t)ctx->n_rows) * sizeof(double)));
-    if (tiles) {
-        // partial sums of jk_tile_kernel (one density per pass for now) and the per-pass outputs of its reductions
-        const tf_ctx::TileList &D = ctx->tl1;
-        const size_t pml = (size_t)std::max(1, ctx->tiles.pm_len);
-        auto alloc_t = [&](double **p, size_t doubles, bool zero) -> int {
-            HIPCHK(ctx, tf_malloc((void **)p, std::max<size_t>(1, doubles) * sizeof(double)));
-            ctx->tile_allocs.push_back(*p);
-            if (zero) HIPCHK(ctx, hipMemset(*p, 0, std::max<size_t>(1, doubles) * sizeof(double)));
-            return TF_OK;
-        };
-        if ((rc = alloc_t(&ctx->t_X, 8 * nn, false)) || (rc = alloc_t(&ctx->t_Pm, 8 * pml, true)) || (rc = alloc_t(&ctx->t_out, 2 * 6 * 8 * nn, true)) ||
-            (rc = alloc_t(&ctx->t_JtTot, 8 * pml, true)))
-            return rc;
-        (void)D;
-    } else if (packed) {
-        // everything sized for a two-density pass (second density behind the first)
-        const size_t npr = (size_t)std::max<long long>(1, H.NPtot);    // padded pair index space
-        const size_t ny = (size_t)std::max(ctx->jkt[0].ypart_len, 2 * ctx->jkt[1].ypart_len);
-        const size_t ng = (size_t)std::max(ctx->jkt[0].n_groups, 2 * ctx->jkt[1].n_groups);
-        const int nsegmax = std::max(ctx->jkt[0].nseg, ctx->jkt[1].nseg);
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_Psym, 2 * nn * sizeof(double)));
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_Pp, 2 * npr * sizeof(double)));
-        HIPCHK(ctx, hipMemset(ctx->d_Pp, 0, 2 * npr * sizeof(double)));   // pad slots stay zero
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_ypart, std::max<size_t>(1, ny) * sizeof(double)));
-        // column parts [.][N] followed by the row parts [.][RS]
-        // partial sums: [one-density pass | two-density pass], each [column parts | row parts] per density.  The passes have separate
-        // regions (their groups differ), every region is zeroed once: the set of entries a pass writes does not depend on the density,
-        // and the reductions rely on the entries no task writes being zero.
-        const size_t per_g = (size_t)N * H.MP + H.RS, nr1 = std::max<size_t>(1, (size_t)ctx->n_rows);
-        const size_t di_doubles = ((size_t)std::max(1, ctx->jkt[0].n_groups) + 2 * (size_t)std::max(1, ctx->jkt[1].n_groups)) * per_g;
-        const size_t dj_doubles = 3 * nr1 * per_g;
-        ctx->cd_bytes[1] = std::max<size_t>(1, (size_t)ctx->jkt[0].ypart_len + 2 * (size_t)ctx->jkt[1].ypart_len) * sizeof(double); ctx->cd_bytes[2] = di_doubles * sizeof(double); ctx->cd_bytes[3] = dj_doubles * sizeof(double);
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_DI, di_doubles * sizeof(double)));
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_DJ, dj_doubles * sizeof(double)));
-        HIPCHK(ctx, hipMemset(ctx->d_DI, 0, di_doubles * sizeof(double)));
-        HIPCHK(ctx, hipMemset(ctx->d_DJ, 0, dj_doubles * sizeof(double)));
-        HIPCHK(ctx, hipMemset(ctx->d_ypart, 0, std::max<size_t>(1, ny) * sizeof(double)));
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_Jt, 2 * (size_t)nsegmax * npr * sizeof(double)));
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_D, 2 * nn * sizeof(double)));
-    } else
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_Kp, 2 * std::max<size_t>(1, (size_t)ctx->n_rows) * 2 * ld * sizeof(double)));
-    HIPCHK(ctx, tf_malloc((void **)&ctx->d_Ppad, 2 * (size_t)N * ld * sizeof(double)));
-    const size_t npass = tiles ? 8 : 2;                             // densities of one call of tf_fock_jk that go through the tensor together
-    HIPCHK(ctx, tf_malloc((void **)&ctx->d_J, npass * nn * sizeof(double)));
-    HIPCHK(ctx, tf_malloc((void **)&ctx->d_K, npass * nn * sizeof(double)));
-    HIPCHK(ctx, tf_malloc((void **)&ctx->d_P, npass * nn * sizeof(double)));
-    return TF_OK;
-}
-
 }  // extern "C++"
 
 int tf_build_eri(tf_ctx *ctx, int spherical)
@@ -2585,471 +2536,12 @@ int tf_sample_eri(tf_ctx *ctx, int64_t n_idx, const int32_t *idx, double *values
     return TF_OK;
 }
 
-// ---- J/K ------------------------------------------------------------------------------------------
+// ---- the Fock build: state of a tensor build, passes per layout, entry points.  Included HERE: the order in
+// which the kernel templates are first used decides the order of the kernels in the code object, which stays what it was. -------------
+#include "tf_jk_host.hip.h"
+int EriBuild::alloc_jk_scratch() { return jk_alloc_state(ctx); }
 
-// nd = 1 or 2 densities in one pass over the tensor.  dP/dJ/dK: nd dense [N,N] device matrices each.
-// One pass of jk_packed_kernel over ND densities (device, symmetric for the exchange part; X = what the D terms contract with) and the
-// reductions; dDout[d]: the D matrix of density d.  Tables: set ND - 1.
-extern "C++" {
-template <int ND>
-static int jk_packed_pass(tf_ctx *ctx, hipStream_t st, double *const *dDout, bool cd = false)
-{
-    const BLayout &L = ctx->bl;
-    const int N = ctx->N, NW = L.NW;
-    const size_t nn = (size_t)N * N, npr = (size_t)L.NPtot, nrows = (size_t)std::max<long long>(1, ctx->n_rows);
-    const tf_ctx::JKTables &T = ctx->jkt[ND - 1];
-    const size_t ng = (size_t)std::max(1, T.n_groups);
-    // layout of the partial arrays: [column parts of density 0 | .. density 1 | row parts of density 0 | .. density 1]
-    JKStrides S{};
-    const int MP = ctx->hl.MP;
-    S.KS = ctx->hl.KS; S.MP = MP;
-    S.planeJd = nrows * NW; S.planeI = ng * N; S.planeJ = nrows * N;
-    S.P = nn; S.Pp = npr; S.y = (size_t)T.ypart_len; S.Jd = MP * S.planeJd;
-    S.DIc = MP * S.planeI; S.DIr = ng * (size_t)L.RS; S.DJc = MP * S.planeJ; S.DJr = nrows * (size_t)L.RS;
-    // region of this pass type inside the partial buffers (tf_build_eri: [one-density pass | two-density pass])
-    const size_t per_g = (size_t)N * MP + L.RS;
-    // cd: the class-diagonal task list with its own partial-sum buffers (launch_jk_packed decides)
-    // (the Jt partials of the two pass types are laid out by their own super-groups: in the general buffer every pass overwrites what it
-    // reads, in the class-diagonal buffer the slots of skipped tasks must STAY zero -- each pass type has its own region there)
-    double *const pJrow = cd ? ctx->cd_Jrow : ctx->d_Jrow;
-    double *const pY = cd ? ctx->cd_ypart + (ND == 2 ? (size_t)std::max<long long>(0, ctx->jkt[0].ypart_len) : 0) : ctx->d_ypart;
-    const JKTask *const tasks = cd ? T.d_tasks_cd : T.d_tasks;
-    const int n_tasks = cd ? T.n_tasks_cd : T.n_tasks;
-    const int *const bucket = cd ? T.bucket_cd : T.bucket;
-    double *DI0 = (cd ? ctx->cd_DI : ctx->d_DI) + (ND == 2 ? (size_t)std::max(1, ctx->jkt[0].n_groups) * per_g : 0);
-    double *DJ0 = (cd ? ctx->cd_DJ : ctx->d_DJ) + (ND == 2 ? nrows * per_g : 0);
-    double *DIc = DI0, *DIr = DI0 + ND * S.DIc, *DJc = DJ0, *DJr = DJ0 + ND * S.DJc;
-    if (n_tasks > 0) {
-        hipEvent_t ev_after = nullptr;
-        if (ctx->prof_jk) {
-            if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
-                hipEvent_t a, b;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ctx->prof_ev.push_back(a); ctx->prof_ev.push_back(b); }
-            }
-            if (ctx->prof_used + 2 <= ctx->prof_ev.size()) {
-                (void)hipEventRecord(ctx->prof_ev[ctx->prof_used], st);
-                ev_after = ctx->prof_ev[ctx->prof_used + 1];
-                ctx->prof_used += 2;
-            }
-        }
-        // one launch per workgroup size; the launches are independent (disjoint tasks): the smaller ones go to side streams so that
-        // their ramp-up and tail overlap the big one (fork / join on events; TF_JK_SERIAL=1: all on the caller's stream)
-        static const bool serial = getenv("TF_JK_SERIAL") != nullptr;
-        int n_launch = 0;
-        for (int b = 0; b < 3; ++b) n_launch += (bucket[b + 1] > bucket[b] && (TF_JKP_W >> b) >= 1) ? 1 : 0;
-        // Few tasks (small tensors: N2/cc-pVTZ has 1 400): ONE launch of full-size workgroups over all of them -- the idle waves of the
-        // narrower tasks cost nothing on a chip the build cannot fill, two launches and the fork / join events of the side streams do
-        // (a Fock build at N = 60 is ~90 us of launches, not of work)
-        static const int one_launch_below = getenv("TF_JK_ONE_LAUNCH") ? atoi(getenv("TF_JK_ONE_LAUNCH")) : 12000;   // (measured: N = 60 99 -> 69 us per build, 118: 155 -> 108, 160: 202 -> 183, 200: equal, 300: 874 against 907)
-        // (one rank only: the rows of a rank of several are short runs of j -- mostly one group per super-group, three of four waves idle
-        // in the barriers of a LONG walk; measured at N = 400 on 8 ranks: 0.72 ms per local build in one launch against 0.46 ms in three)
-        // (a rank of several only when its super-groups are full -- the whole-shell plan: >= 24 rows per super-group on average; 0.382 -> 0.363 ms
-        // per local build on 8 ranks.  Under the segment plan a rank's super-groups hold a few rows each: see above.)
-        const bool full_supers = T.n_supers > 0 && ctx->n_rows >= 24LL * T.n_supers;
-        const bool one_launch = n_launch > 1 && n_tasks < one_launch_below && (ctx->world == 1 || full_supers);
-        const bool fork = !serial && !one_launch && ctx->have_streams && n_launch > 1;
-        if (fork) (void)hipEventRecord(ctx->sev[0], st);
-        int side = 0;
-        bool first = true;
-        if (one_launch)
-            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)n_tasks), dim3(64 * TF_JKP_W), 0, st, ctx->d_eri, T.d_groups,
-                               T.d_supers, tasks, L, L.kinfo, ctx->d_Psym, ctx->d_Pp, pJrow, pY, DIc, DIr, DJc, DJr, S);
-        for (int b = 0; b < 3 && !one_launch; ++b) {
-            const int t0 = bucket[b], t1 = bucket[b + 1];
-            if (!(t1 > t0 && (TF_JKP_W >> b) >= 1)) continue;
-            hipStream_t ls = st;
-            if (fork && !first) {
-                ++side;
-                ls = ctx->streams[side];
-                (void)hipStreamWaitEvent(ls, ctx->sev[0], 0);
-            }
-            first = false;
-            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)(t1 - t0)), dim3(64 * (TF_JKP_W >> b)), 0, ls, ctx->d_eri, T.d_groups,
-                               T.d_supers, tasks + t0, L, L.kinfo, ctx->d_Psym, ctx->d_Pp, pJrow, pY, DIc, DIr, DJc, DJr, S);
-            if (ls != st) {
-                (void)hipEventRecord(ctx->sev[side], ls);
-                (void)hipStreamWaitEvent(st, ctx->sev[side], 0);
-            }
-        }
-        if (ev_after) (void)hipEventRecord(ev_after, st);
-    }
-    JKReduce R{};
-    R.ypart = pY; R.sy = S.y; R.supers = T.d_supers; R.MC = ctx->hl.MC; R.MP = MP; R.planeI = S.planeI; R.planeJ = S.planeJ; R.nseg = T.nseg; R.jp = T.jp;
-    R.Jt = ctx->d_Jt; R.sJt = (size_t)T.nseg * npr;
-    R.DIc = DIc; R.sDIc = S.DIc; R.DIr = DIr; R.sDIr = S.DIr; R.DJc = DJc; R.sDJc = S.DJc; R.DJr = DJr; R.sDJr = S.DJr;
-    R.gfirst = T.d_gfirst; R.jptr = ctx->d_jptr; R.jrows = ctx->d_jrows; R.row_ij = ctx->d_row_ij; R.xorder = ctx->d_xorder;
-    for (int d = 0; d < ND; ++d) R.D[d] = dDout[d];
-    { static const int jkr_dbg = getenv("TF_JKR_DBG") ? atoi(getenv("TF_JKR_DBG")) : 0; R.dbg = jkr_dbg; }
-    const unsigned nblk = (unsigned)ND * ((unsigned)N * ((N + 127) / 128) + (unsigned)T.jp.bfirst[4] * T.nseg);
-    hipLaunchKernelGGL(jk_reduce_kernel, dim3(nblk), dim3(TF_JKR_THREADS), 0, st, R, L);
-    return TF_OK;
-}
-}  // extern "C++"
-
-// nonsym[d] != 0: density d is not symmetric -- two passes (K = D(P^T) + D(P)^T); nullptr = all symmetric.
-static int launch_jk_packed(tf_ctx *ctx, int nd, const double *const *dP, double *const *dJ, double *const *dK, hipStream_t st,
-                            const int *nonsym)
-{
-    const BLayout &L = ctx->bl;
-    const int N = ctx->N, NW = L.NW;
-    const size_t nn = (size_t)N * N, npr = (size_t)L.NPtot, nrows = (size_t)std::max<long long>(1, ctx->n_rows);
-    const dim3 gN((N * N + 255) / 256), b256(256);
-    static const bool no_fuse = getenv("TF_JK_NOFUSE") != nullptr;
-    // Class-diagonal densities (what an SCF cycle of a diatomic without a transverse field produces: no element between AOs of
-    // different x/y parity) need a quarter fewer tasks -- see JKTables::d_tasks_cd.  Only when the caller expects them (the native cycles
-    // set jk_try_class_diagonal: the test costs a small kernel and one 16-byte read-back per call) and only when no density of the call
-    // has an element between two classes above 1e-14 of its largest element -- the threshold under which the blocked eigensolver
-    // (tf_scf.hip.h) already treats such elements as zero.  With exact zeros there (densities built from class-pure orbitals) the skipped
-    // products are exact zeros and J, K come out bit for bit the same; DIIS mixtures that carry 1e-16 of a host-made guess differ by that.
-    bool cd = false;
-    {
-        static const bool cd_off = getenv("TF_JK_CLASS_DIAGONAL") && getenv("TF_JK_CLASS_DIAGONAL")[0] == '0';
-        bool any_general = false;
-        for (int d = 0; d < nd; ++d) any_general = any_general || (nonsym && nonsym[d]);
-        // (the test is a kernel and a read-back, ~30 us: a build of a small tensor takes less than that in all -- N2/cc-pVTZ 70 us)
-        static const int cd_nmin = getenv("TF_JK_CD_NMIN") ? atoi(getenv("TF_JK_CD_NMIN")) : 160;
-        if (ctx->jk_try_class_diagonal && !cd_off && !any_general && N >= cd_nmin && ctx->jkt[0].n_tasks_cd < ctx->jkt[0].n_tasks) {
-            if (!ctx->d_cdflag) HIPCHK(ctx, tf_malloc((void **)&ctx->d_cdflag, 2 * sizeof(unsigned long long)));
-            cd = true;
-            for (int d = 0; d < nd && cd; ++d) {                   // (per density: the threshold is relative to ITS largest element)
-                HIPCHK(ctx, hipMemsetAsync(ctx->d_cdflag, 0, 2 * sizeof(unsigned long long), st));
-                hipLaunchKernelGGL(class_cross_max_kernel, dim3((unsigned)N), dim3(256), 0, st, dP[d], L, ctx->d_cdflag);
-                double h[2] = {0.0, 1.0};
-                HIPCHK(ctx, hipMemcpyAsync(h, ctx->d_cdflag, sizeof(h), hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipStreamSynchronize(st));
-                cd = std::isfinite(h[0]) && h[0] < 1e299 && h[1] <= 1e-14 * h[0];
-            }
-            if (cd && !ctx->cd_Jrow) {                             // the second set of partial-sum buffers: zeroed once, like the first
-                double **bufs[4] = {&ctx->cd_Jrow, &ctx->cd_ypart, &ctx->cd_DI, &ctx->cd_DJ};
-                for (int q = 0; q < 4; ++q) {
-                    if (tf_malloc((void **)bufs[q], ctx->cd_bytes[q]) != hipSuccess) {     // no room: the full list then
-                        (void)hipGetLastError();
-                        for (int u = 0; u < q; ++u) { (void)tf_free(*bufs[u]); *bufs[u] = nullptr; }
-                        cd = false;
-                        break;
-                    }
-                    HIPCHK(ctx, hipMemsetAsync(*bufs[q], 0, ctx->cd_bytes[q], st));
-                }
-            }
-            if (cd) ++ctx->jk_cd_passes; else ++ctx->jk_cd_declined;
-        }
-    }
-    double *const pJrow = cd ? ctx->cd_Jrow : ctx->d_Jrow;
-    if (nd == 2 && !no_fuse && !(nonsym && (nonsym[0] || nonsym[1]))) {
-        // two symmetric densities (UHF alpha / beta): one pass over the tensor, groups of 4 rows x 2 densities
-        for (int d = 0; d < 2; ++d)
-            hipLaunchKernelGGL(pack_density_kernel, gN, b256, 0, st, dP[d], L, 0, ctx->d_Psym + d * nn, ctx->d_Pp + d * npr);
-        double *dD[2] = {ctx->d_D, ctx->d_D + nn};
-        int rc = jk_packed_pass<2>(ctx, st, dD, cd);
-        if (rc) return rc;
-        const int nseg = ctx->jkt[1].nseg;
-        for (int d = 0; d < 2; ++d)
-            hipLaunchKernelGGL(jk_packed_final_kernel, gN, b256, 0, st, dD[d], dD[d], pJrow + d * ctx->hl.MP * nrows * NW, nrows * NW,
-                               ctx->hl.KS, ctx->hl.MP, ctx->d_Jt + (size_t)d * nseg * npr, nseg, ctx->d_rowmap, L, dJ[d], dK[d]);
-        return TF_OK;
-    }
-    for (int d = 0; d < nd; ++d)                                 // one density per pass over the packed tensor
-      for (int pass = 0; pass < ((nonsym && nonsym[d]) ? 2 : 1); ++pass) {
-        const bool general = nonsym && nonsym[d];
-        double *dD = (pass == 0) ? ctx->d_D : ctx->d_D + nn;
-        hipLaunchKernelGGL(pack_density_kernel, gN, b256, 0, st, dP[d], L, (general && pass == 0) ? 1 : 0, ctx->d_Psym, ctx->d_Pp);
-        double *dDp[1] = {dD};
-        int rc = jk_packed_pass<1>(ctx, st, dDp, cd);
-        if (rc) return rc;
-        if (general && pass == 0) continue;
-        hipLaunchKernelGGL(jk_packed_final_kernel, gN, b256, 0, st, ctx->d_D, dD, pJrow, nrows * NW, ctx->hl.KS, ctx->hl.MP, ctx->d_Jt,
-                           ctx->jkt[0].nseg, ctx->d_rowmap, L, dJ[d], dK[d]);
-      }
-    return TF_OK;
-}
-
-// Fock build from the tiles layout (tf_jktile.hip.h): pack -> jk_tile_kernel beside jk_edge_kernel -> jk_tile_reduce_kernel ->
-// jk_tile_final_kernel.  One density per pass (a non-symmetric one: two passes, K = D(P^T) + D(P)^T), or -- symmetric densities only --
-// up to eight per pass: densities = columns of the B operands of the matrix-core products (ND = 4 or 8; fewer: zero columns).
-extern "C++" {
-// the partial-sum buffers of a list for nd densities per pass
-static int tile_list_buffers(tf_ctx *ctx, tf_ctx::TileList &D, int nd)
-{
-    if (D.nd_cap >= nd) return TF_OK;
-    auto alloc_t = [&](double **p, size_t doubles) -> int {
-        HIPCHK(ctx, tf_malloc((void **)p, std::max<size_t>(1, doubles) * sizeof(double)));
-        ctx->tile_allocs.push_back(*p);
-        return TF_OK;
-    };
-    int rc;
-    if ((rc = alloc_t(&D.DJ, (size_t)D.dj_len * nd)) || (rc = alloc_t(&D.Jt, (size_t)D.jt_len * nd)) || (rc = alloc_t(&D.Jd, (size_t)D.jd_len * nd)) ||
-        (rc = alloc_t(&D.DIk, (size_t)D.n_di * 64 * nd)) || (rc = alloc_t(&D.DIl, (size_t)D.n_di * 16 * nd)))
-        return rc;
-    D.nd_cap = nd;
-    return TF_OK;
-}
-// device copy of a task list
-static int tile_list_upload(tf_ctx *ctx, const tft::TaskList &TL, bool own_shapes, tf_ctx::TileList &D)
-{
-    auto up_t = [&](const auto &h, auto **d) -> int {
-        int rc3 = upload(ctx, h, d, false);
-        if (!rc3) ctx->tile_allocs.push_back(*d);
-        return rc3;
-    };
-    int rc;
-    if (own_shapes && ((rc = up_t(TL.pairs, &D.d_pairs)) || (rc = up_t(TL.runs, &D.d_runs)))) return rc;   // (the shapes of the DJ vectors differ with the strip height)
-    if ((rc = up_t(TL.tasks, &D.d_tasks)) || (rc = up_t(TL.itask_ptr, &D.d_itask_ptr)) || (rc = up_t(TL.itasks, &D.d_itasks))) return rc;
-    D.n_tasks = (int)TL.tasks.size(); D.ksub = TL.ksub; D.n_di = TL.n_di; D.dj_len = TL.dj_len; D.jd_len = TL.jd_len; D.jt_len = TL.jt_len;
-    for (int b = 0; b <= TT_W; ++b) D.bucket[b] = TL.bucket[b];
-    return TF_OK;
-}
-
-// one pass over the tensor for the ND densities in ctx->t_X / t_Pm (packed by the caller); `out`: [6][ND][N][N]
-template <int ND>
-static int jk_tiles_pass(tf_ctx *ctx, tf_ctx::TileList &D, hipStream_t st, double *out)
-{
-    const int N = ctx->N;
-    const size_t nn = (size_t)N * N;
-    const tft::Tables &TT = ctx->tiles;
-    int rc = tile_list_buffers(ctx, D, ND);
-    if (rc) return rc;
-    int jt_rows = 0;
-    for (int p = 0; p < TT.npair; ++p) jt_rows += ctx->hl.csize[TT.pa[p]];
-    const size_t edge_lds = (size_t)(2 + 3 * TT_EDGE_WAVES) * N * sizeof(double), red_lds = std::max((size_t)2 * TT_RED_WAVES * N, (size_t)TT_RED_WAVES * 64 * std::max(TT_RED_CT, ND)) * sizeof(double);
-    if (std::max(edge_lds, red_lds) > ctx->tile_lds_set) {                // (beyond the default 64 KB per workgroup: N > 580)
-        if (std::max(edge_lds, red_lds) > (size_t)160 * 1024 - 1024) TF_FAIL(ctx, TF_EINVAL, "N = %d exceeds the LDS rows of the tiles layout's reductions", N);
-        const int want = (int)std::max(edge_lds, red_lds);
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_edge_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_edge_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_edge_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_tile_reduce_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_tile_reduce_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&jk_tile_reduce_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        ctx->tile_lds_set = (size_t)want;
-    }
-    TJArgs A{};
-    A.DJ = D.DJ; A.Jt = D.Jt; A.Jd = D.Jd; A.DIk = D.DIk; A.DIl = D.DIl; A.sJt = (size_t)D.jt_len; A.sDIk = (size_t)D.n_di * 64; A.sDIl = (size_t)D.n_di * 16;
-    A.N = N; A.pm_len = TT.pm_len;
-    TEArgs E{};
-    E.edge_base = TT.edge_base; E.N = N; E.tab = ctx->d_tvtab; E.EJ = out + 5 * ND * nn; E.ED = out + 2 * ND * nn; E.EDT = out + 3 * ND * nn; E.sE = nn;
-    const bool fork = ctx->have_streams && getenv("TF_JK_SERIAL") == nullptr;
-    if (D.n_tasks > 0) {
-        hipEvent_t ev_after = nullptr;
-        if (ctx->prof_jk) {
-            if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
-                hipEvent_t a, b;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ctx->prof_ev.push_back(a); ctx->prof_ev.push_back(b); }
-            }
-            if (ctx->prof_used + 2 <= ctx->prof_ev.size()) {
-                (void)hipEventRecord(ctx->prof_ev[ctx->prof_used], st);
-                ev_after = ctx->prof_ev[ctx->prof_used + 1];
-                ctx->prof_used += 2;
-            }
-        }
-        if (fork) (void)hipEventRecord(ctx->sev[0], st);
-        // ONE launch of full-size workgroups over all tasks (measured at N = 400: 1.57 ms against 1.82 for one launch per workgroup size
-        // on side streams -- loads only); the idle waves of the narrower tasks wait in the task's barriers
-        static const int pf_env = getenv("TF_TILE_PF") ? atoi(getenv("TF_TILE_PF")) : 2;
-        const dim3 grid((unsigned)D.n_tasks), block(64 * TT_W);
-#define TF_TJ_LAUNCH(NDV, MBV, PFV) hipLaunchKernelGGL((jk_tile_kernel<NDV, MBV, PFV>), grid, block, 0, st, ctx->d_eri, D.d_tasks, ctx->t_X, ctx->t_Pm, A)
-        if constexpr (ND == 1) {
-            if (D.ksub == 16) { if (pf_env == 1) TF_TJ_LAUNCH(1, 1, 1); else TF_TJ_LAUNCH(1, 1, 2); }
-            else if (D.ksub == 32) { if (pf_env == 1) TF_TJ_LAUNCH(1, 2, 1); else TF_TJ_LAUNCH(1, 2, 2); }
-            else TF_TJ_LAUNCH(1, 4, 1);
-        } else {
-            if (D.ksub != 16) TF_FAIL(ctx, TF_EINVAL, "tiles layout: the wide pass needs the list of 16-row strips");
-            if (pf_env == 1) TF_TJ_LAUNCH(ND, 1, 1); else TF_TJ_LAUNCH(ND, 1, 2);
-        }
-#undef TF_TJ_LAUNCH
-        if (ev_after) (void)hipEventRecord(ev_after, st);
-    }
-    {
-        // the edge elements beside the tile launch
-        hipStream_t ls = st;
-        if (fork && D.n_tasks > 0) { ls = ctx->streams[1]; (void)hipStreamWaitEvent(ls, ctx->sev[0], 0); }
-        hipLaunchKernelGGL((jk_edge_kernel<ND>), dim3((unsigned)N, (unsigned)ND), dim3(64 * TT_EDGE_WAVES), edge_lds, ls, ctx->d_eri, ctx->t_X, D.d_runs, E);
-        if (ls != st) { (void)hipEventRecord(ctx->sev[1], ls); (void)hipStreamWaitEvent(st, ctx->sev[1], 0); }
-    }
-    TRArgs R{};
-    R.itask_ptr = D.d_itask_ptr; R.itasks = D.d_itasks; R.jlist_ptr = ctx->d_jlist_ptr; R.clsI = ctx->bl.clsI;
-    R.DJ = D.DJ; R.Jt = D.Jt; R.Jd = D.Jd; R.DIk = D.DIk; R.DIl = D.DIl; R.T = ctx->d_eri; R.X = ctx->t_X;
-    R.sJt = A.sJt; R.sDIk = A.sDIk; R.sDIl = A.sDIl; R.sO = nn;
-    R.Dj = out; R.Di = out + (size_t)ND * nn; R.JD = out + (size_t)4 * ND * nn; R.JtTot = ctx->t_JtTot;
-    R.edge_base = TT.edge_base; R.N = N; R.ksub = D.ksub; R.npair = TT.npair; R.nd = ND; R.pm_len = TT.pm_len; R.tab = ctx->d_tvtab;
-    R.jt_rows = jt_rows;
-    const unsigned nblk = ND == 1 ? (unsigned)(5 * N + jt_rows) : (unsigned)(4 * N) + (unsigned)ND * (unsigned)(N + jt_rows);
-    hipLaunchKernelGGL(jk_tile_reduce_kernel<ND>, dim3(nblk), dim3(TT_RED_THREADS), red_lds, st, D.d_tasks, D.d_pairs, D.d_runs, ctx->d_jlist, R);
-    return TF_OK;
-}
-}  // extern "C++"
-
-static int launch_jk_tiles(tf_ctx *ctx, int nd, const double *const *dP, double *const *dJ, double *const *dK, hipStream_t st, const int *nonsym)
-{
-    const int N = ctx->N;
-    const size_t nn = (size_t)N * N, pml = (size_t)std::max(1, ctx->tiles.pm_len);
-    const dim3 gN((unsigned)((nn + 255) / 256)), b256(256);
-    auto final_launch = [&](const double *o0, const double *o1, int ndp, int d, const double *jtt, double *J, double *K) {
-        TFArgs F{};                                                          // out sets: [6][ndp][N][N]; D of the first pass, D2 of the last
-        F.Dj = o0 + (size_t)(0 * ndp + d) * nn; F.Di = o0 + (size_t)(1 * ndp + d) * nn; F.ED = o0 + (size_t)(2 * ndp + d) * nn; F.EDT = o0 + (size_t)(3 * ndp + d) * nn;
-        F.Dj2 = o1 + (size_t)(0 * ndp + d) * nn; F.Di2 = o1 + (size_t)(1 * ndp + d) * nn; F.ED2 = o1 + (size_t)(2 * ndp + d) * nn; F.EDT2 = o1 + (size_t)(3 * ndp + d) * nn;
-        F.JD = o1 + (size_t)(4 * ndp + d) * nn; F.EJ = o1 + (size_t)(5 * ndp + d) * nn; F.JtTot = jtt; F.tab = ctx->d_tvtab;
-        hipLaunchKernelGGL(jk_tile_final_kernel, gN, b256, 0, st, F, ctx->bl, J, K);
-    };
-    bool any_general = false;
-    for (int d = 0; d < nd; ++d) any_general = any_general || (nonsym && nonsym[d]);
-    static const int wide_min = getenv("TF_TILE_WIDE_MIN") ? atoi(getenv("TF_TILE_WIDE_MIN")) : 2;     // fewest densities that go through the wide pass
-    if (nd >= wide_min && nd >= 2 && !any_general) {
-        // the list of 16-row strips (one row block per wave: the registers hold ND accumulator sets), built at first use
-        if (!ctx->tlw.d_tasks) {
-            static const int part_steps = std::min(TT_STEPS_MAX, getenv("TF_TILE_PART_STEPS") ? std::max(1, atoi(getenv("TF_TILE_PART_STEPS"))) : TT_STEPS_MAX);
-            const tft::TaskList *TL = &ctx->tsubw;
-            if (ctx->ksub1 == 16) TL = &ctx->tsub1;
-            else {
-                const std::string e = tft::build_list(ctx->tclass, ctx->tiles, ctx->trows, 16, part_steps, ctx->tsubw);
-                if (!e.empty()) TF_FAIL(ctx, TF_EINVAL, "%s", e.c_str());
-            }
-            int rc = tile_list_upload(ctx, *TL, true, ctx->tlw);
-            if (rc) return rc;
-        }
-        for (int d0 = 0; d0 < nd;) {
-            const int left = nd - d0, ndp = left > 4 ? 8 : 4, n = std::min(left, ndp);
-            for (int d = 0; d < n; ++d)
-                hipLaunchKernelGGL(pack_density_tiles_kernel, gN, b256, 0, st, dP[d0 + d], ctx->bl, ctx->tv, 0, ctx->t_X + (size_t)d * nn, ctx->t_Pm + (size_t)d * pml);
-            if (n < ndp) {                                                   // empty columns
-                HIPCHK(ctx, hipMemsetAsync(ctx->t_X + (size_t)n * nn, 0, (size_t)(ndp - n) * nn * sizeof(double), st));
-                HIPCHK(ctx, hipMemsetAsync(ctx->t_Pm + (size_t)n * pml, 0, (size_t)(ndp - n) * pml * sizeof(double), st));
-            }
-            int rc = ndp == 8 ? jk_tiles_pass<8>(ctx, ctx->tlw, st, ctx->t_out) : jk_tiles_pass<4>(ctx, ctx->tlw, st, ctx->t_out);
-            if (rc) return rc;
-            for (int d = 0; d < n; ++d) final_launch(ctx->t_out, ctx->t_out, ndp, d, ctx->t_JtTot + (size_t)d * pml, dJ[d0 + d], dK[d0 + d]);
-            d0 += n;
-        }
-        return TF_OK;
-    }
-    for (int d = 0; d < nd; ++d) {
-        const bool general = nonsym && nonsym[d];
-        for (int pass = 0; pass < (general ? 2 : 1); ++pass) {
-            double *out = ctx->t_out + (size_t)pass * 6 * nn;
-            hipLaunchKernelGGL(pack_density_tiles_kernel, gN, b256, 0, st, dP[d], ctx->bl, ctx->tv, (general && pass == 0) ? 1 : 0, ctx->t_X, ctx->t_Pm);
-            int rc = jk_tiles_pass<1>(ctx, ctx->tl1, st, out);
-            if (rc) return rc;
-            if (general && pass == 0) continue;
-            final_launch(ctx->t_out, out, 1, 0, ctx->t_JtTot, dJ[d], dK[d]);
-        }
-    }
-    return TF_OK;
-}
-
-static int launch_jk(tf_ctx *ctx, int nd, const double *const *dP, double *const *dJ, double *const *dK, hipStream_t st,
-                     const int *nonsym = nullptr)
-{
-    if (ctx->layout == 2) return launch_jk_tiles(ctx, nd, dP, dJ, dK, st, nonsym);
-    if (ctx->layout == 1) return launch_jk_packed(ctx, nd, dP, dJ, dK, st, nonsym);
-    const int N = ctx->N, ld = ctx->ld;
-    const double *Ppad[2] = {dP[0], nd > 1 ? dP[1] : dP[0]};
-    if (ld != N) {
-        for (int d = 0; d < nd; ++d) {
-            double *dst = ctx->d_Ppad + (size_t)d * N * ld;
-            hipLaunchKernelGGL(pad_matrix_kernel, dim3((N * ld + 255) / 256), dim3(256), 0, st, dP[d], dst, N, ld);
-            Ppad[d] = dst;
-        }
-    }
-    if (ctx->n_rows > 0) {
-        const int npair = ld / 2;
-        // rows per workgroup: share each P tile among JB rows, but keep >= ~2 workgroups per CU in flight
-        int JB = (ctx->n_rows >= 4 * 2048) ? 4 : (ctx->n_rows >= 2 * 2048 ? 2 : 1);
-        if (nd == 2 && JB == 4) JB = 2;                         // register budget
-        int nlc = (npair <= TF_JK_THREADS) ? 1 : (npair <= 2 * TF_JK_THREADS ? 2 : 4);
-        // test hooks (tests/test_gpu_sharded.py): exercise the variants that only N > 512 would select
-        if (const char *e = getenv("TF_JK_FORCE_NLC")) nlc = std::max(nlc, atoi(e));
-        if (const char *e = getenv("TF_JK_FORCE_JB")) { const int f = atoi(e); if (f == 1 || f == 2 || (f == 4 && nd == 1)) JB = f; }
-        // instantiated combinations: (NLC 4, one density) up to JB 2; (NLC 4, two densities) JB 1 -- the grid below must match
-        if (nlc == 4 && nd == 1 && JB == 4) JB = 2;
-        if (nlc == 4 && nd == 2) JB = 1;
-        const size_t smem = (size_t)(2 * nd * JB * N + 4 * TF_JK_THREADS) * sizeof(double);
-        const dim3 grid((unsigned)((ctx->n_rows + JB - 1) / JB)), block(TF_JK_THREADS);
-        hipEvent_t ev_after = nullptr;
-        if (ctx->prof_jk) {
-            if (ctx->prof_used + 2 > ctx->prof_ev.size()) {
-                hipEvent_t a, b;
-                if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ctx->prof_ev.push_back(a); ctx->prof_ev.push_back(b); }
-            }
-            if (ctx->prof_used + 2 <= ctx->prof_ev.size()) {
-                (void)hipEventRecord(ctx->prof_ev[ctx->prof_used], st);
-                ev_after = ctx->prof_ev[ctx->prof_used + 1];
-                ctx->prof_used += 2;
-            }
-        }
-#define TF_JK_LAUNCH(NLC, JBV, NDV)                                                                                         \
-        hipLaunchKernelGGL((jk_rows_kernel<NLC, JBV, NDV>), grid, block, smem, st, ctx->d_eri, ctx->d_row_ij, ctx->n_rows, N, ld, \
-                           Ppad[0], Ppad[1], ctx->d_Jrow, ctx->d_Kp)
-        if (npair > 4 * TF_JK_THREADS) TF_FAIL(ctx, TF_EINVAL, "N = %d exceeds the J/K kernel's row length limit (2048)", N);
-        if (nd == 1) {
-            if (nlc == 1) {
-                if (JB == 4) TF_JK_LAUNCH(1, 4, 1); else if (JB == 2) TF_JK_LAUNCH(1, 2, 1); else TF_JK_LAUNCH(1, 1, 1);
-            } else if (nlc == 2) {
-                if (JB == 4) TF_JK_LAUNCH(2, 4, 1); else if (JB == 2) TF_JK_LAUNCH(2, 2, 1); else TF_JK_LAUNCH(2, 1, 1);
-            } else {
-                if (JB >= 2) TF_JK_LAUNCH(4, 2, 1); else TF_JK_LAUNCH(4, 1, 1);
-            }
-        } else {
-            if (nlc == 1) {
-                if (JB == 2) TF_JK_LAUNCH(1, 2, 2); else TF_JK_LAUNCH(1, 1, 2);
-            } else if (nlc == 2) {
-                if (JB == 2) TF_JK_LAUNCH(2, 2, 2); else TF_JK_LAUNCH(2, 1, 2);
-            } else
-                TF_JK_LAUNCH(4, 1, 2);
-        }
-#undef TF_JK_LAUNCH
-        if (ev_after) (void)hipEventRecord(ev_after, st);
-    }
-    for (int d = 0; d < nd; ++d)
-        hipLaunchKernelGGL(jk_reduce_kernel, dim3(N, (N + 63) / 64), dim3(256), 0, st, ctx->d_Jrow + (size_t)d * ctx->n_rows,
-                           ctx->d_Kp + (size_t)d * ctx->n_rows * 2 * ld, ctx->d_rowmap, N, ld, dJ[d], dK[d]);
-    return TF_OK;
-}
-
-// The single exchange step of a sharded Fock build: the partial J and K of nd densities are stacked in one
-// staging buffer [2][nd][N][N] and summed over the ranks by the caller's all-reduce (torch.distributed over RCCL in tuna_amd).
-static int allreduce_jk(tf_ctx *ctx, int nd, double *const *dJ, double *const *dK, hipStream_t st)
-{
-    if (ctx->world == 1) return TF_OK;
-    if (ctx->comm) {
-        // in the library: ncclAllReduce of J and of K where they lie, one group, on the build's stream (no staging copy, no status word: a
-        // failed rank fails the collective for every rank)
-        const size_t nn1 = (size_t)ctx->N * ctx->N;
-        int grc = tfrccl::GroupStart();
-        for (int d = 0; d < nd && !grc; ++d) {
-            grc = tfrccl::AllReduce(dJ[d], dJ[d], nn1, tfrccl::kFloat64, tfrccl::kSum, ctx->comm, st);
-            if (!grc) grc = tfrccl::AllReduce(dK[d], dK[d], nn1, tfrccl::kFloat64, tfrccl::kSum, ctx->comm, st);
-        }
-        const int erc = tfrccl::GroupEnd();
-        if (grc || erc) TF_FAIL(ctx, TF_ENODEVICE, "ncclAllReduce of [J;K] failed: %s", tfrccl::errstr(grc ? grc : erc).c_str());
-        return TF_OK;
-    }
-    if (!ctx->allreduce)
-        TF_FAIL(ctx, TF_EINVAL, "the tensor is sharded over %d ranks: attach an RCCL communicator (tf_comm_init) or register the all-reduce of the partial [J;K] with tf_set_allreduce", ctx->world);
-    const size_t nn = (size_t)ctx->N * ctx->N, need = 2 * (size_t)nd * nn;
-    // one slot beyond the payload carries a status word through the same collective: a rank whose exchange step failed locally (the
-    // hook sets it) makes the sum non-zero on EVERY rank, so that all of them return an error instead of some waiting in a collective
-    if (ctx->jkstage_doubles < need + 1) {
-        if (ctx->d_jkstage) (void)tf_free(ctx->d_jkstage);
-        ctx->d_jkstage = nullptr; ctx->jkstage_doubles = 0;
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_jkstage, (need + 1) * sizeof(double)));
-        ctx->jkstage_doubles = need + 1;
-    }
-    for (int d = 0; d < nd; ++d) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage + (size_t)d * nn, dJ[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage + (size_t)(nd + d) * nn, dK[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_jkstage + need, 0, sizeof(double), st));
-    const int rc = ctx->allreduce(ctx->allreduce_user, ctx->d_jkstage, (int64_t)(need + 1), (void *)st);
-    if (rc) TF_FAIL(ctx, TF_ENODEVICE, "the registered all-reduce failed (code %d)", rc);
-    double status = 0.0;
-    HIPCHK(ctx, hipMemcpyAsync(&status, ctx->d_jkstage + need, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (status != 0.0) TF_FAIL(ctx, TF_ENODEVICE, "the exchange step of the sharded Fock build failed on %g rank(s): every rank stops", status);
-    for (int d = 0; d < nd; ++d) {
-        HIPCHK(ctx, hipMemcpyAsync(dJ[d], ctx->d_jkstage + (size_t)d * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(dK[d], ctx->d_jkstage + (size_t)(nd + d) * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    return TF_OK;
-}
+// ---- collectives over the ranks, debug aids, the communicator ----------------------------------------------------------------------
 
 // Collective control flow of the native cycles on a sharded tensor (tfscf::Workspace::agree): the values are summed over the ranks
 // through the registered all-reduce; a rank whose values differ from the mean makes EVERY rank fail instead of leaving some of them
@@ -3087,15 +2579,15 @@ static int agree_over_ranks(tf_ctx *ctx, const double *vals, int n, std::string 
 long long tf_debug_partials(tf_ctx *ctx, int which, double *host, long long n)
 {
     if (!ctx || !ctx->have_eri || ctx->layout != 1 || !host) return TF_EINVAL;
-    const tf_ctx::JKTables &T = ctx->jkt[0];
+    const tf_ctx::JKTables &T = ctx->jk.packed.t[0];
     const size_t ng = (size_t)std::max(1, T.n_groups), nrows = (size_t)std::max<long long>(1, ctx->n_rows), N = (size_t)ctx->N, RS = (size_t)ctx->bl.RS;
     const double *src = nullptr; size_t cnt = 0;
     switch (which) {
-    case 0: src = ctx->d_DI; cnt = ng * N; break;
-    case 1: src = ctx->d_DI + ng * N; cnt = ng * RS; break;
-    case 2: src = ctx->d_DJ; cnt = nrows * N; break;
-    case 3: src = ctx->d_DJ + nrows * N; cnt = nrows * RS; break;
-    case 4: src = ctx->d_D; cnt = N * N; break;
+    case 0: src = ctx->jk.packed.DI; cnt = ng * N; break;
+    case 1: src = ctx->jk.packed.DI + ng * N; cnt = ng * RS; break;
+    case 2: src = ctx->jk.packed.DJ; cnt = nrows * N; break;
+    case 3: src = ctx->jk.packed.DJ + nrows * N; cnt = nrows * RS; break;
+    case 4: src = ctx->jk.packed.D; cnt = N * N; break;
     default: return TF_EINVAL;
     }
     cnt = std::min<size_t>(cnt, (size_t)n);
@@ -3106,7 +2598,7 @@ long long tf_debug_partials(tf_ctx *ctx, int which, double *host, long long n)
 int tf_debug_groups(tf_ctx *ctx, int32_t *out5, int max_groups)
 {
     if (!ctx || !ctx->have_eri || ctx->layout != 1) return TF_EINVAL;
-    const tf_ctx::JKTables &T = ctx->jkt[0];
+    const tf_ctx::JKTables &T = ctx->jk.packed.t[0];
     std::vector<JKGroup> g((size_t)T.n_groups);
     if (T.n_groups && hipMemcpy(g.data(), T.d_groups, g.size() * sizeof(JKGroup), hipMemcpyDeviceToHost) != hipSuccess) return TF_ENODEVICE;
     for (int k = 0; k < T.n_groups && k < max_groups; ++k) { out5[5 * k] = g[k].i; out5[5 * k + 1] = g[k].j0; out5[5 * k + 2] = g[k].nr; out5[5 * k + 3] = g[k].r0; out5[5 * k + 4] = g[k].c; }
@@ -3161,80 +2653,6 @@ int tf_comm_destroy(tf_ctx *ctx)
 }
 
 int tf_comm_attached(const tf_ctx *ctx) { return (ctx && ctx->comm) ? 1 : 0; }
-
-int tf_fock_jk_device(tf_ctx *ctx, int n_dens, const double *dP, double *dJ, double *dK, void *stream)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_fock_jk: call tf_build_eri first");
-    if (n_dens < 1 || !dP || !dJ || !dK) TF_FAIL(ctx, TF_EINVAL, "tf_fock_jk: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)ctx->N * ctx->N;
-    const int chunk = ctx->layout == 2 ? 8 : 2;                  // densities per pass over the tensor: two (packed / rows), up to eight (tiles)
-    for (int d = 0; d < n_dens; d += chunk) {
-        const int nd = std::min(chunk, n_dens - d);
-        const double *p[8]; double *j[8], *k[8];
-        for (int q = 0; q < 8; ++q) { const int dq = d + std::min(q, nd - 1); p[q] = dP + dq * nn; j[q] = dJ + dq * nn; k[q] = dK + dq * nn; }
-        int rc = launch_jk(ctx, nd, p, j, k, (hipStream_t)stream);
-        if (rc) return rc;
-        if (ctx->comm && ctx->world > 1 && (rc = allreduce_jk(ctx, nd, j, k, (hipStream_t)stream))) return rc;   // in the library, on the same stream
-    }
-    return TF_OK;
-}
-
-int tf_fock_jk(tf_ctx *ctx, int n_dens, const double *P, double *J, double *K)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_fock_jk: call tf_build_eri first");
-    if (n_dens < 1 || !P || !J || !K) TF_FAIL(ctx, TF_EINVAL, "tf_fock_jk: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)ctx->N * ctx->N;
-    const int chunk = ctx->layout == 2 ? 8 : 2;
-    for (int d = 0; d < n_dens; d += chunk) {
-        const int nd = std::min(chunk, n_dens - d);
-        HIPCHK(ctx, hipMemcpy(ctx->d_P, P + d * nn, nd * nn * sizeof(double), hipMemcpyHostToDevice));
-        const double *p[8]; double *j[8], *k[8];
-        for (int q = 0; q < 8; ++q) { const int dq = std::min(q, nd - 1); p[q] = ctx->d_P + dq * nn; j[q] = ctx->d_J + dq * nn; k[q] = ctx->d_K + dq * nn; }
-        int nonsym[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // the packed / tiles layouts need a second pass for a non-symmetric density
-        const int N = ctx->N;
-        for (int q = 0; q < nd; ++q) {
-            const double *Pq = P + (d + q) * nn;
-            for (int a = 0; a < N && !nonsym[q]; ++a)
-                for (int b = 0; b < a; ++b)
-                    if (Pq[(size_t)a * N + b] != Pq[(size_t)b * N + a]) { nonsym[q] = 1; break; }
-        }
-        int rc = launch_jk(ctx, nd, p, j, k, 0, nonsym);
-        if (rc) return rc;
-        if (ctx->comm && ctx->world > 1 && (rc = allreduce_jk(ctx, nd, j, k, 0))) return rc;     // a communicator is attached: the sums over the ranks
-        HIPCHK(ctx, hipMemcpy(J + d * nn, ctx->d_J, nd * nn * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(K + d * nn, ctx->d_K, nd * nn * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    HIPCHK(ctx, hipGetLastError());
-    return TF_OK;
-}
-
-int tf_jk_profile(tf_ctx *ctx, int enable)
-{
-    if (!ctx) return TF_EINVAL;
-    ctx->prof_jk = enable != 0;
-    ctx->prof_used = 0;
-    return TF_OK;
-}
-
-int tf_jk_profile_read(tf_ctx *ctx, double *seconds_total, int64_t *launches)
-{
-    if (!ctx || !seconds_total || !launches) return TF_EINVAL;
-    double tot = 0.0;
-    for (size_t k = 0; k + 1 < ctx->prof_used; k += 2) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->prof_ev[k + 1]));
-        float ms = 0.f;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->prof_ev[k], ctx->prof_ev[k + 1]));
-        tot += ms * 1e-3;
-    }
-    *seconds_total = tot;
-    *launches = (int64_t)(ctx->prof_used / 2);
-    ctx->prof_used = 0;
-    return TF_OK;
-}
 
 // ---- one-electron integrals -------------------------------------------------------------------------
 
@@ -3386,12 +2804,12 @@ int tf_dft_vxc(tf_ctx *ctx, const double *P, double *Vxc, double *n_elec, double
     if (!P || !Vxc) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc: bad arguments");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nn = (size_t)ctx->N * ctx->N;
-    HIPCHK(ctx, hipMemcpy(ctx->d_P, P, nn * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->jk.all.P, P, nn * sizeof(double), hipMemcpyHostToDevice));
     std::string msg;
     double o3[3];
-    int rc = tfdft::vxc(ctx->scf.blas, ctx->grid, ctx->d_P, ctx->d_J, o3, msg);
+    int rc = tfdft::vxc(ctx->scf.blas, ctx->grid, ctx->jk.all.P, ctx->jk.all.J, o3, msg);
     if (rc) { ctx->err = msg; return rc; }
-    HIPCHK(ctx, hipMemcpy(Vxc, ctx->d_J, nn * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(Vxc, ctx->jk.all.J, nn * sizeof(double), hipMemcpyDeviceToHost));
     if (n_elec) *n_elec = o3[0];
     if (e_x) *e_x = o3[1];
     if (e_c) *e_c = o3[2];
@@ -3478,9 +2896,7 @@ static int cycle_jk(tf_ctx *ctx, int nd, const double *dPa, const double *dPb, d
 {
     const double *p[2] = {dPa, dPb};
     double *j[2] = {dJa, dJb}, *k[2] = {dKa, dKb};
-    ctx->jk_try_class_diagonal = true;                              // (a cycle's densities are class-diagonal unless a field along x / y mixes the classes)
-    int rcj = launch_jk(ctx, nd, p, j, k, st);
-    ctx->jk_try_class_diagonal = false;
+    int rcj = launch_jk(ctx, nd, p, j, k, st, nullptr, true);       // (a cycle's densities are class-diagonal unless a field along x / y mixes the classes)
     return rcj ? rcj : allreduce_jk(ctx, nd, j, k, st);
 }
 
@@ -3551,9 +2967,7 @@ struct LockstepJK {
             const double *p[8];
             double *j[8], *k[8];
             for (int d = 0; d < nd; ++d) { p[d] = req[q + d].dP; j[d] = req[q + d].dJ; k[d] = req[q + d].dK; }
-            ctx->jk_try_class_diagonal = true;                      // (under the mutex of the batch: one pass at a time)
-            rc = launch_jk(ctx, nd, p, j, k, st, nullptr);
-            ctx->jk_try_class_diagonal = false;
+            rc = launch_jk(ctx, nd, p, j, k, st, nullptr, true);
             ++passes; builds += nd;
         }
         if (hipEventRecord(ev[generation & 1], st) != hipSuccess && rc == TF_OK) rc = TF_ENODEVICE;
