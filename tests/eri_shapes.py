@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: the systems, slab settings and Boys-seam geometries that pin the launch structure of tf_build_eri (EriBuild in
-tf_device.hip: plan_slab_size / run_slab, launch_class, launch_generic, teamc_tasks), with their oracle tensors cached per process.
+tf_eri_host.hip.h: plan_slab_size / run_slab, launch_class, launch_generic, teamc_tasks), with their oracle tensors cached per process.
 Used by tests/test_eri_shapes.py (CPU) and tests/test_gpu_eri_shapes.py (GPU, and its child processes).  Nothing in the product imports
 this module."""
 from __future__ import annotations

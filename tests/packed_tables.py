@@ -31,7 +31,7 @@ def lib():
         so = os.path.join(HERE, "packed_model", "_build", "libpackedtables.so")
         csrc = os.path.join(HERE, "..", "tuna_amd", "csrc")
         src = [os.path.join(HERE, "packed_model", "packed_tables.cpp")] + [os.path.join(csrc, h) for h in
-                                                                           ("tf_packed.h", "tf_packed_host.h", "tf_tiles.h", "tf_tiles_host.h", "tf_internal.h", "tf_jk_plan.h")]
+                                                                           ("tf_packed.h", "tf_packed_host.h", "tf_tiles.h", "tf_tiles_host.h", "tf_internal.h", "tf_jk_plan.h", "tf_eri_types.h", "tf_eri_plan.h")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
             subprocess.check_call(["sh", os.path.join(HERE, "packed_model", "build.sh")])
         L = C.CDLL(so)
@@ -113,3 +113,98 @@ def jk_plan(N, n_rows, NW, MP, RS, NPtot, n_groups, ypart_len, nseg):
     plan = {k: int(v) for k, v in zip(PLAN_SIZES, out)}
     plan["pass"] = {nd: {k: int(v) for k, v in zip(PLAN_PASS, out[len(PLAN_SIZES) + (nd - 1) * len(PLAN_PASS):])} for nd in (1, 2)}
     return plan
+
+
+# ---- the LDS plans of the ERI kernels (tuna_amd/csrc/tf_eri_plan.h): integers in, the members of the launch record out ----------
+ERI_Q_FIELDS = ("offR", "offPref", "offPQ", "offRed", "offEab", "offEcd", "offScale", "offLmn", "offBlk", "offG", "offTab", "offCsr", "lds_doubles",
+                "PB", "stride", "G", "ncp", "tupG_off", "tupXZ_off", "stage")
+ERI_FAMILY = {"multi": 0, "fact": 1, "class": 2, "component_lane": 3}
+ERI_CF_FIELDS = ("offR", "capR", "offPref", "offPQ", "offPP", "offG", "capG", "offX", "offZ", "capXZ", "offTupG", "offTupXZ", "offEab", "capEab",
+                 "offEcd", "capEcd", "offRed", "lds_doubles", "tri", "gtab_doubles", "dbg_npq_lo", "dbg_npq_hi", "offKm", "capKm", "team_lmax",
+                 "team_pqmax", "fit", "gtab")
+ERI_LREC_FIELDS = ("L", "nM", "tsize", "nT", "xz", "gsz", "lgG", "lgX", "nb_cap", "tupG_off", "tupXZ_off", "pad")
+ERI_TEAM_FIELDS = ("oE12", "oOffA", "oScA", "oOffK", "oTp", "oTk", "oTc", "oRowOff", "oCompW", "oOutW", "flat_off", "nflat")
+ERI_TEAM_SIZE_FIELDS = ("vcap", "team_doubles", "shared_doubles", "flat", "bytes")
+_ERI_READY = False
+
+
+def _eri():
+    global _ERI_READY
+    L = lib()
+    if not _ERI_READY:
+        vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
+        L.ptm_eri_carve.restype = ll; L.ptm_eri_carve.argtypes = [ci, vp, ci, ci, vp]
+        L.ptm_eri_lp_group.restype = ci; L.ptm_eri_lp_group.argtypes = [ci]
+        L.ptm_eri_group_stat.restype = None; L.ptm_eri_group_stat.argtypes = [ci, vp, vp]
+        L.ptm_eri_cfact.restype = ll; L.ptm_eri_cfact.argtypes = [vp, vp]
+        L.ptm_eri_lrec.restype = ll; L.ptm_eri_lrec.argtypes = [vp, ci, vp, vp, vp]
+        L.ptm_eri_team.restype = ll; L.ptm_eri_team.argtypes = [ci, vp, vp]
+        L.ptm_eri_choose_team.restype = ci; L.ptm_eri_choose_team.argtypes = [vp, vp, ci, ci, ll, ci, ci]
+        L.ptm_eri_team_grid_x.restype = ll; L.ptm_eri_team_grid_x.argtypes = [ci, ci, ll, ll, ll]
+        _ERI_READY = True
+    return L
+
+
+def eri_carve(family, cases, tupG=0, tupXZ=0):
+    """cases[n][10] = La Lb Lc Ld nca ncb ncc ncd npp_ab npp_cd -> {member: int64[n]} of the QClass the family's carve function fills"""
+    L, fam = _eri(), ERI_FAMILY[family]
+    cases = np.ascontiguousarray(cases, dtype=np.int32)
+    out = np.zeros((len(cases), len(ERI_Q_FIELDS)), dtype=np.int32)
+    for k in range(len(cases)):
+        assert L.ptm_eri_carve(fam, cases[k].ctypes.data, tupG, tupXZ, out[k].ctypes.data) == len(ERI_Q_FIELDS)
+    return {f: out[:, i].astype(np.int64) for i, f in enumerate(ERI_Q_FIELDS)}
+
+
+def eri_lp_group(lp):
+    return int(_eri().ptm_eri_lp_group(int(lp)))
+
+
+def eri_group_stat(pairs):
+    """pairs[n][5] = La Lb npp nE component pairs -> (maxLp, maxT, maxLp1, maxE, maxcomp, maxnpp)"""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 5)
+    out = np.zeros(6, dtype=np.int32)
+    _eri().ptm_eri_group_stat(len(pairs), pairs.ctypes.data, out.ctypes.data)
+    return tuple(int(v) for v in out)
+
+
+def eri_cfact(cases):
+    """cases[n][21] = GroupStat bra, GroupStat ket, bra contracted, ket contracted, nbt, xz, e, km members, packed, team_lmax, team_pqmax"""
+    L = _eri()
+    cases = np.ascontiguousarray(cases, dtype=np.int32)
+    out = np.zeros((len(cases), len(ERI_CF_FIELDS)), dtype=np.int32)
+    for k in range(len(cases)):
+        assert L.ptm_eri_cfact(cases[k].ctypes.data, out[k].ctypes.data) == len(ERI_CF_FIELDS)
+    return {f: out[:, i].astype(np.int64) for i, f in enumerate(ERI_CF_FIELDS)}
+
+
+def eri_lrec(L4, caps=()):
+    """(La, Lb, Lc, Ld), [(capR, capG, capXZ), ..] -> ({member: int}, the gsz G words and xz X/Z words)"""
+    L4 = np.ascontiguousarray(L4, dtype=np.int32)
+    caps = np.ascontiguousarray(caps, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros(len(ERI_LREC_FIELDS), dtype=np.int32)
+    n = _eri().ptm_eri_lrec(L4.ctypes.data, len(caps), caps.ctypes.data, out.ctypes.data, None)
+    words = np.zeros(n, dtype=np.uint16)
+    _eri().ptm_eri_lrec(L4.ctypes.data, len(caps), caps.ctypes.data, out.ctypes.data, words.ctypes.data)
+    return {f: int(v) for f, v in zip(ERI_LREC_FIELDS, out)}, words
+
+
+def eri_team(per_class, cases):
+    """cases[n][16] = La Lb Lc Ld nab ncd nkap nnzT nacc nout foff maxblk maxK nnzc nEab nEcd -> {member: int64[n]}, per-size members
+    as member_16 / _64 / _256"""
+    L = _eri()
+    cases = np.ascontiguousarray(cases, dtype=np.int32)
+    nf = len(ERI_TEAM_FIELDS) + 3 * len(ERI_TEAM_SIZE_FIELDS)
+    out = np.zeros((len(cases), nf), dtype=np.int64)
+    for k in range(len(cases)):
+        assert L.ptm_eri_team(int(per_class), cases[k].ctypes.data, out[k].ctypes.data) == nf
+    names = list(ERI_TEAM_FIELDS) + [f"{f}_{tm}" for tm in (16, 64, 256) for f in ERI_TEAM_SIZE_FIELDS]
+    return {f: out[:, i] for i, f in enumerate(names)}
+
+
+def eri_choose_team(avail, nbytes, nT, nnzc, soft64, t16_nnz, force):
+    a, b = np.ascontiguousarray(avail, dtype=np.int32), np.ascontiguousarray(nbytes, dtype=np.int64)
+    return int(_eri().ptm_eri_choose_team(a.ctypes.data, b.ctypes.data, int(nT), int(nnzc), int(soft64), int(t16_nnz), int(force)))
+
+
+def eri_team_grid_x(n_ket, team, n_bra, kpw_div, kpw_max):
+    return int(_eri().ptm_eri_team_grid_x(int(n_ket), int(team), int(n_bra), int(kpw_div), int(kpw_max)))

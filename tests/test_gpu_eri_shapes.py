@@ -1,4 +1,4 @@
-"""GPU: the launch structure of tf_build_eri (EriBuild in tf_device.hip) -- forced slab cuts, every ERI kernel family, the seams of
+"""GPU: the launch structure of tf_build_eri (EriBuild in tf_eri_host.hip.h) -- forced slab cuts, every ERI kernel family, the seams of
 the Boys function -- element by element against the CPU oracle.  The systems, slab settings and seam geometries are in
 tests/eri_shapes.py; Engine.eri_build_stats() (tf_eri_build_stats) tells which path a build took.
   (a) slab cuts: one slab, TF_SLAB_MB=1, TF_SLAB_ROWS=R_mid and TF_SLAB_ROWS=1 (one bra shell pair per slab) in both ERI modes on the

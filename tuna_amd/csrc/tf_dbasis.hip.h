@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "tf_internal.h"
 #include "tf_layout.hip.h"
+#include "tf_eri_types.h"
 
 namespace tfk {
 
@@ -17,11 +18,6 @@ struct DPair {
     int tab_off;                 // component-pair tables of this pair in DBasis::ct_* (nca * ncb entries)
     int pcls[5];                 // ct_ord: component pairs ordered by (x, y) parity class; class c is [pcls[c], pcls[c + 1])
 };
-
-// What a shell quartet with the angular momenta (La, Lb | Lc, Ld) needs to know, tabulated once per tf_build_eri (index
-// ((La * 6 + Lb) * 6 + Lc) * 6 + Ld): sizes of the per-axis factor tables of eri_cfact_kernel, the index words of their entries
-// (DBasis::tup) and the primitive quartets per batch the launch of its shell-pair groups has LDS for.
-struct LRec { int L, nM, tsize, nT, xz, gsz, lgG, lgX, nb_cap, tupG_off, tupXZ_off, pad; };
 
 struct DBasis {
     const DShell *shells;

@@ -12,26 +12,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "tf_kernels.hip.h"
+#include "tf_eri_types.h"
 
 namespace tfk {
-
-struct QClass {
-    int La, Lb, Lc, Ld, L, tsize;
-    int nca, ncb, ncc, ncd, ncomp;
-    int npp_ab, npp_cd, npq;   // maxima over the launch (LDS capacity); the actual depths come from the pair records
-    int nEab, nEcd;
-    int PB, stride;        // primitive quartets per LDS batch, LDS column stride of the R tables
-    int G, ncp;            // multi kernel: shell quartets per workgroup, padded components per quartet
-    int n_ket;             // ket pairs in this launch
-    int fused, spherical, nsc, nsd, Nout, ld, offBlk;   // fused ket transform: output dims of shells C, D; T2 geometry; LDS block buffer
-    int offG;              // factorised kernel: ket half of the z tables, (Lc+1)(Ld+1)(La+Lb+1) nM doubles
-    int offTab;            // factorised kernel: per-pair component tables, (nab + ncc*ncd) * 2 doubles (scale, two offset words)
-    int offCsr;            // fused spherical ket transform: LDS copy of the two shells' Cartesian->spherical CSR rows (TF_CSR_DOUBLES)
-    int tri;               // packed layout: only kets with first shell <= the bra's first shell are needed ((kl) <= (ij))
-    int tupG_off, tupXZ_off;   // factorised kernel: index words of its table entries in DBasis::tup (LRec of the class)
-    // LDS carve-out, offsets in doubles
-    int offR, offPref, offPQ, offRed, offEab, offEcd, offScale, offLmn, lds_doubles;
-};
 
 // component info staged in LDS: packed (lx | ly << 8 | lz << 16) and the normalisation ratio
 __device__ __forceinline__ void stage_components(const DBasis &B, int comp_off, int ncomp, int *dstLmn, double *dstScale, int tid,
@@ -110,11 +93,6 @@ __device__ __forceinline__ double hermite_sum(const CompQuartet &Q, const double
 }
 
 
-#define TF_BLK_DOUBLES 1024   // LDS doubles of the Cartesian (cc,cd) sub-block buffer of the fused ket transform
-
-// LDS copy of the Cartesian->spherical rows of shell types C and D (the global CSR is a chain of dependent L2 loads per output)
-#define TF_CSR_CAP 144                                     // entries per shell type (h shells: 11 rows)
-#define TF_CSR_DOUBLES (2 * TF_CSR_CAP + (2 * TF_CSR_CAP + 32) / 2)
 struct KetCsr { const double *valC, *valD; const int *ptrC, *ptrD, *idxC, *idxD; bool ok; };
 
 __device__ __forceinline__ KetCsr stage_ket_csr(const DBasis &B, const QClass &qc, double *sCsr, int tid, int nthreads)
@@ -702,16 +680,6 @@ __global__ __launch_bounds__(TF_ERI_THREADS) void eri_fact_kernel(DBasis B, QCla
 // batch loop); a component costs one unrolled triple-table sum per primitive quartet.  Components < 256: lane groups split the
 // primitive quartets of a batch and are combined in fixed order at the end; more: up to TF_CF_KMAX components per thread in
 // registers.  Uncontracted quartets (one primitive quartet) take the same path with direct stores.  Cartesian output (unfused).
-#define TF_CF_KMAX 2
-struct CFCaps {
-    int offR, capR, offPref, offPQ, offPP, offG, capG, offX, offZ, capXZ, offTupG, offTupXZ, offEab, capEab, offEcd, capEcd;
-    int offRed, lds_doubles, tri;
-    int gtab_doubles;                // GTAB launches: offG / offX / offZ are relative to the workgroup's block of this many doubles in global memory
-    int dbg_npq_lo, dbg_npq_hi;      // profiling aid (TF_ERI_DBG_NPQ=lo:hi): only quartets with lo <= primitive quartets <= hi are computed
-    int offKm, capKm;                // FAMILY launches: weights of the members' primitive pairs, [member][primitive pair] (capKm doubles)
-    int team_lmax, team_pqmax;       // quartets with both pair sums <= team_lmax and <= team_pqmax primitive quartets belong to eri_teamc_kernel (-1: none)
-};
-
 // GTAB: the G / X / Z tables of the workgroup live in global memory (gtab, one block of cap.gtab_doubles per workgroup, L2-resident)
 // instead of LDS -- the very top of the angular momenta ((hh|hh): 2 x 14 256 + 4 356 doubles) does not fit the 160 KB.
 // FAMILIES (MM > 1; general contractions, round 3): TUNA keeps every contracted function of a generally contracted set as a shell of its

@@ -21,30 +21,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "tf_dbasis.hip.h"
+#include "tf_eri_types.h"
 
 namespace tfk {
-
-struct TClass {
-    int La, Lb, Lc, Ld;
-    int nTab, nTcd, nT;           // exponent tuples of one axis: (La+1)(Lb+1), (Lc+1)(Ld+1), their product
-    float inv_nTcd;
-    int nab, ncd;                 // Cartesian component pairs of the bra / ket shell pair
-    int pA[5], pK[5], pS[5];      // parity-class offsets: bra component pairs, ket component pairs, ket output pairs (class-sorted lists)
-    int nkap, nnzT;               // ket output pairs; entries of the ket pair transform
-    int tabA, tabK;               // DBasis::ct_* offsets of a representative bra / ket pair (the tables are the same for a whole class)
-    int ktp_off, kte_off;         // ket pair transform of the ket class: row pointers at kt_ptr[ktp_off ..], entries at kt_k / kt_c[kte_off ..]
-    int n_ket;                    // ket pairs of the launch (class list prefix)
-    int nEab, nEcd;               // doubles of one Hermite table of the bra / ket pair
-    int vcap;                     // doubles of a team's component block (eri_teamc_kernel: of its table scratch)
-    int nacc;                     // parity-allowed Cartesian components of a quartet (eri_teamc_kernel: the accumulation block)
-    int oE12, oOffA, oScA, oOffK, oTp, oTk, oTc, shared_doubles, team_doubles;   // LDS carve-out, in doubles
-    // flat component / output lists (classes whose parity-allowed components fit the team's block: one loop over all of them instead
-    // of one per parity class): DBasis::tflat[flat_off ..] = nacc words (bra index | ket index << 16, class-sorted indices), then nout
-    // pairs (bra index | output pair << 16, offset of the bra row inside the block)
-    int flat, flat_off, nflat, nout, oCompW, oOutW, oRowOff;   // nflat: words to stage (components padded to an even count, then outputs)
-    float invK[4], invS[4];       // 1 / (ket component pairs of class c), 1 / (ket output pairs of class c)
-    long long RLS;                // stride of a slab row
-};
 
 // What a team needs of a ket / bra shell pair (uncontracted: one primitive pair), parallel to the launch's pair lists: no pointer chasing
 // through DBasis::pairs.  Kq = weight product / exponent sum (the 1 / (p q) of the prefactor folded in on the host).

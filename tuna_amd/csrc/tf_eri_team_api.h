@@ -2,10 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "tf_dbasis.hip.h"
+#include "tf_eri_types.h"   // TF_TEAM_LMAX
 
 namespace tfk {
-
-#define TF_TEAM_LMAX 6           // pair sums La + Lb, Lc + Ld the team kernels are instantiated for (up to two f shells)
 
 struct TClass;                    // tf_eri_team.hip.h
 struct BraRec;

@@ -5,10 +5,10 @@
 #include "tf_internal.h"
 #include "tf_layout.hip.h"
 #include "tf_dbasis.hip.h"
+#include "tf_eri_types.h"   // TF_ERI_THREADS
 
 namespace tfk {
 
-#define TF_ERI_THREADS 256
 #define TF_RT_DOUBLES 6400   // LDS doubles for the per-batch R tables
 
 // (2k-1)!! for k = 0..10  (the closed form of the x/y Hermite-Coulomb integrals at zero x/y separation,
