@@ -480,6 +480,55 @@ typedef struct {
 int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip,
                tf_cis_result *out);
 
+/* ---- closed-shell TD-DFT and TDA for the local-density functionals: replaces calculate_restricted_exchange_correlation_kernel_matrices
+ * (tuna_dft.py:1097-1147) and the density-functional branch of calculate_A_matrix / calculate_B_matrix (tuna_ci.py:719-845) ---- */
+
+/* The launch plan of the kernel build for dim = o v and n_points grid points, a pure function of the two (no context, no device):
+ * out = {64-wide blocks n_b, tiles n_b (n_b + 1) / 2, slabs, slab length, LDS bytes of a workgroup, points per chunk, the shortest slab
+ * the plan cuts, tile edge}.  Slab s covers the points [s slab_length, min(n_points, (s + 1) slab_length)).  TF_EINVAL on dim or n_points < 1. */
+int tf_xc_kernel_plan(int64_t dim, int64_t n_points, int64_t out[8]);
+/* The matrix-core kernel of the build and its slab sum on their own (instrumentation, tests): host psi_o [n_o][n_points],
+ * psi_v [n_v][n_points], u_singlet, u_triplet [n_points] (any values), and
+ *   K_singlet[(ia)][(jb)] = sum_g u_singlet(g) psi_o[i][g] psi_v[a][g] psi_o[j][g] psi_v[b][g],  (ia) = i n_v + a,   K_triplet likewise,
+ * host [dim][dim].  Runs the very routine tf_xc_kernel_rhf and tf_tddft_rhf call; only the transposition of psi to the production
+ * operand [n_points][n_o + n_v] is added.  Needs no basis, tensor or grid.  Both results are symmetric to the last bit, and two calls
+ * give the same bits: tiles with row block <= column block only, slab partials added in slab order, no atomics.
+ * TF_EINVAL (the context stays usable) on a size < 1 or a NULL pointer; TF_ENOMEM with the size in the message. */
+int tf_xc_kernel_probe(tf_ctx *ctx, int n_o, int n_v, int64_t n_points, const double *psi_o, const double *psi_v, const double *u_singlet,
+                       const double *u_triplet, double *K_singlet, double *K_triplet);
+/* K_XC_singlet, K_XC_triplet [dim][dim] (host) of the grid's functional for the orbitals C [N,N], windows as tf_cis_rhf, at the density
+ * P [N,N] (the converged closed-shell SCF density, as the reference passes it): rho through the path of tf_dft_vxc, floored at 1e-23,
+ *   f_X = 2 d2(n e_X)/dn2,  f_C^S = 2 d2(n e_C)/dn2,  f_C^T = 2 f_mm  (Slater: tuna_xc.py:5956-5983; VWN3: :5994-6061; VWN5: :6151-6236),
+ *   u_S = w (DFX f_X + DFC f_C^S),  u_T = w (DFX f_X + DFC f_C^T),  psi = Phi C over the two windows (one GEMM), then the kernel of
+ * tf_xc_kernel_probe.  f_points (may be NULL): [4][n_points] = the floored rho, f_X, f_C^S, f_C^T.
+ * TF_EINVAL (the context stays usable) without a tensor, without a grid of tf_dft_setup, on a NULL C, P or K, unless
+ * 0 <= n_frozen < n_occ < N, with world > 1, or when the grid's functional has a gradient-corrected part (x_functional >= 2 or
+ * c_functional >= 3: the message names it).  TF_ENOMEM with the size in the message. */
+int tf_xc_kernel_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *P, double *K_singlet, double *K_triplet, double *f_points);
+/* Seconds of the last kernel build of the context by stage: {psi GEMM, density and point kernels, K kernel, slab sum}
+ * (tf_xc_kernel_probe: the last two). */
+int tf_xc_kernel_timings(tf_ctx *ctx, double out[4]);
+
+typedef struct {
+    int32_t tda;                /* 1 = TDA (the matrix A alone), 0 = full TD-DFT   */
+    int32_t singlets;           /* as tf_cis_opts */
+    int32_t triplets;
+    int32_t n_keep;
+    double hfx;                 /* HFX_prop: the share of exact exchange (1 with the null functional = TDHF, 0 for the pure functionals) */
+} tf_tddft_opts;
+
+/* Closed-shell TD-DFT / TDA from canonical Kohn-Sham orbitals: tf_cis_rhf with (calculate_A_matrix / calculate_B_matrix, tuna_ci.py:719-845)
+ *     singlet: A = Delta + 2 (ia|jb) - hfx (ij|ab) + K_S,  B = 2 (ia|jb) - hfx (ib|ja) + K_S;
+ *     triplet: A = Delta - hfx (ij|ab) + K_T,              B = -hfx (ib|ja) + K_T,
+ * K_S, K_T of tf_xc_kernel_rhf at the density P, added after the symmetrisation (they are symmetric to the last bit).  With hfx = 0 the
+ * block (ab|ij) is neither built nor read.  With the null functional (tf_dft_setup with x_functional = c_functional = 0) no kernel is
+ * built, and with hfx = 1 every output equals tf_cis_rhf's bit for bit.  The solve stages, the transition moments and the rule
+ * "unstable reference: TF_ELINALG" are tf_cis_rhf's own code.  seconds as tf_cis_rhf; the kernel build is counted in the assembly slot [2].
+ * TF_EINVAL as tf_cis_rhf and tf_xc_kernel_rhf together (no tensor, no grid, a gradient-corrected functional, NULL opts, C, eps, P or
+ * out, bad windows, world > 1, hfx not finite).  TF_ENOMEM with the size in the message. */
+int tf_tddft_rhf(tf_ctx *ctx, const tf_tddft_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *P,
+                 const double *dip, tf_cis_result *out);
+
 /* ---- unrestricted CIS / TDHF: replaces calculate_unrestricted_single_reference_excited_states (tuna_ci.py:1377-1455) and
  * calculate_unrestricted_transition_dipoles (:1529-1571) ---- */
 

@@ -12,6 +12,8 @@
 //     X[p][q], Ht at (q, p) -- contiguous along p: read with p as the lane index into padded LDS tiles and picked up transposed.  Every
 //     global read and write is a run of up to 32 consecutive doubles; no atomics; out[p][q] and out[q][p] are the same two terms added in
 //     either order, so every matrix is symmetric to the last bit.
+// TD-DFT / TDA (tf_tddft_rhf) is the same pass with H and X scaled by the share of exact exchange and the exchange-correlation kernel
+// matrix of tf_xckernel.hip.h added per matrix: A gains K, A + B gains 2 K, A - B nothing (AssembleArgs::hfx, K, kfac).
 // TDHF is solved through A - B = L L^T: (L^T (A + B) L) Z = w^2 Z, X + Y = L Z / sqrt(w), X - Y = sqrt(w) L^-T Z (the caller,
 // tf_device.hip: rocSOLVER dpotrf and dsyevd, rocBLAS dtrmm and dtrsm), which gives X.X - Y.Y = (X + Y).(X - Y) = 1.  Every reduction
 // is per block, the blocks summed in block order: bitwise repeatable.
@@ -61,6 +63,12 @@ struct AssembleArgs {
     int n_out;                    // matrices of this call (<= 3)
     int kind[3];
     double *out[3];               // [dim][dim] each
+    // TD-DFT (tf_tddft_rhf): H and X enter scaled by hfx (Ht may be null when hfx = 0: the block is then neither built nor read), and
+    // matrix m gains kfac[m] K[m] after the symmetrisation -- K [dim][dim] is symmetric to the last bit (tf_xckernel.hip.h).  The
+    // defaults are Hartree-Fock: hfx = 1 multiplies exactly, a null K adds nothing.
+    double hfx = 1.0;
+    const double *K[3] = {nullptr, nullptr, nullptr};
+    double kfac[3] = {0.0, 0.0, 0.0};
 };
 
 // block (32, 8), grid (dim / 32, dim / 32) rounded up: tile rows p0 .., columns q0 ..
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs A)
                 const int j = (int)(q / v), b = (int)(q - (long long)j * v);
                 sG[y][tx] = A.g1[q * dim + p];
                 sX[y][tx] = A.g1[((long long)i * v + b) * dim + (long long)j * v + a];                  // (ib|ja)
-                sH[y][tx] = A.Ht[(((long long)j * o + i) * v + b) * v + a];                             // (ji|ba)
+                sH[y][tx] = A.Ht ? A.Ht[(((long long)j * o + i) * v + b) * v + a] : 0.0;                // (ji|ba)
             }
         }
     }
@@ -96,13 +104,17 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs A)
         const int i = (int)(p / v), a = (int)(p - (long long)i * v);
         const double G = A.g1[p * dim + q];
         const double X = sX[tx][y];                                                                      // (ib|ja) = X[p][q]
-        const double H = A.Ht[(((long long)i * o + j) * v + a) * v + b];
+        const double H = A.Ht ? A.Ht[(((long long)i * o + j) * v + a) * v + b] : 0.0;
         const double Gt = sG[tx][y];
         const double Xt = A.g1[((long long)j * v + a) * dim + (long long)i * v + b];                     // (ja|ib) = X[q][p]
         const double Hq = sH[tx][y];
         const double delta = p == q ? A.eps[A.n_occ + a] - A.eps[A.n_frozen + i] : 0.0;
-        for (int m = 0; m < A.n_out; ++m)
-            A.out[m][p * dim + q] = 0.5 * (cis_element(A.kind[m], delta, G, H, X) + cis_element(A.kind[m], delta, Gt, Hq, Xt));
+        const double hH = A.hfx * H, hX = A.hfx * X, hHq = A.hfx * Hq, hXt = A.hfx * Xt;
+        for (int m = 0; m < A.n_out; ++m) {
+            double r = 0.5 * (cis_element(A.kind[m], delta, G, hH, hX) + cis_element(A.kind[m], delta, Gt, hHq, hXt));
+            if (A.K[m]) r += A.kfac[m] * A.K[m][p * dim + q];
+            A.out[m][p * dim + q] = r;
+        }
     }
 }
 

@@ -1,5 +1,5 @@
 // tf_corr_host.hip.h -- the host drivers of the correlated methods: the AO->MO transformation, RMP2 / UMP2, MP3, MP4, LCCD / CCD,
-// LCCSD / QCISD / CCSD, the perturbative triples, CIS / TDHF, CIS(D) and the ladder probe.  Included by tf_device.hip (one translation unit:
+// LCCSD / QCISD / CCSD, the perturbative triples, CIS / TDHF, TD-DFT / TDA with the exchange-correlation kernel, CIS(D) and the probes.  Included by tf_device.hip (one translation unit:
 // struct tf_ctx, tf_malloc, launch_jk, TF_FAIL and HIPCHK are defined there, above the include); the kernels are in tf_mp2.hip.h ...
 // tf_cisd.hip.h.  First the pieces the drivers share, then the drivers.  DESIGN.md section 4.5a has the table of who uses what and the
 // invariants: every driver keeps its order of launches, rocBLAS calls and copies on the null stream, and the order of its host sums.
@@ -1482,64 +1482,86 @@ static bool cis_tdhf_workspace(CisSolve &s, DeviceBlocks &mem, size_t *bytes)
 // dtrmm and -- for the kept states -- one dtrsm (TDHF); the transition moments of the singlets as GEMMs.  All dim x dim arrays of the
 // solves are symmetric or read column by column (state n = column n = dim contiguous values), so rocSOLVER's column-major view needs no
 // transposition.
-int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip, tf_cis_result *out)
+// tf_tddft_rhf is the same driver with xc set: the exchange blocks scaled by hfx ((ab|ij) not built when hfx = 0) and, unless the grid's
+// functional is the null one, K_S / K_T of xc_kernel_build added in the assembly pass (counted in the assembly slot of seconds).
+struct __attribute__((visibility("hidden"))) CisXc { double hfx = 1.0; const double *P = nullptr; };
+
+static int xc_kernel_build(tf_ctx *ctx, const char *who, const CorrSetup &S, const double *P, DeviceBlocks &mem, double **pKS, double **pKT,
+                           double *f_points);
+static int xc_kernel_checks(tf_ctx *ctx, const char *who, const double *P);
+
+static int cis_rhf_driver(tf_ctx *ctx, const char *who, const tf_cis_opts *opts, const CisXc *xc, int n_occ, int n_frozen, const double *C,
+                          const double *eps, const double *dip, tf_cis_result *out)
 {
-    static const char *who = "tf_cis_rhf";
+    const std::string me = who;
     int rc = corr_args(ctx, who, opts && C && eps && out, " (needs opts, C, eps, out and 0 <= n_frozen < n_occ < N)", n_occ, n_frozen);
     if (rc) return rc;
-    if (!opts->singlets && !opts->triplets) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: neither singlets nor triplets asked for: there are no excited states to calculate");
-    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: n_keep must not be negative");
-    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: transition dipoles and oscillator strengths need the AO dipole matrices (dip)");
+    if (!opts->singlets && !opts->triplets) TF_FAIL(ctx, TF_EINVAL, "%s: neither singlets nor triplets asked for: there are no excited states to calculate", who);
+    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "%s: n_keep must not be negative", who);
+    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "%s: transition dipoles and oscillator strengths need the AO dipole matrices (dip)", who);
+    if (xc && (rc = xc_kernel_checks(ctx, who, xc->P))) return rc;
+    if (xc && !std::isfinite(xc->hfx)) TF_FAIL(ctx, TF_EINVAL, "%s: hfx must be finite", who);
     CorrSetup S;
     if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
     const int N = S.N, o = S.o, v = S.v;
     const long long ov = S.ov, B2 = S.B2;
-    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "tf_cis_rhf: dimension overflow");   // (grids of 32-wide tiles)
+    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);   // (grids of 32-wide tiles)
     const int dim = (int)ov, nk = std::min(opts->n_keep, dim);
     const bool tda = opts->tda != 0, sing = opts->singlets != 0, trip = opts->triplets != 0, moments = sing && dip && (out->tdm || out->osc);
+    const double hfx = xc ? xc->hfx : 1.0;
+    const bool with_k = xc && (ctx->grid.xid != 0 || ctx->grid.cid != 0);
     out->dim = dim;
     DeviceBlocks mem;
     double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr;
     auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
-    // ---- MO blocks, as tf_mp3_rhf makes them ((ki|lj) is not needed here)
-    if ((rc = mp3_mo_blocks(ctx, who, S, mem, &g1, &g2, &g3))) return rc;
-    mem.release(g3);
+    // ---- MO blocks, as tf_mp3_rhf makes them ((ki|lj) is not needed here); without exact exchange (ia|jb) alone
+    if (hfx == 0.0) {
+        if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g1, nullptr))) return rc;
+    } else {
+        if ((rc = mp3_mo_blocks(ctx, who, S, mem, &g1, &g2, &g3))) return rc;
+        mem.release(g3);
+    }
     const auto t1 = corr_stamp();
+    // ---- the exchange-correlation kernel matrices (TD-DFT)
+    double *KS = nullptr, *KT = nullptr;
+    if (with_k && (rc = xc_kernel_build(ctx, who, S, xc->P, mem, &KS, &KT, nullptr))) return rc;
     // ---- work space: the matrices (CIS: A per multiplicity; TDHF: A + B per multiplicity, A - B and one more dim^2 array for the
     //      triangular products), the transposed (ij|ab) until the assembly is done, the kept vectors, and the small arrays:
     //      w | w2 | e (dsyevd) | stat[2] | eps [N] | D_ia [3][dim] | mu [dim][3] | f [dim] | C_o | C_v | D C_v [N][v] | D [3][N][N]
     const int n_mats = (sing ? 1 : 0) + (trip ? 1 : 0) + (tda ? 0 : 2);
     const size_t nsmall = 3 * (size_t)dim + 2 + (size_t)N + 7 * (size_t)dim + (size_t)N * o + 2 * (size_t)N * v + 3 * (size_t)N * N;
     const size_t nkept = (size_t)std::max(1, nk) * dim * (tda ? 0 : 3);
-    double *Ht = mem.alloc((size_t)B2), *Ms = sing ? mem.alloc((size_t)B2) : nullptr, *Mt = trip ? mem.alloc((size_t)B2) : nullptr,
+    double *Ht = g2 ? mem.alloc((size_t)B2) : nullptr, *Ms = sing ? mem.alloc((size_t)B2) : nullptr, *Mt = trip ? mem.alloc((size_t)B2) : nullptr,
            *Mm = tda ? nullptr : mem.alloc((size_t)B2), *small = mem.alloc(nsmall);
     rocblas_int *d_info = mem.alloc_int(4);
-    if (!Ht || (sing && !Ms) || (trip && !Mt) || (!tda && !Mm) || !small || !d_info) {
+    if ((g2 && !Ht) || (sing && !Ms) || (trip && !Mt) || (!tda && !Mm) || !small || !d_info) {
         char text[200];
-        snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space (%d arrays of (o v)^2 = %lld^2 values)",
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space (%d arrays of (o v)^2 = %lld^2 values)", who,
                  (double)(((size_t)n_mats + 1) * (size_t)B2 + nkept + nsmall) * sizeof(double) / 1e9, n_mats + 1, ov);
         return fail(TF_ENOMEM, text);
     }
     double *d_w = small, *d_w2 = d_w + dim, *d_e = d_w2 + dim, *d_stat = d_e + dim, *d_eps = d_stat + 2, *d_Dia = d_eps + N, *d_mu = d_Dia + 3 * (size_t)dim,
            *d_f = d_mu + 3 * (size_t)dim, *d_Co = d_f + dim, *d_Cv = d_Co + (size_t)N * o, *d_T1 = d_Cv + (size_t)N * v, *d_dip = d_T1 + (size_t)N * v;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, me + ": copy failed");
     // ---- assembly
-    tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+    if (g2) tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
     {
         tfcis::AssembleArgs A{};
         A.g1 = g1; A.Ht = Ht; A.eps = d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v;
-        if (sing) { A.kind[A.n_out] = tda ? 0 : 2; A.out[A.n_out++] = Ms; }
-        if (trip) { A.kind[A.n_out] = tda ? 1 : 3; A.out[A.n_out++] = Mt; }
+        A.hfx = hfx;
+        const double kf = tda ? 1.0 : 2.0;                        // A gains K, A + B gains 2 K, A - B nothing
+        if (sing) { A.kind[A.n_out] = tda ? 0 : 2; A.K[A.n_out] = KS; A.kfac[A.n_out] = kf; A.out[A.n_out++] = Ms; }
+        if (trip) { A.kind[A.n_out] = tda ? 1 : 3; A.K[A.n_out] = KT; A.kfac[A.n_out] = kf; A.out[A.n_out++] = Mt; }
         if (!tda) { A.kind[A.n_out] = 4; A.out[A.n_out++] = Mm; }
         tfcis::launch_assemble(A, 0);
     }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: the assembly kernels failed on the device");
-    mem.release(g1); mem.release(g2); mem.release(Ht);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, me + ": the assembly kernels failed on the device");
+    mem.release(g1); mem.release(g2); mem.release(Ht); mem.release(KS); mem.release(KT);
     {
         const std::pair<double *, const double *> outs[3] = {{out->m_plus_singlet, Ms}, {out->m_plus_triplet, Mt}, {out->m_minus, Mm}};
         for (const auto &pr : outs)
             if (pr.first && pr.second && hipMemcpy(pr.first, pr.second, (size_t)B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+                return fail(TF_ENODEVICE, me + ": copy failed");
     }
     const auto t2 = corr_stamp();
     // ---- solves (the stages shared with tf_cis_uhf)
@@ -1550,7 +1572,7 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
         size_t bytes = 0;
         if (!cis_tdhf_workspace(sv, mem, &bytes)) {
             char text[200];
-            snprintf(text, sizeof text, "tf_cis_rhf: out of device memory for %.2f GB of work space for the TDHF reduction", (double)bytes / 1e9);
+            snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space for the TDHF reduction", who, (double)bytes / 1e9);
             return fail(TF_ENOMEM, text);
         }
     }
@@ -1559,7 +1581,7 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
         if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_Co, S.Co.data(), (size_t)N * o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_Cv, S.Cv.data(), (size_t)N * v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+            return fail(TF_ENODEVICE, me + ": copy failed");
         if ((rc = cis_dipole_block(sv, N, o, v, d_dip, d_Co, d_Cv, d_T1, d_Dia, 0))) return rc;     // D^c_ia = C_o^T D^c C_v
     }
     if (!tda && (rc = cis_tdhf_factor(sv, Mm, " for singlets or triplets"))) return rc;             // A - B = L L^T, once for both multiplicities
@@ -1571,19 +1593,197 @@ int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, co
                *y_out = mult == 0 ? out->y_singlet : out->y_triplet;
         if ((rc = tda ? cis_tda_solve(sv, M, name, x_out, y_out) : cis_tdhf_solve(sv, Mm, M, name, x_out, y_out))) return rc;
         const double *V = tda ? M : sv.T;                         // the transition vectors X + Y, state by state
-        if (e_out && hipMemcpy(e_out, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: copy failed");
+        if (e_out && hipMemcpy(e_out, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, me + ": copy failed");
         if (mult == 0 && moments) {                               // mu_n[c] = sqrt(2) sum_ia D^c_ia V[ia][n]
             const int mrc = cis_transition_moments(sv, V, std::sqrt(2.0), d_Dia, d_mu, d_f, out->tdm, out->osc);
-            if (mrc) return fail(mrc, "tf_cis_rhf: the transition moments failed on the device");
+            if (mrc) return fail(mrc, me + ": the transition moments failed on the device");
         }
     }
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_rhf: a kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, me + ": a kernel launch failed");
     const auto t3 = corr_stamp();
     out->seconds[0] = corr_secs(t3 - S.t0);
     out->seconds[1] = corr_secs(t1 - S.t0);
     out->seconds[2] = corr_secs(t2 - t1);
     out->seconds[3] = corr_secs(t3 - t2);
     return TF_OK;
+}
+
+int tf_cis_rhf(tf_ctx *ctx, const tf_cis_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *dip, tf_cis_result *out)
+{
+    return cis_rhf_driver(ctx, "tf_cis_rhf", opts, nullptr, n_occ, n_frozen, C, eps, dip, out);
+}
+
+// ---- TD-DFT / TDA for the local-density functionals: the exchange-correlation kernel matrices (tf_xckernel.hip.h) ----------------------
+
+static const char *const XCK_X_NAMES[4] = {"none", "Slater", "B88", "B3 (0.9 B88 + 0.1 Slater)"};
+static const char *const XCK_C_NAMES[6] = {"none", "VWN5", "VWN3", "LYP", "3P (0.81 LYP + 0.19 VWN5)", "3P (0.81 LYP + 0.19 VWN3)"};
+
+// What the kernel build needs besides the driver's own checks: a grid for this tensor, a local-density functional, the density
+static int xc_kernel_checks(tf_ctx *ctx, const char *who, const double *P)
+{
+    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "%s: call tf_dft_setup first (the exchange-correlation kernel is integrated on its grid)", who);
+    if (!ctx->have_eri || ctx->grid.N != ctx->N)
+        TF_FAIL(ctx, TF_EINVAL, "%s: the grid was set up for a different tensor (call tf_build_eri, then tf_dft_setup again)", who);
+    const tfdft::Grid &g = ctx->grid;
+    if (g.xid >= tfdft::X_B88 || g.cid >= tfdft::C_LYP)
+        TF_FAIL(ctx, TF_EINVAL, "%s: the exchange-correlation kernel of exchange \"%s\" with correlation \"%s\" is not implemented: only the "
+                "local-density functionals (Slater exchange, VWN3 / VWN5 correlation) have one", who, XCK_X_NAMES[g.xid], XCK_C_NAMES[g.cid]);
+    if (!P) TF_FAIL(ctx, TF_EINVAL, "%s: bad arguments (needs the density P)", who);
+    if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "%s: a sharded tensor (world > 1) is not supported", who);
+    return TF_OK;
+}
+
+// The production path from psi to K: the plan, the slab partials (mem's, released here), xck_kernel and xck_sum_kernel on the null stream.
+// psi [G][o + v] on the device.  seconds2: the K kernel, the slab sum (tf_xc_kernel_timings).
+static int xc_kernel_matrices(tf_ctx *ctx, const char *who, long long G, int o, int v, const double *psi, const double *uS, const double *uT,
+                              DeviceBlocks &mem, double *KS, double *KT, double *seconds2)
+{
+    const XckPlan P = xck_plan((long long)o * v, G);
+    double *part = mem.alloc(P.partial_doubles);
+    if (!part) {
+        char text[200];
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of slab partials (%d slabs of 2 x %lld^2 values)", who,
+                 (double)P.partial_doubles * sizeof(double) / 1e9, P.n_slabs, P.dim);
+        return corr_fail(ctx, TF_ENOMEM, text);
+    }
+    tfxck::Args A{psi, uS, uT, part, P.G, P.slab_len, o + v, o, v, (int)P.dim, P.n_b};
+    const auto t0 = corr_stamp();
+    hipLaunchKernelGGL(tfxck::xck_kernel, dim3((unsigned)P.n_tiles, (unsigned)P.n_slabs), dim3(XCK_THREADS), 0, 0, A);
+    const auto t1 = corr_stamp();
+    hipLaunchKernelGGL(tfxck::xck_sum_kernel, dim3((unsigned)((P.dim * P.dim + 255) / 256)), dim3(256), 0, 0, part, P.n_slabs, (int)P.dim, KS, KT);
+    const auto t2 = corr_stamp();
+    seconds2[0] = corr_secs(t1 - t0); seconds2[1] = corr_secs(t2 - t1);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the exchange-correlation kernel build failed on the device");
+    mem.release(part);
+    return TF_OK;
+}
+
+// K_S, K_T [dim][dim] (mem's) for the windows of S, the density P (host) and the grid's functional; f_points (host, may be null):
+// [4][G] = rho, f_X, f_C^S, f_C^T.  ctx->xck_seconds: psi GEMM, density + point kernels, K kernel, slab sum.
+static int xc_kernel_build(tf_ctx *ctx, const char *who, const CorrSetup &S, const double *P, DeviceBlocks &mem, double **pKS, double **pKT,
+                           double *f_points)
+{
+    double *seconds4 = ctx->xck_seconds;
+    tfdft::Grid &g = ctx->grid;
+    const int N = S.N, o = S.o, v = S.v, n = o + v;
+    const long long G = g.G;
+    const size_t dd = (size_t)S.B2;
+    rocblas_handle blas = ctx->scf.blas;
+    double *KS = mem.alloc(dd), *KT = mem.alloc(dd), *u = mem.alloc(2 * (size_t)G), *psi = mem.alloc((size_t)G * n), *Cw = mem.alloc((size_t)N * n),
+           *fp = f_points ? mem.alloc(4 * (size_t)G) : nullptr;
+    if (!KS || !KT || !u || !psi || !Cw || (f_points && !fp)) {
+        char text[200];
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space of the exchange-correlation kernel (2 x %lld^2 values and "
+                 "%lld x %d orbital values)", who, (double)(2 * dd + (size_t)G * (n + 6) + (size_t)N * n) * sizeof(double) / 1e9, S.ov, G, n);
+        return corr_fail(ctx, TF_ENOMEM, text);
+    }
+    // C_w = [C_o | C_v]
+    std::vector<double> hC((size_t)N * n);
+    for (int m = 0; m < N; ++m) {
+        std::copy(S.Co.begin() + (size_t)m * o, S.Co.begin() + (size_t)(m + 1) * o, hC.begin() + (size_t)m * n);
+        std::copy(S.Cv.begin() + (size_t)m * v, S.Cv.begin() + (size_t)(m + 1) * v, hC.begin() + (size_t)m * n + o);
+    }
+    const size_t nn = (size_t)N * N;
+    if (hipMemcpy(Cw, hC.data(), hC.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ctx->jk.all.P, P, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    BlasAtomicsOff no_atomics(blas);
+    const auto t0 = corr_stamp();
+    // psi [G][n] = Phi [G][N] C_w [N][n]
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, false, (int)G, n, N, 1.0, g.phi, N, Cw, n, 0.0, psi, n));
+    const auto t1 = corr_stamp();
+    // rho through the path of V_XC: B = Phi P, rho_g = <B_g, Phi_g>; then the point kernels
+    CORR_BLAS(tfmp3::gemm_rm(blas, false, false, (int)G, N, N, 1.0, g.phi, N, ctx->jk.all.P, N, 0.0, g.B, N));
+    hipLaunchKernelGGL(tfdft::xc_density_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.B, 0, g.rho, g.grad);
+    hipLaunchKernelGGL(tfdft::xc_fpoint_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha, g.rho, g.w,
+                       u, u + G, fp);
+    const auto t2 = corr_stamp();
+    seconds4[0] = corr_secs(t1 - t0); seconds4[1] = corr_secs(t2 - t1);
+    const int rc = xc_kernel_matrices(ctx, who, G, o, v, psi, u, u + G, mem, KS, KT, seconds4 + 2);
+    if (rc) return rc;
+    if (f_points && hipMemcpy(f_points, fp, 4 * (size_t)G * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    mem.release(u); mem.release(psi); mem.release(Cw); mem.release(fp);
+    *pKS = KS; *pKT = KT;
+    return TF_OK;
+}
+
+int tf_xc_kernel_plan(int64_t dim, int64_t n_points, int64_t out[8])
+{
+    if (dim < 1 || n_points < 1 || !out) return TF_EINVAL;
+    const XckPlan P = xck_plan(dim, n_points);
+    out[0] = P.n_b; out[1] = P.n_tiles; out[2] = P.n_slabs; out[3] = P.slab_len; out[4] = (int64_t)P.lds_bytes; out[5] = XCK_CHUNK;
+    out[6] = XCK_SLAB_MIN; out[7] = XCK_TILE;
+    return TF_OK;
+}
+
+int tf_xc_kernel_timings(tf_ctx *ctx, double out[4])
+{
+    if (!ctx || !out) return TF_EINVAL;
+    std::copy(ctx->xck_seconds, ctx->xck_seconds + 4, out);
+    return TF_OK;
+}
+
+int tf_xc_kernel_probe(tf_ctx *ctx, int n_o, int n_v, int64_t n_points, const double *psi_o, const double *psi_v, const double *u_singlet,
+                       const double *u_triplet, double *K_singlet, double *K_triplet)
+{
+    static const char *who = "tf_xc_kernel_probe";
+    if (!ctx) return TF_EINVAL;
+    if (n_o < 1 || n_v < 1 || n_points < 1 || !psi_o || !psi_v || !u_singlet || !u_triplet || !K_singlet || !K_triplet)
+        TF_FAIL(ctx, TF_EINVAL, "%s: bad arguments (needs n_o, n_v, n_points >= 1 and every pointer)", who);
+    const long long ov = (long long)n_o * n_v, G = n_points;
+    if (ov > 2000000LL || (long long)G * (n_o + n_v) > (1LL << 40)) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int n = n_o + n_v;
+    const size_t dd = (size_t)ov * ov;
+    DeviceBlocks mem;
+    double *psi = mem.alloc((size_t)G * n), *u = mem.alloc(2 * (size_t)G), *KS = mem.alloc(dd), *KT = mem.alloc(dd);
+    if (!psi || !u || !KS || !KT) TF_FAIL(ctx, TF_ENOMEM, "%s: out of device memory for %.2f GB", who, (double)((size_t)G * (n + 2) + 2 * dd) * 8 / 1e9);
+    std::vector<double> h((size_t)G * n);                     // the production operand: psi [G][o + v]
+    for (long long g = 0; g < G; ++g) {
+        for (int i = 0; i < n_o; ++i) h[(size_t)g * n + i] = psi_o[(size_t)i * G + g];
+        for (int a = 0; a < n_v; ++a) h[(size_t)g * n + n_o + a] = psi_v[(size_t)a * G + g];
+    }
+    if (hipMemcpy(psi, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(u, u_singlet, (size_t)G * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(u + G, u_triplet, (size_t)G * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    ctx->xck_seconds[0] = ctx->xck_seconds[1] = 0.0;
+    const int rc = xc_kernel_matrices(ctx, who, G, n_o, n_v, psi, u, u + G, mem, KS, KT, ctx->xck_seconds + 2);
+    if (rc) return rc;
+    if (hipMemcpy(K_singlet, KS, dd * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(K_triplet, KT, dd * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    return TF_OK;
+}
+
+int tf_xc_kernel_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *P, double *K_singlet, double *K_triplet, double *f_points)
+{
+    static const char *who = "tf_xc_kernel_rhf";
+    int rc = corr_args(ctx, who, C && K_singlet && K_triplet, " (needs C, K_singlet, K_triplet and 0 <= n_frozen < n_occ < N)", n_occ, n_frozen);
+    if (rc) return rc;
+    if ((rc = xc_kernel_checks(ctx, who, P))) return rc;
+    CorrSetup S;
+    if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
+    if (S.ov > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);
+    DeviceBlocks mem;
+    double *KS = nullptr, *KT = nullptr;
+    if ((rc = xc_kernel_build(ctx, who, S, P, mem, &KS, &KT, f_points))) return rc;
+    if (hipMemcpy(K_singlet, KS, (size_t)S.B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(K_triplet, KT, (size_t)S.B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    return TF_OK;
+}
+
+int tf_tddft_rhf(tf_ctx *ctx, const tf_tddft_opts *opts, int n_occ, int n_frozen, const double *C, const double *eps, const double *P,
+                 const double *dip, tf_cis_result *out)
+{
+    tf_cis_opts co{};
+    CisXc xc;
+    if (opts) { co.tda = opts->tda; co.singlets = opts->singlets; co.triplets = opts->triplets; co.n_keep = opts->n_keep; xc.hfx = opts->hfx; }
+    xc.P = P;
+    return cis_rhf_driver(ctx, "tf_tddft_rhf", opts ? &co : nullptr, &xc, n_occ, n_frozen, C, eps, dip, out);
 }
 
 // ---- unrestricted CIS / TDHF and the stability analysis ----------------------------------------------------------------------------

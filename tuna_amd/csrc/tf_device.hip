@@ -46,6 +46,7 @@
 #include "tf_mp2dens.hip.h"
 #include "tf_triples.hip.h"
 #include "tf_dft.hip.h"
+#include "tf_xckernel.hip.h"
 
 // ---- small-block cache for THIS file's device allocations ------------------------------------------------------------------------
 // A tensor build uploads ~40 small tables (layout, rows, work lists) and frees them again; every hipMalloc / hipFree pair costs 20-40 us
@@ -296,6 +297,7 @@ struct tf_ctx {
     tfscf::Workspace scf;
     std::vector<std::unique_ptr<tfscf::Workspace>> scf_batch;   // one workspace per cycle of a lockstep batch (tf_scf_rhf_batch), kept across calls
     tfdft::Grid grid;                    // Kohn-Sham integration grid with the AOs evaluated on it (tf_dft_setup)
+    double xck_seconds[4] = {0, 0, 0, 0};   // the last exchange-correlation kernel build by stage (tf_xc_kernel_timings)
     // persistent helpers of tf_build_eri (creating streams / freeing GiB-sized buffers costs tens of ms per call)
     static const int NSTREAM_MAX = 8;
     hipStream_t streams[NSTREAM_MAX] = {};

@@ -7,6 +7,8 @@
 // construct_density_on_grid :677-703, calculate_density_gradient :714-744, calculate_V_X/V_C :788-888,
 // calculate_restricted_exchange_correlation_matrix tuna_scf.py:600-654, functionals tuna_xc.py (Slater :199-213, B88 :385-438,
 // B3 :1462-1494, VWN :1512-1630 + :1802-1860, LYP :2200-2260, 3P :5843-5881), floors tuna_util.py:95-99.
+// For TD-DFT the second derivatives of the local-density functionals per grid point (xc_fpoint_kernel: Slater tuna_xc.py:5956-5983,
+// VWN3 :5994-6061, VWN5 :6151-6236, the factors of tuna_dft.py:1109-1124); their matrix elements are tf_xckernel.hip.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -229,6 +231,80 @@ __global__ void xc_point_kernel(long long G, int gga, int xid, int cid, double d
     vsig[g] = dfx * X.dfds + dfc * C.dfds;
     ex[g] = X.e * n;
     ec[g] = C.e * n;
+}
+
+// ---- second functional derivatives of the local-density functionals: the exchange-correlation kernel of TD-DFT ------------------------
+// (calculate_restricted_exchange_correlation_kernel_matrices, tuna_dft.py:1109-1124.)  With f = n e per functional,
+//     f_X = 2 d2(n e_X)/dn2,   f_C^singlet = 2 d2(n e_C)/dn2,   f_C^triplet = 2 f_mm   (f_mm: the spin stiffness over the density)
+
+__device__ inline double slater_d2f(double n, double x_alpha)                   // tuna_xc.py:5956-5983
+{
+    const double ic = 1.0 / cbrt(n);
+    return -(x_alpha / 2.0) * cbrt(3.0 / 3.141592653589793) * ic * ic;
+}
+
+__device__ inline void vwn_pot(double n, double x_0, double b, double c, double A, double &e, double &dedr);   // (below, with the spin path)
+
+struct VwnD2 { double e, dedr, d2edr2, r_s, x, combo, dcombo; };
+
+__device__ inline VwnD2 vwn_d2(double n, double x_0, double b, double c, double A)   // tuna_xc.py:6247-6297
+{
+    const double Q = sqrt(4.0 * c - b * b);
+    const double X_0 = x_0 * x_0 + b * x_0 + c;
+    const double c_1 = -b * x_0 / X_0;
+    const double c_2 = 2.0 * b * (c - x_0 * x_0) / (Q * X_0);
+    VwnD2 o;
+    o.r_s = cbrt(3.0 / (4.0 * 3.141592653589793) * (1.0 / n));
+    o.x = sqrt(o.r_s);
+    const double x = o.x, xm = x - x_0, Xx = o.r_s + b * x + c, X2 = Xx * Xx, xm2 = xm * xm;
+    o.e = A * (log(o.r_s / Xx) + c_1 * log(xm2 / Xx) + c_2 * atan(Q / (2.0 * x + b)));
+    o.combo = 2.0 / x + 2.0 * c_1 / xm - (2.0 * x + b) * (1.0 + c_1) / Xx - (1.0 / 2.0) * c_2 * Q / Xx;
+    o.dcombo = (-2.0 / o.r_s - 2.0 * c_1 / xm2 - 2.0 * (1.0 + c_1) / Xx + ((2.0 * x + b) * (2.0 * x + b)) * (1.0 + c_1) / X2 +
+                (1.0 / 2.0) * c_2 * Q * (2.0 * x + b) / X2);
+    o.dedr = (A / 2.0) * o.combo / x;
+    o.d2edr2 = A * (x * o.dcombo - o.combo) / (4.0 * x * x * x);
+    return o;
+}
+
+// d2(n e_C)/dn2 and f_mm of VWN-III (tuna_xc.py:5994-6061) and VWN-V (:6151-6236)
+__device__ inline void vwn3_kernel(double n, double &d2f, double &fmm)
+{
+    const VwnD2 p = vwn_d2(n, -0.409286, 13.0720, 42.7198, 0.0310907);
+    d2f = (p.r_s * p.r_s * p.d2edr2 - 2.0 * p.r_s * p.dedr) / (9.0 * n);
+    double e1, d1;
+    vwn_pot(n, -0.743294, 20.1231, 101.578, 0.01554535, e1, d1);
+    const double t = cbrt(2.0), fpp0 = 8.0 / (9.0 * (t * t * t * t - 2.0));
+    fmm = fpp0 * (e1 - p.e) / n;
+}
+__device__ inline void vwn5_kernel(double n, double &d2f, double &fmm)
+{
+    const VwnD2 p = vwn_d2(n, -0.10498, 3.72744, 12.9352, 0.0310907);
+    d2f = (p.x * 0.0310907) / (36.0 * n) * (p.x * p.dcombo - 5.0 * p.combo);
+    double ma, dma;
+    vwn_pot(n, -0.0047584, 1.13107, 13.0045, 1.0 / (6.0 * 3.141592653589793 * 3.141592653589793), ma, dma);
+    fmm = -ma / n;
+}
+
+// rho (floored as in xc_point_kernel) of a point from xc_density_kernel's sum; the weights of the kernel matrices
+//     u_S = w (dfx f_X + dfc f_C^S),   u_T = w (dfx f_X + dfc f_C^T);
+// fpts (may be null): [4][G] = rho, f_X, f_C^S, f_C^T.  Local-density ids only (the caller refuses the others).
+__global__ void xc_fpoint_kernel(long long G, int xid, int cid, double dfx, double dfc, double x_alpha, double *__restrict__ rho,
+                                 const double *__restrict__ w, double *__restrict__ uS, double *__restrict__ uT, double *__restrict__ fpts)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const double n = fmax(rho[g], 1e-23);
+    double fX = 0.0, fS = 0.0, fT = 0.0;
+    if (xid == X_SLATER) fX = 2.0 * slater_d2f(n, x_alpha);
+    if (cid == C_VWN5 || cid == C_VWN3) {
+        double d2f, fmm;
+        if (cid == C_VWN5) vwn5_kernel(n, d2f, fmm); else vwn3_kernel(n, d2f, fmm);
+        fS = 2.0 * d2f; fT = 2.0 * fmm;
+    }
+    rho[g] = n;
+    uS[g] = w[g] * (dfx * fX + dfc * fS);
+    uT[g] = w[g] * (dfx * fX + dfc * fT);
+    if (fpts) { fpts[g] = n; fpts[G + g] = fX; fpts[2 * G + g] = fS; fpts[3 * G + g] = fT; }
 }
 
 // D[g][n] = w (vrho phi + 4 vsig sum_a grad_a dphi_a)

@@ -33,6 +33,9 @@ FUNCTIONALS = {
     "B1LYP": ("B", "LYP", 0.75, 0.25, 1.0), "SLYP": ("S", "LYP", 1.0, 0.0, 1.0), "B3LYP": ("B3", "3P", 0.80, 0.20, 1.0),
     "B3LYP/G": ("B3", "3P/G", 0.80, 0.20, 1.0),
 }
+# the functionals with an exchange-correlation kernel, i.e. with TD-DFT / TDA excited states: the reference's rows with
+# time_dependent_available = True (tuna_util.py:1445-1452) that FUNCTIONALS has -- the local-density ones
+TD_AVAILABLE = ("HFS", "SVWN", "LSDA", "LDA", "SVWN3", "SVWN5")
 
 
 def real_vdw_radius(symbol: str) -> float:

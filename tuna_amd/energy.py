@@ -10,7 +10,8 @@ with ML n >= 2, or with a U prefix such as UB3LYP), the basis sets shipped in tu
 CARTHARM, DECONTRACT, COREGUESS/SADGUESS, CH n, ML n).  After the SCF: MP2 / MP3 and their SCS forms, MP4(SDQ) / MP4(DQ) (also written
 MP4[SDQ] / MP4[DQ]; full MP4 with triples through Calculation.mp4 = "SDTQ", not on the input line), and the coupled-cluster doubles
 methods LCCD and CCD on a closed-shell restricted reference (AMPCONV x, CORRMAXITER n, CORRDAMP [x]; DIIS n / NODIIS act on their
-iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, or TD on an HF line
+iterations too), and the vertical excitation spectrum of a closed-shell restricted reference: CIS, TDHF / RPA, TD on an HF line, or TD on
+the line of a local-density functional (tuna_amd.dft.TD_AVAILABLE: TD-DFT with the exchange-correlation kernel on the device)
 (TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x; (D) or [D] adds CIS(D) to the ROOT state), and STAB, the stability analysis of a Hartree-Fock SCF (RHF or UHF) in front
 of any post-SCF stage.  Through calculate_energy, a Calculation with reference "UHF" and excited_state set runs the spin-conserving CIS /
 TDHF of the open shell.  Everything numerical runs on the GPU through the C ABI.  The initial
@@ -458,8 +459,8 @@ def run_stability_analysis(calc: Calculation, molecule, out, engine: Engine, sil
     spin-conserving for UHF -- with the reference's block (:946-983, :1014-1036, :1092-1106) and its threshold of -1e-5.  out.stability
     holds the eigenvalues, which matrix each came from, the verdicts and the seconds.  An unstable solution is reported, not raised."""
     if calc.functional is not None:
-        raise TunaError("STAB: the stability analysis of a Kohn-Sham solution needs the exchange-correlation kernel, which is not built: "
-                        "STAB is available on Hartree-Fock references (HF, UHF, and the correlated methods on them).")
+        raise TunaError("STAB: the stability analysis of a Kohn-Sham solution (the orbital Hessian with the exchange-correlation kernel) is "
+                        "not built: STAB is available on Hartree-Fock references (HF, UHF, and the correlated methods on them).")
     N = molecule.n_basis
     threshold = ORB_HESS_EIG_THRESH
     nf = frozen_core_orbitals(molecule, calc)
@@ -725,7 +726,9 @@ def merge_excited_states(E_singlet, E_triplet, tdm_singlet=None, osc_singlet=Non
 
 
 def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engine, silent=True, log=print):
-    """Closed-shell CIS / TDHF on the device-resident tensor (all-electron), tf_cis_rhf: the flow of run_excited_state_calculation
+    """Closed-shell CIS / TDHF on the device-resident tensor (all-electron), tf_cis_rhf -- and, when calc.functional is one of
+    tuna_amd.dft.TD_AVAILABLE, TD-DFT / TDA with the exchange-correlation kernel at the SCF density out.P, tf_tddft_rhf with
+    calc.HFX_prop, on the grid the Kohn-Sham SCF left on the engine: the flow of run_excited_state_calculation
     (tuna_ci.py:2150-2290; kernel:1175-1190, :1289-1301) with its log lines (tuna_ci.py:1222-1273, :1324-1362, :1736-1863).  All states of
     the requested multiplicities are merged and sorted; out.energy = E_SCF + the excitation energy of ROOT; out.excited holds the
     merged energies, labels, |mu|, oscillator strengths, the root's X and Y and E_transition.  The root's difference density (P_diff of
@@ -733,6 +736,8 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
     calc.do_perturbative_doubles the root gets its CIS(D) correction after the spectrum (run_perturbative_doubles).  A TDHF run on an
     unstable reference raises the library's TunaError (TF_ELINALG) where the reference warns and drops states."""
     if calc.reference == "UHF":
+        if calc.functional is not None:
+            raise TunaError("Unrestricted time-dependent DFT is not built: TD-DFT runs on a closed-shell restricted Kohn-Sham reference.")
         return run_unrestricted_excited_states(calc, molecule, integrals, out, engine, silent, log)
     n_occ, N = molecule.n_doubly_occ, molecule.n_basis
     v = N - n_occ
@@ -741,10 +746,22 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
     if v <= 0:
         raise TunaError("Excited state calculation requested on system with no virtual orbitals!")   # kernel:1181
     tda = calc.tamm_dancoff_approximation
+    ks = calc.functional is not None                         # TD-DFT / TDA with the exchange-correlation kernel (tuna_ci.py:2199-2201)
+    if ks:
+        from . import dft as dft_mod
+        if calc.functional not in dft_mod.TD_AVAILABLE:
+            raise TunaError("Time-dependent DFT is not yet available for this exchange-correlation functional!")   # tuna_ci.py:2175
+        if calc.do_perturbative_doubles:
+            raise TunaError("The (D) correction of a TD-DFT state is not built: (D) applies to a CIS, TDHF, RPA or HF ... : TD state.")
     if not silent:
         log("\n Beginning excited state calculation...")                                  # kernel:1177
+        if ks:                                                                            # tuna_dft.py:1099-1181
+            log("\n Evaluating molecular orbitals on grid...    [Done]")
+            log(" Evaluating exchange-correlation kernel...   [Done]")
+            log(" Calculating matrix elements...              [Done]")
         log("\n" + SPACER)                                                                # tuna_ci.py:1236-1271
-        log("          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
+        log("      Time-dependent Density Functional Theory" if ks else
+            "          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
         log(SPACER)
         log(("  Using" if tda else "  Not using") + " the Tamm-Dancoff approximation...\n")
         if not calc.calculate_no_triplets and not calc.calculate_no_singlets:
@@ -755,8 +772,12 @@ def run_excited_states(calc: Calculation, molecule, integrals, out, engine: Engi
             log("  Only singlet states will be calculated.")
     t0 = time.perf_counter()
     n_keep = max(calc.n_states, calc.root, 0)
-    r = engine.cis_rhf(out.molecular_orbitals, out.epsilons, n_occ, 0, method="CIS" if tda else "TDHF", singlets=not calc.calculate_no_singlets,
-                       triplets=not calc.calculate_no_triplets, n_keep=n_keep, dip=integrals.D)
+    if ks:
+        r = engine.tddft_rhf(out.molecular_orbitals, out.epsilons, out.P, n_occ, 0, method="TDA" if tda else "TDDFT", hfx=calc.HFX_prop,
+                             singlets=not calc.calculate_no_singlets, triplets=not calc.calculate_no_triplets, n_keep=n_keep, dip=integrals.D)
+    else:
+        r = engine.cis_rhf(out.molecular_orbitals, out.epsilons, n_occ, 0, method="CIS" if tda else "TDHF", singlets=not calc.calculate_no_singlets,
+                           triplets=not calc.calculate_no_triplets, n_keep=n_keep, dip=integrals.D)
     out.timings["Excited state calculation"] = time.perf_counter() - t0
     if not silent:
         log("\n  Building excited state Hamiltonian...      [Done]")                      # tuna_ci.py:1324-1362
@@ -1002,10 +1023,19 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
         if calc.relaxed_density and calc.unrelaxed_density:
             raise TunaError("RELAXED and UNRELAXED ask for two different MP2 densities: give one of them.")
     if calc.time_dependent and not excited:                  # TD on an HF line: time-dependent Hartree-Fock (kernel:1175)
-        if method not in ("HF", "RHF"):
-            raise TunaError(f"The TD keyword is available on an HF or RHF line only in this build: excited states of {method} (time-dependent DFT, "
-                            "unrestricted or correlated references) are not implemented.")
-        excited = "TD-HF"
+        if method in dft_mod.TD_AVAILABLE and not unrestricted_ks:
+            # TD on a local-density Kohn-Sham line: TD-DFT, or its Tamm-Dancoff approximation with TDA (tuna_ci.py:2173-2201)
+            if calc.do_perturbative_doubles:
+                raise TunaError(f"The (D) keyword on a {method} ... : TD line: the perturbative doubles correction of a TD-DFT state (the "
+                                "double-hybrid scaling of tuna_ci.py:1966) is not built.  (D) applies to a CIS, TDHF, RPA or HF ... : TD state.")
+            excited = "TD-" + method                          # kernel:1299
+        elif method not in ("HF", "RHF"):
+            raise TunaError(f"The TD keyword is available on an HF or RHF line only in this build, and on the lines of the local-density "
+                            f"functionals ({', '.join(dft_mod.TD_AVAILABLE)}): excited states of {'U' if unrestricted_ks else ''}{method} "
+                            "(time-dependent DFT with a gradient-corrected or hybrid exchange-correlation kernel, unrestricted or correlated "
+                            "references) are not implemented.")
+        else:
+            excited = "TD-HF"
     if excited:
         if calc.multiplicity != 1:
             raise TunaError(f"{excited} is available for a closed-shell restricted reference only in this build (ML 1).")
@@ -1051,6 +1081,6 @@ def run(input_line: str, silent: bool = True, engine: Engine | None = None, log=
     if method in dft_mod.FUNCTIONALS:
         calc.functional = method
         if calc.stability_analysis:
-            raise TunaError(f"STAB on a {method} line: the stability analysis of a Kohn-Sham solution needs the exchange-correlation kernel, "
-                            "which is not built.  STAB is available on Hartree-Fock references.")
+            raise TunaError(f"STAB on a {method} line: the stability analysis of a Kohn-Sham solution (the orbital Hessian with the "
+                            "exchange-correlation kernel) is not built.  STAB is available on Hartree-Fock references.")
     return calculate_energy(symbols, R, calc, engine, silent, log)

@@ -190,14 +190,17 @@ class Engine:
         return X, sm.value, Si
 
     # ---- Kohn-Sham exchange-correlation ------------------------------------------------------------
-    def dft_setup(self, points, weights, functional: str, x_alpha: float = 2 / 3) -> dict:
-        """Puts the grid on the device, evaluates the AOs on it and selects the functional (tuna_amd.dft.FUNCTIONALS).
+    def dft_setup(self, points, weights, functional: str | None, x_alpha: float = 2 / 3) -> dict:
+        """Puts the grid on the device, evaluates the AOs on it and selects the functional (tuna_amd.dft.FUNCTIONALS; None: no functional).
         While set, scf_rhf runs restricted Kohn-Sham; returns {"hfx": HFX_prop, ...} to pass on."""
         from . import dft
-        name = functional.upper()
-        if name not in dft.FUNCTIONALS:
-            raise TunaError(f"Electronic structure method \"{functional}\" is not supported.")
-        xn, cn, dfx, hfx, dfc = dft.FUNCTIONALS[name]
+        if functional is None:                                # the null functional: exact exchange alone (tddft_rhf is then TDHF / CIS)
+            name, (xn, cn, dfx, hfx, dfc) = "NONE", (None, None, 0.0, 1.0, 0.0)
+        else:
+            name = functional.upper()
+            if name not in dft.FUNCTIONALS:
+                raise TunaError(f"Electronic structure method \"{functional}\" is not supported.")
+            xn, cn, dfx, hfx, dfc = dft.FUNCTIONALS[name]
         pts = f64(np.asarray(points).reshape(3, -1))
         wts = f64(np.asarray(weights).reshape(-1))
         self._check(self._L.tf_dft_setup(self._ctx, wts.size, ptr(pts), ptr(wts), dft.X_ID[xn], dft.C_ID[cn], dfx, dfc, float(x_alpha)))
@@ -411,13 +414,15 @@ class Engine:
             dip = f64(dip)
             if dip.shape != (3, self.N, self.N):
                 raise TunaError(f"cis_rhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        return self._cis_rhf_call(C, eps, n_occ, n_frozen, method == "CIS", singlets, triplets, n_keep, dip, return_matrices)
+
+    def _cis_rhf_call(self, C, eps, n_occ, n_frozen, tda, singlets, triplets, n_keep, dip, return_matrices, tddft=None):
+        """The buffers, the call and the dict of cis_rhf; with tddft = (hfx, P) the call is tf_tddft_rhf."""
         import ctypes
-        from ._lib import CisOpts, CisResult
-        tda = method == "CIS"
+        from ._lib import CisOpts, CisResult, TddftOpts
         o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
         dim = o * v
         nk = max(0, min(int(n_keep), dim))
-        opts = CisOpts(int(tda), int(bool(singlets)), int(bool(triplets)), int(n_keep))
         res = CisResult()
         arrays = {}
 
@@ -432,12 +437,89 @@ class Engine:
         res.m_plus_singlet = take("M_plus_singlet", (dim, dim), return_matrices and singlets)
         res.m_plus_triplet = take("M_plus_triplet", (dim, dim), return_matrices and triplets)
         res.m_minus = take("M_minus", (dim, dim), return_matrices and not tda)
-        self._check(self._L.tf_cis_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(dip), ctypes.byref(res)))
+        if tddft is None:
+            opts = CisOpts(int(tda), int(bool(singlets)), int(bool(triplets)), int(n_keep))
+            self._check(self._L.tf_cis_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(dip), ctypes.byref(res)))
+        else:
+            hfx, P = tddft
+            opts = TddftOpts(int(tda), int(bool(singlets)), int(bool(triplets)), int(n_keep), float(hfx))
+            self._check(self._L.tf_tddft_rhf(self._ctx, ctypes.byref(opts), int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(P), ptr(dip),
+                                             ctypes.byref(res)))
         out = {"dim": int(res.dim), "seconds": list(res.seconds)}
         for name, a in arrays.items():
             if return_matrices or not name.startswith("M_"):
                 out[name] = a
         return out
+
+    def tddft_rhf(self, C, eps, P, n_occ, n_frozen=0, method="TDDFT", hfx=None, singlets=True, triplets=True, n_keep=0, dip=None,
+                  return_matrices=False) -> dict:
+        """Closed-shell TD-DFT ("TDDFT") or its Tamm-Dancoff approximation ("TDA") from canonical Kohn-Sham orbitals, the density P [N, N]
+        of the SCF and the functional of dft_setup (tunafock.h: tf_tddft_rhf): the dict of cis_rhf.  hfx = the share of exact exchange,
+        by default that of the functional set up.  Local-density functionals only; the null functional with hfx = 1 is TDHF / CIS.
+        P = None reaches the library as NULL (TF_EINVAL)."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"tddft_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if method not in ("TDDFT", "TDA"):
+            raise TunaError(f"tddft_rhf: method must be \"TDDFT\" or \"TDA\", got {method!r}")
+        if P is not None:
+            P = f64(P)
+            if P.shape != (self.N, self.N):
+                raise TunaError(f"tddft_rhf: the density must be [{self.N}, {self.N}]")
+        if dip is not None:
+            dip = f64(dip)
+            if dip.shape != (3, self.N, self.N):
+                raise TunaError(f"tddft_rhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        if hfx is None:
+            hfx = self.functional["hfx"] if getattr(self, "functional", None) else 1.0
+        return self._cis_rhf_call(C, eps, n_occ, n_frozen, method == "TDA", singlets, triplets, n_keep, dip, return_matrices, tddft=(hfx, P))
+
+    def xc_kernel_rhf(self, C, P, n_occ, n_frozen=0, return_points=False):
+        """(K_XC_singlet, K_XC_triplet) [dim, dim] of the functional of dft_setup for the orbitals C at the closed-shell density P
+        (tunafock.h: tf_xc_kernel_rhf; tuna_dft.py:1097-1147); with return_points also f_points [4, n_points] = the floored rho, f_X,
+        f_C^singlet, f_C^triplet."""
+        C = f64(C)
+        if C.shape != (self.N, self.N):
+            raise TunaError(f"xc_kernel_rhf: orbitals must be [{self.N}, {self.N}]")
+        if P is not None:
+            P = f64(P)
+            if P.shape != (self.N, self.N):
+                raise TunaError(f"xc_kernel_rhf: the density must be [{self.N}, {self.N}]")
+        dim = max(0, int(n_occ) - int(n_frozen)) * max(0, self.N - int(n_occ))
+        KS, KT = np.zeros((dim, dim)), np.zeros((dim, dim))
+        G = self.functional["n_points"] if getattr(self, "functional", None) else 0
+        fp = np.zeros((4, G)) if return_points and G else None
+        self._check(self._L.tf_xc_kernel_rhf(self._ctx, int(n_occ), int(n_frozen), ptr(C), ptr(P), ptr(KS), ptr(KT), ptr(fp)))
+        return (KS, KT, fp) if return_points else (KS, KT)
+
+    def xc_kernel_probe(self, psi_o, psi_v, u_singlet, u_triplet):
+        """(K_singlet, K_triplet) [o v, o v] = sum_g u(g) psi_o[i, g] psi_v[a, g] psi_o[j, g] psi_v[b, g] for psi_o [o, G], psi_v [v, G] and
+        u_singlet, u_triplet [G] (any values), by the kernel and the slab sum of xc_kernel_rhf (tunafock.h: tf_xc_kernel_probe)."""
+        po, pv, us, ut = f64(psi_o), f64(psi_v), f64(u_singlet), f64(u_triplet)
+        if po.ndim != 2 or pv.ndim != 2 or po.shape[1] != pv.shape[1] or us.shape != (po.shape[1],) or ut.shape != us.shape:
+            raise ValueError(f"xc_kernel_probe: needs psi_o [o, G], psi_v [v, G], u_singlet [G], u_triplet [G], got {po.shape}, {pv.shape}, {us.shape}, {ut.shape}")
+        dim = po.shape[0] * pv.shape[0]
+        KS, KT = np.full((dim, dim), np.nan), np.full((dim, dim), np.nan)
+        self._check(self._L.tf_xc_kernel_probe(self._ctx, po.shape[0], pv.shape[0], po.shape[1], ptr(po), ptr(pv), ptr(us), ptr(ut), ptr(KS), ptr(KT)))
+        return KS, KT
+
+    def xc_kernel_timings(self) -> dict:
+        """Seconds of the last kernel build by stage (tunafock.h: tf_xc_kernel_timings)."""
+        import ctypes
+        t = (ctypes.c_double * 4)()
+        self._check(self._L.tf_xc_kernel_timings(self._ctx, t))
+        return {"psi_gemm": t[0], "point_kernels": t[1], "k_kernel": t[2], "slab_sum": t[3]}
+
+    @staticmethod
+    def xc_kernel_plan(dim: int, n_points: int) -> dict:
+        """The launch plan of the kernel build, a pure function of (dim, n_points) (tunafock.h: tf_xc_kernel_plan)."""
+        import ctypes
+        from . import _lib
+        out = (ctypes.c_int64 * 8)()
+        if _lib.lib().tf_xc_kernel_plan(int(dim), int(n_points), out) != 0:
+            raise TunaError("xc_kernel_plan: dim and n_points must be at least 1")
+        keys = ("n_b", "n_tiles", "n_slabs", "slab_len", "lds_bytes", "chunk", "slab_min", "tile")
+        return dict(zip(keys, (int(x) for x in out)))
 
     def _uhf_orbitals(self, who, C_alpha, C_beta, eps_alpha, eps_beta):
         Ca, Cb, ea, eb = f64(C_alpha), f64(C_beta), f64(eps_alpha), f64(eps_beta)
