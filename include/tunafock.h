@@ -506,7 +506,9 @@ int tf_xc_kernel_probe(tf_ctx *ctx, int n_o, int n_v, int64_t n_points, const do
  * c_functional >= 3: the message names it).  TF_ENOMEM with the size in the message. */
 int tf_xc_kernel_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *P, double *K_singlet, double *K_triplet, double *f_points);
 /* Seconds of the last kernel build of the context by stage: {psi GEMM, density and point kernels, K kernel, slab sum}
- * (tf_xc_kernel_probe: the last two). */
+ * (tf_xc_kernel_probe and tf_xc_kernel_spin_probe: the last two).  The spin-blocked build (tf_xc_kernel_uhf, tf_tddft_uhf,
+ * tf_stability_uks) reports its stages in the same slots: both psi GEMMs, both densities and the spin-resolved point kernels, the
+ * spin-blocked K kernel, its slab sum. */
 int tf_xc_kernel_timings(tf_ctx *ctx, double out[4]);
 
 typedef struct {
@@ -604,6 +606,71 @@ typedef struct {
 int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, tf_stability_result *out);
 int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
                      const double *C_beta, const double *eps_alpha, const double *eps_beta, tf_stability_result *out);
+
+/* ---- unrestricted TD-DFT / TDA and the Kohn-Sham stability analysis for the local-density functionals: replaces
+ * calculate_unrestricted_exchange_correlation_kernel_matrices (tuna_dft.py:1194-1281), the "UHF" branches of calculate_A_matrix /
+ * calculate_B_matrix with K_XC (tuna_ci.py:719-845) and determine_self_consistent_field_stability with K_XC_singlet / K_XC_triplet /
+ * K_XC (tuna_ci.py:1049-1106) ---- */
+
+/* The launch plan of the spin-blocked kernel build for d_alpha = o_a v_a, d_beta = o_b v_b and n_points grid points, a pure function of
+ * the three (no context, no device): out = {64-wide blocks of the alpha part, of the beta part, tiles, slabs, slab length, LDS bytes of a
+ * workgroup, doubles of the slab partials [slabs][dim][dim], columns of a tile (its rows are 64)}.  Blocks are cut per spin:
+ * the last alpha block is padded, not continued into beta; a tile is one row block times one column block (the default) or two adjacent
+ * column blocks of one spin (tf_xc_kernel_spin_cols), so every tile has one pair of spins and one weight vector, and the tiles listed are
+ * those that hold an element with row <= column (64 x 64: n (n + 1) / 2 of n blocks); an empty spin block has no block.  The slab cut is tf_xc_kernel_plan's rule on this tile count.  TF_EINVAL on a negative d, d_alpha + d_beta < 1 or
+ * n_points < 1. */
+int tf_xc_kernel_spin_plan(int64_t d_alpha, int64_t d_beta, int64_t n_points, int64_t out[8]);
+/* The tile shape of the spin-blocked kernel build of this context (instrumentation: tools/gpu_utddft_timing.py measures both): cols = 1
+ * for 64 x 64 tiles, 2 for 64 x 128 tiles (two adjacent column blocks of one spin per workgroup), 0 for the library's default, the shape
+ * tf_xc_kernel_spin_plan describes.  Either shape gives the same bits.  TF_EINVAL on any other value. */
+int tf_xc_kernel_spin_cols(tf_ctx *ctx, int cols);
+/* The spin-blocked matrix-core kernel and its slab sum on their own (instrumentation, tests): host psi_oa [o_a][n_points],
+ * psi_va [v_a][n_points], psi_ob, psi_vb likewise, u_aa, u_ab, u_bb [n_points] (any values), and K host [dim][dim], dim = o_a v_a + o_b v_b,
+ *   K[p][q] = sum_g u_st(g) psi_o^s[i][g] psi_v^s[a][g] psi_o^t[j][g] psi_v^t[b][g],   p = (ia) of spin s, q = (jb) of spin t,
+ * in the compound index of tf_cis_uhf (the alpha block first).  The beta-alpha rectangle is the transpose of the alpha-beta one and is
+ * never computed.  Runs the very routine tf_xc_kernel_uhf, tf_tddft_uhf and tf_stability_uks call.  Needs no basis, tensor or grid.  An
+ * empty spin (o_s v_s = 0) has no tile and its pointers may be NULL.  K is symmetric to the last bit, and two calls give the same bits: no
+ * atomics, slab partials added in slab order.  TF_EINVAL (the context stays usable) on a negative size, n_points < 1, dim = 0 or a NULL
+ * pointer that is needed; TF_ENOMEM with the size in the message. */
+int tf_xc_kernel_spin_probe(tf_ctx *ctx, int o_a, int v_a, int o_b, int v_b, int64_t n_points, const double *psi_oa, const double *psi_va,
+                            const double *psi_ob, const double *psi_vb, const double *u_aa, const double *u_ab, const double *u_bb, double *K);
+/* K_XC [dim][dim] (host) of the grid's functional for the orbitals C_alpha, C_beta, windows and index order as tf_cis_uhf, at the spin
+ * densities P_alpha, P_beta [N,N]: rho_alpha, rho_beta through the path of tf_dft_vxc_unrestricted, floored at 1e-23 each, n their sum,
+ *   f_X,ss = 2 f_X(2 rho_s) (the bare Slater function, tuna_xc.py:5956-5983),  f_C,aa / ab / bb the second derivatives of n e_C
+ *   (VWN3: tuna_xc.py:6072-6140; VWN5: :6308-6438; zeta clipped to [-1, 1], 1 +- zeta floored at 1e-23 in f''(zeta) only),
+ *   u_ss = w (DFX f_X,ss + DFC f_C,ss),  u_ab = w DFC f_C,ab,  psi_s = Phi C_s over the two windows (one GEMM per spin), then the kernel
+ * of tf_xc_kernel_spin_probe.  f_points (may be NULL): [7][n_points] = rho_alpha, rho_beta, f_X,aa, f_X,bb, f_C,aa, f_C,ab, f_C,bb.
+ * TF_EINVAL (the context stays usable) as tf_cis_uhf's windows (dim = 0 included) and tf_xc_kernel_rhf's grid and functional checks, on
+ * a NULL C, P or K, or with world > 1.  TF_ENOMEM with the size in the message.  tf_xc_kernel_timings reports its stages. */
+int tf_xc_kernel_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+                     const double *P_alpha, const double *P_beta, double *K, double *f_points);
+
+typedef struct {
+    int32_t tda;                /* 1 = TDA (the matrix A alone), 0 = full TD-DFT */
+    int32_t n_keep;             /* as tf_ucis_opts */
+    double hfx;                 /* HFX_prop: the share of exact exchange (1 with the null functional = TDHF, 0 for the pure functionals) */
+} tf_utddft_opts;
+
+/* Spin-conserving TD-DFT / TDA from canonical unrestricted Kohn-Sham orbitals: tf_cis_uhf with, G = (ia s|jb t), H = (ij|ab), X = (ib|ja),
+ *     A = d_st (Delta - hfx H) + G + K,    A + B = d_st (Delta - hfx H - hfx X) + 2 G + 2 K,    A - B = d_st (Delta - hfx H + hfx X),
+ * K of tf_xc_kernel_uhf at the densities P_alpha, P_beta, added after the symmetrisation (it is symmetric to the last bit).  With hfx = 0
+ * the two (ab|ij) blocks are neither built nor read.  With the null functional no kernel is built, and with hfx = 1 every output equals
+ * tf_cis_uhf's bit for bit.  The solve stages, the transition moments and the rule "A +- B not positive definite: TF_ELINALG" are
+ * tf_cis_uhf's own code.  seconds as tf_cis_uhf; the kernel build is counted in the assembly slot [2].
+ * TF_EINVAL as tf_cis_uhf and tf_xc_kernel_uhf together (hfx not finite included).  TF_ENOMEM with the size in the message. */
+int tf_tddft_uhf(tf_ctx *ctx, const tf_utddft_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+                 const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *P_alpha, const double *P_beta, const double *dip,
+                 tf_ucis_result *out);
+
+/* The stability analysis of a Kohn-Sham solution: tf_stability_rhf / tf_stability_uhf with the exchange blocks scaled by hfx ((ab|ij) not
+ * built when hfx = 0) and the kernel in A + B -- restricted: 2 K_S in the singlet and 2 K_T in the triplet matrix (tf_xc_kernel_rhf at the
+ * density P); unrestricted: 2 K (tf_xc_kernel_uhf at P_alpha, P_beta).  A - B carries no kernel.  With the null functional and hfx = 1 the
+ * results equal the Hartree-Fock routines'.  An unstable solution is a result, not an error.
+ * TF_EINVAL as the Hartree-Fock routine and the kernel build together (hfx not finite included).  TF_ENOMEM with the size in the message. */
+int tf_stability_rks(tf_ctx *ctx, double hfx, int n_occ, int n_frozen, const double *C, const double *eps, const double *P, tf_stability_result *out);
+int tf_stability_uks(tf_ctx *ctx, double hfx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+                     const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *P_alpha, const double *P_beta,
+                     tf_stability_result *out);
 
 /* ---- CIS(D): replaces calculate_restricted_doubles_correction (tuna_ci.py:1874-1982), the perturbative doubles correction of
  * Head-Gordon, Rico, Oumi and Lee to closed-shell CIS / TDHF states ---- */

@@ -79,6 +79,10 @@ class UcisOpts(C.Structure):                              # tf_ucis_opts
     _fields_ = [("tda", C.c_int32), ("n_keep", C.c_int32)]
 
 
+class UtddftOpts(C.Structure):                            # tf_utddft_opts
+    _fields_ = [("tda", C.c_int32), ("n_keep", C.c_int32), ("hfx", C.c_double)]
+
+
 class UcisResult(C.Structure):                            # tf_ucis_result
     _fields_ = [("dim", C.c_int32), ("dim_alpha", C.c_int32), ("e", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("tdm", C.c_void_p),
                 ("osc", C.c_void_p), ("m_plus", C.c_void_p), ("m_minus", C.c_void_p), ("seconds", C.c_double * 4)]
@@ -108,7 +112,8 @@ EXPORTS = ["tf_create", "tf_destroy", "tf_last_error", "tf_version", "tf_normali
            "tf_copy_eri", "tf_sample_eri", "tf_eri_element", "tf_fock_jk", "tf_fock_jk_device", "tf_scf_rhf", "tf_scf_uhf",
            "tf_orthogonaliser", "tf_eri_timings", "tf_eri_counts", "tf_eri_build_stats", "tf_shard_plan", "tf_jk_profile",
            "tf_jk_profile_read", "tf_diagonalise", "tf_eigh_probe", "tf_eigh_stats", "tf_jk_path_stats", "tf_ao_to_mo", "tf_mp2_rhf", "tf_mp2_uhf", "tf_mp3_rhf", "tf_mp4_rhf", "tf_mp3_ladder_probe", "tf_ccd_rhf", "tf_ccsd_rhf", "tf_triples_rhf", "tf_cis_rhf", "tf_cis_uhf", "tf_stability_rhf", "tf_stability_uhf", "tf_cis_d_rhf", "tf_mp2_density_rhf", "tf_natural_orbitals", "tf_dft_setup", "tf_dft_vxc", "tf_dft_vxc_unrestricted", "tf_scf_uks",
-           "tf_dft_clear", "tf_xc_kernel_plan", "tf_xc_kernel_probe", "tf_xc_kernel_rhf", "tf_xc_kernel_timings", "tf_tddft_rhf", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
+           "tf_dft_clear", "tf_xc_kernel_plan", "tf_xc_kernel_probe", "tf_xc_kernel_rhf", "tf_xc_kernel_timings", "tf_tddft_rhf", "tf_xc_kernel_spin_plan", "tf_xc_kernel_spin_cols", "tf_xc_kernel_spin_probe",
+           "tf_xc_kernel_uhf", "tf_tddft_uhf", "tf_stability_rks", "tf_stability_uks", "tf_set_eri_layout", "tf_eri_layout", "tf_shard_plan_pairs", "tf_packed_pad", "tf_eri_flops", "tf_segment_pad", "tf_set_allreduce", "tf_scf_rhf_batch",
            "tf_comm_unique_id", "tf_comm_init", "tf_comm_destroy", "tf_comm_attached"]
 
 _lib = None
@@ -198,6 +203,13 @@ def lib():
     L.tf_xc_kernel_probe.restype = ci; L.tf_xc_kernel_probe.argtypes = [vp, ci, ci, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.tf_xc_kernel_rhf.restype = ci; L.tf_xc_kernel_rhf.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
     L.tf_xc_kernel_timings.restype = ci; L.tf_xc_kernel_timings.argtypes = [vp, dp]
+    L.tf_xc_kernel_spin_plan.restype = ci; L.tf_xc_kernel_spin_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, lp]
+    L.tf_xc_kernel_spin_cols.restype = ci; L.tf_xc_kernel_spin_cols.argtypes = [vp, ci]
+    L.tf_xc_kernel_spin_probe.restype = ci; L.tf_xc_kernel_spin_probe.argtypes = [vp, ci, ci, ci, ci, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tf_xc_kernel_uhf.restype = ci; L.tf_xc_kernel_uhf.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.tf_tddft_uhf.restype = ci; L.tf_tddft_uhf.argtypes = [vp, C.POINTER(UtddftOpts), ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, C.POINTER(UcisResult)]
+    L.tf_stability_rks.restype = ci; L.tf_stability_rks.argtypes = [vp, C.c_double, ci, ci, vp, vp, vp, C.POINTER(StabilityResult)]
+    L.tf_stability_uks.restype = ci; L.tf_stability_uks.argtypes = [vp, C.c_double, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, C.POINTER(StabilityResult)]
     L.tf_tddft_rhf.restype = ci; L.tf_tddft_rhf.argtypes = [vp, C.POINTER(TddftOpts), ci, ci, vp, vp, vp, vp, C.POINTER(CisResult)]
     L.tf_eigh_probe.restype = ci; L.tf_eigh_probe.argtypes = [vp, ci, ci, ci, dp]
     L.tf_eigh_stats.restype = ci; L.tf_eigh_stats.argtypes = [vp, C.POINTER(C.c_int64)]

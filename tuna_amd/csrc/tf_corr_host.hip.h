@@ -1821,8 +1821,9 @@ static int ucis_begin(tf_ctx *ctx, const char *who, bool pointers_ok, int n_alph
 }
 
 // The five MO blocks of tfucis::uassemble_kernel through the general transformation, on every layout (mem's): per spin with d_s > 0
-// (ia|jb) and (ab|ij), the latter transposed to [i][j][a][b]; (ia alpha|jb beta) when both spins have excitations
-static int ucis_mo_blocks(tf_ctx *ctx, const char *who, const UcisSetup &U, DeviceBlocks &mem, tfucis::AssembleArgs &A)
+// (ia|jb) and -- with_H -- (ab|ij), the latter transposed to [i][j][a][b]; (ia alpha|jb beta) when both spins have excitations.  Without
+// exact exchange (with_H false) the two (ab|ij) blocks are neither built nor read.
+static int ucis_mo_blocks(tf_ctx *ctx, const char *who, const UcisSetup &U, DeviceBlocks &mem, tfucis::AssembleArgs &A, bool with_H = true)
 {
     int rc;
     for (int s = 0; s < 2; ++s) {
@@ -1831,6 +1832,8 @@ static int ucis_mo_blocks(tf_ctx *ctx, const char *who, const UcisSetup &U, Devi
         const int o = S.o, v = S.v;
         double *g = nullptr;
         if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g, nullptr))) return rc;
+        A.s[s].g = g;
+        if (!with_H) continue;
         double *g2 = mem.alloc((size_t)v * v * o * o), *Ht = g2 ? mem.alloc((size_t)v * v * o * o) : nullptr;
         if (!Ht) {
             char text[200];
@@ -1843,7 +1846,7 @@ static int ucis_mo_blocks(tf_ctx *ctx, const char *who, const UcisSetup &U, Devi
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
             return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the transposition of (ab|ij) failed on the device");
         mem.release(g2);
-        A.s[s].g = g; A.s[s].Ht = Ht;
+        A.s[s].Ht = Ht;
     }
     if (U.d[0] > 0 && U.d[1] > 0) {
         double *g = nullptr;
@@ -1880,15 +1883,27 @@ static int ucis_assemble(tf_ctx *ctx, const char *who, const UcisSetup &U, Devic
 // blocks; every matrix of the call assembled in one pass, after which the blocks are freed; then the solve stages of tf_cis_rhf on the
 // spin-blocked matrices (CIS: one dsyevd; TDHF: dpotrf of A - B, two dtrmm, dsyevd, dtrmm, and dtrsm for the kept states); the
 // transition moments with D_ia of both spins side by side in the compound index, without the sqrt(2) of the restricted singlets.
-int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
-               const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *dip, tf_ucis_result *out)
+// tf_tddft_uhf is the same driver with xc set: the exchange blocks scaled by hfx (the two (ab|ij) not built when hfx = 0) and, unless the
+// grid's functional is the null one, the spin-blocked K of xc_kernel_spin_build added in the assembly pass (counted in the assembly slot).
+struct __attribute__((visibility("hidden"))) UcisXc { double hfx = 1.0; const double *Pa = nullptr, *Pb = nullptr; };
+
+static int xc_kernel_spin_build(tf_ctx *ctx, const char *who, const UcisSetup &U, const double *Pa, const double *Pb, DeviceBlocks &mem, double **pK,
+                                double *f_points);
+static int xc_kernel_spin_checks(tf_ctx *ctx, const char *who, const UcisXc &xc);
+
+static int ucis_driver(tf_ctx *ctx, const char *who, const tf_ucis_opts *opts, const UcisXc *xc, int n_alpha, int n_beta, int n_frozen_alpha,
+                       int n_frozen_beta, const double *C_alpha, const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *dip,
+                       tf_ucis_result *out)
 {
-    static const char *who = "tf_cis_uhf";
+    const std::string me = who;
     UcisSetup U;
     int rc = ucis_begin(ctx, who, opts && C_alpha && C_beta && eps_alpha && eps_beta && out, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, U);
     if (rc) return rc;
-    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "tf_cis_uhf: n_keep must not be negative");
-    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "tf_cis_uhf: transition dipoles and oscillator strengths need the AO dipole matrices (dip)");
+    if (opts->n_keep < 0) TF_FAIL(ctx, TF_EINVAL, "%s: n_keep must not be negative", who);
+    if ((out->tdm || out->osc) && !dip) TF_FAIL(ctx, TF_EINVAL, "%s: transition dipoles and oscillator strengths need the AO dipole matrices (dip)", who);
+    if (xc && (rc = xc_kernel_spin_checks(ctx, who, *xc))) return rc;
+    const double hfx = xc ? xc->hfx : 1.0;
+    const bool with_k = xc && (ctx->grid.xid != 0 || ctx->grid.cid != 0);
     const int N = U.N, dim = U.dim, nk = std::min(opts->n_keep, dim);
     const size_t B2 = (size_t)dim * dim;
     const bool tda = opts->tda != 0, moments = dip && (out->tdm || out->osc);
@@ -1896,8 +1911,11 @@ int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, i
     DeviceBlocks mem;
     auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
     tfucis::AssembleArgs A{};
-    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A))) return rc;
+    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A, hfx != 0.0))) return rc;
     const auto t1 = corr_stamp();
+    // ---- the exchange-correlation kernel matrix (TD-DFT)
+    double *K = nullptr;
+    if (with_k && (rc = xc_kernel_spin_build(ctx, who, U, xc->Pa, xc->Pb, mem, &K, nullptr))) return rc;
     // ---- work space: the matrices (CIS: A; TDHF: A + B and A - B) and the small arrays
     //      w | w2 | e (dsyevd) | stat[2] | eps [2][N] | D_ia [3][dim] | mu [dim][3] | f [dim] | C_o | C_v | D C_v [N][v] (the larger spin) | D [3][N][N]
     const int omax = std::max(U.s[0].o, U.s[1].o), vmax = std::max(U.s[0].v, U.s[1].v);
@@ -1906,7 +1924,7 @@ int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, i
     rocblas_int *d_info = mem.alloc_int(4);
     if (!Mp || (!tda && !Mm) || !small || !d_info) {
         char text[200];
-        snprintf(text, sizeof text, "tf_cis_uhf: out of device memory for %.2f GB of work space (%d arrays of (d_alpha + d_beta)^2 = %d^2 values)",
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space (%d arrays of (d_alpha + d_beta)^2 = %d^2 values)", who,
                  (double)((tda ? 1 : 2) * B2 + nsmall) * sizeof(double) / 1e9, tda ? 1 : 2, dim);
         return fail(TF_ENOMEM, text);
     }
@@ -1916,10 +1934,12 @@ int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, i
     // ---- assembly
     A.kind[0] = tda ? 0 : 1; A.out[0] = Mp; A.n_out = 1;
     if (!tda) { A.kind[1] = 2; A.out[1] = Mm; A.n_out = 2; }
+    A.hfx = hfx; A.K = K; A.kfac[0] = tda ? 1.0 : 2.0;           // A gains K, A + B gains 2 K, A - B nothing
     if ((rc = ucis_assemble(ctx, who, U, mem, A, eps_alpha, eps_beta, d_eps))) return rc;
+    mem.release(K);
     if ((out->m_plus && hipMemcpy(out->m_plus, Mp, B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
         (out->m_minus && Mm && hipMemcpy(out->m_minus, Mm, B2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+        return fail(TF_ENODEVICE, me + ": copy failed");
     const auto t2 = corr_stamp();
     // ---- solves
     CisSolve sv;
@@ -1929,19 +1949,19 @@ int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, i
         size_t bytes = 0;
         if (!cis_tdhf_workspace(sv, mem, &bytes)) {
             char text[200];
-            snprintf(text, sizeof text, "tf_cis_uhf: out of device memory for %.2f GB of work space for the TDHF reduction", (double)bytes / 1e9);
+            snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space for the TDHF reduction", who, (double)bytes / 1e9);
             return fail(TF_ENOMEM, text);
         }
     }
     BlasAtomicsOff no_atomics(sv.blas);                       // no atomics in the products: split-K sums would change from run to run
     if (moments) {
-        if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+        if (hipMemcpy(d_dip, dip, 3 * (size_t)N * N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, me + ": copy failed");
         for (int s = 0; s < 2; ++s) {
             if (U.d[s] == 0) continue;
             const CorrSetup &S = U.s[s];
             if (hipMemcpy(d_Co, S.Co.data(), (size_t)N * S.o * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(d_Cv, S.Cv.data(), (size_t)N * S.v * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-                return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+                return fail(TF_ENODEVICE, me + ": copy failed");
             if ((rc = cis_dipole_block(sv, N, S.o, S.v, d_dip, d_Co, d_Cv, d_T1, d_Dia, s ? (size_t)U.d[0] : 0))) return rc;
         }
     }
@@ -1951,18 +1971,235 @@ int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, i
         if ((rc = cis_tdhf_factor(sv, Mm, ""))) return rc;
         if ((rc = cis_tdhf_solve(sv, Mm, Mp, "spin-conserving", out->x, out->y))) return rc;
     }
-    if (out->e && hipMemcpy(out->e, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: copy failed");
+    if (out->e && hipMemcpy(out->e, d_w, (size_t)dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(TF_ENODEVICE, me + ": copy failed");
     if (moments) {                                            // mu_n[c] = sum over both spins of D^c_ia V[ia][n]: no sqrt(2)
         const int mrc = cis_transition_moments(sv, tda ? Mp : sv.T, 1.0, d_Dia, d_mu, d_f, out->tdm, out->osc);
-        if (mrc) return fail(mrc, "tf_cis_uhf: the transition moments failed on the device");
+        if (mrc) return fail(mrc, me + ": the transition moments failed on the device");
     }
-    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, "tf_cis_uhf: a kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(TF_ENODEVICE, me + ": a kernel launch failed");
     const auto t3 = corr_stamp();
     out->seconds[0] = corr_secs(t3 - U.t0);
     out->seconds[1] = corr_secs(t1 - U.t0);
     out->seconds[2] = corr_secs(t2 - t1);
     out->seconds[3] = corr_secs(t3 - t2);
     return TF_OK;
+}
+
+int tf_cis_uhf(tf_ctx *ctx, const tf_ucis_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+               const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *dip, tf_ucis_result *out)
+{
+    return ucis_driver(ctx, "tf_cis_uhf", opts, nullptr, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, eps_alpha, eps_beta, dip, out);
+}
+
+// ---- unrestricted TD-DFT / TDA and the Kohn-Sham stability analysis: the spin-blocked kernel matrix (tf_xckernel.hip.h) ------------------
+
+static int xc_kernel_spin_checks(tf_ctx *ctx, const char *who, const UcisXc &xc)
+{
+    const int rc = xc_kernel_checks(ctx, who, xc.Pa && xc.Pb ? xc.Pa : nullptr);
+    if (rc) return rc;
+    if (!std::isfinite(xc.hfx)) TF_FAIL(ctx, TF_EINVAL, "%s: hfx must be finite", who);
+    return TF_OK;
+}
+
+// The production path from psi of both spins to K: the plan, the slab partials (mem's, released here), xck_spin_kernel and
+// xck_spin_sum_kernel on the null stream.  psi[s] [G][o_s + v_s] on the device (not read when d_s = 0), u [3][G] = u_aa, u_ab, u_bb.
+// seconds2: the K kernel, the slab sum (tf_xc_kernel_timings).
+static int xc_kernel_spin_matrices(tf_ctx *ctx, const char *who, long long G, const int o[2], const int v[2], const double *const psi[2], const double *u,
+                                   DeviceBlocks &mem, double *K, double *seconds2)
+{
+    const XckSpinPlan P = xck_spin_plan((long long)o[0] * v[0], (long long)o[1] * v[1], G, ctx->xck_spin_cols ? ctx->xck_spin_cols : XCK_SPIN_COLS);
+    if (P.lds_bytes > XCK_LDS_LIMIT) return corr_fail(ctx, TF_EINVAL, std::string(who) + ": the kernel build's LDS carve-out exceeds the workgroup's");
+    double *part = mem.alloc(P.partial_doubles);
+    rocblas_int *d_tiles = mem.alloc_int(3 * (size_t)P.n_tiles);
+    if (!part || !d_tiles) {
+        char text[200];
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of slab partials (%d slabs of %lld^2 values)", who,
+                 (double)P.partial_doubles * sizeof(double) / 1e9, P.n_slabs, P.dim);
+        return corr_fail(ctx, TF_ENOMEM, text);
+    }
+    tfxck::SpinArgs A{};
+    for (int s = 0; s < 2; ++s) {
+        A.psi[s] = P.d[s] ? psi[s] : nullptr;
+        A.n[s] = o[s] + v[s]; A.o[s] = o[s]; A.v[s] = v[s]; A.d[s] = (int)P.d[s]; A.n_b[s] = P.n_b[s];
+    }
+    A.u[0] = u; A.u[1] = u + G; A.u[2] = u + 2 * G;
+    A.part = part; A.G = P.G; A.slab_len = P.slab_len; A.dim = (int)P.dim;
+    {
+        std::vector<XckSpinTile> tiles((size_t)P.n_tiles);    // the plan's list: {row block, first column block, column blocks} per tile
+        xck_spin_tiles(P, tiles.data());
+        static_assert(sizeof(XckSpinTile) == 3 * sizeof(rocblas_int), "XckSpinTile is three ints");
+        if (hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(XckSpinTile), hipMemcpyHostToDevice) != hipSuccess)
+            return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+        A.tiles = d_tiles;
+    }
+    const auto t0 = corr_stamp();
+    if (P.cols == 2) hipLaunchKernelGGL(tfxck::xck_spin_kernel<2>, dim3((unsigned)P.n_tiles, (unsigned)P.n_slabs), dim3(XCK_THREADS), 0, 0, A);
+    else hipLaunchKernelGGL(tfxck::xck_spin_kernel<1>, dim3((unsigned)P.n_tiles, (unsigned)P.n_slabs), dim3(XCK_THREADS), 0, 0, A);
+    const auto t1 = corr_stamp();
+    hipLaunchKernelGGL(tfxck::xck_spin_sum_kernel, dim3((unsigned)((P.dim * P.dim + 255) / 256)), dim3(256), 0, 0, part, P.n_slabs, (int)P.dim, K);
+    const auto t2 = corr_stamp();
+    seconds2[0] = corr_secs(t1 - t0); seconds2[1] = corr_secs(t2 - t1);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": the exchange-correlation kernel build failed on the device");
+    mem.release(part); mem.release(d_tiles);
+    return TF_OK;
+}
+
+// K [dim][dim] (mem's) for the windows of U, the spin densities Pa, Pb (host) and the grid's functional; f_points (host, may be null):
+// [7][G] = rho_a, rho_b, f_X,aa, f_X,bb, f_C,aa, f_C,ab, f_C,bb.  ctx->xck_seconds: psi GEMMs, densities + point kernels, K kernel, slab sum.
+static int xc_kernel_spin_build(tf_ctx *ctx, const char *who, const UcisSetup &U, const double *Pa, const double *Pb, DeviceBlocks &mem, double **pK,
+                                double *f_points)
+{
+    double *seconds4 = ctx->xck_seconds;
+    tfdft::Grid &g = ctx->grid;
+    const int N = U.N;
+    const long long G = g.G;
+    const size_t dd = (size_t)U.dim * U.dim, nn = (size_t)N * N;
+    rocblas_handle blas = ctx->scf.blas;
+    std::string msg;
+    int rc = tfdft::ensure_spin(g, msg);
+    if (rc) { ctx->err = std::string(who) + ": " + msg; return rc; }
+    int o[2], v[2], n[2];
+    for (int s = 0; s < 2; ++s) { o[s] = U.d[s] ? U.s[s].o : 0; v[s] = U.d[s] ? U.s[s].v : 0; n[s] = o[s] + v[s]; }
+    const int nmax = std::max(n[0], n[1]);
+    double *K = mem.alloc(dd), *u = mem.alloc(3 * (size_t)G), *psi[2] = {n[0] ? mem.alloc((size_t)G * n[0]) : nullptr, n[1] ? mem.alloc((size_t)G * n[1]) : nullptr},
+           *Cw = mem.alloc((size_t)N * nmax), *fp = f_points ? mem.alloc(7 * (size_t)G) : nullptr;
+    if (!K || !u || (n[0] && !psi[0]) || (n[1] && !psi[1]) || !Cw || (f_points && !fp)) {
+        char text[240];
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space of the exchange-correlation kernel (%d^2 values and "
+                 "%lld x %d orbital values)", who, (double)(dd + (size_t)G * (n[0] + n[1] + 10) + (size_t)N * nmax) * sizeof(double) / 1e9, U.dim, G, n[0] + n[1]);
+        return corr_fail(ctx, TF_ENOMEM, text);
+    }
+    if (hipMemcpy(g.sio, Pa, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(g.sio + nn, Pb, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    BlasAtomicsOff no_atomics(blas);
+    double t_psi = 0.0;
+    // psi_s [G][n_s] = Phi [G][N] [C_o | C_v] of spin s [N][n_s]
+    for (int s = 0; s < 2; ++s) {
+        if (!n[s]) continue;
+        const CorrSetup &S = U.s[s];
+        std::vector<double> hC((size_t)N * n[s]);
+        for (int m = 0; m < N; ++m) {
+            std::copy(S.Co.begin() + (size_t)m * o[s], S.Co.begin() + (size_t)(m + 1) * o[s], hC.begin() + (size_t)m * n[s]);
+            std::copy(S.Cv.begin() + (size_t)m * v[s], S.Cv.begin() + (size_t)(m + 1) * v[s], hC.begin() + (size_t)m * n[s] + o[s]);
+        }
+        if (hipMemcpy(Cw, hC.data(), hC.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+        const auto t0 = corr_stamp();
+        CORR_BLAS(tfmp3::gemm_rm(blas, false, false, (int)G, n[s], N, 1.0, g.phi, N, Cw, n[s], 0.0, psi[s], n[s]));
+        t_psi += corr_secs(corr_stamp() - t0);
+    }
+    const auto t1 = corr_stamp();
+    // rho_a, rho_b through the path of the unrestricted V_XC: B2 = Phi [P_a | P_b], rho_s(g) = <B2_s(g), Phi(g)>; then the point kernels
+    {
+        const double one = 1.0, zero = 0.0;
+        const int N2 = 2 * N;
+        hipLaunchKernelGGL(tfdft::pack2_kernel, dim3((unsigned)((2 * nn + 255) / 256)), dim3(256), 0, 0, g.sio, g.sio + nn, g.sP, N);
+        CORR_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none, N2, (rocblas_int)G, N, &one, g.sP, N2, g.phi, N, &zero, g.sB, N2));
+        hipLaunchKernelGGL(tfdft::xc_density2_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.sB, 0, g.spt);
+        hipLaunchKernelGGL(tfdft::xc_fpoint2_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha, g.spt, g.w,
+                           u, fp);
+    }
+    const auto t2 = corr_stamp();
+    seconds4[0] = t_psi; seconds4[1] = corr_secs(t2 - t1);
+    rc = xc_kernel_spin_matrices(ctx, who, G, o, v, psi, u, mem, K, seconds4 + 2);
+    if (rc) return rc;
+    if (f_points && hipMemcpy(f_points, fp, 7 * (size_t)G * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    mem.release(u); mem.release(psi[0]); mem.release(psi[1]); mem.release(Cw); mem.release(fp);
+    *pK = K;
+    return TF_OK;
+}
+
+int tf_xc_kernel_spin_plan(int64_t d_alpha, int64_t d_beta, int64_t n_points, int64_t out[8])
+{
+    if (d_alpha < 0 || d_beta < 0 || d_alpha + d_beta < 1 || n_points < 1 || !out) return TF_EINVAL;
+    const XckSpinPlan P = xck_spin_plan(d_alpha, d_beta, n_points);
+    out[0] = P.n_b[0]; out[1] = P.n_b[1]; out[2] = P.n_tiles; out[3] = P.n_slabs; out[4] = P.slab_len; out[5] = (int64_t)P.lds_bytes;
+    out[6] = (int64_t)P.partial_doubles; out[7] = XCK_TILE * P.cols;
+    return TF_OK;
+}
+
+int tf_xc_kernel_spin_cols(tf_ctx *ctx, int cols)
+{
+    if (!ctx) return TF_EINVAL;
+    if (cols < 0 || cols > 2) TF_FAIL(ctx, TF_EINVAL, "tf_xc_kernel_spin_cols: cols must be 0 (the default shape), 1 (64 x 64 tiles) or 2 (64 x 128 tiles)");
+    ctx->xck_spin_cols = cols;
+    return TF_OK;
+}
+
+int tf_xc_kernel_spin_probe(tf_ctx *ctx, int o_a, int v_a, int o_b, int v_b, int64_t n_points, const double *psi_oa, const double *psi_va,
+                            const double *psi_ob, const double *psi_vb, const double *u_aa, const double *u_ab, const double *u_bb, double *K)
+{
+    static const char *who = "tf_xc_kernel_spin_probe";
+    if (!ctx) return TF_EINVAL;
+    if (o_a < 0 || v_a < 0 || o_b < 0 || v_b < 0 || n_points < 1 || !u_aa || !u_ab || !u_bb || !K)
+        TF_FAIL(ctx, TF_EINVAL, "%s: bad arguments (needs sizes >= 0, n_points >= 1 and u_aa, u_ab, u_bb, K)", who);
+    const long long da = (long long)o_a * v_a, db = (long long)o_b * v_b, G = n_points;
+    if (da + db == 0) TF_FAIL(ctx, TF_EINVAL, "%s: no element (o v = 0 for both spins): there is nothing to calculate", who);
+    if ((da && (!psi_oa || !psi_va)) || (db && (!psi_ob || !psi_vb))) TF_FAIL(ctx, TF_EINVAL, "%s: bad arguments (a spin with o v > 0 needs its psi_o and psi_v)", who);
+    if (da + db > 2000000LL || (long long)G * ((long long)o_a + v_a + o_b + v_b) > (1LL << 40)) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int o[2] = {da ? o_a : 0, db ? o_b : 0}, v[2] = {da ? v_a : 0, db ? v_b : 0};
+    const double *po[2] = {psi_oa, psi_ob}, *pv[2] = {psi_va, psi_vb};
+    const size_t dd = (size_t)(da + db) * (size_t)(da + db);
+    DeviceBlocks mem;
+    double *psi[2] = {nullptr, nullptr}, *u = mem.alloc(3 * (size_t)G), *Kd = mem.alloc(dd);
+    bool ok = u && Kd;
+    for (int s = 0; s < 2 && ok; ++s)
+        if (o[s]) { psi[s] = mem.alloc((size_t)G * (o[s] + v[s])); ok = psi[s] != nullptr; }
+    if (!ok) TF_FAIL(ctx, TF_ENOMEM, "%s: out of device memory for %.2f GB", who, (double)((size_t)G * (o[0] + v[0] + o[1] + v[1] + 3) + dd) * 8 / 1e9);
+    for (int s = 0; s < 2; ++s) {
+        if (!o[s]) continue;
+        const int n = o[s] + v[s];
+        std::vector<double> h((size_t)G * n);                 // the production operand: psi [G][o + v]
+        for (long long g = 0; g < G; ++g) {
+            for (int i = 0; i < o[s]; ++i) h[(size_t)g * n + i] = po[s][(size_t)i * G + g];
+            for (int a = 0; a < v[s]; ++a) h[(size_t)g * n + o[s] + a] = pv[s][(size_t)a * G + g];
+        }
+        if (hipMemcpy(psi[s], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    }
+    if (hipMemcpy(u, u_aa, (size_t)G * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(u + G, u_ab, (size_t)G * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(u + 2 * G, u_bb, (size_t)G * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    ctx->xck_seconds[0] = ctx->xck_seconds[1] = 0.0;
+    const int rc = xc_kernel_spin_matrices(ctx, who, G, o, v, psi, u, mem, Kd, ctx->xck_seconds + 2);
+    if (rc) return rc;
+    if (hipMemcpy(K, Kd, dd * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    return TF_OK;
+}
+
+int tf_xc_kernel_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+                     const double *P_alpha, const double *P_beta, double *K, double *f_points)
+{
+    static const char *who = "tf_xc_kernel_uhf";
+    UcisSetup U;
+    int rc = ucis_begin(ctx, who, C_alpha && C_beta && K, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, U);
+    if (rc) return rc;
+    UcisXc xc;
+    xc.hfx = 0.0; xc.Pa = P_alpha; xc.Pb = P_beta;
+    if ((rc = xc_kernel_spin_checks(ctx, who, xc))) return rc;
+    DeviceBlocks mem;
+    double *Kd = nullptr;
+    if ((rc = xc_kernel_spin_build(ctx, who, U, P_alpha, P_beta, mem, &Kd, f_points))) return rc;
+    if (hipMemcpy(K, Kd, (size_t)U.dim * U.dim * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
+    return TF_OK;
+}
+
+int tf_tddft_uhf(tf_ctx *ctx, const tf_utddft_opts *opts, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha,
+                 const double *C_beta, const double *eps_alpha, const double *eps_beta, const double *P_alpha, const double *P_beta, const double *dip,
+                 tf_ucis_result *out)
+{
+    tf_ucis_opts uo{};
+    UcisXc xc;
+    if (opts) { uo.tda = opts->tda; uo.n_keep = opts->n_keep; xc.hfx = opts->hfx; }
+    xc.Pa = P_alpha; xc.Pb = P_beta;
+    return ucis_driver(ctx, "tf_tddft_uhf", opts ? &uo : nullptr, &xc, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, eps_alpha, eps_beta,
+                       dip, out);
 }
 
 // The solves of the stability analysis: the eigenvalues of each of the n matrices M[k] (order dim) to spec[k][dim] on the host, and --
@@ -2000,43 +2237,58 @@ static void stability_verdict(int dim, const std::vector<double> &spec, const st
 }
 
 // RHF stability (tuna_ci.py:926-985): tf_cis_rhf's MO blocks and assembly pass with kinds 2, 3, 4, then three dsyevd
-int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, tf_stability_result *out)
+// tf_stability_rks is the same driver with xc set (tuna_ci.py:1049-1106): the exchange blocks scaled by hfx ((ab|ij) not built when
+// hfx = 0), 2 K_S added to the singlet A + B and 2 K_T to the triplet A + B (xc_kernel_build); A - B carries no kernel.
+static int stability_restricted(tf_ctx *ctx, const char *who, const CisXc *xc, int n_occ, int n_frozen, const double *C, const double *eps,
+                                tf_stability_result *out)
 {
-    static const char *who = "tf_stability_rhf";
+    const std::string me = who;
     int rc = corr_args(ctx, who, C && eps && out, " (needs C, eps, out and 0 <= n_frozen < n_occ < N)", n_occ, n_frozen);
     if (rc) return rc;
+    if (xc && (rc = xc_kernel_checks(ctx, who, xc->P))) return rc;
+    if (xc && !std::isfinite(xc->hfx)) TF_FAIL(ctx, TF_EINVAL, "%s: hfx must be finite", who);
+    const double hfx = xc ? xc->hfx : 1.0;
+    const bool with_k = xc && (ctx->grid.xid != 0 || ctx->grid.cid != 0);
     CorrSetup S;
     if ((rc = corr_begin(ctx, who, n_occ, n_frozen, C, S))) return rc;
     const int N = S.N, o = S.o, v = S.v;
     const long long ov = S.ov, B2 = S.B2;
-    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "tf_stability_rhf: dimension overflow");
+    if (ov > 2000000LL || (long long)v * v > 2000000LL) TF_FAIL(ctx, TF_EINVAL, "%s: dimension overflow", who);
     const int dim = (int)ov;
     out->dim = dim; out->dim_alpha = dim; out->n_matrices = 3;
     DeviceBlocks mem;
     auto fail = [&](int code, const std::string &m) { return corr_fail(ctx, code, m); };
     double *g1 = nullptr, *g2 = nullptr, *g3 = nullptr;
-    if ((rc = mp3_mo_blocks(ctx, who, S, mem, &g1, &g2, &g3))) return rc;
-    mem.release(g3);
+    if (hfx == 0.0) {
+        if ((rc = mo_transform_device(ctx, S.Co.data(), o, S.Cv.data(), v, S.Co.data(), o, S.Cv.data(), v, mem, &g1, nullptr))) return rc;
+    } else {
+        if ((rc = mp3_mo_blocks(ctx, who, S, mem, &g1, &g2, &g3))) return rc;
+        mem.release(g3);
+    }
     const auto t1 = corr_stamp();
-    double *Ht = mem.alloc((size_t)B2), *M[3] = {mem.alloc((size_t)B2), mem.alloc((size_t)B2), mem.alloc((size_t)B2)}, *small = mem.alloc(2 * (size_t)dim + N);
+    double *KS = nullptr, *KT = nullptr;
+    if (with_k && (rc = xc_kernel_build(ctx, who, S, xc->P, mem, &KS, &KT, nullptr))) return rc;
+    double *Ht = g2 ? mem.alloc((size_t)B2) : nullptr, *M[3] = {mem.alloc((size_t)B2), mem.alloc((size_t)B2), mem.alloc((size_t)B2)}, *small = mem.alloc(2 * (size_t)dim + N);
     rocblas_int *d_info = mem.alloc_int(4);
-    if (!Ht || !M[0] || !M[1] || !M[2] || !small || !d_info) {
+    if ((g2 && !Ht) || !M[0] || !M[1] || !M[2] || !small || !d_info) {
         char text[200];
-        snprintf(text, sizeof text, "tf_stability_rhf: out of device memory for %.2f GB of work space (4 arrays of (o v)^2 = %lld^2 values)",
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space (4 arrays of (o v)^2 = %lld^2 values)", who,
                  (double)(4 * (size_t)B2 + 2 * (size_t)dim + N) * sizeof(double) / 1e9, ov);
         return fail(TF_ENOMEM, text);
     }
     double *d_w = small, *d_e = d_w + dim, *d_eps = d_e + dim;
-    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, "tf_stability_rhf: copy failed");
-    tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
+    if (hipMemcpy(d_eps, eps, (size_t)N * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(TF_ENODEVICE, me + ": copy failed");
+    if (g2) tfcis::launch_transpose(g2, (long long)v * v, (long long)o * o, Ht, 0);
     {
         tfcis::AssembleArgs A{};
         A.g1 = g1; A.Ht = Ht; A.eps = d_eps; A.n_frozen = n_frozen; A.n_occ = n_occ; A.o = o; A.v = v; A.n_out = 3;
         for (int k = 0; k < 3; ++k) { A.kind[k] = 2 + k; A.out[k] = M[k]; }
+        A.hfx = hfx;
+        A.K[0] = KS; A.kfac[0] = 2.0; A.K[1] = KT; A.kfac[1] = 2.0;     // A + B gains 2 K, A - B nothing
         tfcis::launch_assemble(A, 0);
     }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, "tf_stability_rhf: the assembly kernels failed on the device");
-    mem.release(g1); mem.release(g2); mem.release(Ht);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TF_ENODEVICE, me + ": the assembly kernels failed on the device");
+    mem.release(g1); mem.release(g2); mem.release(Ht); mem.release(KS); mem.release(KT);
     const auto t2 = corr_stamp();
     std::vector<double> spec, vec0;
     if ((rc = stability_solves(ctx, who, dim, 3, M, d_w, d_e, d_info, out->kappa != nullptr, spec, vec0))) return rc;
@@ -2050,33 +2302,52 @@ int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, cons
     return TF_OK;
 }
 
-// UHF stability (tuna_ci.py:994-1038; the spin-conserving Hessian of build_orbital_hessian): tf_cis_uhf's blocks and assembly pass with
-// A + B and A - B, then two dsyevd
-int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
-                     const double *eps_alpha, const double *eps_beta, tf_stability_result *out)
+int tf_stability_rhf(tf_ctx *ctx, int n_occ, int n_frozen, const double *C, const double *eps, tf_stability_result *out)
 {
-    static const char *who = "tf_stability_uhf";
+    return stability_restricted(ctx, "tf_stability_rhf", nullptr, n_occ, n_frozen, C, eps, out);
+}
+
+int tf_stability_rks(tf_ctx *ctx, double hfx, int n_occ, int n_frozen, const double *C, const double *eps, const double *P, tf_stability_result *out)
+{
+    CisXc xc;
+    xc.hfx = hfx; xc.P = P;
+    return stability_restricted(ctx, "tf_stability_rks", &xc, n_occ, n_frozen, C, eps, out);
+}
+
+// UHF stability (tuna_ci.py:994-1038; the spin-conserving Hessian of build_orbital_hessian): tf_cis_uhf's blocks and assembly pass with
+// A + B and A - B, then two dsyevd.  tf_stability_uks is the same driver with xc set: the exchange blocks scaled by hfx and 2 K of
+// xc_kernel_spin_build added to A + B.
+static int stability_unrestricted(tf_ctx *ctx, const char *who, const UcisXc *xc, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta,
+                                  const double *C_alpha, const double *C_beta, const double *eps_alpha, const double *eps_beta, tf_stability_result *out)
+{
     UcisSetup U;
     int rc = ucis_begin(ctx, who, C_alpha && C_beta && eps_alpha && eps_beta && out, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, U);
     if (rc) return rc;
+    if (xc && (rc = xc_kernel_spin_checks(ctx, who, *xc))) return rc;
+    const double hfx = xc ? xc->hfx : 1.0;
+    const bool with_k = xc && (ctx->grid.xid != 0 || ctx->grid.cid != 0);
     const int N = U.N, dim = U.dim;
     const size_t B2 = (size_t)dim * dim;
     out->dim = dim; out->dim_alpha = (int)U.d[0]; out->n_matrices = 2;
     DeviceBlocks mem;
     tfucis::AssembleArgs A{};
-    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A))) return rc;
+    if ((rc = ucis_mo_blocks(ctx, who, U, mem, A, hfx != 0.0))) return rc;
     const auto t1 = corr_stamp();
+    double *K = nullptr;
+    if (with_k && (rc = xc_kernel_spin_build(ctx, who, U, xc->Pa, xc->Pb, mem, &K, nullptr))) return rc;
     double *M[2] = {mem.alloc(B2), mem.alloc(B2)}, *small = mem.alloc(2 * (size_t)dim + 2 * (size_t)N);
     rocblas_int *d_info = mem.alloc_int(4);
     if (!M[0] || !M[1] || !small || !d_info) {
         char text[200];
-        snprintf(text, sizeof text, "tf_stability_uhf: out of device memory for %.2f GB of work space (2 arrays of (d_alpha + d_beta)^2 = %d^2 values)",
+        snprintf(text, sizeof text, "%s: out of device memory for %.2f GB of work space (2 arrays of (d_alpha + d_beta)^2 = %d^2 values)", who,
                  (double)(2 * B2 + 2 * (size_t)dim + 2 * (size_t)N) * sizeof(double) / 1e9, dim);
         return corr_fail(ctx, TF_ENOMEM, text);
     }
     double *d_w = small, *d_e = d_w + dim, *d_eps = d_e + dim;
     A.n_out = 2; A.kind[0] = 1; A.out[0] = M[0]; A.kind[1] = 2; A.out[1] = M[1];
+    A.hfx = hfx; A.K = K; A.kfac[0] = 2.0;                       // A + B gains 2 K, A - B nothing
     if ((rc = ucis_assemble(ctx, who, U, mem, A, eps_alpha, eps_beta, d_eps))) return rc;
+    mem.release(K);
     const auto t2 = corr_stamp();
     std::vector<double> spec, vec0;
     if ((rc = stability_solves(ctx, who, dim, 2, M, d_w, d_e, d_info, out->kappa != nullptr, spec, vec0))) return rc;
@@ -2088,6 +2359,20 @@ int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, i
     out->seconds[2] = corr_secs(t2 - t1);
     out->seconds[3] = corr_secs(t3 - t2);
     return TF_OK;
+}
+
+int tf_stability_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+                     const double *eps_alpha, const double *eps_beta, tf_stability_result *out)
+{
+    return stability_unrestricted(ctx, "tf_stability_uhf", nullptr, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, eps_alpha, eps_beta, out);
+}
+
+int tf_stability_uks(tf_ctx *ctx, double hfx, int n_alpha, int n_beta, int n_frozen_alpha, int n_frozen_beta, const double *C_alpha, const double *C_beta,
+                     const double *eps_alpha, const double *eps_beta, const double *P_alpha, const double *P_beta, tf_stability_result *out)
+{
+    UcisXc xc;
+    xc.hfx = hfx; xc.Pa = P_alpha; xc.Pb = P_beta;
+    return stability_unrestricted(ctx, "tf_stability_uks", &xc, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, C_alpha, C_beta, eps_alpha, eps_beta, out);
 }
 #undef CIS_BLAS
 

@@ -298,6 +298,7 @@ struct tf_ctx {
     std::vector<std::unique_ptr<tfscf::Workspace>> scf_batch;   // one workspace per cycle of a lockstep batch (tf_scf_rhf_batch), kept across calls
     tfdft::Grid grid;                    // Kohn-Sham integration grid with the AOs evaluated on it (tf_dft_setup)
     double xck_seconds[4] = {0, 0, 0, 0};   // the last exchange-correlation kernel build by stage (tf_xc_kernel_timings)
+    int xck_spin_cols = 0;                   // column blocks per tile of the spin-blocked kernel build: 0 = XCK_SPIN_COLS (tf_xc_kernel_spin_cols)
     // persistent helpers of tf_build_eri (creating streams / freeing GiB-sized buffers costs tens of ms per call)
     static const int NSTREAM_MAX = 8;
     hipStream_t streams[NSTREAM_MAX] = {};

@@ -621,6 +621,97 @@ __global__ void xc_point2_kernel(long long G, int gga, int xid, int cid, double 
     pt[18 * G + g] = C.e * n;
 }
 
+// ---- spin-resolved second derivatives of the local-density functionals: the exchange-correlation kernel of unrestricted TD-DFT and of
+// the Kohn-Sham stability analysis (calculate_unrestricted_exchange_correlation_kernel_matrices, tuna_dft.py:1233-1248) -----------------
+//     f_X,ss = 2 f_X(2 rho_s) with the bare Slater function (slater_d2f, not the restricted kernel's doubled f_X); f_X,ab = 0
+//     f_C,st = d2(n e_C)/d rho_s d rho_t in the variables (n, zeta) through the chain rule (VWN3: tuna_xc.py:6072-6140; VWN5: :6308-6438)
+// Guards as the reference: rho_s floored at 1e-23 each (the caller), zeta clipped to [-1, 1], 1 +- zeta floored at 1e-23 in f''(zeta) only.
+
+struct XcSpinKernel { double faa, fab, fbb; };
+
+// The chain rule from (n, zeta) to (rho_a, rho_b), in one fixed order of its terms: faa(rho_a, rho_b) and fbb(rho_b, rho_a) are the same
+// operations on the same numbers wherever the call is inlined
+__device__ __forceinline__ XcSpinKernel spin_chain(double n, double z, double r_s, double de_dr, double d2e_dr2, double de_dz, double d2e_dz2,
+                                                   double d2e_drdz)
+{
+#pragma clang fp contract(off)
+    const double f_nn = (r_s * r_s * d2e_dr2 - 2.0 * r_s * de_dr) / (9.0 * n);
+    const double f_nz = de_dz - (r_s / 3.0) * d2e_drdz;
+    const double f_zz = n * d2e_dz2;
+    const double f_z = n * de_dz;
+    const double n2 = n * n;
+    const double zu = (1.0 - z) / n, zw = -(1.0 + z) / n;
+    const double zuu = -2.0 * (1.0 - z) / n2, zww = 2.0 * (1.0 + z) / n2, zuw = 2.0 * z / n2;
+    XcSpinKernel o;
+    o.faa = ((f_nn + 2.0 * f_nz * zu) + f_zz * (zu * zu)) + f_z * zuu;
+    o.fbb = ((f_nn + 2.0 * f_nz * zw) + f_zz * (zw * zw)) + f_z * zww;
+    o.fab = ((f_nn + f_nz * (zu + zw)) + f_zz * (zu * zw)) + f_z * zuw;
+    return o;
+}
+
+// f''(zeta) of the spin-scaling function with the reference's floor at full polarisation
+__device__ inline double spin_fpp(double z)
+{
+    const double t = cbrt(2.0);
+    const double p = cbrt(fmax(1.0 + z, 1e-23)), m = cbrt(fmax(1.0 - z, 1e-23));
+    return (4.0 / 9.0) * (1.0 / (p * p) + 1.0 / (m * m)) / (t * t * t * t - 2.0);
+}
+
+__device__ inline XcSpinKernel vwn3_spin_kernel(double na, double nb, double n)       // tuna_xc.py:6072-6140
+{
+    const VwnD2 p0 = vwn_d2(n, -0.409286, 13.0720, 42.7198, 0.0310907), p1 = vwn_d2(n, -0.743294, 20.1231, 101.578, 0.01554535);
+    const double z = fmin(fmax((na - nb) / (na + nb), -1.0), 1.0);
+    const double f = spin_f(z), fp = spin_fp(z), fpp = spin_fpp(z);
+    const double de_dr = p0.dedr * (1.0 - f) + p1.dedr * f;
+    const double d2e_dr2 = p0.d2edr2 * (1.0 - f) + p1.d2edr2 * f;
+    const double de_dz = (p1.e - p0.e) * fp, d2e_dz2 = (p1.e - p0.e) * fpp, d2e_drdz = (p1.dedr - p0.dedr) * fp;
+    return spin_chain(n, z, p0.r_s, de_dr, d2e_dr2, de_dz, d2e_dz2, d2e_drdz);
+}
+
+__device__ inline XcSpinKernel vwn5_spin_kernel(double na, double nb, double n)       // tuna_xc.py:6308-6438
+{
+    const VwnD2 p0 = vwn_d2(n, -0.10498, 3.72744, 12.9352, 0.0310907), p1 = vwn_d2(n, -0.32500, 7.06042, 18.0578, 0.01554535),
+                pa = vwn_d2(n, -0.0047584, 1.13107, 13.0045, 1.0 / (6.0 * 3.141592653589793 * 3.141592653589793));
+    const double al = -pa.e, dal = -pa.dedr, d2al = -pa.d2edr2;                     // the spin stiffness and its r_s derivatives
+    const double z = fmin(fmax((na - nb) / (na + nb), -1.0), 1.0);
+    const double t = cbrt(2.0), fpp0 = 8.0 / (9.0 * (t * t * t * t - 2.0));
+    const double f = spin_f(z), fp = spin_fp(z), fpp = spin_fpp(z);
+    const double z2 = z * z, z3 = z2 * z, z4 = z3 * z;
+    const double h = f * z4, hp = fp * z4 + 4.0 * f * z3, hpp = fpp * z4 + 8.0 * fp * z3 + 12.0 * f * z2;
+    const double g = f * (1.0 - z4) / fpp0, gp = (fp * (1.0 - z4) - 4.0 * f * z3) / fpp0,
+                 gpp = (fpp * (1.0 - z4) - 8.0 * fp * z3 - 12.0 * f * z2) / fpp0;
+    const double de_dr = p0.dedr * (1.0 - h) + p1.dedr * h + dal * g;
+    const double d2e_dr2 = p0.d2edr2 * (1.0 - h) + p1.d2edr2 * h + d2al * g;
+    const double de_dz = (p1.e - p0.e) * hp + al * gp, d2e_dz2 = (p1.e - p0.e) * hpp + al * gpp;
+    const double d2e_drdz = (p1.dedr - p0.dedr) * hp + dal * gp;
+    return spin_chain(n, z, p0.r_s, de_dr, d2e_dr2, de_dz, d2e_dz2, d2e_drdz);
+}
+
+// rho_a, rho_b (rows 0, 1 of pt: xc_density2_kernel's sums, floored here as in xc_point2_kernel) of a point; the three weights of the
+// spin-blocked kernel matrix  u[0] = u_aa = w (dfx f_X,aa + dfc f_C,aa),  u[1] = u_ab = w dfc f_C,ab,  u[2] = u_bb likewise  ([3][G]);
+// fpts (may be null): [7][G] = rho_a, rho_b, f_X,aa, f_X,bb, f_C,aa, f_C,ab, f_C,bb.  Local-density ids only (the caller refuses the others).
+__global__ void xc_fpoint2_kernel(long long G, int xid, int cid, double dfx, double dfc, double x_alpha, double *__restrict__ pt,
+                                  const double *__restrict__ w, double *__restrict__ u, double *__restrict__ fpts)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const double na = fmax(pt[g], 1e-23), nb = fmax(pt[G + g], 1e-23);
+    const double n = na + nb;
+    double fXa = 0.0, fXb = 0.0;
+    XcSpinKernel C{0.0, 0.0, 0.0};
+    if (xid == X_SLATER) { fXa = 2.0 * slater_d2f(2.0 * na, x_alpha); fXb = 2.0 * slater_d2f(2.0 * nb, x_alpha); }
+    if (cid == C_VWN5) C = vwn5_spin_kernel(na, nb, n);
+    else if (cid == C_VWN3) C = vwn3_spin_kernel(na, nb, n);
+    pt[g] = na; pt[G + g] = nb;
+    u[g] = w[g] * (dfx * fXa + dfc * C.faa);
+    u[G + g] = w[g] * (dfc * C.fab);
+    u[2 * G + g] = w[g] * (dfx * fXb + dfc * C.fbb);
+    if (fpts) {
+        fpts[g] = na; fpts[G + g] = nb; fpts[2 * G + g] = fXa; fpts[3 * G + g] = fXb;
+        fpts[4 * G + g] = C.faa; fpts[5 * G + g] = C.fab; fpts[6 * G + g] = C.fbb;
+    }
+}
+
 // D2[g][s N + i] = w (v_rho_s phi + c_s . grad phi): one element of Phi (and of grad Phi) per thread, both spins written
 __global__ void xc_dmat2_kernel(long long G, int N, const double *__restrict__ w, const double *__restrict__ phi, const double *__restrict__ dphi,
                                 const double *__restrict__ pt, int gga, double *__restrict__ D2)

@@ -48,6 +48,12 @@ struct AssembleArgs {
     int n_out;                    // matrices of this call (<= 2)
     int kind[2];
     double *out[2];               // [dim][dim] each
+    // TD-DFT / Kohn-Sham stability (tf_tddft_uhf, tf_stability_uks): H and X enter scaled by hfx (Ht may be null when hfx = 0: the block is
+    // then neither built nor read), and matrix m gains kfac[m] K after the symmetrisation -- K [dim][dim], the spin-blocked kernel matrix
+    // of tf_xckernel.hip.h, is symmetric to the last bit.  The defaults are Hartree-Fock: hfx = 1 multiplies exactly, a null K adds nothing.
+    double hfx = 1.0;
+    const double *K = nullptr;
+    double kfac[2] = {0.0, 0.0};
 };
 
 // block (32, 8), grid (dim / 32, dim / 32) rounded up: tile rows p0 .., columns q0 ..
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void uassemble_kernel(AssembleArgs A)
                     const int j = (int)(ql / v), b = (int)(ql - (long long)j * v);
                     sG[y][tx] = S.g[ql * d + pl];
                     sX[y][tx] = S.g[((long long)i * v + b) * d + (long long)j * v + a];               // (ib|ja)
-                    sH[y][tx] = S.Ht[(((long long)j * o + i) * v + b) * v + a];                      // (ji|ba)
+                    sH[y][tx] = S.Ht ? S.Ht[(((long long)j * o + i) * v + b) * v + a] : 0.0;         // (ji|ba)
                 } else if (!sq) {
                     sG[y][tx] = A.g_ab[ql * db + pl];                                                // q alpha, p beta: (q|p)
                 }
@@ -102,18 +108,24 @@ __global__ __launch_bounds__(256) void uassemble_kernel(AssembleArgs A)
             const int j = (int)(ql / v), b = (int)(ql - (long long)j * v);
             const double G = S.g[pl * d + ql];
             const double X = sX[tx][y];                                                              // (ib|ja) = X[p][q]
-            const double H = S.Ht[(((long long)i * o + j) * v + a) * v + b];
+            const double H = S.Ht ? S.Ht[(((long long)i * o + j) * v + a) * v + b] : 0.0;
             const double Gt = sG[tx][y];
             const double Xt = S.g[((long long)j * v + a) * d + (long long)i * v + b];                 // (ja|ib) = X[q][p]
             const double Hq = sH[tx][y];
             const double delta = p == q ? S.eps[S.n_occ + a] - S.eps[S.n_frozen + i] : 0.0;
-            for (int m = 0; m < A.n_out; ++m)
-                A.out[m][p * dim + q] = 0.5 * (ucis_element(A.kind[m], true, delta, G, H, X) + ucis_element(A.kind[m], true, delta, Gt, Hq, Xt));
+            const double hH = A.hfx * H, hX = A.hfx * X, hHq = A.hfx * Hq, hXt = A.hfx * Xt;
+            for (int m = 0; m < A.n_out; ++m) {
+                double r = 0.5 * (ucis_element(A.kind[m], true, delta, G, hH, hX) + ucis_element(A.kind[m], true, delta, Gt, hHq, hXt));
+                if (A.K) r += A.kfac[m] * A.K[p * dim + q];
+                A.out[m][p * dim + q] = r;
+            }
         } else {
             const double G = sp ? sG[tx][y] : A.g_ab[pl * db + ql];                                  // the one stored (alpha|beta) number
             for (int m = 0; m < A.n_out; ++m) {
                 const double e = ucis_element(A.kind[m], false, 0.0, G, 0.0, 0.0);
-                A.out[m][p * dim + q] = 0.5 * (e + e);
+                double r = 0.5 * (e + e);
+                if (A.K) r += A.kfac[m] * A.K[p * dim + q];
+                A.out[m][p * dim + q] = r;
             }
         }
     }

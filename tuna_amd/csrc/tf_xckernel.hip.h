@@ -116,4 +116,118 @@ __global__ void xck_sum_kernel(const double *__restrict__ part, int n_slabs, int
     KS[(size_t)q * dim + p] = s; KT[(size_t)q * dim + p] = t;
 }
 
+// ---- the spin-blocked build: K of an unrestricted reference (calculate_unrestricted_exchange_correlation_kernel_matrices,
+// tuna_dft.py:1194-1281), compound index = the alpha block then the beta block (tf_ucis.hip.h):
+//     K[p][q] = sum_g u_st(g) psi_i^s(g) psi_a^s(g) psi_j^t(g) psi_b^t(g),     s the spin of p, t the spin of q.
+// Blocks of XCK_TILE are cut per spin (XckSpinPlan), and a tile is one row block times NC adjacent column blocks of ONE spin, so it has one
+// pair of spins: its left operand is staged from psi of s, its right operand from psi of t, its weight is u_aa, u_ab or u_bb.  The tiles
+// come from the plan's list (xck_spin_tiles: those with an element row <= column; the beta-alpha rectangle is the transpose of alpha-beta
+// and is never computed).  Staging, LDS layout and the wave's strip are xck_kernel's; there is one accumulator set, and with NC = 2
+// (64 x 128: the registers the second set freed) one read of the left operand feeds eight matrix-core instructions and the left operand
+// is staged once per 128 columns.  Every element is the same sequence of operations on the same values for either NC: the same bits.
+
+struct SpinArgs {
+    const double *psi[2];         // per spin [G][n_s]: columns 0 .. o_s - 1 the occupied window, then the virtual window
+    const double *u[3];           // [G] each: u_aa, u_ab, u_bb
+    const int *tiles;             // [n_tiles][3] = row block, first column block, column blocks (XckSpinTile)
+    double *part;                 // [n_slabs][dim][dim]
+    long long G, slab_len;
+    int n[2], o[2], v[2], d[2], n_b[2];
+    int dim;
+};
+
+// blockIdx.x = tile of the plan's list, blockIdx.y = slab
+template <int NC>
+__global__ __launch_bounds__(XCK_THREADS) void xck_spin_kernel(SpinArgs A)
+{
+    constexpr int RROW = NC * XCK_TILE + 16;                         // doubles between the grid points of the right operand: 16 (mod 32)
+    __shared__ double sL[XCK_CHUNK * XCK_ROW], sR[XCK_CHUNK * RROW], sU[XCK_CHUNK];
+    const int bi = A.tiles[3 * blockIdx.x], bj = A.tiles[3 * blockIdx.x + 1], nc = A.tiles[3 * blockIdx.x + 2];
+    const int si = bi >= A.n_b[0], sj = bj >= A.n_b[0];           // si <= sj; all nc column blocks have spin sj
+    const int p0 = (bi - (si ? A.n_b[0] : 0)) * XCK_TILE, q0 = (bj - (sj ? A.n_b[0] : 0)) * XCK_TILE;   // within the spin's part
+    const double *psiL = A.psi[si], *psiR = A.psi[sj], *u = A.u[si + sj];
+    const int nL = A.n[si], nR = A.n[sj];
+    const long long g_first = (long long)blockIdx.y * A.slab_len;
+    const long long g_last = g_first + A.slab_len < A.G ? g_first + A.slab_len : A.G;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = lane & 15, kk = lane >> 4;
+    const int r = threadIdx.x & 63, gq = threadIdx.x >> 6;
+    const int p = p0 + r;
+    const bool vp = p < A.d[si];
+    const int pi = vp ? p / A.v[si] : 0, pa = A.o[si] + (vp ? p - pi * A.v[si] : 0);
+    bool vq[NC];
+    int qi[NC], qa[NC];
+#pragma unroll
+    for (int b = 0; b < NC; ++b) {                                   // (columns past the spin's part, and the second block of a narrow tile: zeros)
+        const int q = q0 + b * XCK_TILE + r;
+        vq[b] = b < nc && q < A.d[sj];
+        qi[b] = vq[b] ? q / A.v[sj] : 0;
+        qa[b] = A.o[sj] + (vq[b] ? q - qi[b] * A.v[sj] : 0);
+    }
+    constexpr int NT = NC * XCK_TILE / 16;
+    tfm_v4d acc[NT];
+#pragma unroll
+    for (int c = 0; c < NT; ++c) acc[c] = tfm_v4d{0.0, 0.0, 0.0, 0.0};
+    for (long long g0 = g_first; g0 < g_last; g0 += XCK_CHUNK) {
+        __syncthreads();                                             // the previous chunk is no longer read
+#pragma unroll
+        for (int gl = gq; gl < XCK_CHUNK; gl += XCK_THREADS / 64) {
+            const long long g = g0 + gl;
+            const bool in = g < g_last;
+            const long long gr = in ? g : g_first;
+            const double *rowL = psiL + gr * nL, *rowR = psiR + gr * nR;
+            sL[gl * XCK_ROW + r] = in && vp ? rowL[pi] * rowL[pa] : 0.0;
+#pragma unroll
+            for (int b = 0; b < NC; ++b) sR[gl * RROW + b * XCK_TILE + r] = in && vq[b] ? rowR[qi[b]] * rowR[qa[b]] : 0.0;
+        }
+        if (threadIdx.x < XCK_CHUNK) {
+            const long long g = g0 + threadIdx.x;
+            sU[threadIdx.x] = g < g_last ? u[g] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k0 = 0; k0 < XCK_CHUNK; k0 += 4) {
+            const int gl = k0 + kk;
+            const double a = sL[gl * XCK_ROW + 16 * w + m];
+            const double ug = sU[gl];
+#pragma unroll
+            for (int c = 0; c < NT; ++c) {
+                const double b = sR[gl * RROW + 16 * c + m];
+                acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b * ug, acc[c], 0, 0, 0);
+            }
+        }
+    }
+    // ---- the tile in the compound index: rows offL + p0 + ..., columns offR + q0 + ...; elements with row <= column only
+    const int offL = si ? A.d[0] : 0, offR = sj ? A.d[0] : 0;
+    double *out = A.part + (size_t)blockIdx.y * (size_t)A.dim * A.dim;
+#pragma unroll
+    for (int vv = 0; vv < 4; ++vv) {
+        const int rl = p0 + 16 * w + 4 * vv + kk;
+        if (rl >= A.d[si]) continue;
+        const int row = offL + rl;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            const int cl = q0 + 16 * c + m;
+            if (16 * c >= nc * XCK_TILE || cl >= A.d[sj]) continue;
+            const int col = offR + cl;
+            if (col < row) continue;
+            out[(size_t)row * A.dim + col] = acc[c][vv];
+        }
+    }
+}
+
+// K[p][q] = K[q][p] = sum over the slabs, in slab order, of part[slab][p][q] for p <= q
+__global__ void xck_spin_sum_kernel(const double *__restrict__ part, int n_slabs, int dim, double *__restrict__ K)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long dd = (long long)dim * dim;
+    if (e >= dd) return;
+    const int p = (int)(e / dim), q = (int)(e - (long long)p * dim);
+    if (q < p) return;
+    double s = 0.0;
+    for (int k = 0; k < n_slabs; ++k) s += part[(size_t)k * dd + e];
+    K[e] = s;
+    K[(size_t)q * dim + p] = s;
+}
+
 }  // namespace tfxck

@@ -14,7 +14,9 @@ iterations too), and the vertical excitation spectrum of a closed-shell restrict
 the line of a local-density functional (tuna_amd.dft.TD_AVAILABLE: TD-DFT with the exchange-correlation kernel on the device)
 (TDA, NSTATES n, ROOT n / STATE n, NOSINGLETS, NOTRIPLETS, EXTHRESH x; (D) or [D] adds CIS(D) to the ROOT state), and STAB, the stability analysis of a Hartree-Fock SCF (RHF or UHF) in front
 of any post-SCF stage.  Through calculate_energy, a Calculation with reference "UHF" and excited_state set runs the spin-conserving CIS /
-TDHF of the open shell.  Everything numerical runs on the GPU through the C ABI.  The initial
+TDHF of the open shell -- with a functional of tuna_amd.dft.TD_AVAILABLE, unrestricted TD-DFT / TDA (run_unrestricted_tddft) -- and a
+Calculation with stability_analysis set and such a functional the stability analysis of the Kohn-Sham solution, restricted or
+unrestricted (run_kohn_sham_stability); the input lines of both stay refused.  Everything numerical runs on the GPU through the C ABI.  The initial
 guess is the reference's default for single points, the superposition of atomic densities (tuna_amd/guess.py).
 """
 from __future__ import annotations
@@ -349,7 +351,10 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                 label = "\n Unrestricted Hartree-Fock energy: " if calc.reference == "UHF" else "\n Restricted Hartree-Fock energy:   "
                 log(label + f"{out.energy:16.10f}")                                      # kernel:846-850
         if calc.stability_analysis:                          # after the SCF's energy components, before any post-SCF stage (kernel:1144-1148)
-            run_stability_analysis(calc, molecule, out, engine, silent, log)
+            if kohn_sham_kernel_available(calc):
+                run_kohn_sham_stability(calc, molecule, out, engine, silent, log)
+            else:
+                run_stability_analysis(calc, molecule, out, engine, silent, log)
         if calc.method == "MP2" and calc.mp4:
             run_restricted_mp4(calc, molecule, out, engine, silent, log)
         elif calc.method == "MP2":
@@ -414,7 +419,9 @@ def calculate_energy(symbols, R_bohr, calc: Calculation, engine: Engine | None =
                 run_perturbative_triples(calc, molecule, out, engine, silent, log)
         elif calc.coupled_cluster:
             run_coupled_cluster_doubles(calc, molecule, out, engine, silent, log)
-        if calc.excited_state:
+        if calc.excited_state and calc.reference == "UHF" and kohn_sham_kernel_available(calc):
+            run_unrestricted_tddft(calc, molecule, integrals, out, engine, silent, log)
+        elif calc.excited_state:
             run_excited_states(calc, molecule, integrals, out, engine, silent, log)
         if not silent:
             log(" Final single point energy:        " + f"{out.energy:16.10f}")        # kernel:1305
@@ -461,6 +468,27 @@ def run_stability_analysis(calc: Calculation, molecule, out, engine: Engine, sil
     if calc.functional is not None:
         raise TunaError("STAB: the stability analysis of a Kohn-Sham solution (the orbital Hessian with the exchange-correlation kernel) is "
                         "not built: STAB is available on Hartree-Fock references (HF, UHF, and the correlated methods on them).")
+    _stability_analysis(calc, molecule, out, engine, silent, log, False)
+
+
+def kohn_sham_kernel_available(calc: Calculation) -> bool:
+    """A Kohn-Sham Calculation whose functional has an exchange-correlation kernel in this build (tuna_amd.dft.TD_AVAILABLE)"""
+    from . import dft as dft_mod
+    return calc.functional is not None and calc.functional in dft_mod.TD_AVAILABLE
+
+
+def run_kohn_sham_stability(calc: Calculation, molecule, out, engine: Engine, silent=True, log=print):
+    """STAB on a Kohn-Sham solution of a functional of tuna_amd.dft.TD_AVAILABLE, restricted or unrestricted
+    (determine_self_consistent_field_stability with K_XC_singlet / K_XC_triplet / K_XC, tuna_ci.py:1049-1106): tf_stability_rks /
+    tf_stability_uks with calc.HFX_prop at the SCF densities, on the grid the Kohn-Sham SCF left on the engine.  Prints the three lines of
+    the kernel build (tuna_dft.py:1099-1181, :1221-1254), then the reference's block with its threshold; out.stability as
+    run_stability_analysis.  Reached through calculate_energy with a Calculation; the input lines stay refused by run()."""
+    if not kohn_sham_kernel_available(calc):
+        raise TunaError("Stability analysis is not yet available for this exchange-correlation functional!")       # tuna_ci.py:1072
+    _stability_analysis(calc, molecule, out, engine, silent, log, True)
+
+
+def _stability_analysis(calc: Calculation, molecule, out, engine: Engine, silent, log, ks):
     N = molecule.n_basis
     threshold = ORB_HESS_EIG_THRESH
     nf = frozen_core_orbitals(molecule, calc)
@@ -468,14 +496,21 @@ def run_stability_analysis(calc: Calculation, molecule, out, engine: Engine, sil
     if calc.reference == "UHF":
         if (molecule.n_alpha - nf) * (N - molecule.n_alpha) + (molecule.n_beta - nf) * (N - molecule.n_beta) <= 0:
             raise TunaError("Stability analysis requested on system with no orbital rotations!")
-        r = engine.stability_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, molecule.n_alpha,
-                                 molecule.n_beta, nf, nf)
+        if ks:
+            r = engine.stability_uks(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, out.P_alpha,
+                                     out.P_beta, molecule.n_alpha, molecule.n_beta, nf, nf, hfx=calc.HFX_prop)
+        else:
+            r = engine.stability_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, molecule.n_alpha,
+                                     molecule.n_beta, nf, nf)
         lowest = r["lowest"]
         st = {"reference": "UHF", "lowest": lowest, "source": r["source"], "unstable_unrestricted": lowest <= threshold, "stable": lowest > threshold}
     else:
         if N - molecule.n_doubly_occ <= 0:
             raise TunaError("Stability analysis requested on system with no orbital rotations!")
-        r = engine.stability_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, nf)
+        if ks:
+            r = engine.stability_rks(out.molecular_orbitals, out.epsilons, out.P, molecule.n_doubly_occ, nf, hfx=calc.HFX_prop)
+        else:
+            r = engine.stability_rhf(out.molecular_orbitals, out.epsilons, molecule.n_doubly_occ, nf)
         ls, lt = r["lowest_singlet"], r["lowest_triplet"]
         st = {"reference": "RHF", "lowest_singlet": ls, "lowest_triplet": lt, "source_singlet": r["source_singlet"], "source_triplet": r["source_triplet"],
               "unstable_restricted": ls <= threshold, "unstable_unrestricted": lt <= threshold, "stable": ls > threshold and lt > threshold}
@@ -484,6 +519,10 @@ def run_stability_analysis(calc: Calculation, molecule, out, engine: Engine, sil
     out.stability = st
     if silent:
         return
+    if ks:
+        log("\n Evaluating molecular orbitals on grid...    [Done]")
+        log(" Evaluating exchange-correlation kernel...   [Done]")
+        log(" Calculating matrix elements...              [Done]")
     log("\n" + SPACER)
     log("                  Stability Analysis")
     log(SPACER)
@@ -851,6 +890,23 @@ def run_unrestricted_excited_states(calc: Calculation, molecule, integrals, out,
     out.excited holds the energies, |mu|, oscillator strengths, the root's X and Y split by spin and E_transition.  The root's density and
     difference density are not formed, and (D) on an unrestricted state is refused.  A TDHF run on an unstable reference raises the
     library's TunaError (TF_ELINALG)."""
+    _unrestricted_states(calc, molecule, integrals, out, engine, silent, log, False)
+
+
+def run_unrestricted_tddft(calc: Calculation, molecule, integrals, out, engine: Engine, silent=True, log=print):
+    """Spin-conserving TD-DFT / TDA of an unrestricted Kohn-Sham determinant for a functional of tuna_amd.dft.TD_AVAILABLE, tf_tddft_uhf with
+    calc.HFX_prop at the SCF spin densities out.P_alpha, out.P_beta on the grid the Kohn-Sham SCF left on the engine: the "UHF" branch of
+    run_excited_state_calculation with density_functional_method on (tuna_ci.py:2215-2290).  Prints the three lines of the kernel build
+    (tuna_dft.py:1221-1254) and then the reference's unrestricted block; everything else as run_unrestricted_excited_states.  Reached
+    through calculate_energy with reference == "UHF", a functional and calc.excited_state set; the input lines stay refused by run()."""
+    if calc.reference != "UHF":
+        raise TunaError("run_unrestricted_tddft needs an unrestricted Kohn-Sham reference (reference == \"UHF\").")
+    if not kohn_sham_kernel_available(calc):
+        raise TunaError("Time-dependent DFT is not yet available for this exchange-correlation functional!")       # tuna_ci.py:2175
+    _unrestricted_states(calc, molecule, integrals, out, engine, silent, log, True)
+
+
+def _unrestricted_states(calc: Calculation, molecule, integrals, out, engine: Engine, silent, log, ks):
     if calc.do_perturbative_doubles:
         raise TunaError("The (D) keyword is available for a closed-shell restricted reference only in this build: the unrestricted perturbative "
                         "doubles correction is not built.")
@@ -863,14 +919,23 @@ def run_unrestricted_excited_states(calc: Calculation, molecule, integrals, out,
     tda = calc.tamm_dancoff_approximation or calc.excited_state == "CIS"                  # tuna_ci.py:1401
     if not silent:
         log("\n Beginning excited state calculation...")                                  # kernel:1177
+        if ks:                                                                            # tuna_dft.py:1221-1254
+            log("\n Evaluating molecular orbitals on grid...    [Done]")
+            log(" Evaluating exchange-correlation kernel...   [Done]")
+            log(" Calculating matrix elements...              [Done]")
         log("\n" + SPACER)                                                                # tuna_ci.py:1236-1257
-        log("          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
+        log("      Time-dependent Density Functional Theory" if ks else
+            "          Configuration Interaction Singles" if tda else "            Time-dependent Hartree-Fock")
         log(SPACER)
         log(("  Using" if tda else "  Not using") + " the Tamm-Dancoff approximation...\n")
     t0 = time.perf_counter()
     n_keep = max(calc.n_states, calc.root, 0)
-    r = engine.cis_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, na, nb, nf, nf,
-                       method="CIS" if tda else "TDHF", n_keep=n_keep, dip=integrals.D)
+    if ks:
+        r = engine.tddft_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, out.P_alpha, out.P_beta,
+                             na, nb, nf, nf, method="TDA" if tda else "TDDFT", hfx=calc.HFX_prop, n_keep=n_keep, dip=integrals.D)
+    else:
+        r = engine.cis_uhf(out.molecular_orbitals_alpha, out.molecular_orbitals_beta, out.epsilons_alpha, out.epsilons_beta, na, nb, nf, nf,
+                           method="CIS" if tda else "TDHF", n_keep=n_keep, dip=integrals.D)
     out.timings["Excited state calculation"] = time.perf_counter() - t0
     energies = np.asarray(r["E"], dtype=float)
     mu, f = np.linalg.norm(np.asarray(r["tdm"], dtype=float).reshape(len(energies), -1), axis=1), np.asarray(r["osc"], dtype=float)

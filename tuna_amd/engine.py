@@ -542,12 +542,14 @@ class Engine:
             dip = f64(dip)
             if dip.shape != (3, self.N, self.N):
                 raise TunaError(f"cis_uhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        return self._cis_uhf_call(Ca, Cb, ea, eb, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, method == "CIS", n_keep, dip, return_matrices)
+
+    def _cis_uhf_call(self, Ca, Cb, ea, eb, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, tda, n_keep, dip, return_matrices, tddft=None):
+        """The buffers, the call and the dict of cis_uhf; with tddft = (hfx, P_alpha, P_beta) the call is tf_tddft_uhf."""
         import ctypes
-        from ._lib import UcisOpts, UcisResult
-        tda = method == "CIS"
+        from ._lib import UcisOpts, UcisResult, UtddftOpts
         dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
         nk = max(0, min(int(n_keep), dim))
-        opts = UcisOpts(int(tda), int(n_keep))
         res = UcisResult()
         arrays = {}
 
@@ -558,13 +560,103 @@ class Engine:
         res.x, res.y = take("X", (nk, dim), nk > 0), take("Y", (nk, dim), nk > 0)
         res.tdm, res.osc = take("tdm", (dim, 3), dip is not None), take("osc", dim, dip is not None)
         res.m_plus, res.m_minus = take("M_plus", (dim, dim), return_matrices), take("M_minus", (dim, dim), return_matrices and not tda)
-        self._check(self._L.tf_cis_uhf(self._ctx, ctypes.byref(opts), int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca), ptr(Cb),
-                                       ptr(ea), ptr(eb), ptr(dip), ctypes.byref(res)))
+        if tddft is None:
+            opts = UcisOpts(int(tda), int(n_keep))
+            self._check(self._L.tf_cis_uhf(self._ctx, ctypes.byref(opts), int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca),
+                                           ptr(Cb), ptr(ea), ptr(eb), ptr(dip), ctypes.byref(res)))
+        else:
+            hfx, Pa, Pb = tddft
+            opts = UtddftOpts(int(tda), int(n_keep), float(hfx))
+            self._check(self._L.tf_tddft_uhf(self._ctx, ctypes.byref(opts), int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca),
+                                             ptr(Cb), ptr(ea), ptr(eb), ptr(Pa), ptr(Pb), ptr(dip), ctypes.byref(res)))
         out = {"dim": int(res.dim), "dim_alpha": int(res.dim_alpha), "seconds": list(res.seconds)}
         for name, a in arrays.items():
             if return_matrices or not name.startswith("M_"):
                 out[name] = a
         return out
+
+    def _spin_densities(self, who, P_alpha, P_beta):
+        """The two densities as float64 [N, N]; None stays None and reaches the library as NULL (TF_EINVAL)."""
+        out = []
+        for P in (P_alpha, P_beta):
+            if P is not None:
+                P = f64(P)
+                if P.shape != (self.N, self.N):
+                    raise TunaError(f"{who}: the densities must be [{self.N}, {self.N}]")
+            out.append(P)
+        return out
+
+    def _default_hfx(self, hfx):
+        if hfx is None:
+            hfx = self.functional["hfx"] if getattr(self, "functional", None) else 1.0
+        return float(hfx)
+
+    def tddft_uhf(self, C_alpha, C_beta, eps_alpha, eps_beta, P_alpha, P_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0, method="TDDFT",
+                  hfx=None, n_keep=0, dip=None, return_matrices=False) -> dict:
+        """Spin-conserving TD-DFT ("TDDFT") or its Tamm-Dancoff approximation ("TDA") from canonical unrestricted Kohn-Sham orbitals, the
+        spin densities of the SCF and the functional of dft_setup (tunafock.h: tf_tddft_uhf): the dict of cis_uhf.  hfx = the share of
+        exact exchange, by default that of the functional set up.  Local-density functionals only; the null functional with hfx = 1 is
+        cis_uhf bit for bit."""
+        Ca, Cb, ea, eb = self._uhf_orbitals("tddft_uhf", C_alpha, C_beta, eps_alpha, eps_beta)
+        if method not in ("TDDFT", "TDA"):
+            raise TunaError(f"tddft_uhf: method must be \"TDDFT\" or \"TDA\", got {method!r}")
+        Pa, Pb = self._spin_densities("tddft_uhf", P_alpha, P_beta)
+        if dip is not None:
+            dip = f64(dip)
+            if dip.shape != (3, self.N, self.N):
+                raise TunaError(f"tddft_uhf: the dipole matrices must be [3, {self.N}, {self.N}]")
+        return self._cis_uhf_call(Ca, Cb, ea, eb, n_alpha, n_beta, n_frozen_alpha, n_frozen_beta, method == "TDA", n_keep, dip, return_matrices,
+                                  tddft=(self._default_hfx(hfx), Pa, Pb))
+
+    def xc_kernel_uhf(self, C_alpha, C_beta, P_alpha, P_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0, return_points=False):
+        """K_XC [dim, dim] of the functional of dft_setup in the compound index of cis_uhf (alpha block, then beta block) at the spin
+        densities P_alpha, P_beta (tunafock.h: tf_xc_kernel_uhf; tuna_dft.py:1194-1281); with return_points also f_points [7, n_points] =
+        rho_alpha, rho_beta (floored), f_X,aa, f_X,bb, f_C,aa, f_C,ab, f_C,bb."""
+        Ca, Cb = f64(C_alpha), f64(C_beta)
+        if Ca.shape != (self.N, self.N) or Cb.shape != (self.N, self.N):
+            raise TunaError(f"xc_kernel_uhf: orbitals must be [{self.N}, {self.N}] for both spins")
+        Pa, Pb = self._spin_densities("xc_kernel_uhf", P_alpha, P_beta)
+        dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
+        K = np.zeros((dim, dim))
+        G = self.functional["n_points"] if getattr(self, "functional", None) else 0
+        fp = np.zeros((7, G)) if return_points and G else None
+        self._check(self._L.tf_xc_kernel_uhf(self._ctx, int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta), ptr(Ca), ptr(Cb), ptr(Pa),
+                                             ptr(Pb), ptr(K), ptr(fp)))
+        return (K, fp) if return_points else K
+
+    def xc_kernel_spin_probe(self, psi_oa, psi_va, psi_ob, psi_vb, u_aa, u_ab, u_bb):
+        """K [dim, dim], dim = o_a v_a + o_b v_b, K[p, q] = sum_g u_st(g) psi_o^s[i, g] psi_v^s[a, g] psi_o^t[j, g] psi_v^t[b, g] in the compound
+        index of cis_uhf, for psi_oa [o_a, G], psi_va [v_a, G], psi_ob [o_b, G], psi_vb [v_b, G] (a spin may have no rows) and u_aa, u_ab,
+        u_bb [G] (any values), by the kernel and the slab sum of xc_kernel_uhf (tunafock.h: tf_xc_kernel_spin_probe)."""
+        us = [f64(u) for u in (u_aa, u_ab, u_bb)]
+        G = us[0].shape[0] if us[0].ndim == 1 else -1
+        ps = [f64(x) if np.size(x) else np.zeros((0, max(G, 0))) for x in (psi_oa, psi_va, psi_ob, psi_vb)]      # no rows: any empty array
+        if G < 1 or any(u.shape != (G,) for u in us) or any(x.ndim != 2 or x.shape[1] != G for x in ps):
+            raise ValueError("xc_kernel_spin_probe: needs psi_oa [o_a, G], psi_va [v_a, G], psi_ob [o_b, G], psi_vb [v_b, G] and u_aa, u_ab, u_bb [G], "
+                             f"got {[x.shape for x in ps]}, {[u.shape for u in us]}")
+        oa, va, ob, vb = (x.shape[0] for x in ps)
+        dim = oa * va + ob * vb
+        K = np.full((dim, dim), np.nan)
+        self._check(self._L.tf_xc_kernel_spin_probe(self._ctx, oa, va, ob, vb, G, *(ptr(x) if x.size else None for x in ps), *(ptr(u) for u in us), ptr(K)))
+        return K
+
+    def xc_kernel_spin_cols(self, cols: int = 0):
+        """The tile shape of this engine's spin-blocked kernel build: 1 = 64 x 64, 2 = 64 x 128, 0 = the library's default (tunafock.h:
+        tf_xc_kernel_spin_cols).  Either shape gives the same bits; tools/gpu_utddft_timing.py measures both."""
+        self._check(self._L.tf_xc_kernel_spin_cols(self._ctx, int(cols)))
+        return self
+
+    @staticmethod
+    def xc_kernel_spin_plan(d_alpha: int, d_beta: int, n_points: int) -> dict:
+        """The launch plan of the spin-blocked kernel build, a pure function of (d_alpha, d_beta, n_points) (tunafock.h:
+        tf_xc_kernel_spin_plan)."""
+        import ctypes
+        from . import _lib
+        out = (ctypes.c_int64 * 8)()
+        if _lib.lib().tf_xc_kernel_spin_plan(int(d_alpha), int(d_beta), int(n_points), out) != 0:
+            raise TunaError("xc_kernel_spin_plan: d_alpha, d_beta must not be negative, their sum and n_points at least 1")
+        keys = ("n_b_alpha", "n_b_beta", "n_tiles", "n_slabs", "slab_len", "lds_bytes", "partial_doubles", "tile_cols")
+        return dict(zip(keys, (int(x) for x in out)))
 
     def _stability(self, call, dim, n_matrices, return_spectra, return_mode):
         import ctypes
@@ -589,9 +681,12 @@ class Engine:
         if C.shape != (self.N, self.N) or eps.shape != (self.N,):
             raise TunaError(f"stability_rhf: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
         o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
+        return self._stability_restricted(lambda r: self._L.tf_stability_rhf(self._ctx, int(n_occ), int(n_frozen), ptr(C), ptr(eps), r), o, v,
+                                          return_spectra, return_mode)
+
+    def _stability_restricted(self, call, o, v, return_spectra, return_mode):
         names = self.STABILITY_MATRICES_RHF
-        res, spectra, kappa = self._stability(lambda r: self._L.tf_stability_rhf(self._ctx, int(n_occ), int(n_frozen), ptr(C), ptr(eps), r), o * v, 3,
-                                              return_spectra, return_mode)
+        res, spectra, kappa = self._stability(call, o * v, 3, return_spectra, return_mode)
         return {"dim": int(res.dim), "lowest_singlet": res.lowest[0], "lowest_triplet": res.lowest[1], "source_singlet": names[res.source[0]],
                 "source_triplet": names[res.source[1]], "spectra": dict(zip(names, spectra)) if return_spectra else None,
                 "mode_singlet": kappa[0].reshape(o, v) if return_mode else None, "mode_triplet": kappa[1].reshape(o, v) if return_mode else None,
@@ -605,11 +700,42 @@ class Engine:
         unstable reference."""
         Ca, Cb, ea, eb = self._uhf_orbitals("stability_uhf", C_alpha, C_beta, eps_alpha, eps_beta)
         dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
+        return self._stability_unrestricted(lambda r: self._L.tf_stability_uhf(self._ctx, int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta),
+                                                                                ptr(Ca), ptr(Cb), ptr(ea), ptr(eb), r), dim, return_spectra, return_mode)
+
+    def _stability_unrestricted(self, call, dim, return_spectra, return_mode):
         names = self.STABILITY_MATRICES_UHF
-        res, spectra, kappa = self._stability(lambda r: self._L.tf_stability_uhf(self._ctx, int(n_alpha), int(n_beta), int(n_frozen_alpha), int(n_frozen_beta),
-                                                                                  ptr(Ca), ptr(Cb), ptr(ea), ptr(eb), r), dim, 2, return_spectra, return_mode)
+        res, spectra, kappa = self._stability(call, dim, 2, return_spectra, return_mode)
         return {"dim": int(res.dim), "dim_alpha": int(res.dim_alpha), "lowest": res.lowest[0], "source": names[res.source[0]],
                 "spectra": dict(zip(names, spectra)) if return_spectra else None, "mode": kappa[0] if return_mode else None, "seconds": list(res.seconds)}
+
+    def stability_rks(self, C, eps, P, n_occ, n_frozen=0, hfx=None, return_spectra=False, return_mode=False) -> dict:
+        """stability_rhf for a restricted Kohn-Sham solution: the exchange blocks scaled by hfx (by default that of the functional set up)
+        and 2 K_S / 2 K_T of xc_kernel_rhf at the density P in the singlet / triplet A + B (tunafock.h: tf_stability_rks;
+        tuna_ci.py:1049-1106).  The dict of stability_rhf."""
+        C, eps = f64(C), f64(eps)
+        if C.shape != (self.N, self.N) or eps.shape != (self.N,):
+            raise TunaError(f"stability_rks: orbitals must be [{self.N}, {self.N}] and eigenvalues [{self.N}]")
+        if P is not None:
+            P = f64(P)
+            if P.shape != (self.N, self.N):
+                raise TunaError(f"stability_rks: the density must be [{self.N}, {self.N}]")
+        o, v = max(0, int(n_occ) - int(n_frozen)), max(0, self.N - int(n_occ))
+        hfx = self._default_hfx(hfx)
+        return self._stability_restricted(lambda r: self._L.tf_stability_rks(self._ctx, hfx, int(n_occ), int(n_frozen), ptr(C), ptr(eps), ptr(P), r), o, v,
+                                          return_spectra, return_mode)
+
+    def stability_uks(self, C_alpha, C_beta, eps_alpha, eps_beta, P_alpha, P_beta, n_alpha, n_beta, n_frozen_alpha=0, n_frozen_beta=0, hfx=None,
+                      return_spectra=False, return_mode=False) -> dict:
+        """stability_uhf for an unrestricted Kohn-Sham solution: the exchange blocks scaled by hfx and 2 K of xc_kernel_uhf at the spin
+        densities in A + B (tunafock.h: tf_stability_uks).  The dict of stability_uhf."""
+        Ca, Cb, ea, eb = self._uhf_orbitals("stability_uks", C_alpha, C_beta, eps_alpha, eps_beta)
+        Pa, Pb = self._spin_densities("stability_uks", P_alpha, P_beta)
+        dim = sum(max(0, int(n) - int(nf)) * max(0, self.N - int(n)) for n, nf in ((n_alpha, n_frozen_alpha), (n_beta, n_frozen_beta)))
+        hfx = self._default_hfx(hfx)
+        return self._stability_unrestricted(lambda r: self._L.tf_stability_uks(self._ctx, hfx, int(n_alpha), int(n_beta), int(n_frozen_alpha),
+                                                                                int(n_frozen_beta), ptr(Ca), ptr(Cb), ptr(ea), ptr(eb), ptr(Pa), ptr(Pb), r),
+                                            dim, return_spectra, return_mode)
 
     def cis_d_rhf(self, C, eps, n_occ, n_frozen=0, *, b, omega, triplet) -> dict:
         """CIS(D), the perturbative doubles correction to closed-shell CIS / TDHF states (tunafock.h: tf_cis_d_rhf; tuna_ci.py:1874-1982).
