@@ -23,7 +23,7 @@
 //     E_indirect = sum_ia b_ia y_ia - sum_ija b_ia b_ja Goo_ij - sum_iab b_ia b_ib Gvv_ba
 // whose three sums of o v, o^2 v and o v^2 terms are made on the host in a fixed order.
 //
-// Work space of the driver (tf_cis_d_rhf, tf_corr_host.hip.h): 5 arrays of o^2 v^2 values -- g, t, tt, L and M -- plus, while a block
+// Work space of the driver (tf_cis_d_rhf, tf_excited_host.hip.h): 5 arrays of o^2 v^2 values -- g, t, tt, L and M -- plus, while a block
 // is being transformed on the packed and tiles layouts, the 2 halves mo_transform_device adds up; (ki|jb) is o^3 v.  Nothing of size
 // o v^3 or v^4 exists anywhere.
 #pragma once

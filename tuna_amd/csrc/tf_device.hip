@@ -1111,8 +1111,10 @@ int tf_dft_vxc_unrestricted(tf_ctx *ctx, const double *P_alpha, const double *P_
     return TF_OK;
 }
 
-// ---- AO->MO transformation, MP2 ... CCSD(T), CIS / TDHF: the drivers of the correlated methods (consumers of the resident tensor) ----
+// ---- AO->MO transformation, MP2 ... CCSD(T), the MP2 density: the drivers of the correlated methods (consumers of the resident tensor) ----
 #include "tf_corr_host.hip.h"
+// ---- CIS / TDHF, TD-DFT / TDA, the stability analysis, CIS(D): the drivers of the excited states, on the shared pieces of the above ----
+#include "tf_excited_host.hip.h"
 
 int tf_eigh_probe(tf_ctx *ctx, int n, int variant, int reps, double *seconds)
 {
