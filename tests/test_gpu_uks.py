@@ -120,6 +120,60 @@ def test_random_densities_every_functional_pair(engine):
     print(f"MEASURED random worst: V {worst[0]:.2e} E {worst[1]:.2e}")
 
 
+_O2_POOL = {}
+
+
+def _o2_pool(engine):
+    """O2 / STO-3G on the engine; the AOs, U and the loose grid's points with w > 1e-6 within 4 bohr of the bond midpoint (computed once)."""
+    from tuna_amd import dft
+    from tuna_amd.spherical import transformation_matrix
+    atoms = mol.make_atoms(["O", "O"], mol.angstrom_to_bohr(1.2075))
+    shells = mol.build_shells(atoms, "STO-3G")
+    aos = mol.expand_cartesian_aos(shells)
+    engine.set_basis(aos).build_eri(True)
+    if not _O2_POOL:
+        pts, wts, _ = dft.integration_grid(atoms, "loose")
+        pts, wts = np.asarray(pts).reshape(3, -1), np.asarray(wts).reshape(-1)
+        mid = 0.5 * (np.asarray(atoms[0].origin, dtype=float) + np.asarray(atoms[1].origin, dtype=float))
+        r = np.sqrt(((pts - mid[:, None]) ** 2).sum(axis=0))
+        keep = np.flatnonzero((wts > 1e-6) & (r < 4.0))
+        _O2_POOL.update(pts=pts, wts=wts, keep=keep, U=transformation_matrix([s.L for s in shells]))
+    return aos, _O2_POOL
+
+
+@pytest.mark.parametrize("G", [1, 127, 128, 129, 256, 128 * 3 + 5])
+def test_split_k_branches_unrestricted(engine, G):
+    """The 2N-wide V assembly at its split-K edges, as test_gpu_dft_reference.py::test_split_k_branches pins the restricted one: real
+    points and weights of O2 / STO-3G (N = 10, loose grid; those with w > 1e-6 within 4 bohr of the bond midpoint, in the random order of
+    default_rng(G), so that the remainder rows are as significant as the others) cut to G points: G < 128 runs only the remainder GEMM, a
+    multiple of 128 no remainder GEMM, the others both.  B3LYP ids, random PSD densities, against xc_reference_spin; V_alpha, V_beta
+    exactly symmetric; a second call gives the same bits.  Bars: TOL_V and TOL_E of the whole grids.  Measured worst on the build
+    before the two assemblies were folded into one and on the one after, the same figures: V 6.8e-16 (G = 1), integrals 7.2e-16 (G = 1)."""
+    aos, pool = _o2_pool(engine)
+    assert pool["wts"].size == 28196 and pool["keep"].size == 8680
+    idx = np.random.default_rng(G).permutation(pool["keep"])[:G]
+    assert idx.size == G
+    pts, wts = np.ascontiguousarray(pool["pts"][:, idx]), np.ascontiguousarray(pool["wts"][idx])
+    N = engine.N
+    assert N == 10
+    rng = np.random.default_rng(11)
+    Pa, Pb = _random_psd(rng, N, 6, 0.3), _random_psd(rng, N, 4, 0.2)
+    xid, cid, dfx, dfc = 3, 4, 0.8, 1.0                                         # B3LYP: B3 exchange, 3P (VWN5) correlation
+    assert engine._L.tf_dft_setup(engine._ctx, G, ptr(pts), ptr(wts), xid, cid, dfx, dfc, 2.0 / 3.0) == 0
+    rc, Va, Vb, n, ex, ec = _vxcu_rc(engine, Pa, Pb)
+    again = _vxcu_rc(engine, Pa, Pb)
+    engine.dft_clear()
+    assert rc == 0 and again[0] == 0
+    Var, Vbr, nr, exr, ecr = xs.vxc_unrestricted(aos, pts, wts, Pa, Pb, xid, cid, dfx, dfc, grid=xr.ao_grid(aos, pts, pool["U"]))
+    eV = max(np.abs(Va - Var).max() / np.abs(Var).max(), np.abs(Vb - Vbr).max() / np.abs(Vbr).max())
+    eE = max(abs(a - b) / abs(b) for a, b in zip([*n, *ex, ec], [*nr, *exr, ecr]) if b != 0.0)
+    print(f"MEASURED split-K unrestricted G={G}: V {eV:.2e} E {eE:.2e}")
+    assert eV < TOL_V and eE < TOL_E, (G, eV, eE)
+    assert np.abs(Va - Va.T).max() == 0.0 and np.abs(Vb - Vb.T).max() == 0.0
+    assert np.array_equal(Va, again[1]) and np.array_equal(Vb, again[2])
+    assert np.array_equal(n, again[3]) and np.array_equal(ex, again[4]) and ec == again[5]
+
+
 SP_BASIS = {7: [("S", [(0.9, 1.0)]), ("P", [(0.6, 1.0)])]}
 
 

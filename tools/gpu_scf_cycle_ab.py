@@ -8,15 +8,16 @@ non-zero or is killed by its time limit and starts nothing after it.
                        N2/cc-pVDZ (28) (the fused n <= 64 paths), N2/cc-pVTZ (60), Ar2/cc-pVQZ (118, blocked refinement), synth-200
                        (refinement as the library chooses it; the report says which), each with damping none / dynamic / fixed 0.3,
                        max_diis 2 and 6, DIIS off, a field term and a run cut off at max_iter = 3; N2/cc-pVTZ once more on tiles; one RKS run
-                       (N2/6-31G, BLYP); UHF on the O2 triplet (STO-3G, cc-pVDZ), the Li doublet, the H atom and the Li quartet (both n_beta = 0) in 6-31G and,
+                       (N2/6-31G, BLYP) and, on the same tensor, tf_dft_vxc and tf_dft_vxc_unrestricted themselves (SVWN, BLYP, B3LYP; the loose
+                       grid whole and cut to 127, 128, 129 and 12 801 points; each call twice and once after a fresh set-up); UHF on the O2 triplet (STO-3G, cc-pVDZ), the Li doublet, the H atom and the Li quartet (both n_beta = 0) in 6-31G and,
                        above n = 64, the NO doublet in cc-pVQZ with damping on and off; UKS on the golden O2 triplet B3LYP/STO-3G; a lockstep
                        batch of three field cycles.  Every run also records what tf_eigh_stats and tf_jk_path_stats counted during it.
                        LIB_A runs twice (A, A'): B is compared byte for byte with A on every array on which A and A' agree byte for
                        byte.  Only arrays of the lockstep batch may be left out that way; those are compared with the tolerance
                        tests/test_host_logic.py has for the batch (energies to 1e-10, equal iteration counts).
   --time LIB_A LIB_B   warm, in the process order A, B, A', three times over: the two SCF legs of bench.py (synth-400, TIGHT, DIIS 6 with the
-                       bench's fall-back to dynamic damping; N2/cc-pVTZ, EXTREME, no damping), one UHF cycle (synth-200 triplet) and one UKS
-                       cycle (O2 triplet B3LYP/cc-pVDZ): wall_seconds, fock_seconds and eig_seconds of each, the medians of the three series
+                       bench's fall-back to dynamic damping; N2/cc-pVTZ, EXTREME, no damping), one UHF cycle (synth-200 triplet), one UKS
+                       cycle (O2 triplet B3LYP/cc-pVDZ) and one RKS cycle (CO B3LYP/def2-TZVP, medium grid: BASELINE config 4): wall_seconds, fock_seconds and eig_seconds of each, the medians of the three series
                        and the A-against-A' spread B is to be read against.  Prints one JSON line.
 
 Usage: python tools/gpu_scf_cycle_ab.py (--bits | --time) LIB_A LIB_B [--out DIR] [--limit SECONDS]
@@ -99,6 +100,38 @@ def restricted_runs(rec, eng, tag, S, T, V, D, X, C0, nao, vnn, nocc, conv):
     return P0, E0, kw
 
 
+def direct_vxc(out, eng, atoms):
+    """tf_dft_vxc and tf_dft_vxc_unrestricted themselves on the tensor the engine holds (N2/6-31G): SVWN, BLYP and B3LYP on the loose grid
+    whole and cut to 127, 128, 129 and 12 801 points in random order (the split-K edges of the V assembly), random PSD densities, every
+    call twice, and once more after dft_clear + dft_setup; everything returned is kept"""
+    from tuna_amd import dft
+    pts, wts = dft.integration_grid(atoms, "loose")[:2]
+    pts, wts = np.asarray(pts).reshape(3, -1), np.asarray(wts).reshape(-1)
+    rng = np.random.default_rng(5)
+    psd = [c @ c.T / c.shape[1] for c in (rng.standard_normal((eng.N, k)) for k in (7, 6, 4))]
+    P, Pa, Pb = psd[0], 0.5 * psd[1], 0.3 * psd[2]
+
+    def keep(name, res):
+        for k, v in enumerate(res):
+            out[f"{name}.{k}"] = np.asarray(v)
+
+    for functional in ("SVWN", "BLYP", "B3LYP"):
+        for G in (None, 127, 128, 129, 12801):
+            idx = slice(None) if G is None else np.random.default_rng(G).permutation(wts.size)[:G]
+            p, w = np.ascontiguousarray(pts[:, idx]), np.ascontiguousarray(wts[idx])
+            assert G is None or w.size == G
+            tag = f"vxc.{functional}.{'whole' if G is None else G}"
+            eng.dft_setup(p, w, functional)
+            for rep in ("first", "second"):
+                keep(f"{tag}.restricted.{rep}", eng.dft_vxc(P))
+                keep(f"{tag}.unrestricted.{rep}", eng.dft_vxc_unrestricted(Pa, Pb))
+            eng.dft_clear()
+            eng.dft_setup(p, w, functional)
+            keep(f"{tag}.unrestricted.fresh", eng.dft_vxc_unrestricted(Pa, Pb))
+            keep(f"{tag}.restricted.fresh", eng.dft_vxc(P))
+            eng.dft_clear()
+
+
 def child_bits(path):
     from tuna_amd import dft
     from tuna_amd.engine import Engine
@@ -125,6 +158,7 @@ def child_bits(path):
         P0, E0 = guess(C0, T, V, 7, 2.0)
         rec("rks.n2_631g_blyp", lambda: eng.scf_rhf(S, T, V, P0, E0, 7, vnn, X=X, conv="extreme", hfx=f["hfx"], n_atom_ao=nao))
         eng.dft_clear()
+        direct_vxc(rec.out, eng, atoms)
 
         uhf = [("o2_sto3g", (["O", "O"], 1.2075, "STO-3G"), 9, 7, ("dynamic", "none")), ("o2_ccpvdz", (["O", "O"], 1.2075, "cc-pVDZ"), 9, 7, ("dynamic",)),
                ("li_631g", (["LI"], None, "6-31G"), 2, 1, ("dynamic", "none")), ("h_631g", (["H"], None, "6-31G"), 1, 0, ("dynamic", "none")),
@@ -195,6 +229,14 @@ def child_time():
         (Pa3, Ea3), (Pb3, Eb3) = guess(C3, T3, V3, 9, 1.0), guess(C3, T3, V3, 7, 1.0)
         timed("uks o2/cc-pvdz b3lyp", lambda: eng.scf_uks(S3, T3, V3, Pa3, Pb3, Ea3 + Eb3, 9, 7, vnn3, X=X3, conv="tight", damping="dynamic", hfx=f["hfx"],
                                                           n_atom_ao=nao3, max_iter=200))
+        eng.dft_clear()
+
+        atoms, shells = system(["C", "O"], 1.128, "def2-TZVP")     # BASELINE config 4
+        S4, T4, V4, D, X4, C4, nao4, vnn4 = prepare(eng, atoms, shells)
+        f = eng.dft_setup(*dft.integration_grid(atoms, "medium")[:2], "B3LYP")
+        P4, E4 = guess(C4, T4, V4, 7, 2.0)
+        timed("rks co/def2-tzvp b3lyp", lambda: eng.scf_rhf(S4, T4, V4, P4, E4, 7, vnn4, X=X4, conv="tight", damping="dynamic", hfx=f["hfx"],
+                                                            n_atom_ao=nao4, max_iter=200))
         eng.dft_clear()
     print(json.dumps(res))
 

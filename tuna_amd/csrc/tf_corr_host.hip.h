@@ -39,17 +39,7 @@ struct __attribute__((visibility("hidden"))) BlasAtomicsOff {
 #define CORR_BLAS_WHAT(what, call) do { if ((call) != rocblas_status_success) return corr_fail(ctx, TF_ELINALG, std::string(who) + ": " what " failed: " #call); } while (0)
 #define CORR_BLAS(call) CORR_BLAS_WHAT("rocBLAS", call)
 
-// out[q] = sum over the blocks, in block order, of d_part[block][q], q < k: the energies that are summed on the host
-static hipError_t sum_partials_host(const double *d_part, int nblk, int k, double *out)
-{
-    std::vector<double> part((size_t)k * nblk);
-    const hipError_t e = hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    for (int q = 0; q < k; ++q) out[q] = 0.0;
-    for (int b = 0; b < nblk; ++b)
-        for (int q = 0; q < k; ++q) out[q] += part[(size_t)k * b + q];
-    return hipSuccess;
-}
+// (sum_partials_host, the host sum of the blocks' partials in block order, is defined in tf_device.hip: the Kohn-Sham path uses it too)
 
 // launch_jk for nd <= 8 general (non-symmetric) densities P [nd][N][N] with J and K [nd][N][N]: all eight argument slots filled, the
 // slots past nd repeating the last density

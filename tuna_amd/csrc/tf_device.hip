@@ -362,6 +362,19 @@ static int upload(tf_ctx *ctx, const std::vector<T> &h, T **d, DeviceBlocks &own
     return TF_OK;
 }
 
+// out[q] = sum over the blocks, in block order, of d_part[block][q], q < k: the energies and
+// integrals that are summed on the host (tf_corr_host.hip.h, tf_excited_host.hip.h, tf_dft_host.hip.h)
+static hipError_t sum_partials_host(const double *d_part, int nblk, int k, double *out)
+{
+    std::vector<double> part((size_t)k * nblk);
+    const hipError_t e = hipMemcpy(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (int q = 0; q < k; ++q) out[q] = 0.0;
+    for (int b = 0; b < nblk; ++b)
+        for (int q = 0; q < k; ++q) out[q] += part[(size_t)k * b + q];
+    return hipSuccess;
+}
+
 // ---- RCCL, loaded on demand (include/tunafock.h: tf_comm_*) ------------------------------------------------------------------------
 namespace tfrccl {
 typedef struct { char internal[128]; } UniqueId;                // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128)
@@ -1010,106 +1023,7 @@ int tf_diagonalise(tf_ctx *ctx, int n, const double *F, const double *X, double 
 
 // ---- Kohn-Sham exchange-correlation (next row of the hot path: SURVEY.md section 8f rank 2) --------------------------
 
-int tf_dft_clear(tf_ctx *ctx)
-{
-    if (!ctx) return TF_EINVAL;
-    (void)hipSetDevice(ctx->device);
-    tfdft::release(ctx->grid);
-    return TF_OK;
-}
-
-int tf_dft_setup(tf_ctx *ctx, int64_t n_points, const double *xyz, const double *weights, int x_functional, int c_functional, double dfx,
-                 double dfc, double x_alpha)
-{
-    if (!ctx) return TF_EINVAL;
-    if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_dft_setup: call tf_build_eri first (it fixes the AO representation)");
-    if (n_points < 1 || !xyz || !weights || x_functional < 0 || x_functional > 3 || c_functional < 0 || c_functional > 5)
-        TF_FAIL(ctx, TF_EINVAL, "tf_dft_setup: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    tfdft::release(ctx->grid);
-    tfdft::Grid &g = ctx->grid;
-    const tf::Basis &bs = ctx->bs;
-    const int N = ctx->N;
-    const long long G = n_points;
-    g.G = G; g.N = N; g.xid = x_functional; g.cid = c_functional; g.dfx = dfx; g.dfc = dfc; g.x_alpha = x_alpha;
-    g.gga = (x_functional >= tfdft::X_B88) || (c_functional >= tfdft::C_LYP);
-    std::string err;
-    tfone::DevBuf buf;
-    tfone::DAO A = tfone::upload_aos(bs, buf, err);
-    if (!err.empty()) TF_FAIL(ctx, TF_ENODEVICE, "%s", err.c_str());
-    double *d_xyz = buf.alloc<double>((size_t)3 * G, err);
-    if (!err.empty()) TF_FAIL(ctx, TF_ENOMEM, "%s", err.c_str());
-    HIPCHK(ctx, hipMemcpy(d_xyz, xyz, (size_t)3 * G * sizeof(double), hipMemcpyHostToDevice));
-    const size_t GN = (size_t)G * N;
-    // (the grid's buffers are released by tfdft::release in tf_dft.hip.h with the runtime's own hipFree: they bypass this file's block cache)
-    HIPCHK(ctx, ::hipMalloc((void **)&g.w, (size_t)G * sizeof(double)));
-    HIPCHK(ctx, hipMemcpy(g.w, weights, (size_t)G * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.phi, GN * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.dphi, (g.gga ? 3 : 1) * GN * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.B, GN * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.D, GN * sizeof(double)));
-    for (double **p : {&g.rho, &g.vrho, &g.vsig, &g.ex, &g.ec}) HIPCHK(ctx, ::hipMalloc((void **)p, (size_t)G * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.grad, (size_t)3 * G * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.V, (size_t)(tfdft::VSPLIT + 2) * N * N * sizeof(double)));
-    HIPCHK(ctx, ::hipMalloc((void **)&g.part, (size_t)3 * tfdft::NPART * sizeof(double)));
-    tfdft::DAOs D{A.z, A.lmn, A.prim_off, A.exps, A.w};
-    hipLaunchKernelGGL(tfdft::ao_on_grid_kernel, dim3((unsigned)((GN + 127) / 128)), dim3(128), 0, 0, D, d_xyz, G, N, ctx->d_csr_ptr,
-                       ctx->d_csr_idx, ctx->d_csr_val, g.phi, g.dphi, g.gga ? 1 : 0);
-    HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipGetLastError());
-    std::string msg;
-    int rc = tfscf::ensure(ctx->scf, N, 6, msg);           // makes sure the rocBLAS handle exists
-    if (rc) { ctx->err = msg; return rc; }
-    return TF_OK;
-}
-
-int tf_dft_vxc(tf_ctx *ctx, const double *P, double *Vxc, double *n_elec, double *e_x, double *e_c)
-{
-    if (!ctx) return TF_EINVAL;
-    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc: call tf_dft_setup first");
-    if (!ctx->have_eri || ctx->grid.N != ctx->N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc: the grid was set up for a different tensor (call tf_build_eri, then tf_dft_setup again)");
-    if (!P || !Vxc) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nn = (size_t)ctx->N * ctx->N;
-    HIPCHK(ctx, hipMemcpy(ctx->jk.all.P, P, nn * sizeof(double), hipMemcpyHostToDevice));
-    std::string msg;
-    double o3[3];
-    int rc = tfdft::vxc(ctx->scf.blas, ctx->grid, ctx->jk.all.P, ctx->jk.all.J, o3, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    HIPCHK(ctx, hipMemcpy(Vxc, ctx->jk.all.J, nn * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_elec) *n_elec = o3[0];
-    if (e_x) *e_x = o3[1];
-    if (e_c) *e_c = o3[2];
-    return TF_OK;
-}
-
-int tf_dft_vxc_unrestricted(tf_ctx *ctx, const double *P_alpha, const double *P_beta, double *Vxc_alpha, double *Vxc_beta, double n_elec[2],
-                            double e_x[2], double *e_c)
-{
-    if (!ctx) return TF_EINVAL;
-    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: call tf_dft_setup first");
-    if (!ctx->have_eri || ctx->grid.N != ctx->N)
-        TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: the grid was set up for a different tensor (call tf_build_eri, then tf_dft_setup again)");
-    if (!P_alpha || !P_beta || !Vxc_alpha || !Vxc_beta) TF_FAIL(ctx, TF_EINVAL, "tf_dft_vxc_unrestricted: bad arguments");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    int rc = tfdft::ensure_spin(ctx->grid, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    const size_t nn = (size_t)ctx->N * ctx->N;
-    double *io = ctx->grid.sio;                                  // P_alpha, P_beta, V_alpha, V_beta
-    HIPCHK(ctx, hipMemcpy(io, P_alpha, nn * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(io + nn, P_beta, nn * sizeof(double), hipMemcpyHostToDevice));
-    double o5[5];
-    rc = tfdft::vxc_unrestricted(ctx->scf.blas, ctx->grid, io, io + nn, io + 2 * nn, io + 3 * nn, o5, msg);
-    if (rc) { ctx->err = msg; return rc; }
-    HIPCHK(ctx, hipMemcpy(Vxc_alpha, io + 2 * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(Vxc_beta, io + 3 * nn, nn * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_elec) { n_elec[0] = o5[0]; n_elec[1] = o5[1]; }
-    if (e_x) { e_x[0] = o5[2]; e_x[1] = o5[3]; }
-    if (e_c) *e_c = o5[4];
-    return TF_OK;
-}
+#include "tf_dft_host.hip.h"
 
 // ---- AO->MO transformation, MP2 ... CCSD(T), the MP2 density: the drivers of the correlated methods (consumers of the resident tensor) ----
 #include "tf_corr_host.hip.h"
@@ -1199,7 +1113,8 @@ int tf_scf_rhf(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     auto jk = [&](const double *dP, double *dJ, double *dK, hipStream_t st) { return cycle_jk(ctx, 1, dP, dP, dJ, dJ, dK, dK, st); };
     tfscf::XCFn xc;
     if (ctx->grid.G > 0) {
-        if (ctx->grid.N != ctx->N) TF_FAIL(ctx, TF_EINVAL, "tf_scf_rhf: the DFT grid was set up for a different AO dimension");
+        const int rc = dft_grid_checks(ctx, "tf_scf_rhf", "", true);
+        if (rc) return rc;
         xc = [&](const double *dP, double *dV, double *o3) { return tfdft::vxc(ctx->scf.blas, ctx->grid, dP, dV, o3, msg); };
     }
     ShardedCycleGuard guard(ctx);
@@ -1347,8 +1262,8 @@ int tf_scf_uks(tf_ctx *ctx, const tf_scf_opts *opts, const double *S, const doub
     if (!ctx->have_eri) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: call tf_build_eri first");
     if (!opts || !S || !T || !V || !P0_alpha || !P0_beta || !out || n_alpha < 1 || n_alpha > ctx->N || n_beta < 0 || n_beta > n_alpha)
         TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: bad arguments");
-    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: call tf_dft_setup first (unrestricted Hartree-Fock is tf_scf_uhf)");
-    if (ctx->grid.N != ctx->N) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: the DFT grid was set up for a different AO dimension");
+    const int rc = dft_grid_checks(ctx, "tf_scf_uks", " (unrestricted Hartree-Fock is tf_scf_uhf)", true);
+    if (rc) return rc;
     if (ctx->world > 1) TF_FAIL(ctx, TF_EINVAL, "tf_scf_uks: unrestricted Kohn-Sham runs on an unsharded tensor (world = 1) in this build");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::string msg;

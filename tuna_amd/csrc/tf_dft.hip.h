@@ -9,43 +9,17 @@
 // B3 :1462-1494, VWN :1512-1630 + :1802-1860, LYP :2200-2260, 3P :5843-5881), floors tuna_util.py:95-99.
 // For TD-DFT the second derivatives of the local-density functionals per grid point (xc_fpoint_kernel: Slater tuna_xc.py:5956-5983,
 // VWN3 :5994-6061, VWN5 :6151-6236, the factors of tuna_dft.py:1109-1124); their matrix elements are tf_xckernel.hip.h's.
+// Kernels and functional formulas only: the grid, its buffers and the split are tf_dft_plan.h's, every allocation and rocBLAS call
+// tf_dft_host.hip.h's.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rocblas/rocblas.h>
 
-#include <string>
-#include <vector>
-
-#include "../../include/tunafock.h"
-#include "tf_internal.h"
+#include "tf_dft_plan.h"
 
 namespace tfdft {
 
 enum { X_NONE = 0, X_SLATER = 1, X_B88 = 2, X_B3 = 3 };
 enum { C_NONE = 0, C_VWN5 = 1, C_VWN3 = 2, C_LYP = 3, C_3P_VWN5 = 4, C_3P_VWN3 = 5 };
-
-struct Grid {
-    long long G = 0;
-    int N = 0, xid = 0, cid = 0;
-    bool gga = false;
-    double dfx = 0, dfc = 0, x_alpha = 2.0 / 3.0;
-    double *w = nullptr, *phi = nullptr, *dphi = nullptr;        // [G], [G][N], [3][G][N]
-    double *B = nullptr, *D = nullptr;                           // [G][N]
-    double *rho = nullptr, *grad = nullptr, *vrho = nullptr, *vsig = nullptr, *ex = nullptr, *ec = nullptr;   // [G], [3][G], ...
-    double *V = nullptr, *part = nullptr;                        // [VSPLIT + 1][N][N] split-K partials of V, reduction partials
-    // unrestricted path (vxc_unrestricted), allocated on its first use: both spins side by side in every row
-    double *sP = nullptr, *sB = nullptr, *sD = nullptr;          // [N][2N] packed P_alpha|P_beta rows, [G][2N], [G][2N]
-    double *spt = nullptr, *sV = nullptr, *spart = nullptr;      // [SPT][G] per-point data, [VSPLIT + 2][N][2N], [5][NPART]
-    double *sio = nullptr;                                       // [4][N][N] host <-> device staging of tf_dft_vxc_unrestricted
-};
-
-inline void release(Grid &g)
-{
-    for (double *p : {g.w, g.phi, g.dphi, g.B, g.D, g.rho, g.grad, g.vrho, g.vsig, g.ex, g.ec, g.V, g.part, g.sP, g.sB, g.sD, g.spt, g.sV,
-                      g.spart, g.sio})
-        if (p) (void)hipFree(p);
-    g = Grid();
-}
 
 struct DAOs { const double *z; const int *lmn, *prim_off; const double *exps, *w; };
 
@@ -355,57 +329,6 @@ __global__ void sym_kernel(const double *__restrict__ tmp, double *__restrict__ 
     out[e] = (1.0 / 2.0) * (tmp[e] + tmp[(size_t)j * n + i]);
 }
 
-// V = Phi^T D contracts over ~10^5 grid points into an N x N matrix: as ONE GEMM rocBLAS runs it in a single workgroup (4.7 ms for CO /
-// def2-TZVP); split over the grid points into VSPLIT batch entries it fills the GPU, and the partials are added in fixed order.
-const int VSPLIT = 128;            // (512 partials of 200 grid points each cost more to add up -- 0.18 ms -- than the GEMM they split)
-
-#define TFD_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + " failed: " + hipGetErrorString(_e); return (_e == hipErrorOutOfMemory ? TF_ENOMEM : TF_ENODEVICE); } } while (0)
-#define TFD_BLAS(call) do { rocblas_status _s = (call); if (_s != rocblas_status_success) { msg = std::string(#call) + " failed (rocBLAS status " + std::to_string((int)_s) + ")"; return TF_ELINALG; } } while (0)
-
-const int NPART = 512;
-
-// V_XC (device, [N][N]) and the integrals {n_elec, E_X*dfx, E_C*dfc} for the device density dP
-inline int vxc(rocblas_handle blas, Grid &g, const double *dP, double *dVxc, double out3[3], std::string &msg)
-{
-    const int N = g.N;
-    const long long G = g.G;
-    const double one = 1.0, zero = 0.0;
-    // B (G x N, row-major) = Phi (G x N) * P (N x N)
-    TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none, N, (rocblas_int)G, N, &one, dP, N, g.phi, N, &zero, g.B, N));
-    hipLaunchKernelGGL(xc_density_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.B, g.gga ? 1 : 0, g.rho, g.grad);
-    hipLaunchKernelGGL(xc_point_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.gga ? 1 : 0, g.xid, g.cid,
-                       g.dfx, g.dfc, g.x_alpha, g.rho, g.grad, g.vrho, g.vsig, g.ex, g.ec);
-    hipLaunchKernelGGL(xc_dmat_kernel, dim3((unsigned)((G * N + 255) / 256)), dim3(256), 0, 0, G, N, g.w, g.phi, g.dphi, g.grad, g.vrho, g.vsig,
-                       g.gga ? 1 : 0, g.D);
-    // V (N x N, row-major) = Phi^T (N x G) * D (G x N), split over the grid points
-    {
-        const long long Kc = G / VSPLIT, rem = G - Kc * VSPLIT;
-        const size_t nn = (size_t)N * N;
-        int nparts = 0;
-        if (Kc > 0) {
-            TFD_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, N, N, (rocblas_int)Kc, &one, g.D, N,
-                                                   (rocblas_stride)(Kc * N), g.phi, N, (rocblas_stride)(Kc * N), &zero, g.V, N, (rocblas_stride)nn,
-                                                   VSPLIT));
-            nparts = VSPLIT;
-        }
-        if (rem > 0) {
-            TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_transpose, N, N, (rocblas_int)rem, &one, g.D + Kc * VSPLIT * N, N,
-                                   g.phi + Kc * VSPLIT * N, N, &zero, g.V + (size_t)nparts * nn, N));
-            ++nparts;
-        }
-        double *tmp = g.V + (size_t)(VSPLIT + 1) * nn;                  // (the slot behind the partials)
-        hipLaunchKernelGGL(sum_parts_kernel, dim3((N * N + 255) / 256), dim3(256), 0, 0, g.V, nparts, tmp, N * N);
-        hipLaunchKernelGGL(sym_kernel, dim3((N * N + 255) / 256), dim3(256), 0, 0, tmp, dVxc, N);
-    }
-    hipLaunchKernelGGL(xc_reduce_kernel, dim3(NPART), dim3(256), 0, 0, G, g.w, g.rho, g.ex, g.ec, g.part);
-    std::vector<double> h(3 * NPART);
-    TFD_HIP(hipMemcpy(h.data(), g.part, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    out3[0] = out3[1] = out3[2] = 0.0;
-    for (int b = 0; b < NPART; ++b) { out3[0] += h[3 * b]; out3[1] += h[3 * b + 1]; out3[2] += h[3 * b + 2]; }
-    out3[1] *= g.dfx; out3[2] *= g.dfc;
-    return TF_OK;
-}
-
 // ---- unrestricted (spin-polarised) path: calculate_unrestricted_exchange_correlation_matrix, tuna_scf.py:665-750 --------------------
 // Exchange of spin s is the closed-shell functional at (2 rho_s, 4 sigma_ss), integrated against rho_s (tuna_scf.py:467-468, :719-741);
 // correlation is the spin-polarised functional of (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb).  Per point and spin the D row is
@@ -523,9 +446,7 @@ __device__ inline XcSpin lyp_spin(double na, double nb, double n, double saa, do
     return o;
 }
 
-// per-point rows of Grid::spt ([SPT][G]): 0-1 rho_a, rho_b (raw, then floored); 2-4, 5-7 grad rho_a, grad rho_b; 8-9 v_rho_a, v_rho_b;
-// 10-12, 13-15 c_a, c_b; 16-18 e_X,a rho_a, e_X,b rho_b, e_C rho
-const int SPT = 19;
+// (the rows of the spin set's per-point array pt [SPT][G]: tf_dft_plan.h)
 
 // rho_s and grad rho_s of both spins from B2 = Phi [P_a | P_b]: sixteen lanes per grid point as xc_density_kernel, every Phi / grad Phi
 // element read once for both spins
@@ -776,72 +697,5 @@ __global__ void sym2_kernel(const double *__restrict__ tmp, double *__restrict__
     const long long r = q / N, c = q - r * N;
     (s ? Vb : Va)[q] = (1.0 / 2.0) * (tmp[r * 2 * N + s * N + c] + tmp[c * 2 * N + s * N + r]);
 }
-
-inline int ensure_spin(Grid &g, std::string &msg)
-{
-    if (g.sB) return TF_OK;
-    const size_t G = (size_t)g.G, N = (size_t)g.N, nn = N * N;
-    const size_t sizes[7] = {2 * nn, G * 2 * N, G * 2 * N, (size_t)SPT * G, (size_t)(VSPLIT + 2) * 2 * nn, (size_t)5 * NPART, 4 * nn};
-    double **ptrs[7] = {&g.sP, &g.sB, &g.sD, &g.spt, &g.sV, &g.spart, &g.sio};
-    for (int k = 0; k < 7; ++k) {
-        const hipError_t e = ::hipMalloc((void **)ptrs[k], sizes[k] * sizeof(double));
-        if (e != hipSuccess) {
-            for (int q = 0; q < 7; ++q) if (*ptrs[q]) { (void)hipFree(*ptrs[q]); *ptrs[q] = nullptr; }
-            msg = std::string("unrestricted V_XC buffers: hipMalloc failed: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? TF_ENOMEM : TF_ENODEVICE;
-        }
-    }
-    if (!g.gga) TFD_HIP(hipMemset(g.spt, 0, (size_t)SPT * G * sizeof(double)));   // (LDA: the gradient rows stay zero)
-    return TF_OK;
-}
-
-// V_XC^alpha, V_XC^beta (device, [N][N]) and {n_alpha, n_beta, E_X,alpha*DFX, E_X,beta*DFX, E_C*DFC} for the device densities dPa, dPb
-inline int vxc_unrestricted(rocblas_handle blas, Grid &g, const double *dPa, const double *dPb, double *dVa, double *dVb, double out5[5],
-                            std::string &msg)
-{
-    int rc = ensure_spin(g, msg);
-    if (rc) return rc;
-    const int N = g.N, N2 = 2 * g.N;
-    const long long G = g.G;
-    const size_t nn = (size_t)N * N;
-    const double one = 1.0, zero = 0.0;
-    hipLaunchKernelGGL(pack2_kernel, dim3((unsigned)((2 * nn + 255) / 256)), dim3(256), 0, 0, dPa, dPb, g.sP, N);
-    // B2 (G x 2N, row-major) = Phi (G x N) * [P_a | P_b] (N x 2N)
-    TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none, N2, (rocblas_int)G, N, &one, g.sP, N2, g.phi, N, &zero, g.sB, N2));
-    hipLaunchKernelGGL(xc_density2_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.sB, g.gga ? 1 : 0, g.spt);
-    hipLaunchKernelGGL(xc_point2_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.gga ? 1 : 0, g.xid, g.cid, g.dfx, g.dfc,
-                       g.x_alpha, g.spt);
-    hipLaunchKernelGGL(xc_dmat2_kernel, dim3((unsigned)((G * N + 255) / 256)), dim3(256), 0, 0, G, N, g.w, g.phi, g.dphi, g.spt,
-                       g.gga ? 1 : 0, g.sD);
-    // [N][2N] = (Phi^T D2)^T, split over the grid points as in vxc
-    {
-        const long long Kc = G / VSPLIT, rem = G - Kc * VSPLIT;
-        const size_t n2 = 2 * nn;
-        int nparts = 0;
-        if (Kc > 0) {
-            TFD_BLAS(rocblas_dgemm_strided_batched(blas, rocblas_operation_none, rocblas_operation_transpose, N2, N, (rocblas_int)Kc, &one, g.sD, N2,
-                                                   (rocblas_stride)(Kc * N2), g.phi, N, (rocblas_stride)(Kc * N), &zero, g.sV, N2, (rocblas_stride)n2,
-                                                   VSPLIT));
-            nparts = VSPLIT;
-        }
-        if (rem > 0) {
-            TFD_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_transpose, N2, N, (rocblas_int)rem, &one, g.sD + Kc * VSPLIT * N2,
-                                   N2, g.phi + Kc * VSPLIT * N, N, &zero, g.sV + (size_t)nparts * n2, N2));
-            ++nparts;
-        }
-        double *tmp = g.sV + (size_t)(VSPLIT + 1) * n2;
-        hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, g.sV, nparts, tmp, (int)n2);
-        hipLaunchKernelGGL(sym2_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, tmp, dVa, dVb, N);
-    }
-    hipLaunchKernelGGL(xc_reduce5_kernel, dim3(NPART), dim3(256), 0, 0, G, g.w, g.spt, g.spart);
-    std::vector<double> h(5 * NPART);
-    TFD_HIP(hipMemcpy(h.data(), g.spart, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int q = 0; q < 5; ++q) out5[q] = 0.0;
-    for (int b = 0; b < NPART; ++b)
-        for (int q = 0; q < 5; ++q) out5[q] += h[5 * b + q];
-    out5[2] *= g.dfx; out5[3] *= g.dfx; out5[4] *= g.dfc;
-    return TF_OK;
-}
-
 
 }  // namespace tfdft

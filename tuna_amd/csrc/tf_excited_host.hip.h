@@ -1,7 +1,8 @@
 // tf_excited_host.hip.h -- the host drivers of the excited states and the stability analysis: CIS / TDHF and TD-DFT / TDA on restricted
 // and unrestricted orbitals, the exchange-correlation kernel builds and their probes, RHF / UHF / RKS / UKS stability, and CIS(D).
 // Included by tf_device.hip after tf_corr_host.hip.h (one translation unit), whose shared pieces it uses: corr_fail, BlasAtomicsOff,
-// CorrSetup, corr_args, corr_begin, mo_transform_device, mo_vvoo_block, mp3_mo_blocks, corr_stamp, corr_secs, corr_stage_seconds.  Kernels:
+// CorrSetup, corr_args, corr_begin, mo_transform_device, mo_vvoo_block, mp3_mo_blocks, corr_stamp, corr_secs, corr_stage_seconds; from
+// tf_dft_host.hip.h: dft_grid_checks, ensure_spin and the density stages of V_XC (density_stage, density2_stage).  Kernels:
 // tf_cis.hip.h, tf_ucis.hip.h, tf_cisd.hip.h, tf_xckernel.hip.h, tf_dft.hip.h; work space: tf_excited_plan.h.  DESIGN.md section 4.5c; the
 // invariants of section 4.5a hold here too: every driver keeps its order of launches, rocBLAS / rocSOLVER calls and copies on the null stream.
 #pragma once
@@ -178,9 +179,8 @@ static const char *const XCK_C_NAMES[6] = {"none", "VWN5", "VWN3", "LYP", "3P (0
 // spin, and a finite hfx (the entry points that build the kernel matrices alone pass 0: nothing of theirs is scaled by it)
 static int xc_kernel_checks(tf_ctx *ctx, const char *who, const ExcXc &xc, int spins)
 {
-    if (ctx->grid.G <= 0) TF_FAIL(ctx, TF_EINVAL, "%s: call tf_dft_setup first (the exchange-correlation kernel is integrated on its grid)", who);
-    if (!ctx->have_eri || ctx->grid.N != ctx->N)
-        TF_FAIL(ctx, TF_EINVAL, "%s: the grid was set up for a different tensor (call tf_build_eri, then tf_dft_setup again)", who);
+    const int rc = dft_grid_checks(ctx, who, " (the exchange-correlation kernel is integrated on its grid)", false);
+    if (rc) return rc;
     const tfdft::Grid &g = ctx->grid;
     if (g.xid >= tfdft::X_B88 || g.cid >= tfdft::C_LYP)
         TF_FAIL(ctx, TF_EINVAL, "%s: the exchange-correlation kernel of exchange \"%s\" with correlation \"%s\" is not implemented: only the "
@@ -230,7 +230,7 @@ static int xc_orbital_windows(tf_ctx *ctx, const char *who, const CorrSetup &S, 
     if (hipMemcpy(Cw, hC.data(), hC.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
     const auto t0 = corr_stamp();
-    CORR_BLAS(tfmp3::gemm_rm(ctx->scf.blas, false, false, (int)ctx->grid.G, n, N, 1.0, ctx->grid.phi, N, Cw, n, 0.0, psi, n));
+    CORR_BLAS(tfmp3::gemm_rm(ctx->scf.blas, false, false, (int)ctx->grid.G, n, N, 1.0, ctx->grid.b(tfdft::GB_PHI), N, Cw, n, 0.0, psi, n));
     *t_end = corr_stamp();
     *t_psi += corr_secs(*t_end - t0);
     return TF_OK;
@@ -273,11 +273,10 @@ static int xc_kernel_build(tf_ctx *ctx, const char *who, const CorrSetup &S, con
     double t_psi = 0.0;
     int rc = xc_orbital_windows(ctx, who, S, Cw, psi, &t_psi, &t1);
     if (rc) return rc;
-    // rho through the path of V_XC: B = Phi P, rho_g = <B_g, Phi_g>; then the point kernels
-    CORR_BLAS(tfmp3::gemm_rm(blas, false, false, (int)G, N, N, 1.0, g.phi, N, ctx->jk.all.P, N, 0.0, g.B, N));
-    hipLaunchKernelGGL(tfdft::xc_density_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.B, 0, g.rho, g.grad);
-    hipLaunchKernelGGL(tfdft::xc_fpoint_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha, g.rho, g.w,
-                       u, u + G, fp);
+    // rho through the density stage of V_XC (its GEMM is the rocblas_dgemm call tfmp3::gemm_rm made here); then the point kernels
+    CORR_BLAS(tfdft::density_stage(blas, g, ctx->jk.all.P, 0));
+    hipLaunchKernelGGL(tfdft::xc_fpoint_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha,
+                       g.b(tfdft::GB_RHO), g.b(tfdft::GB_W), u, u + G, fp);
     const auto t2 = corr_stamp();
     seconds4[0] = t_psi; seconds4[1] = corr_secs(t2 - t1);
     if ((rc = xc_kernel_matrices(ctx, who, G, o, v, psi, u, u + G, mem, KS, KT, seconds4 + 2))) return rc;
@@ -648,8 +647,9 @@ static int xc_kernel_spin_build(tf_ctx *ctx, const char *who, const UcisSetup &U
                  "%lld x %d orbital values)", who, (double)(dd + (size_t)G * (n[0] + n[1] + 10) + (size_t)N * nmax) * sizeof(double) / 1e9, U.dim, G, n[0] + n[1]);
         return corr_fail(ctx, TF_ENOMEM, text);
     }
-    if (hipMemcpy(g.sio, Pa, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(g.sio + nn, Pb, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+    double *io = g.s(tfdft::GS_IO);
+    if (hipMemcpy(io, Pa, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(io + nn, Pb, nn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return corr_fail(ctx, TF_ENODEVICE, std::string(who) + ": copy failed");
     BlasAtomicsOff no_atomics(blas);
     double t_psi = 0.0;
@@ -660,16 +660,10 @@ static int xc_kernel_spin_build(tf_ctx *ctx, const char *who, const UcisSetup &U
         if ((rc = xc_orbital_windows(ctx, who, U.s[s], Cw, psi[s], &t_psi, &t_end))) return rc;
     }
     const auto t1 = corr_stamp();
-    // rho_a, rho_b through the path of the unrestricted V_XC: B2 = Phi [P_a | P_b], rho_s(g) = <B2_s(g), Phi(g)>; then the point kernels
-    {
-        const double one = 1.0, zero = 0.0;
-        const int N2 = 2 * N;
-        hipLaunchKernelGGL(tfdft::pack2_kernel, dim3((unsigned)((2 * nn + 255) / 256)), dim3(256), 0, 0, g.sio, g.sio + nn, g.sP, N);
-        CORR_BLAS(rocblas_dgemm(blas, rocblas_operation_none, rocblas_operation_none, N2, (rocblas_int)G, N, &one, g.sP, N2, g.phi, N, &zero, g.sB, N2));
-        hipLaunchKernelGGL(tfdft::xc_density2_kernel, dim3((unsigned)((G + 15) / 16)), dim3(256), 0, 0, G, N, g.phi, g.dphi, g.sB, 0, g.spt);
-        hipLaunchKernelGGL(tfdft::xc_fpoint2_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha, g.spt, g.w,
-                           u, fp);
-    }
+    // rho_a, rho_b through the spin density stage of the unrestricted V_XC; then the point kernels
+    CORR_BLAS(tfdft::density2_stage(blas, g, io, io + nn, 0));
+    hipLaunchKernelGGL(tfdft::xc_fpoint2_kernel, dim3((unsigned)((G + 127) / 128)), dim3(128), 0, 0, G, g.xid, g.cid, g.dfx, g.dfc, g.x_alpha,
+                       g.s(tfdft::GS_PT), g.b(tfdft::GB_W), u, fp);
     const auto t2 = corr_stamp();
     seconds4[0] = t_psi; seconds4[1] = corr_secs(t2 - t1);
     rc = xc_kernel_spin_matrices(ctx, who, G, o, v, psi, u, mem, K, seconds4 + 2);
