@@ -801,7 +801,7 @@ int tf_eigh_probe(tf_ctx *ctx, int n, int variant, int reps, double *seconds);
 
 /* Counters of the context's eigensolver paths since tf_create (instrumentation, tests): out[0] solves by eigenvector refinement,
  * out[1] refinement steps, out[2] refinements that fell back to a full eigensolve, out[3] eigensolves done block by block
- * (the x/y parity classes of a diatomic solved together, tf_scf.hip.h: eigh_blocked), out[4] eigensolves where the matrix did not
+ * (the x/y parity classes of a diatomic solved together, tf_eigh.hip.h: eigh_blocked), out[4] eigensolves where the matrix did not
  * have the block structure, or a block solve did not converge, and the full matrix was solved, out[5] full-matrix Jacobi solves that did
  * not converge in their sweep cap and were solved again by dsyevd.  A solve that fails on every path (non-finite input, dsyevd not
  * converging) is an error, TF_ELINALG. */

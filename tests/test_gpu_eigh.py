@@ -1,4 +1,4 @@
-"""GPU: every path of the symmetric eigensolver (tf_scf.hip.h: eigh, eigh_blocked; tf_jacobi.hip.h) against LAPACK (numpy.linalg.eigh),
+"""GPU: every path of the symmetric eigensolver (tf_eigh.hip.h: eigh, eigh_blocked; tf_jacobi.hip.h) against LAPACK (numpy.linalg.eigh),
 reached through tf_diagonalise with X = I (eps, C = eigh(A)) -- np.linalg.eigh in diagonalise_Fock_matrix (scf:244).
 
 Paths: the in-LDS Jacobi on the full matrix (2 <= n <= 64), rocsolver_dsyevd (n = 1, n > 64), the batched in-LDS Jacobi over the x/y parity
@@ -401,3 +401,62 @@ def test_jacobi_that_does_not_converge_is_not_a_result():
     assert s1["blocked_declined"] == s0["blocked_declined"] + 1 and s1["blocked_solves"] == s0["blocked_solves"]
     msg, code_ = out["cycle"]
     assert code_ == -5 and "did not converge" in msg, out["cycle"]
+
+
+# ---- one context across sizes and spins -----------------------------------------------------------------------------------------
+def test_one_context_across_sizes_and_spins():
+    """What the eigensolver keeps between calls (tables of the parity blocks, grow-only blocks, the refinement start of each spin) must
+    not leak from one problem into the next: one context runs RHF on N2/cc-pVTZ (n = 60: blocked Jacobi, in-LDS refinement), RHF on
+    Ar2/cc-pVQZ (n = 118: blocks <= 64, blocked refinement), UHF on the O2 triplet in cc-pVDZ (both spin slots), RHF on N2/STO-3G
+    (n = 10: tables and blocks shrink) and N2/cc-pVTZ again, with set_basis and build_eri between them; every run equals the same run on
+    a fresh context: iteration count, `converged`, the eigensolver's path counters, and the energy within the bar
+    tests/test_host_logic.py has for the lockstep batch (1e-10)."""
+    from conftest import atom_arrays, make_system, make_uhf_system
+    from tuna_amd.engine import Engine
+
+    def run(eng, tag):
+        if tag.startswith("o2_"):
+            atoms, shells, aos, na, nb = make_uhf_system(tag)
+        else:
+            atoms, shells, aos, na = make_system(tag)
+            nb = None
+        eng.set_basis(aos).build_eri(True)
+        xyz, chg, org = atom_arrays(atoms)
+        S, T, V, _, _ = eng.one_electron(xyz, chg, org, spherical=True)
+        X, _, _ = eng.orthogonaliser(S)
+        _, C0 = eng.diagonalise(T + V, X)
+        nao = [sum(s.n_sph for s in shells if s.atom == a) for a in range(len(atoms))]
+        vnn = mol.nuclear_repulsion(atoms)
+        conv = "extreme" if eng.N <= 64 else "tight"
+        s0 = eng.eigh_stats()
+        if nb is None:
+            P0 = 2.0 * C0[:, :na] @ C0[:, :na].T
+            P0 = 0.5 * (P0 + P0.T)
+            r = eng.scf_rhf(S, T, V, P0, float(np.sum(P0 * (T + V))), na, vnn, X=X, conv=conv, damping="dynamic", n_atom_ao=nao)
+        else:
+            Pa, Pb = C0[:, :na] @ C0[:, :na].T, C0[:, :nb] @ C0[:, :nb].T
+            r = eng.scf_uhf(S, T, V, 0.5 * (Pa + Pa.T), 0.5 * (Pb + Pb.T), float(np.sum((Pa + Pb) * (T + V))), na, nb, vnn, X=X, conv=conv,
+                            damping="dynamic", n_atom_ao=nao)
+        s1 = eng.eigh_stats()
+        return eng.N, r, {k: s1[k] - s0[k] for k in s0}
+
+    # tag, n, blocked solves expected
+    order = (("c2_n2_ccpvtz", 60, True), ("c3_ar2_ccpvqz", 118, True), ("o2_triplet_ccpvdz", 28, False), ("n2_sto3g", 10, False),
+             ("c2_n2_ccpvtz", 60, True))
+    fresh = {}
+    for tag, _, _ in order:
+        if tag not in fresh:                                      # the reference runs: computed once, left unchanged
+            with Engine(0) as e:
+                fresh[tag] = run(e, tag)
+    with Engine(0) as eng:
+        for tag, n, blocked in order:
+            N, r, paths = run(eng, tag)
+            N0, r0, paths0 = fresh[tag]
+            dE = abs(r["energy"] - r0["energy"])
+            print(f"{tag}: n {N}, {r['n_iter']} iterations, |dE| {dE:.3e} ({'equal to the last bit' if r['energy'] == r0['energy'] else 'NOT bit-equal'}), {paths}")
+            assert N == N0 == n
+            assert r["converged"] and r0["converged"] and r["n_iter"] == r0["n_iter"], (tag, r["n_iter"], r0["n_iter"])
+            assert dE < 1e-10, (tag, r["energy"], r0["energy"])
+            assert paths == paths0, (tag, paths, paths0)
+            assert paths["refined_solves"] > 0, (tag, paths)
+            assert (paths["blocked_solves"] > 0) == blocked, (tag, paths)

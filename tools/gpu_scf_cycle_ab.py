@@ -10,7 +10,10 @@ non-zero or is killed by its time limit and starts nothing after it.
                        max_diis 2 and 6, DIIS off, a field term and a run cut off at max_iter = 3; N2/cc-pVTZ once more on tiles; one RKS run
                        (N2/6-31G, BLYP) and, on the same tensor, tf_dft_vxc and tf_dft_vxc_unrestricted themselves (SVWN, BLYP, B3LYP; the loose
                        grid whole and cut to 127, 128, 129 and 12 801 points; each call twice and once after a fresh set-up); UHF on the O2 triplet (STO-3G, cc-pVDZ), the Li doublet, the H atom and the Li quartet (both n_beta = 0) in 6-31G and,
-                       above n = 64, the NO doublet in cc-pVQZ with damping on and off; UKS on the golden O2 triplet B3LYP/STO-3G; a lockstep
+                       above n = 64, the NO doublet in cc-pVQZ with damping on and off and the Ar2+ doublet in cc-pVQZ (118; blocks <= 64: the
+                       blocked refinement in both spin slots); tf_orthogonaliser and tf_diagonalise themselves on a context without a tensor
+                       (n = 2, 33, 64, 65, 100) and on the n40_blocked, mmax64 and mmax65 tensors of tests/test_gpu_eigh.py with class-diagonal
+                       random matrices of a fixed seed, each call twice; UKS on the golden O2 triplet B3LYP/STO-3G; a lockstep
                        batch of three field cycles.  Every run also records what tf_eigh_stats and tf_jk_path_stats counted during it.
                        LIB_A runs twice (A, A'): B is compared byte for byte with A on every array on which A and A' agree byte for
                        byte.  Only arrays of the lockstep batch may be left out that way; those are compared with the tolerance
@@ -132,11 +135,59 @@ def direct_vxc(out, eng, atoms):
             eng.dft_clear()
 
 
+# the parity-block configurations of tests/test_gpu_eigh.py: (s, p, d, f) shells of an even-tempered basis on N and on O
+EIGH_CONFIGS = {"n40_blocked": ((5, 3, 1, 0), (7, 3, 1, 0)), "mmax64": ((20, 12, 0, 0), (20, 12, 0, 0)), "mmax65": ((20, 12, 0, 0), (21, 12, 0, 0))}
+
+
+def direct_eigh(rec, eng, tag, mats):
+    """tf_orthogonaliser and tf_diagonalise themselves (X = 1: eps, C of the matrix; then X = S^-1/2 of a positive matrix), each call
+    twice: a second solve on tables and blocks that the first one left"""
+    for k, A in enumerate(mats):
+        n = A.shape[0]
+        S = A @ A.T / n + 1e-2 * np.eye(n)
+        S = 0.5 * (S + S.T)
+        for rep in ("first", "second"):
+            rec(f"eigh.{tag}.{k}.diagonalise.{rep}", lambda: dict(zip(("eps", "C"), eng.diagonalise(A, np.eye(n)))))
+            rec(f"eigh.{tag}.{k}.orthogonaliser.{rep}", lambda: dict(zip(("X", "smallest", "S_inv"), eng.orthogonaliser(S))))
+        X = eng.orthogonaliser(S)[0]
+        rec(f"eigh.{tag}.{k}.diagonalise.X", lambda: dict(zip(("eps", "C"), eng.diagonalise(A, X))))
+
+
+def child_eigh(out, paths):
+    from tuna_amd import molecule as mol
+    from tuna_amd.engine import Engine
+    rng = np.random.default_rng(4)
+    with Engine(0) as eng:                                        # no tensor: no symmetry offered, the full-matrix paths
+        rec = Recorder(eng)
+        for n in (2, 33, 64, 65, 100):
+            g = rng.standard_normal((n, n))
+            direct_eigh(rec, eng, f"plain.n{n}", [0.5 * (g + g.T)])
+        out.update(rec.out); paths.update(rec.paths)
+    for name, (ca, cb) in EIGH_CONFIGS.items():                   # a tensor's parity classes: class-diagonal matrices go block by block
+        atoms = mol.make_atoms(["N", "O"], 2.2)
+        shells = mol.build_shells(atoms, {7: mol.even_tempered_basis(*ca), 8: mol.even_tempered_basis(*cb)})
+        with Engine(0) as eng:
+            rec = Recorder(eng)
+            eng.set_basis(mol.expand_cartesian_aos(shells)).build_eri(True)
+            U, lmn = eng.sph_matrix(), np.asarray(eng.aos.lmn)
+            c_cart = (lmn[:, 0] & 1) | ((lmn[:, 1] & 1) << 1)
+            cls = np.array([c_cart[np.flatnonzero(np.abs(U[i]) > 1e-12)[0]] for i in range(U.shape[0])])
+            mats = []
+            for _ in range(2):
+                g = rng.standard_normal((eng.N, eng.N))
+                mats.append(0.5 * (g + g.T) * (cls[:, None] == cls[None, :]))
+            direct_eigh(rec, eng, name, mats)
+            out.update(rec.out); paths.update(rec.paths)
+
+
 def child_bits(path):
     from tuna_amd import dft
     from tuna_amd.engine import Engine
+    eigh_out, eigh_paths = {}, {}
+    child_eigh(eigh_out, eigh_paths)
     with Engine(0) as eng:
         rec = Recorder(eng)
+        rec.out.update(eigh_out); rec.paths.update(eigh_paths)
         sizes = [("n2_sto3g", system(["N", "N"], 1.0977, "STO-3G"), 7, "extreme"), ("n2_ccpvdz", system(["N", "N"], 1.0977, "cc-pVDZ"), 7, "extreme"),
                  ("n2_ccpvtz", system(["N", "N"], 1.0977, "cc-pVTZ"), 7, "extreme"), ("ar2_ccpvqz", system(["AR", "AR"], 3.76, "cc-pVQZ"), 18, "tight"),
                  ("synth200", synthetic(200), 18, "tight")]
@@ -163,7 +214,8 @@ def child_bits(path):
         uhf = [("o2_sto3g", (["O", "O"], 1.2075, "STO-3G"), 9, 7, ("dynamic", "none")), ("o2_ccpvdz", (["O", "O"], 1.2075, "cc-pVDZ"), 9, 7, ("dynamic",)),
                ("li_631g", (["LI"], None, "6-31G"), 2, 1, ("dynamic", "none")), ("h_631g", (["H"], None, "6-31G"), 1, 0, ("dynamic", "none")),
                ("li_quartet_631g", (["LI"], None, "6-31G"), 3, 0, ("dynamic",)),
-               ("no_ccpvqz", (["N", "O"], 1.151, "cc-pVQZ"), 8, 7, ("dynamic", "none"))]
+               ("no_ccpvqz", (["N", "O"], 1.151, "cc-pVQZ"), 8, 7, ("dynamic", "none")),
+               ("ar2plus_ccpvqz", (["AR", "AR"], 3.76, "cc-pVQZ"), 18, 17, ("dynamic",))]   # blocks <= 64: the blocked refinement in both spin slots
         for tag, spec, na, nb, dampings in uhf:
             atoms, shells = system(*spec)
             S, T, V, D, X, C0, nao, vnn = prepare(eng, atoms, shells)

@@ -1050,7 +1050,7 @@ int tf_jk_path_stats(tf_ctx *ctx, int64_t out[2])
 int tf_eigh_stats(tf_ctx *ctx, int64_t out[6])
 {
     if (!ctx || !out) return TF_EINVAL;
-    const tfscf::Workspace &w = ctx->scf;
+    const tfscf::EigState &w = ctx->scf.eig;
     out[0] = w.ref_solves; out[1] = w.ref_steps; out[2] = w.ref_fallbacks; out[3] = w.sym_solves; out[4] = w.sym_declined;
     out[5] = w.jac_fallbacks;
     return TF_OK;

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(TFJ_THREADS) void jacobi_eigh_kernel(int n, double 
                                                                   int max_sweeps, int *__restrict__ info,
                                                                   const int *__restrict__ sizes = nullptr, long long stride = 0, int vstride = 0)
 {
-    // a batch (the symmetry blocks of a matrix, tf_scf.hip.h: eigh_blocked): workgroup b solves the sizes[b] x sizes[b] matrix at
+    // a batch (the symmetry blocks of a matrix, tf_eigh.hip.h: eigh_blocked): workgroup b solves the sizes[b] x sizes[b] matrix at
     // W + b stride (compact: leading dimension sizes[b]); values at vals + b vstride, info[b]
     if (sizes) {
         const long long off = (long long)blockIdx.x * stride;

@@ -1,5 +1,5 @@
 // tf_refine.hip.h -- eigenvector refinement for the small matrices of the SCF cycle (n <= 64) in ONE launch, everything in LDS.
-// Same algorithm as tfscf::ref_refine (tf_scf.hip.h: Newton-Schulz orthonormalisation + first-order rotation, after Ogita &
+// Same algorithm as tfscf::ref_refine (tf_eigh.hip.h: Newton-Schulz orthonormalisation + first-order rotation, after Ogita &
 // Aishima 2018), but the five matrix products of a step run inside one workgroup on LDS-resident matrices -- one 16 x 16 tile per
 // wave on the FP64 matrix core (V_MFMA_F64_16X16X4_F64) -- and the convergence
 // test stays on the device: a whole solve is one kernel and one 4-byte status read, against ~60 rotation rounds with a barrier each
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(TFR_THREADS) void refine_lds_kernel(int n, int n_oc
                                                                  const int *__restrict__ sizes = nullptr, const int *__restrict__ noccs = nullptr,
                                                                  long long stride = 0, int vstride = 0)
 {
-    // a batch (the symmetry blocks of a larger matrix, tf_scf.hip.h: ref_refine_blocks): workgroup b refines the sizes[b] vectors of
+    // a batch (the symmetry blocks of a larger matrix, tf_eigh.hip.h: ref_refine_blocks): workgroup b refines the sizes[b] vectors of
     // block b (compact, leading dimension sizes[b]) against its block of A, with noccs[b] of them occupied; status[2 b], [2 b + 1]
     if (sizes) {
         const long long off = (long long)blockIdx.x * stride;
