@@ -13,7 +13,8 @@ through TUNAFOCK_LIB.
                        tf_eri_timings for equality.  one_p, deep_p, high_l, n2_ccpvdz (tests/eri_shapes.py) and N2/cc-pVTZ on packed,
                        tiles and rows, spherical and Cartesian, TF_ERI_MODE=class and generic, each also with TF_SLAB_ROWS=1; then a
                        child each (packed) for TF_ERI_TEAMC=1, TF_ERI_TEAM=0, TF_ERI_GENERIC_OLD=1, TF_ERI_FAMILIES=1
-                       TF_ERI_BRA_FAMILIES=1 and TF_ERI_NOFACT=1.  LIB_A runs twice (A, A'): B must equal A wherever A equals A'.
+                       TF_ERI_BRA_FAMILIES=1 and TF_ERI_NOFACT=1.  Per basis also tf_one_electron (S, T, V, D, Q), tf_cross_overlap and
+                       tf_eri_element, hashed together.  LIB_A runs twice (A, A'): B must equal A wherever A equals A'.
 Every child runs under its own time limit (--limit); the first child that fails or is killed ends the run, nothing is started after it.
 """
 import argparse
@@ -53,6 +54,7 @@ COUNTS = ("shell_quartets", "primitive_shell_quartets", "component_quartets", "n
 def child_bits(path, layouts):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
     import eri_shapes as es
     from tuna_amd import molecule as mol
     from tuna_amd.engine import Engine
@@ -64,6 +66,14 @@ def child_bits(path, layouts):
             else:
                 aos = es.system(tag)[2]
             eng.set_basis(aos)
+            # the entry points that need a basis and no tensor: tf_one_electron, tf_cross_overlap, tf_eri_element
+            z = sorted({float(o[2]) for o in aos.origin})
+            one = eng.one_electron([[0.0, 0.0, v] for v in z], [7.0] * len(z), [0.0, 0.0, 0.5 * z[-1]], spherical=False)
+            n0 = int(aos.prim_off[1])                                         # (the first AO four times over)
+            first4 = mol.AOList(aos.origin[:1].repeat(4, 0), aos.lmn[:1].repeat(4, 0), aos.nprim[:1].repeat(4), (n0 * np.arange(5)).astype(np.int32),
+                                np.tile(aos.exps[:n0], 4), np.tile(aos.coefs[:n0], 4))
+            h = hashlib.sha256(b"".join(m.tobytes() for m in one) + eng.cross_overlap(aos).tobytes() + np.float64(eng.eri_element(first4)).tobytes())
+            out[f"{tag}.basis_entry_points"] = {"sha256": h.hexdigest(), "bytes": 0, "stats": {}, "counts": {}}
             for layout in layouts:
                 for spherical in (True, False):
                     for mode in ("class", "generic"):

@@ -10,7 +10,7 @@
 
 static const int CORR_NBLK = 1024;     // blocks of the energy and update kernels: their partials are summed in block order
 
-// (DeviceBlocks, the owner of the device allocations of one call -- freed on every return path -- is defined in tf_device.hip)
+// (DeviceBlocks, the owner of the device allocations of one call -- freed on every return path -- is defined in tf_ctx.hip.h)
 
 // "set ctx->err, return the code"; m may be ctx->err itself (a callee's message passed on)
 static int corr_fail(tf_ctx *ctx, int code, const std::string &m)
@@ -39,7 +39,7 @@ struct __attribute__((visibility("hidden"))) BlasAtomicsOff {
 #define CORR_BLAS_WHAT(what, call) do { if ((call) != rocblas_status_success) return corr_fail(ctx, TF_ELINALG, std::string(who) + ": " what " failed: " #call); } while (0)
 #define CORR_BLAS(call) CORR_BLAS_WHAT("rocBLAS", call)
 
-// (sum_partials_host, the host sum of the blocks' partials in block order, is defined in tf_device.hip: the Kohn-Sham path uses it too)
+// (sum_partials_host, the host sum of the blocks' partials in block order, is defined in tf_ctx.hip.h: the Kohn-Sham path uses it too)
 
 // launch_jk for nd <= 8 general (non-symmetric) densities P [nd][N][N] with J and K [nd][N][N]: all eight argument slots filled, the
 // slots past nd repeating the last density
@@ -142,10 +142,7 @@ static void corr_permute(tf_ctx *ctx, CorrSetup &S)
 // The work space of the short-index-first transformations, kept by the context: grown when a call needs more.  false: out of memory
 static bool grow_mo_pool(tf_ctx *ctx, size_t need)
 {
-    if (need <= ctx->mo_pool_bytes) return true;
-    if (ctx->mo_pool) { (void)tf_free(ctx->mo_pool); ctx->mo_pool = nullptr; ctx->mo_pool_bytes = 0; }
-    if (tf_malloc((void **)&ctx->mo_pool, need) != hipSuccess) { ctx->mo_pool = nullptr; (void)hipGetLastError(); return false; }
-    ctx->mo_pool_bytes = need;
+    if (ctx->blk.ensure(CB_MO_POOL, need) != 0) { (void)hipGetLastError(); return false; }
     return true;
 }
 
@@ -188,10 +185,10 @@ static int mo_transform_device(tf_ctx *ctx, const double *C1, int n1, const doub
         if (q1_allowed && nk[c] <= 32 && nk[a] <= 32 && (size_t)N * ((nk[a] + 1) & ~1) * sizeof(double) + (size_t)N * sizeof(int) <= ((size_t)150 << 10)) {
             const size_t need = tfmp2::q1_pool_doubles(N, ctx->n_rows, nk[a], nk[b], nk[c], nk[d]) * sizeof(double);
             size_t free_b = 0, total_b = 0;
-            const bool fits = need <= ctx->mo_pool_bytes || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + ((size_t)2 << 30) <= free_b + ctx->mo_pool_bytes + tfcache::cached());
+            const bool fits = need <= ctx->blk.cap[CB_MO_POOL] || (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + ((size_t)2 << 30) <= free_b + ctx->blk.cap[CB_MO_POOL] + tfcache::cached());
             if (fits && grow_mo_pool(ctx, need)) {
-                int r = tfmp2::transform_q1(ctx->scf.blas, ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
-                                            dC[a], nk[a], dC[b], nk[b], dC[c], nk[c], dC[d], nk[d], dst, ctx->mo_pool, &s1, msg);
+                int r = tfmp2::transform_q1(ctx->scf.blas, ctx->d_eri(), ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
+                                            dC[a], nk[a], dC[b], nk[b], dC[c], nk[c], dC[d], nk[d], dst, ctx->mo_pool(), &s1, msg);
                 secs += s1;
                 return r;
             }
@@ -202,7 +199,7 @@ static int mo_transform_device(tf_ctx *ctx, const double *C1, int n1, const doub
             for (int q = 0; q < 5; ++q) pr.class_row_off[q] = ctx->class_row_off[q];
             pr.d_class_rows = ctx->d_class_rows; pr.d_row_pos = ctx->d_row_pos;
         }
-        int r = tfmp2::transform(ctx->scf.blas, ctx->d_eri, ctx->d_rowmap, (packed && !tiles) ? ctx->d_rowoff : nullptr, ctx->d_rowsec, ctx->bl, pr,
+        int r = tfmp2::transform(ctx->scf.blas, ctx->d_eri(), ctx->d_rowmap, (packed && !tiles) ? ctx->d_rowoff : nullptr, ctx->d_rowsec, ctx->bl, pr,
                                  ctx->d_row_ij, ctx->n_rows, N, ctx->ld, dC[a], nk[a], dC[b], nk[b], dC[c], nk[c], dC[d], nk[d], dst, &s1, msg,
                                  tiles ? &ctx->tv : nullptr);
         secs += s1;
@@ -369,9 +366,9 @@ int tf_mp2_uhf(tf_ctx *ctx, int n_alpha, int n_beta, int n_frozen_alpha, int n_f
         int prc = ok ? TF_OK : TF_ENOMEM;
         for (int s = 0; s < 2 && prc == TF_OK; ++s) {          // ket spin a: G_L(aa|aa), G_L(bb|aa); ket spin b: G_L(aa|bb), G_L(bb|bb)
             if ((s ? ob : oa) == 0) continue;
-            prc = tfmp2::ump2_spin_pass(ctx->scf.blas, ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
+            prc = tfmp2::ump2_spin_pass(ctx->scf.blas, ctx->d_eri(), ctx->d_rowoff, ctx->d_rowsec, ctx->bl, ctx->d_row_ij, ctx->d_rowmap, ctx->n_rows, N,
                                         dCbra, oa, ob, dCva, va, dCvb, vb, s ? dCob : dCoa, s ? ob : oa, s ? dCvb : dCva, s ? vb : va,
-                                        s ? Gab : Gaa, s ? Gbb : Gba, ctx->mo_pool, msg);
+                                        s ? Gab : Gaa, s ? Gbb : Gba, ctx->mo_pool(), msg);
         }
         if (ctx->world > 1) {
             // the L-transforms are linear in the rows a rank owns: sum them before the quadratic energy step.  A rank whose part failed
@@ -429,7 +426,7 @@ static bool mp3_ladder_batch(tf_ctx *ctx, const double *Tm, int nb, double *Tt, 
     int csize[4];
     for (int q = 0; q < 4; ++q) csize[q] = ctx->hl.csize[q];
     hipLaunchKernelGGL(tfmp3::mp3_pairs_last_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 1 << 16)), dim3(256), 0, 0, Tm, N, nb, Tt);
-    tfmp3::LadderArgs LA{ctx->d_eri, ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, tfmp3::ladder_blocks(csize)};
+    tfmp3::LadderArgs LA{ctx->d_eri(), ctx->d_rowoff, ctx->d_rowsec, ctx->d_row_ij, ctx->d_rowmap, Tt, Zh, nb, tfmp3::ladder_blocks(csize)};
     tfmp3::launch_ladder(LA, ctx->bl, N, 0);
     return hipGetLastError() == hipSuccess;
 }

@@ -1,5 +1,5 @@
 // tf_dbasis.hip.h -- device view of the basis (shells, shell pairs, per-pair tables) shared by the translation units that hold
-// ERI kernels (tf_device.hip and tf_eri_team.hip).
+// ERI kernels (tf_device.hip and tf_eri_team.hip).  Its plain records DShell and DPair are in tf_eri_types.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -8,16 +8,6 @@
 #include "tf_eri_types.h"
 
 namespace tfk {
-
-struct DShell { int L, ncomp, comp_off, cart_off; };
-struct DPair {
-    int A, B, La, Lb, npp, pp_off, nE, cls;
-    long long e_off;
-    int nca, ncb, compoff_a, compoff_b, cartoff_a, cartoff_b;
-    int outoff_a, outoff_b;      // first OUTPUT AO (spherical, or Cartesian for CARTHARM) of the two shells; set by tf_build_eri
-    int tab_off;                 // component-pair tables of this pair in DBasis::ct_* (nca * ncb entries)
-    int pcls[5];                 // ct_ord: component pairs ordered by (x, y) parity class; class c is [pcls[c], pcls[c + 1])
-};
 
 struct DBasis {
     const DShell *shells;

@@ -13,7 +13,7 @@ static inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? TF_
 #define TFD_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { msg = std::string(#call) + " failed: " + hipGetErrorString(_e); return tfdft::hip_code(_e); } } while (0)
 #define TFD_BLAS(call) do { rocblas_status _s = (call); if (_s != rocblas_status_success) { msg = std::string(#call) + " failed (rocBLAS status " + std::to_string((int)_s) + ")"; return TF_ELINALG; } } while (0)
 
-// The grid's blocks come from the runtime's own hipMalloc / hipFree: they bypass tf_device.hip's small-block cache on purpose
+// The grid's blocks come from the runtime's own hipMalloc / hipFree: they bypass tf_ctx.hip.h's small-block cache on purpose
 static int grid_alloc(void **p, size_t bytes) { return (int)::hipMalloc(p, bytes); }
 static void grid_free(void *p) { (void)::hipFree(p); }
 
@@ -170,8 +170,8 @@ static int dft_grid_build(tf_ctx *ctx, tfdft::Grid &g, int64_t n_points, const d
     if (e != hipSuccess) TF_FAIL(ctx, tfdft::hip_code(e), "tf_dft_setup: hipMalloc of the grid's buffers failed: %s", hipGetErrorString(e));
     HIPCHK(ctx, hipMemcpy(g.b(tfdft::GB_W), weights, (size_t)G * sizeof(double), hipMemcpyHostToDevice));
     tfdft::DAOs D{A.z, A.lmn, A.prim_off, A.exps, A.w};
-    hipLaunchKernelGGL(tfdft::ao_on_grid_kernel, dim3((unsigned)((len[tfdft::GB_PHI] + 127) / 128)), dim3(128), 0, 0, D, d_xyz, G, N, ctx->d_csr_ptr,
-                       ctx->d_csr_idx, ctx->d_csr_val, g.b(tfdft::GB_PHI), g.b(tfdft::GB_DPHI), g.gga ? 1 : 0);
+    hipLaunchKernelGGL(tfdft::ao_on_grid_kernel, dim3((unsigned)((len[tfdft::GB_PHI] + 127) / 128)), dim3(128), 0, 0, D, d_xyz, G, N, ctx->d_csr_ptr(),
+                       ctx->d_csr_idx(), ctx->d_csr_val(), g.b(tfdft::GB_PHI), g.b(tfdft::GB_DPHI), g.gga ? 1 : 0);
     HIPCHK(ctx, hipDeviceSynchronize());
     HIPCHK(ctx, hipGetLastError());
     std::string msg;

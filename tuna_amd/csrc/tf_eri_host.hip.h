@@ -1,6 +1,7 @@
 // tf_eri_host.hip.h -- host side of the tensor build: the knobs, the plan of one build (struct EriBuild), its units,
 // tf_build_eri and the small tensor queries.  Included by tf_device.hip inside its extern "C" block, one translation unit: tf_ctx,
-// DeviceBlocks, tf_malloc, upload, free_eri, build_blocked_layout and the shard planners are defined there.  No kernel is in here; the
+// DeviceBlocks, tf_malloc, upload and free_eri are defined in tf_ctx.hip.h, build_blocked_layout in tf_basis_host.hip.h, the shard planners
+// in tf_shard_plan.h, all above this include.  No kernel is in here; the
 // LDS carve-outs and the team-size choice are the pure functions of tf_eri_plan.h.
 
 // AO-level CSR of U (or identity for Cartesian output) on the device
@@ -24,13 +25,8 @@ static int upload_csr(tf_ctx *ctx, int spherical)
     } else {
         for (int i = 0; i < bs.n_cart; ++i) { idx.push_back(i); val.push_back(1.0); ptr.push_back(i + 1); }
     }
-    for (void *p : {(void *)ctx->d_csr_ptr, (void *)ctx->d_csr_idx, (void *)ctx->d_csr_val})
-        if (p) (void)tf_free(p);
     int rc;
-    if ((rc = upload(ctx, ptr, &ctx->d_csr_ptr, false)) || (rc = upload(ctx, idx, &ctx->d_csr_idx, false)) ||
-        (rc = upload(ctx, val, &ctx->d_csr_val, false)))
-        return rc;
-    ctx->csr_rows = (int)ptr.size() - 1;
+    if ((rc = upload(ctx, ptr, CB_CSR_PTR)) || (rc = upload(ctx, idx, CB_CSR_IDX)) || (rc = upload(ctx, val, CB_CSR_VAL))) return rc;
     return TF_OK;
 }
 
@@ -346,7 +342,7 @@ int EriBuild::plan_storage()
     {
         std::vector<int> dims(bs.shells.size());
         for (size_t q = 0; q < dims.size(); ++q) dims[q] = out_dim(bs.shells[q]);
-        shard_plan_pairs(dims, sto.packed, ctx->world, sto.owner);           // pair index A(A+1)/2 + B = position in bs.pairs
+        shard_plan_pairs(dims, sto.packed, ctx->world, getenv("TF_SHARD_PLAN"), sto.owner);           // pair index A(A+1)/2 + B = position in bs.pairs
     }
     ctx->my_pairs.clear();
     for (int p = 0; p < sto.npairs; ++p)
@@ -412,14 +408,8 @@ int EriBuild::plan_storage()
 #else
         const size_t need = std::max<size_t>(1, (size_t)ctx->n_elems * sizeof(double));
 #endif
-        if (ctx->d_eri && (ctx->eri_cap < need || ctx->eri_cap > 2 * need + (64u << 20))) {
-            (void)tf_free(ctx->d_eri);
-            ctx->d_eri = nullptr; ctx->eri_cap = 0;
-        }
-        if (!ctx->d_eri) {
-            HIPCHK(ctx, tf_malloc((void **)&ctx->d_eri, need));
-            ctx->eri_cap = need;
-        }
+        if (ctx->blk.cap[CB_ERI] > 2 * need + (64u << 20)) ctx->blk.drop(CB_ERI);
+        HIPCHK(ctx, (hipError_t)ctx->blk.ensure(CB_ERI, need));
     }
     if ((rc = upload_int2(ctx, row_ij, &ctx->d_row_ij)) || (rc = upload(ctx, sto.rows.rowmap, &ctx->d_rowmap, ctx->build_mem))) return rc;
     if (sto.packed) {
@@ -427,7 +417,7 @@ int EriBuild::plan_storage()
         ctx->db.bl = ctx->bl;
         ctx->db.RLS = H.RLS;
     }
-    if (sto.tiles) HIPCHK(ctx, hipMemsetAsync(ctx->d_eri, 0, (size_t)ctx->n_elems * sizeof(double), 0));   // the pad slots of the rows and pieces stay zero
+    if (sto.tiles) HIPCHK(ctx, hipMemsetAsync(ctx->d_eri(), 0, (size_t)ctx->n_elems * sizeof(double), 0));   // the pad slots of the rows and pieces stay zero
     return TF_OK;
 }
 
@@ -495,7 +485,7 @@ int EriBuild::plan_slab_size()
     if ((rc = ensure_scratch(ctx, 0, slab.per_class ? 8 : (size_t)slab.max_rows_c * cart_row_bytes)) ||
         (rc = ensure_scratch(ctx, 2, (size_t)slab.max_rows_c * t2_row_bytes)))
         return rc;
-    slab.d_C = ctx->scr[0]; slab.d_T2 = ctx->scr[2];
+    slab.d_C = ctx->scr(0); slab.d_T2 = ctx->scr(2);
     return TF_OK;
 }
 
@@ -644,20 +634,10 @@ int EriBuild::plan_ket_families()
 // streams so that the many small class launches of a slab overlap
 int EriBuild::setup_streams()
 {
-    const int NSTREAM_MAX = tf_ctx::NSTREAM_MAX;
     run.NSTREAM = knobs.nstream;
-    if (!ctx->have_streams) {
-        for (int k = 0; k < NSTREAM_MAX; ++k) {
-            HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->streams[k], hipStreamNonBlocking));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->sev[k], hipEventDisableTiming));
-        }
-        HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->cstream, hipStreamNonBlocking));
-        for (auto &e : ctx->slab_done) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (auto &e : ctx->slab_lists) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->have_streams = true;
-    }
-    run.streams = ctx->streams;
-    run.sev = ctx->sev;
+    HIPCHK(ctx, (hipError_t)ctx->bstr.create());                 // (all of them or none; made once per context)
+    run.streams = ctx->bstr.streams;
+    run.sev = ctx->bstr.sev;
     return TF_OK;
 }
 
@@ -823,12 +803,9 @@ int EriBuild::make_lrecs(bool with_caps)
             tfe::lrec_words(r, La, Lb, Lc, Ld, tup.data() + r.tupG_off);
             recs[ab * 36 + cd] = r;
         }
-    // (d_lrec / d_tup are context-lifetime blocks, replaced here by hand: DESIGN.md section 3.1, invariant 3)
-    if (ctx->d_lrec) { (void)tf_free(ctx->d_lrec); ctx->d_lrec = nullptr; }
-    if (ctx->d_tup) { (void)tf_free(ctx->d_tup); ctx->d_tup = nullptr; }
     int rc2;
-    if ((rc2 = upload(ctx, recs, &ctx->d_lrec, false)) || (rc2 = upload(ctx, tup, &ctx->d_tup, false))) return rc2;
-    ctx->db.lrec = ctx->d_lrec; ctx->db.tup = ctx->d_tup;
+    if ((rc2 = upload(ctx, recs, CB_LREC)) || (rc2 = upload(ctx, tup, CB_TUP))) return rc2;
+    ctx->db.lrec = ctx->blk.at<LRec>(CB_LREC); ctx->db.tup = ctx->blk.at<unsigned short>(CB_TUP);
     lt.lrecs_host = recs;
     return TF_OK;
 }
@@ -905,17 +882,14 @@ int EriBuild::launch_generic(const std::vector<int> &bra_host, const int *d_bra,
         }
         if (lt.gcaps_gtab[gb][gk]) {
             const size_t need = (size_t)nk * (b1 - b0) * (size_t)c.gtab_doubles * sizeof(double);
-            if (need > ctx->gtab_bytes) {
+            if (need > ctx->blk.cap[CB_GTAB]) {
                 HIPCHK(ctx, hipDeviceSynchronize());           // (earlier launches of this build may still use the old block)
-                if (ctx->d_gtab) (void)tf_free(ctx->d_gtab);
-                ctx->d_gtab = nullptr; ctx->gtab_bytes = 0;
-                HIPCHK(ctx, tf_malloc((void **)&ctx->d_gtab, need));
-                ctx->gtab_bytes = need;
+                HIPCHK(ctx, (hipError_t)ctx->blk.ensure(CB_GTAB, need));
             }
             // launches that share the block must not overlap: they all go to one stream
             count(TF_ERI_STAT_CFACT_GTAB);
             hipLaunchKernelGGL((eri_cfact_kernel<true, true>), dim3((unsigned)nk, (unsigned)(b1 - b0)), dim3(TF_ERI_THREADS), bytes, run.streams[0], ctx->db, c,
-                               d_bra + b0, d_braoff + b0, kets.d_kets_all + kets.kets_goff[gk], sto.Nc, slab.d_C, ctx->d_gtab);
+                               d_bra + b0, d_braoff + b0, kets.d_kets_all + kets.kets_goff[gk], sto.Nc, slab.d_C, ctx->d_gtab());
             load[qi] -= l.cost; load[0] += l.cost;
         } else if (((gb | gk) & 1) == 0) {                   // both groups uncontracted: one primitive quartet per shell quartet
             count(TF_ERI_STAT_CFACT_UNCONTRACTED);
@@ -1339,7 +1313,7 @@ int EriBuild::run_slab()
     }
     // this set of index lists was last read by the kernels of the slab before the previous one: wait for that slab only
     const int set = (int)(ix.slab_no & 1);
-    if (ix.slab_no >= 2) HIPCHK(ctx, hipEventSynchronize(ctx->slab_done[set]));
+    if (ix.slab_no >= 2) HIPCHK(ctx, hipEventSynchronize(ctx->bstr.slab_done(set)));
     ix.d_bra = ix.d_bra_alloc + (size_t)set * ix.cap_bra; ix.d_braoff = ix.d_braoff_alloc + (size_t)set * ix.cap_bra;
     ix.d_out = (char *)ix.d_out_alloc + (size_t)set * ix.out_bytes;
     if (ix.d_brarec_alloc) tt.d_brarec = ix.d_brarec_alloc + (size_t)set * ix.cap_bra;
@@ -1347,7 +1321,7 @@ int EriBuild::run_slab()
     tt.d_bra_base = ix.d_bra;
     ++ix.slab_no;
     ++run.stats[TF_ERI_STAT_SLABS];
-    const hipStream_t cst = ctx->cstream;
+    const hipStream_t cst = ctx->bstr.cstream();
     HIPCHK(ctx, hipMemcpyAsync(ix.d_bra, bra.data(), bra.size() * sizeof(int), hipMemcpyHostToDevice, cst));
     HIPCHK(ctx, hipMemcpyAsync(ix.d_braoff, braoff.data(), braoff.size() * sizeof(long long), hipMemcpyHostToDevice, cst));
     std::vector<BraRec> brec;
@@ -1401,11 +1375,11 @@ int EriBuild::run_slab()
         grid_y_chunks((size_t)rows_c, [&](size_t r0s, unsigned ny) {      // both ket axes in one pass over the slab
             if (sto.packed)
                 hipLaunchKernelGGL(xform_ket_packed, dim3((unsigned)((sto.N + 3) / 4), ny), dim3(256), 0, 0, slab.d_C + (size_t)r0s * sto.Nc * sto.Nc,
-                                   slab.d_T2 + (size_t)r0s * H.RLS, sto.Nc, ctx->bl, (long long)H.RLS, ix.d_rowcls + r0s, ctx->d_csr_ptr, ctx->d_csr_idx,
-                                   ctx->d_csr_val);
+                                   slab.d_T2 + (size_t)r0s * H.RLS, sto.Nc, ctx->bl, (long long)H.RLS, ix.d_rowcls + r0s, ctx->d_csr_ptr(), ctx->d_csr_idx(),
+                                   ctx->d_csr_val());
             else
                 hipLaunchKernelGGL(xform_ket_both, dim3((unsigned)((sto.N + 3) / 4), ny), dim3(256), 0, 0, slab.d_C + (size_t)r0s * sto.Nc * sto.Nc,
-                                   slab.d_T2 + (size_t)r0s * sto.N * sto.ld, sto.Nc, sto.N, sto.ld, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val, 0);
+                                   slab.d_T2 + (size_t)r0s * sto.N * sto.ld, sto.Nc, sto.N, sto.ld, ctx->d_csr_ptr(), ctx->d_csr_idx(), ctx->d_csr_val(), 0);
         });
     }
     if (lt.use_teamc && !tcl.empty() && (rc = launch_teamc(tcl))) return rc;
@@ -1413,28 +1387,28 @@ int EriBuild::run_slab()
     if (!outs.empty()) {
         const unsigned gx = (unsigned)std::min<long long>((sto.row_len + 255) / 256, 4096);
         grid_y_chunks(outs.size(), [&](size_t o0, unsigned ny) {
-            hipLaunchKernelGGL(xform_bra_store, dim3(gx, ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri, reinterpret_cast<const OutRow *>(ix.d_out) + o0,
-                               sto.row_len, ctx->d_csr_ptr, ctx->d_csr_idx, ctx->d_csr_val);
+            hipLaunchKernelGGL(xform_bra_store, dim3(gx, ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri(), reinterpret_cast<const OutRow *>(ix.d_out) + o0,
+                               sto.row_len, ctx->d_csr_ptr(), ctx->d_csr_idx(), ctx->d_csr_val());
         });
     }
     if (!outsP.empty()) {
         int maxlen = 1;
         for (const OutRowP &o : outsP) maxlen = std::max(maxlen, o.len);
         grid_y_chunks(outsP.size(), [&](size_t o0, unsigned ny) {
-            hipLaunchKernelGGL(xform_bra_store_packed, dim3((unsigned)((maxlen + 255) / 256), ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri,
-                               reinterpret_cast<const OutRowP *>(ix.d_out) + o0, (long long)H.RLS, ctx->bl, ctx->d_csr_ptr, ctx->d_csr_idx,
-                               ctx->d_csr_val);
+            hipLaunchKernelGGL(xform_bra_store_packed, dim3((unsigned)((maxlen + 255) / 256), ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri(),
+                               reinterpret_cast<const OutRowP *>(ix.d_out) + o0, (long long)H.RLS, ctx->bl, ctx->d_csr_ptr(), ctx->d_csr_idx(),
+                               ctx->d_csr_val());
         });
     }
     if (!outsT.empty()) {
         grid_y_chunks(outsT.size(), [&](size_t o0, unsigned ny) {
-            hipLaunchKernelGGL(xform_bra_store_tiles, dim3((unsigned)((H.RLS + 255) / 256), ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri,
-                               reinterpret_cast<const OutRowT *>(ix.d_out) + o0, (long long)H.RLS, ctx->bl, ctx->tv, ctx->d_csr_ptr, ctx->d_csr_idx,
-                               ctx->d_csr_val);
+            hipLaunchKernelGGL(xform_bra_store_tiles, dim3((unsigned)((H.RLS + 255) / 256), ny), dim3(256), 0, 0, slab.d_T2, ctx->d_eri(),
+                               reinterpret_cast<const OutRowT *>(ix.d_out) + o0, (long long)H.RLS, ctx->bl, ctx->tv, ctx->d_csr_ptr(), ctx->d_csr_idx(),
+                               ctx->d_csr_val());
         });
     }
     HIPCHK(ctx, hipEventRecord(e4[3], 0));
-    HIPCHK(ctx, hipEventRecord(ctx->slab_done[set], 0));
+    HIPCHK(ctx, hipEventRecord(ctx->bstr.slab_done(set), 0));
     return TF_OK;
 }
 
@@ -1574,11 +1548,11 @@ int tf_copy_eri(tf_ctx *ctx, double *host_out)
     HIPCHK(ctx, tf_malloc((void **)&d_dense, total * sizeof(double)));
     const unsigned g = (unsigned)std::min<size_t>((total + 255) / 256, 1 << 20);
     if (ctx->layout == 2)
-        hipLaunchKernelGGL(expand_dense_tiles_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri, ctx->tv, ctx->bl, d_dense);
+        hipLaunchKernelGGL(expand_dense_tiles_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri(), ctx->tv, ctx->bl, d_dense);
     else if (ctx->layout == 1)
-        hipLaunchKernelGGL(expand_dense_packed_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri, ctx->d_rowmap, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, d_dense);
+        hipLaunchKernelGGL(expand_dense_packed_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri(), ctx->d_rowmap, ctx->d_rowoff, ctx->d_rowsec, ctx->bl, d_dense);
     else
-        hipLaunchKernelGGL(expand_dense_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri, ctx->d_rowmap, ctx->N, ctx->ld, d_dense);
+        hipLaunchKernelGGL(expand_dense_kernel, dim3(g), dim3(256), 0, 0, ctx->d_eri(), ctx->d_rowmap, ctx->N, ctx->ld, d_dense);
     hipError_t e = hipMemcpy(host_out, d_dense, total * sizeof(double), hipMemcpyDeviceToHost);
     (void)tf_free(d_dense);
     HIPCHK(ctx, e);
@@ -1598,12 +1572,12 @@ int tf_sample_eri(tf_ctx *ctx, int64_t n_idx, const int32_t *idx, double *values
     HIPCHK(ctx, tf_malloc((void **)&d_val, (size_t)n_idx * sizeof(double)));
     HIPCHK(ctx, hipMemcpy(d_idx, idx, (size_t)n_idx * 4 * sizeof(int), hipMemcpyHostToDevice));
     if (ctx->layout == 2)
-        hipLaunchKernelGGL(sample_tiles_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri, ctx->tv, ctx->bl, (long long)n_idx, d_idx, d_val);
+        hipLaunchKernelGGL(sample_tiles_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri(), ctx->tv, ctx->bl, (long long)n_idx, d_idx, d_val);
     else if (ctx->layout == 1)
-        hipLaunchKernelGGL(sample_packed_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri, ctx->d_rowmap,
+        hipLaunchKernelGGL(sample_packed_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri(), ctx->d_rowmap,
                            ctx->d_rowoff, ctx->d_rowsec, ctx->bl, (long long)n_idx, d_idx, d_val);
     else
-        hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri, ctx->d_rowmap, ctx->N,
+        hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n_idx + 255) / 256)), dim3(256), 0, 0, ctx->d_eri(), ctx->d_rowmap, ctx->N,
                            ctx->ld, (long long)n_idx, d_idx, d_val);
     hipError_t e = hipMemcpy(values, d_val, (size_t)n_idx * sizeof(double), hipMemcpyDeviceToHost);
     (void)tf_free(d_idx); (void)tf_free(d_val);

@@ -2,6 +2,7 @@
 // the records on the host from integers, the kernel headers (tf_eri.hip.h, tf_eri_team.hip.h, tf_dbasis.hip.h) read them, and
 // tests/packed_model compiles both with g++.
 #pragma once
+#include <vector>
 
 #define TF_ERI_THREADS 256
 #define TF_BLK_DOUBLES 1024   // LDS doubles of the Cartesian (cc,cd) sub-block buffer of the fused ket transform
@@ -12,6 +13,32 @@
 #define TF_CF_KMAX 2
 
 namespace tfk {
+
+// ---- the basis as the kernels read it: one record per shell and per shell pair A >= B (DBasis, tf_dbasis.hip.h, points at arrays of them)
+struct DShell { int L, ncomp, comp_off, cart_off; };
+struct DPair {
+    int A, B, La, Lb, npp, pp_off, nE, cls;
+    long long e_off;
+    int nca, ncb, compoff_a, compoff_b, cartoff_a, cartoff_b;
+    int outoff_a, outoff_b;      // first OUTPUT AO (spherical, or Cartesian for CARTHARM) of the two shells; set by tf_build_eri
+    int tab_off;                 // component-pair tables of this pair in DBasis::ct_* (nca * ncb entries)
+    int pcls[5];                 // ct_ord: component pairs ordered by (x, y) parity class; class c is [pcls[c], pcls[c + 1])
+};
+
+// Every host table of the device basis that follows from a tf::Basis alone (tf::build_device_tables, tf_host.cpp): tf_set_basis uploads
+// them and keeps pair_class, class_pairs, hp and the ct_* mirrors for the tensor build.
+struct DeviceTables {
+    std::vector<DShell> hs;
+    std::vector<DPair> hp;                        // with cls, tab_off and pcls; the output offsets stay 0 (tf_build_eri)
+    std::vector<int> pair_class;                  // class id of every shell pair: same angular momenta, component counts, components, contraction depth class
+    std::vector<std::vector<int>> class_pairs;    // pairs of each class, ascending
+    // component-pair tables of every shell pair (eri_cfact_kernel): index word, position, parity-class order, normalisation ratio
+    std::vector<int> ct_ix, ct_pos, ct_ord;
+    std::vector<double> ct_sc;
+    // per-L spherical rows as CSR over the Cartesian components of one shell
+    std::vector<int> sph_base, sph_ptr, sph_idx;
+    std::vector<double> sph_val;
+};
 
 struct QClass {
     int La, Lb, Lc, Ld, L, tsize;
@@ -68,3 +95,9 @@ struct TClass {
 };
 
 }  // namespace tfk
+
+namespace tf {
+struct Basis;
+// exact_class: pairs of different contraction depth never share a class (TF_ERI_EXACT_CLASS, read by the caller)
+void build_device_tables(const Basis &bs, bool exact_class, tfk::DeviceTables &out);
+}  // namespace tf

@@ -2,10 +2,13 @@
 // Cartesian->spherical coefficients, Boys Taylor grid.  Everything here is O(N^2 K^2) set-up that the
 // reference does serially under the GIL (pyx:1300-1308); the N^4 work is in tf_device.hip.
 #include "tf_internal.h"
+#include "tf_eri_types.h"
 
+#include <array>
 #include <cmath>
 #include <complex>
 #include <cstring>
+#include <map>
 
 namespace tf {
 
@@ -280,6 +283,89 @@ void dense_sph_matrix(const Basis &bs, std::vector<double> &U)
         for (int r = 0; r < sh.nsph; ++r)
             for (int c = 0; c < sh.ncomp; ++c)
                 U[(size_t)(sh.sph_off + r) * bs.n_cart + sh.cart_off + c] = blk[(size_t)r * sh.ncomp + c];
+    }
+}
+
+// The host tables of the device basis (tf_eri_types.h: DeviceTables), all of them functions of the basis alone
+void build_device_tables(const Basis &bs, bool exact_class, tfk::DeviceTables &out)
+{
+    std::vector<tfk::DShell> &hs = out.hs;
+    hs.resize(bs.shells.size());
+    for (size_t i = 0; i < hs.size(); ++i) hs[i] = {bs.shells[i].L, bs.shells[i].ncomp, bs.shells[i].comp_off, bs.shells[i].cart_off};
+    std::vector<tfk::DPair> &hp = out.hp;
+    hp.resize(bs.pairs.size());
+    for (size_t i = 0; i < hp.size(); ++i) {
+        const Pair &p = bs.pairs[i];
+        const Shell &sa = bs.shells[p.A], &sb = bs.shells[p.B];
+        hp[i] = {p.A, p.B, p.La, p.Lb, p.npp, p.pp_off, p.nE, 0, p.e_off, sa.ncomp, sb.ncomp, sa.comp_off, sb.comp_off, sa.cart_off, sb.cart_off, 0, 0};
+    }
+    // shell-pair classes: every pair of a class has the same angular momenta, component counts and contraction depth
+    out.pair_class.assign(hp.size(), 0);
+    out.class_pairs.clear();
+    {
+        // (shells that are not complete -- the one-component shells of the DECONTRACT ordering -- carry their components in the key: the
+        // pairs of a class share one set of component-pair tables)
+        auto comp_code = [&](const Shell &sh) {
+            if (sh.full) return 0;
+            int code = 1;
+            for (int c = 0; c < sh.ncomp && c < 2; ++c)
+                code = code * 4096 + (bs.c_lx[sh.comp_off + c] | (bs.c_ly[sh.comp_off + c] << 4) | (bs.c_lz[sh.comp_off + c] << 8));
+            return code;
+        };
+        std::map<std::array<int, 7>, int> ids;
+        for (size_t i = 0; i < hp.size(); ++i) {
+            const std::array<int, 7> key{hp[i].La, hp[i].Lb, exact_class ? hp[i].npp : (hp[i].npp == 1 ? 1 : 0), hp[i].nca, hp[i].ncb,
+                                         comp_code(bs.shells[bs.pairs[i].A]), comp_code(bs.shells[bs.pairs[i].B])};
+            auto it = ids.find(key);
+            if (it == ids.end()) { it = ids.emplace(key, (int)ids.size()).first; out.class_pairs.emplace_back(); }
+            hp[i].cls = it->second;
+            out.pair_class[i] = it->second;
+            out.class_pairs[it->second].push_back((int)i);
+        }
+    }
+    // per-L spherical rows as CSR over the Cartesian components of one shell
+    std::vector<int> &sph_base = out.sph_base, &sph_ptr = out.sph_ptr, &sph_idx = out.sph_idx;
+    std::vector<double> &sph_val = out.sph_val;
+    sph_base.assign(TF_MAX_L + 2, 0); sph_ptr.assign(1, 0); sph_idx.clear(); sph_val.clear();
+    {
+        std::vector<double> blk;
+        for (int L = 0; L <= TF_MAX_L; ++L) {
+            sph_base[L] = (int)sph_ptr.size() - 1;
+            sph_block(L, blk);
+            const int nc = (L + 1) * (L + 2) / 2;
+            for (int r = 0; r < 2 * L + 1; ++r) {
+                for (int c = 0; c < nc; ++c)
+                    if (blk[(size_t)r * nc + c] != 0.0) { sph_idx.push_back(c); sph_val.push_back(blk[(size_t)r * nc + c]); }
+                sph_ptr.push_back((int)sph_idx.size());
+            }
+        }
+    }
+    // component-pair tables of every shell pair (eri_cfact_kernel): index word, normalisation ratio, position, parity-class order
+    std::vector<int> &ct_ix = out.ct_ix, &ct_pos = out.ct_pos, &ct_ord = out.ct_ord;
+    std::vector<double> &ct_sc = out.ct_sc;
+    ct_ix.clear(); ct_pos.clear(); ct_ord.clear(); ct_sc.clear();
+    for (size_t i = 0; i < hp.size(); ++i) {
+        tfk::DPair &pr = hp[i];
+        const int nab = pr.nca * pr.ncb, L2 = pr.Lb + 1;
+        pr.tab_off = (int)ct_ix.size();
+        std::vector<int> cls(nab);
+        for (int ca = 0; ca < pr.nca; ++ca)
+            for (int cb = 0; cb < pr.ncb; ++cb) {
+                const int a = pr.compoff_a + ca, b = pr.compoff_b + cb;
+                const int ux = bs.c_lx[a], uy = bs.c_ly[a], uz = bs.c_lz[a], wx = bs.c_lx[b], wy = bs.c_ly[b], wz = bs.c_lz[b];
+                const int c = ((ux + wx) & 1) | (((uy + wy) & 1) << 1);
+                cls[ca * pr.ncb + cb] = c;
+                ct_ix.push_back((ux * L2 + wx) | ((uy * L2 + wy) << 8) | ((uz * L2 + wz) << 16) | (c << 24));
+                ct_pos.push_back((ca << 8) | cb);
+                ct_sc.push_back(bs.c_scale[a] * bs.c_scale[b]);
+            }
+        pr.pcls[0] = 0;
+        for (int c = 0; c < 4; ++c) {
+            int n = 0;
+            for (int f = 0; f < nab; ++f)
+                if (cls[f] == c) { ct_ord.push_back(f); ++n; }
+            pr.pcls[c + 1] = pr.pcls[c] + n;
+        }
     }
 }
 

@@ -39,20 +39,17 @@ struct JkKnobs {
     static int force_jb() { return env_int("TF_JK_FORCE_JB", 0); }
 };
 
-// The profiling span around the tensor kernels of one pass (tf_jk_profile): an event pair of ctx->prof_ev, created on demand (if that
+// The profiling span around the tensor kernels of one pass (tf_jk_profile): an event pair of ctx->prof, created on demand (if that
 // fails the span is skipped silently); "before" is recorded on st by the constructor, "after" on st by end().
 struct JkProfSpan {
     hipEvent_t after = nullptr;
     hipStream_t st;
     JkProfSpan(tf_ctx *ctx, hipStream_t s) : st(s)
     {
-        hipEvent_t a, b;
-        if (!ctx->prof_jk) return;
-        if (ctx->prof_used + 2 > ctx->prof_ev.size() && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) { ctx->prof_ev.push_back(a); ctx->prof_ev.push_back(b); }
-        if (ctx->prof_used + 2 > ctx->prof_ev.size()) return;
-        (void)hipEventRecord(ctx->prof_ev[ctx->prof_used], st);
-        after = ctx->prof_ev[ctx->prof_used + 1];
-        ctx->prof_used += 2;
+        hipEvent_t before, b;
+        if (!ctx->prof_jk || !ctx->prof.next(before, b)) return;
+        (void)hipEventRecord(before, st);
+        after = b;
     }
     void end() { if (after) (void)hipEventRecord(after, st); }
 };
@@ -159,12 +156,12 @@ static int jk_packed_pass(tf_ctx *ctx, hipStream_t st, double *const *dDout, boo
         // per local build on 8 ranks.  Under the segment plan a rank's super-groups hold a few rows each: see above.)
         const bool full_supers = T.n_supers > 0 && ctx->n_rows >= 24LL * T.n_supers;
         const bool one_launch = JkKnobs::one_launch_below() > n_tasks && n_launch > 1 && (ctx->world == 1 || full_supers);
-        const bool fork = !JkKnobs::serial_packed() && !one_launch && ctx->have_streams && n_launch > 1;
-        if (fork) (void)hipEventRecord(ctx->sev[0], st);
+        const bool fork = !JkKnobs::serial_packed() && !one_launch && ctx->bstr.live && n_launch > 1;
+        if (fork) (void)hipEventRecord(ctx->bstr.sev[0], st);
         int side = 0;
         bool first = true;
         if (one_launch)
-            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)n_tasks), dim3(64 * TF_JKP_W), 0, st, ctx->d_eri, T.d_groups,
+            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)n_tasks), dim3(64 * TF_JKP_W), 0, st, ctx->d_eri(), T.d_groups,
                                T.d_supers, tasks, L, L.kinfo, K.Psym, K.Pp, pJrow, pY, DIc, DIr, DJc, DJr, S);
         for (int b = 0; b < 3 && !one_launch; ++b) {
             const int t0 = bucket[b], t1 = bucket[b + 1];
@@ -172,15 +169,15 @@ static int jk_packed_pass(tf_ctx *ctx, hipStream_t st, double *const *dDout, boo
             hipStream_t ls = st;
             if (fork && !first) {
                 ++side;
-                ls = ctx->streams[side];
-                (void)hipStreamWaitEvent(ls, ctx->sev[0], 0);
+                ls = ctx->bstr.streams[side];
+                (void)hipStreamWaitEvent(ls, ctx->bstr.sev[0], 0);
             }
             first = false;
-            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)(t1 - t0)), dim3(64 * (TF_JKP_W >> b)), 0, ls, ctx->d_eri, T.d_groups,
+            hipLaunchKernelGGL((jk_packed_kernel<ND>), dim3((unsigned)(t1 - t0)), dim3(64 * (TF_JKP_W >> b)), 0, ls, ctx->d_eri(), T.d_groups,
                                T.d_supers, tasks + t0, L, L.kinfo, K.Psym, K.Pp, pJrow, pY, DIc, DIr, DJc, DJr, S);
             if (ls != st) {
-                (void)hipEventRecord(ctx->sev[side], ls);
-                (void)hipStreamWaitEvent(st, ctx->sev[side], 0);
+                (void)hipEventRecord(ctx->bstr.sev[side], ls);
+                (void)hipStreamWaitEvent(st, ctx->bstr.sev[side], 0);
             }
         }
         span.end();
@@ -328,15 +325,15 @@ static int jk_tiles_pass(tf_ctx *ctx, tf_ctx::TileList &D, hipStream_t st, doubl
     A.N = N; A.pm_len = TT.pm_len;
     TEArgs E{};
     E.edge_base = TT.edge_base; E.N = N; E.tab = Z.tvtab; E.EJ = out + 5 * ND * nn; E.ED = out + 2 * ND * nn; E.EDT = out + 3 * ND * nn; E.sE = nn;
-    const bool fork = ctx->have_streams && !JkKnobs::serial_tiles();
+    const bool fork = ctx->bstr.live && !JkKnobs::serial_tiles();
     if (D.n_tasks > 0) {
         JkProfSpan span(ctx, st);
-        if (fork) (void)hipEventRecord(ctx->sev[0], st);
+        if (fork) (void)hipEventRecord(ctx->bstr.sev[0], st);
         // ONE launch of full-size workgroups over all tasks (measured at N = 400: 1.57 ms against 1.82 for one launch per workgroup size
         // on side streams -- loads only); the idle waves of the narrower tasks wait in the task's barriers
         const int pf_env = JkKnobs::tile_pf();
         const dim3 grid((unsigned)D.n_tasks), block(64 * TT_W);
-#define TF_TJ_LAUNCH(NDV, MBV, PFV) hipLaunchKernelGGL((jk_tile_kernel<NDV, MBV, PFV>), grid, block, 0, st, ctx->d_eri, D.d_tasks, Z.X, Z.Pm, A)
+#define TF_TJ_LAUNCH(NDV, MBV, PFV) hipLaunchKernelGGL((jk_tile_kernel<NDV, MBV, PFV>), grid, block, 0, st, ctx->d_eri(), D.d_tasks, Z.X, Z.Pm, A)
         if constexpr (ND == 1) {
             if (D.ksub == 16) { if (pf_env == 1) TF_TJ_LAUNCH(1, 1, 1); else TF_TJ_LAUNCH(1, 1, 2); }
             else if (D.ksub == 32) { if (pf_env == 1) TF_TJ_LAUNCH(1, 2, 1); else TF_TJ_LAUNCH(1, 2, 2); }
@@ -351,13 +348,13 @@ static int jk_tiles_pass(tf_ctx *ctx, tf_ctx::TileList &D, hipStream_t st, doubl
     {
         // the edge elements beside the tile launch
         hipStream_t ls = st;
-        if (fork && D.n_tasks > 0) { ls = ctx->streams[1]; (void)hipStreamWaitEvent(ls, ctx->sev[0], 0); }
-        hipLaunchKernelGGL((jk_edge_kernel<ND>), dim3((unsigned)N, (unsigned)ND), dim3(64 * TT_EDGE_WAVES), edge_lds, ls, ctx->d_eri, Z.X, D.d_runs, E);
-        if (ls != st) { (void)hipEventRecord(ctx->sev[1], ls); (void)hipStreamWaitEvent(st, ctx->sev[1], 0); }
+        if (fork && D.n_tasks > 0) { ls = ctx->bstr.streams[1]; (void)hipStreamWaitEvent(ls, ctx->bstr.sev[0], 0); }
+        hipLaunchKernelGGL((jk_edge_kernel<ND>), dim3((unsigned)N, (unsigned)ND), dim3(64 * TT_EDGE_WAVES), edge_lds, ls, ctx->d_eri(), Z.X, D.d_runs, E);
+        if (ls != st) { (void)hipEventRecord(ctx->bstr.sev[1], ls); (void)hipStreamWaitEvent(st, ctx->bstr.sev[1], 0); }
     }
     TRArgs R{};
     R.itask_ptr = D.d_itask_ptr; R.itasks = D.d_itasks; R.jlist_ptr = Z.jlist_ptr; R.clsI = ctx->bl.clsI;
-    R.DJ = D.DJ; R.Jt = D.Jt; R.Jd = D.Jd; R.DIk = D.DIk; R.DIl = D.DIl; R.T = ctx->d_eri; R.X = Z.X;
+    R.DJ = D.DJ; R.Jt = D.Jt; R.Jd = D.Jd; R.DIk = D.DIk; R.DIl = D.DIl; R.T = ctx->d_eri(); R.X = Z.X;
     R.sJt = A.sJt; R.sDIk = A.sDIk; R.sDIl = A.sDIl; R.sO = nn;
     R.Dj = out; R.Di = out + (size_t)ND * nn; R.JD = out + (size_t)4 * ND * nn; R.JtTot = Z.JtTot;
     R.edge_base = TT.edge_base; R.N = N; R.ksub = D.ksub; R.npair = TT.npair; R.nd = ND; R.pm_len = TT.pm_len; R.tab = Z.tvtab;
@@ -457,7 +454,7 @@ static int launch_jk(tf_ctx *ctx, int nd, const double *const *dP, double *const
         const dim3 grid((unsigned)((ctx->n_rows + JB - 1) / JB)), block(TF_JK_THREADS);
         JkProfSpan span(ctx, st);
 #define TF_JK_LAUNCH(NLC, JBV, NDV)                                                                                         \
-        hipLaunchKernelGGL((jk_rows_kernel<NLC, JBV, NDV>), grid, block, smem, st, ctx->d_eri, ctx->d_row_ij, ctx->n_rows, N, ld, \
+        hipLaunchKernelGGL((jk_rows_kernel<NLC, JBV, NDV>), grid, block, smem, st, ctx->d_eri(), ctx->d_row_ij, ctx->n_rows, N, ld, \
                            Ppad[0], Ppad[1], A.Jrow, Kp)
         if (npair > 4 * TF_JK_THREADS) TF_FAIL(ctx, TF_EINVAL, "N = %d exceeds the J/K kernel's row length limit (2048)", N);
         if (nd == 1) {
@@ -508,26 +505,21 @@ static int allreduce_jk(tf_ctx *ctx, int nd, double *const *dJ, double *const *d
     const size_t nn = (size_t)ctx->N * ctx->N, need = 2 * (size_t)nd * nn;
     // one slot beyond the payload carries a status word through the same collective: a rank whose exchange step failed locally (the
     // hook sets it) makes the sum non-zero on EVERY rank, so that all of them return an error instead of some waiting in a collective
-    if (ctx->jkstage_doubles < need + 1) {
-        if (ctx->d_jkstage) (void)tf_free(ctx->d_jkstage);
-        ctx->d_jkstage = nullptr; ctx->jkstage_doubles = 0;
-        HIPCHK(ctx, tf_malloc((void **)&ctx->d_jkstage, (need + 1) * sizeof(double)));
-        ctx->jkstage_doubles = need + 1;
-    }
+    HIPCHK(ctx, (hipError_t)ctx->blk.ensure(CB_JKSTAGE, (need + 1) * sizeof(double)));
     for (int d = 0; d < nd; ++d) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage + (size_t)d * nn, dJ[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage + (size_t)(nd + d) * nn, dK[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage() + (size_t)d * nn, dJ[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_jkstage() + (size_t)(nd + d) * nn, dK[d], nn * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_jkstage + need, 0, sizeof(double), st));
-    const int rc = ctx->allreduce(ctx->allreduce_user, ctx->d_jkstage, (int64_t)(need + 1), (void *)st);
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_jkstage() + need, 0, sizeof(double), st));
+    const int rc = ctx->allreduce(ctx->allreduce_user, ctx->d_jkstage(), (int64_t)(need + 1), (void *)st);
     if (rc) TF_FAIL(ctx, TF_ENODEVICE, "the registered all-reduce failed (code %d)", rc);
     double status = 0.0;
-    HIPCHK(ctx, hipMemcpyAsync(&status, ctx->d_jkstage + need, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(&status, ctx->d_jkstage() + need, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     if (status != 0.0) TF_FAIL(ctx, TF_ENODEVICE, "the exchange step of the sharded Fock build failed on %g rank(s): every rank stops", status);
     for (int d = 0; d < nd; ++d) {
-        HIPCHK(ctx, hipMemcpyAsync(dJ[d], ctx->d_jkstage + (size_t)d * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(dK[d], ctx->d_jkstage + (size_t)(nd + d) * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(dJ[d], ctx->d_jkstage() + (size_t)d * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(dK[d], ctx->d_jkstage() + (size_t)(nd + d) * nn, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     return TF_OK;
 }
@@ -585,7 +577,7 @@ int tf_jk_profile(tf_ctx *ctx, int enable)
 {
     if (!ctx) return TF_EINVAL;
     ctx->prof_jk = enable != 0;
-    ctx->prof_used = 0;
+    ctx->prof.used = 0;
     return TF_OK;
 }
 
@@ -593,14 +585,45 @@ int tf_jk_profile_read(tf_ctx *ctx, double *seconds_total, int64_t *launches)
 {
     if (!ctx || !seconds_total || !launches) return TF_EINVAL;
     double tot = 0.0;
-    for (size_t k = 0; k + 1 < ctx->prof_used; k += 2) {
-        HIPCHK(ctx, hipEventSynchronize(ctx->prof_ev[k + 1]));
+    for (size_t k = 0; k + 1 < ctx->prof.used; k += 2) {
+        HIPCHK(ctx, hipEventSynchronize(ctx->prof.ev[k + 1]));
         float ms = 0.f;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->prof_ev[k], ctx->prof_ev[k + 1]));
+        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->prof.ev[k], ctx->prof.ev[k + 1]));
         tot += ms * 1e-3;
     }
     *seconds_total = tot;
-    *launches = (int64_t)(ctx->prof_used / 2);
-    ctx->prof_used = 0;
+    *launches = (int64_t)(ctx->prof.used / 2);
+    ctx->prof.used = 0;
     return TF_OK;
+}
+
+// Debug / test aid: copies of the partial-sum buffers of the last packed J/K pass and of its group table (one density):
+// which = 0 DIc [groups][N], 1 DIr [groups][RS], 2 DJc [rows][N], 3 DJr [rows][RS]; returns the number of doubles copied (<= n) or < 0.
+long long tf_debug_partials(tf_ctx *ctx, int which, double *host, long long n)
+{
+    if (!ctx || !ctx->have_eri || ctx->layout != 1 || !host) return TF_EINVAL;
+    const tf_ctx::JKTables &T = ctx->jk.packed.t[0];
+    const size_t ng = (size_t)std::max(1, T.n_groups), nrows = (size_t)std::max<long long>(1, ctx->n_rows), N = (size_t)ctx->N, RS = (size_t)ctx->bl.RS;
+    const double *src = nullptr; size_t cnt = 0;
+    switch (which) {
+    case 0: src = ctx->jk.packed.DI; cnt = ng * N; break;
+    case 1: src = ctx->jk.packed.DI + ng * N; cnt = ng * RS; break;
+    case 2: src = ctx->jk.packed.DJ; cnt = nrows * N; break;
+    case 3: src = ctx->jk.packed.DJ + nrows * N; cnt = nrows * RS; break;
+    case 4: src = ctx->jk.packed.D; cnt = N * N; break;
+    default: return TF_EINVAL;
+    }
+    cnt = std::min<size_t>(cnt, (size_t)n);
+    if (hipMemcpy(host, src, cnt * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return TF_ENODEVICE;
+    return (long long)cnt;
+}
+// group table of the one-density pass: per group {i, j0, nr, r0, c} (internal indices); returns the number of groups
+int tf_debug_groups(tf_ctx *ctx, int32_t *out5, int max_groups)
+{
+    if (!ctx || !ctx->have_eri || ctx->layout != 1) return TF_EINVAL;
+    const tf_ctx::JKTables &T = ctx->jk.packed.t[0];
+    std::vector<JKGroup> g((size_t)T.n_groups);
+    if (T.n_groups && hipMemcpy(g.data(), T.d_groups, g.size() * sizeof(JKGroup), hipMemcpyDeviceToHost) != hipSuccess) return TF_ENODEVICE;
+    for (int k = 0; k < T.n_groups && k < max_groups; ++k) { out5[5 * k] = g[k].i; out5[5 * k + 1] = g[k].j0; out5[5 * k + 2] = g[k].nr; out5[5 * k + 3] = g[k].r0; out5[5 * k + 4] = g[k].c; }
+    return T.n_groups;
 }

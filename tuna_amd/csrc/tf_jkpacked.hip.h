@@ -47,18 +47,6 @@
 #endif
 
 
-// Weight proxy of the shard plan (tf_shard_plan_pairs works from shell dimensions alone): the row lengths of the unblocked
-// triangle, every triangle row rounded up to TF_TRI_PAD.  The blocked rows are ~1/4 of that, uniformly enough for balancing.
-#ifndef TF_TRI_PAD
-#define TF_TRI_PAD 16
-#endif
-__host__ __device__ inline long long tri_off(long long k)
-{
-    const long long q = k / TF_TRI_PAD, r = k % TF_TRI_PAD;     // sum over m = 1..k of m rounded up to the pad
-    return TF_TRI_PAD * (TF_TRI_PAD * q * (q + 1) / 2 + r * (q + 1));
-}
-__host__ __device__ inline long long packed_row_len(long long i, long long j) { return (tri_off(i) + j + TF_TRI_PAD) & ~(long long)(TF_TRI_PAD - 1); }
-
 #define TF_JKP_KB 4               // k steps per merge block
 
 __device__ __forceinline__ double ld_stream(const double *p) { return __builtin_nontemporal_load(p); }

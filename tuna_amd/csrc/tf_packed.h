@@ -44,3 +44,15 @@ struct JKTask { int super, w, part, pad; };   // part: which stretch of KS steps
 #define TF_JKR_THREADS 256         // (measured: 1024-thread blocks, 16 slices, are slower: 0.41 against 0.34 ms of tail at N = 400) threads of a jk_reduce_kernel block: 64 lanes x TF_JKR_THREADS / 64 slices of the rows / groups of an index
 #endif
 struct JKJtPlan { int sfirst[5]; int bfirst[5]; };   // supers of class c: sfirst[c] .. sfirst[c + 1]; blocks of class c: bfirst[c] .. bfirst[c + 1]
+
+// Weight proxy of the shard plan (tf_shard_plan_pairs works from shell dimensions alone): the row lengths of the unblocked
+// triangle, every triangle row rounded up to TF_TRI_PAD.  The blocked rows are ~1/4 of that, uniformly enough for balancing.
+#ifndef TF_TRI_PAD
+#define TF_TRI_PAD 16
+#endif
+inline long long tri_off(long long k)
+{
+    const long long q = k / TF_TRI_PAD, r = k % TF_TRI_PAD;     // sum over m = 1..k of m rounded up to the pad
+    return TF_TRI_PAD * (TF_TRI_PAD * q * (q + 1) / 2 + r * (q + 1));
+}
+inline long long packed_row_len(long long i, long long j) { return (tri_off(i) + j + TF_TRI_PAD) & ~(long long)(TF_TRI_PAD - 1); }

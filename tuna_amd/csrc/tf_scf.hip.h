@@ -49,7 +49,7 @@ inline void eig_pin_free(void *p) { (void)hipHostFree(p); }
 struct Workspace {
     // Sharded tensors (world > 1): every rank runs the cycle redundantly on identical data, and a last-bit difference must not let one
     // rank leave the loop (or take another branch) while the others wait in the next all-reduce.  `agree` sums a few per-iteration
-    // decision values over the ranks (tf_device.hip: through the registered all-reduce) and fails on EVERY rank when they differ.
+    // decision values over the ranks (tf_ranks_host.hip.h: through the registered all-reduce) and fails on EVERY rank when they differ.
     std::function<int(const double *vals, int n, std::string &msg)> agree;
     rocblas_handle blas = nullptr;
     int n = 0;

@@ -11,7 +11,7 @@
 
 namespace tft {
 
-struct ClassInfo {               // parity classes of the output AOs (tf_device.hip: build_blocked_layout)
+struct ClassInfo {               // parity classes of the output AOs (tf_basis_host.hip.h: build_blocked_layout)
     int N = 0;
     int cstart[4] = {0, 0, 0, 0}, csize[4] = {0, 0, 0, 0};
     std::vector<int> clsI, origI;     // [N] by internal index: class, original index
